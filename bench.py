@@ -1,19 +1,25 @@
 #!/usr/bin/env python3
 """Benchmark of the PREGO step_recognition hot path on MI355X (contract: see the task statement).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the MiniROAD eval path (features -> per-frame probabilities + argmax) over one
 Assembly101-O-test-split-sized set of whole videos (BASELINE.json configs[1]): 182 clips, ragged lengths,
 fp32 [T,2048] rgb and [T,2048] flow features already resident in HBM, 16-bit MFMA operands / fp32 accumulate: IEEE fp16 by
 default (`dtype` in the line; the same width, bytes and matrix rate as the bf16 configs[1] names, 8x less operand rounding -
-DESIGN.md section 3); the same line carries `value_bf16`, `value_fp16x2` (split operands: argmax-identical to the reference)
-and `value_fp32`.
+DESIGN.md section 3).
+A plain run sets up, warms up, times K steps and prints the headline line (`value`, `ms_per_step`, `per_rank`, `pass`).
+Everything else is measured with --full only: per-kernel HIP-event timing of the timed steps and the rooflines built on it, the
+zero-flow fast path, the output sanity check, the secondary paths (`value_bf16`, `value_fp16x2` - split operands: argmax-identical
+to the reference -, `value_fp32`, training, ViTEnc, attention, `main.py --eval` end to end), the CPU baseline and the cost
+model's `predicted` table.
+--dump-outputs DIR writes what the last timed step returned (see dump_outputs) for output-by-output comparisons of two builds;
+the inputs and weights are seeded, so the same arguments give the same inputs in every run.
 With --gpus N every rank owns its own clip set of that size (clip-sharded data parallel, no collective on the
 data path): weak scaling, the default.  `--scaling strong` shards the ONE 182-clip set over the ranks instead
 (data.shard_clips: longest first onto the lightest rank) and reports the frames of that one set / the slowest rank's
 time - bounded by the longest clip's sequential steps (prego_amd/cost_model.py).  Every line carries
-`per_rank` (frames, clips, sequential steps, ms) and `predicted` (the cost model's N = 1/2/4/8 table, weak and strong).
+`per_rank` (frames, clips, sequential steps, ms); with --full also `predicted` (the cost model's N = 1/2/4/8 table, weak and strong).
 Rank 0 prints ONE JSON line.
 """
 from __future__ import annotations
@@ -51,7 +57,12 @@ def parse():
     ap.add_argument("--local-batch", type=int, default=0, help="--mode train: windows per step PER RANK (weak scaling: the global batch grows with N); "
                                                                "0 = split --global-batch over the ranks")
     ap.add_argument("--grad-compress", default=None, choices=["bf16"], help="--mode train: all-reduce the gradient bucket in bf16")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (train step, ViTEnc, causal attention, fp32 mode)")
+    ap.add_argument("--full", action="store_true",
+                    help="--mode eval: also measure what the headline does not need (per-kernel timing and rooflines, zero-flow fast path, "
+                         "output sanity check, secondary paths, CPU baseline, cost-model table)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="--mode eval: write the last timed step's outputs to DIR/<name>.npy (a fixed, seeded sample of the frames)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary measurements (train step, ViTEnc, causal attention, fp32 mode)")
     ap.add_argument("--dry-run", action="store_true", help="rendezvous only (gloo, no GPU work): checks the N-rank launch path on a CPU box")
     ap.add_argument("--steps", type=int, default=10)      # >= 10 timed runs
     ap.add_argument("--warmup", type=int, default=3)     # ... after 3 warm-ups
@@ -60,11 +71,16 @@ def parse():
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16", "fp32", "fp16x2"],
                     help="MFMA operand type of the headline pass: fp16 (default; same rate as bf16, 8x less operand rounding), bf16, fp32, "
                          "fp16x2 (split operands, three fp16 products: fp32-class results, argmax-identical to the reference)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--rows-per-chunk", type=int, default=0, help="pipeline chunk size in packed rows (debug)")
-    ap.add_argument("--no-zero-flow", action="store_true", help="skip the extra zero-flow fast-path timing")
-    return ap.parse_args()
+    ap.add_argument("--no-zero-flow", action="store_true", help="with --full: skip the extra zero-flow fast-path timing")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.mode != "eval" or args.dry_run):
+        ap.error("--dump-outputs writes the outputs of the eval pass: it needs --mode eval without --dry-run")
+    return args
 
 
 def spawn_ranks(args) -> int:
@@ -312,10 +328,14 @@ def main():
     for _ in range(args.warmup):
         step(flow)
     eng.check()
-    dt, out = timed(flow, args.steps, timing=not os.environ.get("PREGO_BENCH_NO_KERNEL_TIMING"))
-    kt = eng.timing_read()
-    eng.timing_enable(False)
+    # per-kernel HIP events around the timed launches cost the pass ~1 % (scripts/probes/timing_cost_ab.sh): --full only
+    dt, out = timed(flow, args.steps, timing=args.full and not os.environ.get("PREGO_BENCH_NO_KERNEL_TIMING"))
+    if args.full:
+        kt = eng.timing_read()
+        eng.timing_enable(False)
     eng.check()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
     pinfo = eng.pass_info()          # mode 0: chunked pass; R > 0: split pass (recurrence on R XCDs beside one feed-forward launch on the rest)
     dt_rank = dt
     per_rank = {"frames": [frames], "clips": [len(lens)], "sequential_steps": [pinfo["steps"]], "pass_mode": [pinfo["mode"]],
@@ -335,7 +355,7 @@ def main():
     value = frames_all * args.steps / dt
 
     extra = {}
-    if not args.no_zero_flow and not synth:
+    if args.full and not args.no_zero_flow and not synth:
         # the shipped Assembly101-O config zeroes the flow half (datasets/dataset.py:69); skipping its half of layer1's K is
         # exact.  Reported beside `value`, never as `value`.
         for _ in range(max(1, args.warmup)):
@@ -347,82 +367,14 @@ def main():
             dtz = float(t.item())
         extra["frames_per_s_zero_flow_fastpath"] = frames_all * args.steps / dtz
 
-    # sanity on the last output: probabilities sum to 1, argmax consistent
-    probs, arg = out[0][0], out[1][0]
-    ok = bool(torch.allclose(probs.sum(1), torch.ones_like(probs[:, 0]), atol=1e-4)) and \
-        bool((probs.argmax(1).int() == arg).all())
+    if args.full:
+        # sanity on the last output: probabilities sum to 1, argmax consistent
+        probs, arg = out[0][0], out[1][0]
+        extra["output_sane"] = bool(torch.allclose(probs.sum(1), torch.ones_like(probs[:, 0]), atol=1e-4)) and \
+            bool((probs.argmax(1).int() == arg).all())
 
     if rank == 0:
-        n_l = max(1, kt["gemm_launches"])
-        # fp16 and bf16 MFMA: the same dense peak; fp16x2 executes 3 fp16 products per algorithmic product, and is priced on the
-        # ALGORITHMIC flops against the fp16 peak (so its ceiling is 1/3)
-        peak = PEAK_BF16_TFLOPS if args.dtype in ("bf16", "fp16", "fp16x2") else 157.3
-        gemm_tflops = kt["gemm_flop"] / (kt["gemm_ms"] * 1e-3) / 1e12 if kt["gemm_ms"] > 0 else 0.0
-        pack_gbs = kt["pack_bytes"] / (kt["pack_ms"] * 1e-3) / 1e9 if kt["pack_ms"] > 0 else 0.0
-        gru_flop = 2.0 * 1024 * 3072 * frames * args.steps                  # recurrent product, algorithmic
-        gru_tflops = gru_flop / (kt["gru_ms"] * 1e-3) / 1e12 if kt["gru_ms"] > 0 else 0.0
-        # HBM traffic per launch is NOT measured in this run (PMC counters need their own rocprofv3 passes): the figures come from
-        # the committed PMC summary, and the line says which file / workload / tree they belong to
-        traffic = {}
-        tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
-        if os.path.exists(tpath):
-            try:
-                traffic = json.load(open(tpath))
-            except Exception:
-                traffic = {}
-        traffic_source = {"file": traffic.get("source"), "collected_at_git": traffic.get("git"), "operand_dtype": traffic.get("dtype"),
-                          "workload": traffic.get("workload", "64 clips x 0.25 length of the bench workload: identical per-launch shapes (49 152-row chunks)"),
-                          "measured_in_this_run": False} if traffic else None
         step_ms = dt / args.steps * 1e3
-        gemm_name = {"bf16": "gemm_bf16_nt_pingpong_kernel<EPI_STORE_BF16, bf16>", "fp16": "gemm_bf16_nt_pingpong_kernel<EPI_STORE_BF16, f16>",
-                     "fp32": "gemm_f32_nt_kernel", "fp16x2": "gemm_bf16_nt_pingpong_kernel<EPI_STORE, f16, SPLIT> (3 fp16 products per product)"}[args.dtype] + \
-            " (layer1 + W_ih projections)"
-        rl_gemm = {"bound": "mfma", "kernel": gemm_name, "achieved": gemm_tflops, "peak": peak, "unit": "TFLOP/s",
-                   "frac": gemm_tflops / peak, "traffic": traffic.get("gemm_bytes_per_launch"),
-                   "avg_launch_ms": kt["gemm_ms"] / n_l, "launches": kt["gemm_launches"], "ms_per_step": kt["gemm_ms"] / args.steps}
-        rl_gru = {"bound": "mfma", "kernel": "gru_recurrence_kernel (persistent, T sequential steps: latency-bound, see DESIGN.md section 5)",
-                  "achieved": gru_tflops, "peak": peak, "unit": "TFLOP/s", "frac": gru_tflops / peak,
-                  "traffic": traffic.get("gru_bytes_per_launch"),      # HBM-side bytes (gi in, relu(h) out); the per-step hand-off stays in the XCDs' L2
-                  "avg_launch_ms": kt["gru_ms"] / max(1, kt["gru_launches"]), "launches": kt["gru_launches"],
-                  "ms_per_step": kt["gru_ms"] / args.steps, "us_per_timestep": kt["gru_ms"] / args.steps * 1e3 / max(lens),
-                  "sequential_timesteps": max(lens)}
-        rl_pack = {"bound": "hbm", "kernel": "pack_rows_kernel (feature streaming fp32 -> packed bf16)", "achieved": pack_gbs,
-                   "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": pack_gbs / PEAK_HBM_GBS,
-                   "traffic": traffic.get("pack_bytes_per_launch"), "ms_per_step": kt["pack_ms"] / args.steps}
-        dominant = rl_gru if kt["gru_ms"] >= kt["gemm_ms"] else rl_gemm
-        if pinfo["mode"] > 0:
-            # split pass: two persistent launches per pass.  The library reports the feed-forward launch (pack + layer1 GEMM + LayerNorm +
-            # W_ih GEMM jobs on 8 - R XCDs) in the pack slot of its timing and counts the projections' flops as before; the recurrence
-            # launch spans the whole pass on R XCDs (16 R slots, continuous batching: more sequential steps than the longest clip)
-            R = pinfo["mode"]
-            ff_ms = kt["pack_ms"]
-            ff_tflops = kt["gemm_flop"] / (ff_ms * 1e-3) / 1e12 if ff_ms > 0 else 0.0
-            share = (8 - R) / 8.0
-            rl_gemm = {"bound": "mfma", "kernel": f"ff_pass_kernel (persistent: pack + layer1 GEMM + LayerNorm + W_ih GEMM jobs of the whole pass on {8 - R} of 8 XCDs)",
-                       "achieved": ff_tflops, "peak": peak, "unit": "TFLOP/s", "frac": ff_tflops / peak, "xcds": 8 - R,
-                       "frac_of_its_xcds": ff_tflops / (peak * share), "traffic": traffic.get("ff_pass_bytes_per_launch"),
-                       "avg_launch_ms": ff_ms / max(1, kt["pack_launches"]), "launches": kt["pack_launches"], "ms_per_step": ff_ms / args.steps,
-                       "note": "achieved = the two projections' algorithmic flops / the launch's duration; the launch also streams the features (pack) and normalises the rows",
-                       "traffic_note": "HBM-side bytes per launch (FETCH_SIZE x 2 + WRITE_SIZE) of this launch REPLAYED ALONE on the same workload (scripts/split_replay.py on the "
-                                       "debug library: counter collection serialises dispatches, so the pair itself can never run under it); "
-                                       "algorithmic = 47 104 B per frame (DESIGN 4): what exceeds it is weight slabs and ring rows that were re-read over the fabric "
-                                       "instead of from the unit's own XCD's L2 (Infinity-Cache hits are counted)"}
-            alg_ff = traffic.get("ff_pass_algorithmic_bytes_per_launch")
-            if rl_gemm["traffic"] and alg_ff:
-                rl_gemm["traffic_algorithmic"] = alg_ff
-                rl_gemm["traffic_over_algorithmic"] = rl_gemm["traffic"] / alg_ff
-            rl_gru.update({"kernel": f"gru_recurrence_kernel<PASS> (one launch per pass on {R} of 8 XCDs, {pinfo['slots']} slots)", "xcds": R,
-                           "us_per_timestep": kt["gru_ms"] / args.steps * 1e3 / max(1, pinfo["steps"]), "sequential_timesteps": pinfo["steps"],
-                           "traffic": traffic.get("gru_pass_bytes_per_launch")})
-            alg_rec = traffic.get("gru_pass_algorithmic_bytes_per_launch")
-            if rl_gru["traffic"] and alg_rec:
-                rl_gru["traffic_algorithmic"] = alg_rec          # 6 144 B of GI in + 2 048 B of relu(h) out per frame; the per-step hand-off stays in the XCDs' L2
-                rl_gru["traffic_over_algorithmic"] = rl_gru["traffic"] / alg_rec
-            if traffic.get("split_source") and traffic_source is not None:
-                traffic_source = dict(traffic_source, file=traffic.get("split_source"), collected_at_git=traffic.get("split_git"),
-                                      workload=traffic.get("split_workload"))
-            rl_pack = None
-            dominant = rl_gemm       # both launches span the pass; the feed-forward one holds the larger share of the chip
         line = {
             "metric": "frames/sec (per-frame action logits) on Assembly101-O TSN features",
             "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -441,12 +393,8 @@ def main():
                         "parallelism": (f"clip-sharded dp{world}, no collective: the ONE eval set sharded over the ranks (longest clip first onto the lightest rank)"
                                         if strong else f"clip-sharded dp{world}, no collective: every rank its own eval-set-sized clip list"),
                         "weights": "random init, seed 20"}),
-            "frames_per_step_all_ranks": frames_all, "per_rank": per_rank, "predicted": predicted_tables(args),
-            # the kernel with the largest share of the timed region; every kernel's own roofline is under "rooflines"
-            "roofline": dict(dominant, traffic_source=traffic_source),
-            "rooflines": {"gemm": rl_gemm, "gru_recurrence": rl_gru, "pack": rl_pack},
+            "frames_per_step_all_ranks": frames_all, "per_rank": per_rank,
             "model_flop_per_frame": FLOP_PER_FRAME, "model_tflops": value * FLOP_PER_FRAME / 1e12,
-            "output_sane": ok,
             "pass": ({"mode": "split", "recurrence_xcds": pinfo["mode"], "slots": pinfo["slots"], "sequential_steps": pinfo["steps"]} if pinfo["mode"] > 0
                      else {"mode": "chunked", "slots": pinfo["slots"], "sequential_steps": pinfo["steps"]}),
         }
@@ -456,8 +404,11 @@ def main():
             line["build"] = {k: bi.get(k) for k in ("build_mode", "built_at", "host", "hipcc", "git_head_at_build", "sources_match_tree")}
         except Exception as e:       # provenance only: never fails the measurement
             line["build"] = {"build_mode": f"unknown ({e})"}
-        line.update(extra)
-        if not args.no_secondary and world == 1 and not synth and args.dtype in ("bf16", "fp16"):
+        if args.full:
+            line["predicted"] = predicted_tables(args)
+            line.update(kernel_rooflines(args, kt, pinfo, lens, frames))
+            line.update(extra)
+        if args.full and not args.no_secondary and world == 1 and not synth and args.dtype in ("bf16", "fp16"):
             del rgb, flow, out
             torch.cuda.empty_cache()
             line["secondary"] = secondary(dev, lens, sd, args.dtype)
@@ -465,12 +416,107 @@ def main():
             line["value_fp16x2"] = line["secondary"].get("value_fp16x2")
             other = "bf16" if args.dtype == "fp16" else "fp16"
             line[f"value_{other}"] = line["secondary"].get(f"value_{other}")
-        if not args.no_cpu_baseline and world == 1:      # the CPU baseline is timed on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # the CPU baseline is timed on rank 0 at N = 1 only
             line["cpu_baseline"] = cpu_baseline(sd, lens, args.cpu_budget)
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_ROWS = 131072      # frames per dump: 131 072 x (86 probabilities + argmax) in fp32 + the frame indices in fp64 = 46.7 MB
+
+
+def dump_outputs(dirname, out, rank, world):
+    """--dump-outputs: what the last timed step handed its caller - per-frame probabilities [T, C] and argmax [T] of every clip -
+    on a fixed, seeded sample of DUMP_ROWS frames of the rank's clips concatenated in order (all frames if there are fewer):
+    rows.npy (float64 frame indices into the concatenation), probs.npy (float32 [rows, C]), argmax.npy (float32 [rows]).
+    With --gpus N every rank writes its own sample of DUMP_ROWS / N frames, the names suffixed _rank<r>."""
+    probs, arg = torch.cat(out[0]), torch.cat(out[1])
+    n = probs.shape[0]
+    rows = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_ROWS // world), replace=False))
+    idx = torch.from_numpy(rows).to(probs.device)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, f"rows{sfx}.npy"), rows.astype(np.float64))
+    np.save(os.path.join(dirname, f"probs{sfx}.npy"), probs[idx].float().cpu().numpy())
+    np.save(os.path.join(dirname, f"argmax{sfx}.npy"), arg[idx].float().cpu().numpy())
+
+
+def kernel_rooflines(args, kt, pinfo, lens, frames):
+    """--full: `roofline` (the kernel with the largest share of the timed region) and every kernel's own under `rooflines`, from the
+    library's per-kernel HIP-event timing `kt` of the timed steps"""
+    n_l = max(1, kt["gemm_launches"])
+    # fp16 and bf16 MFMA: the same dense peak; fp16x2 executes 3 fp16 products per algorithmic product, and is priced on the
+    # ALGORITHMIC flops against the fp16 peak (so its ceiling is 1/3)
+    peak = PEAK_BF16_TFLOPS if args.dtype in ("bf16", "fp16", "fp16x2") else 157.3
+    gemm_tflops = kt["gemm_flop"] / (kt["gemm_ms"] * 1e-3) / 1e12 if kt["gemm_ms"] > 0 else 0.0
+    pack_gbs = kt["pack_bytes"] / (kt["pack_ms"] * 1e-3) / 1e9 if kt["pack_ms"] > 0 else 0.0
+    gru_flop = 2.0 * 1024 * 3072 * frames * args.steps                  # recurrent product, algorithmic
+    gru_tflops = gru_flop / (kt["gru_ms"] * 1e-3) / 1e12 if kt["gru_ms"] > 0 else 0.0
+    # HBM traffic per launch is NOT measured in this run (PMC counters need their own rocprofv3 passes): the figures come from
+    # the committed PMC summary, and the line says which file / workload / tree they belong to
+    traffic = {}
+    tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
+    if os.path.exists(tpath):
+        try:
+            traffic = json.load(open(tpath))
+        except Exception:
+            traffic = {}
+    traffic_source = {"file": traffic.get("source"), "collected_at_git": traffic.get("git"), "operand_dtype": traffic.get("dtype"),
+                      "workload": traffic.get("workload", "64 clips x 0.25 length of the bench workload: identical per-launch shapes (49 152-row chunks)"),
+                      "measured_in_this_run": False} if traffic else None
+    gemm_name = {"bf16": "gemm_bf16_nt_pingpong_kernel<EPI_STORE_BF16, bf16>", "fp16": "gemm_bf16_nt_pingpong_kernel<EPI_STORE_BF16, f16>",
+                 "fp32": "gemm_f32_nt_kernel", "fp16x2": "gemm_bf16_nt_pingpong_kernel<EPI_STORE, f16, SPLIT> (3 fp16 products per product)"}[args.dtype] + \
+        " (layer1 + W_ih projections)"
+    rl_gemm = {"bound": "mfma", "kernel": gemm_name, "achieved": gemm_tflops, "peak": peak, "unit": "TFLOP/s",
+               "frac": gemm_tflops / peak, "traffic": traffic.get("gemm_bytes_per_launch"),
+               "avg_launch_ms": kt["gemm_ms"] / n_l, "launches": kt["gemm_launches"], "ms_per_step": kt["gemm_ms"] / args.steps}
+    rl_gru = {"bound": "mfma", "kernel": "gru_recurrence_kernel (persistent, T sequential steps: latency-bound, see DESIGN.md section 5)",
+              "achieved": gru_tflops, "peak": peak, "unit": "TFLOP/s", "frac": gru_tflops / peak,
+              "traffic": traffic.get("gru_bytes_per_launch"),      # HBM-side bytes (gi in, relu(h) out); the per-step hand-off stays in the XCDs' L2
+              "avg_launch_ms": kt["gru_ms"] / max(1, kt["gru_launches"]), "launches": kt["gru_launches"],
+              "ms_per_step": kt["gru_ms"] / args.steps, "us_per_timestep": kt["gru_ms"] / args.steps * 1e3 / max(lens),
+              "sequential_timesteps": max(lens)}
+    rl_pack = {"bound": "hbm", "kernel": "pack_rows_kernel (feature streaming fp32 -> packed bf16)", "achieved": pack_gbs,
+               "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": pack_gbs / PEAK_HBM_GBS,
+               "traffic": traffic.get("pack_bytes_per_launch"), "ms_per_step": kt["pack_ms"] / args.steps}
+    dominant = rl_gru if kt["gru_ms"] >= kt["gemm_ms"] else rl_gemm
+    if pinfo["mode"] > 0:
+        # split pass: two persistent launches per pass.  The library reports the feed-forward launch (pack + layer1 GEMM + LayerNorm +
+        # W_ih GEMM jobs on 8 - R XCDs) in the pack slot of its timing and counts the projections' flops as before; the recurrence
+        # launch spans the whole pass on R XCDs (16 R slots, continuous batching: more sequential steps than the longest clip)
+        R = pinfo["mode"]
+        ff_ms = kt["pack_ms"]
+        ff_tflops = kt["gemm_flop"] / (ff_ms * 1e-3) / 1e12 if ff_ms > 0 else 0.0
+        share = (8 - R) / 8.0
+        rl_gemm = {"bound": "mfma", "kernel": f"ff_pass_kernel (persistent: pack + layer1 GEMM + LayerNorm + W_ih GEMM jobs of the whole pass on {8 - R} of 8 XCDs)",
+                   "achieved": ff_tflops, "peak": peak, "unit": "TFLOP/s", "frac": ff_tflops / peak, "xcds": 8 - R,
+                   "frac_of_its_xcds": ff_tflops / (peak * share), "traffic": traffic.get("ff_pass_bytes_per_launch"),
+                   "avg_launch_ms": ff_ms / max(1, kt["pack_launches"]), "launches": kt["pack_launches"], "ms_per_step": ff_ms / args.steps,
+                   "note": "achieved = the two projections' algorithmic flops / the launch's duration; the launch also streams the features (pack) and normalises the rows",
+                   "traffic_note": "HBM-side bytes per launch (FETCH_SIZE x 2 + WRITE_SIZE) of this launch REPLAYED ALONE on the same workload (scripts/split_replay.py on the "
+                                   "debug library: counter collection serialises dispatches, so the pair itself can never run under it); "
+                                   "algorithmic = 47 104 B per frame (DESIGN 4): what exceeds it is weight slabs and ring rows that were re-read over the fabric "
+                                   "instead of from the unit's own XCD's L2 (Infinity-Cache hits are counted)"}
+        alg_ff = traffic.get("ff_pass_algorithmic_bytes_per_launch")
+        if rl_gemm["traffic"] and alg_ff:
+            rl_gemm["traffic_algorithmic"] = alg_ff
+            rl_gemm["traffic_over_algorithmic"] = rl_gemm["traffic"] / alg_ff
+        rl_gru.update({"kernel": f"gru_recurrence_kernel<PASS> (one launch per pass on {R} of 8 XCDs, {pinfo['slots']} slots)", "xcds": R,
+                       "us_per_timestep": kt["gru_ms"] / args.steps * 1e3 / max(1, pinfo["steps"]), "sequential_timesteps": pinfo["steps"],
+                       "traffic": traffic.get("gru_pass_bytes_per_launch")})
+        alg_rec = traffic.get("gru_pass_algorithmic_bytes_per_launch")
+        if rl_gru["traffic"] and alg_rec:
+            rl_gru["traffic_algorithmic"] = alg_rec          # 6 144 B of GI in + 2 048 B of relu(h) out per frame; the per-step hand-off stays in the XCDs' L2
+            rl_gru["traffic_over_algorithmic"] = rl_gru["traffic"] / alg_rec
+        if traffic.get("split_source") and traffic_source is not None:
+            traffic_source = dict(traffic_source, file=traffic.get("split_source"), collected_at_git=traffic.get("split_git"),
+                                  workload=traffic.get("split_workload"))
+        rl_pack = None
+        dominant = rl_gemm       # both launches span the pass; the feed-forward one holds the larger share of the chip
+    return {"roofline": dict(dominant, traffic_source=traffic_source),
+            "rooflines": {"gemm": rl_gemm, "gru_recurrence": rl_gru, "pack": rl_pack}}
 
 
 def _time_ms(fn, n=10, warm=3, reps=3):

@@ -6,6 +6,6 @@ cd $GRAFT_REPO_ROOT
 for r in 1 2 3; do
   for L in new old; do
     if [ $L = old ]; then export PREGO_AMD_LIB=$ALT; else unset PREGO_AMD_LIB; fi
-    echo "$L $(python3 bench.py --no-cpu-baseline --no-secondary --no-zero-flow --steps 10 "$@" 2>&1 | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(round(d['ms_per_step'],2),'ms', d['pass'], 'rec us/step', round(d['rooflines']['gru_recurrence']['us_per_timestep'],4))")"
+    echo "$L $(python3 bench.py --full --no-cpu-baseline --no-secondary --no-zero-flow --steps 10 "$@" 2>&1 | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(round(d['ms_per_step'],2),'ms', d['pass'], 'rec us/step', round(d['rooflines']['gru_recurrence']['us_per_timestep'],4))")"
   done
 done

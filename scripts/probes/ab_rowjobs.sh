@@ -10,6 +10,6 @@ bash scripts/probes/ab_lib.sh prego_amd/lib_ab/libold.so
 for r in 1 2; do
 for L in new old; do
   if [ $L = old ]; then export PREGO_AMD_LIB=$GRAFT_REPO_ROOT/prego_amd/lib_ab/libold.so; else unset PREGO_AMD_LIB; fi
-  echo "with zero-flow $L $(python3 bench.py --no-cpu-baseline --no-secondary --steps 10 2>&1 | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(round(d['ms_per_step'],2),'ms;  zero-flow M frames/s', round(d.get('frames_per_s_zero_flow_fastpath',0)/1e6,3))")"
+  echo "with zero-flow $L $(python3 bench.py --full --no-cpu-baseline --no-secondary --steps 10 2>&1 | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(round(d['ms_per_step'],2),'ms;  zero-flow M frames/s', round(d.get('frames_per_s_zero_flow_fastpath',0)/1e6,3))")"
 done
 done

@@ -5,7 +5,7 @@ export PREGO_AMD_DEBUG_LIB=1   # tuning knobs (PREGO_SPLIT_LAG*, PREGO_PLAN_SLOT
 for mt in 1 0; do
 for sl in 128 256 512; do
   if [ $mt = 1 ]; then unset PREGO_GRU_NO_MT; else export PREGO_GRU_NO_MT=1; fi
-  PREGO_PLAN_SLOTS=$sl timeout 300 python bench.py --steps 10 --warmup 3 --workload synth512 --no-cpu-baseline --no-secondary 2>/dev/null > /tmp/sw.json
+  PREGO_PLAN_SLOTS=$sl timeout 300 python bench.py --full --steps 10 --warmup 3 --workload synth512 --no-cpu-baseline --no-secondary 2>/dev/null > /tmp/sw.json
   python - "$sl" "$mt" <<'PY'
 import json, sys
 sl, mt = int(sys.argv[1]), int(sys.argv[2])

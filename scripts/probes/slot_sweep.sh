@@ -3,7 +3,7 @@ export PREGO_AMD_DEBUG_LIB=1   # tuning knobs (PREGO_SPLIT_LAG*, PREGO_PLAN_SLOT
 # recurrence cost per time step by live tiles per group (calibrates kStepCost in csrc/miniroad.cpp): synth512 workload,
 # slots forced to 128 / 256 / 512 = 1 / 2 / 4 tiles per group
 for sl in 128 256 512; do
-  PREGO_PLAN_SLOTS=$sl python bench.py --steps 10 --warmup 3 --workload synth512 --no-cpu-baseline 2>/dev/null > /tmp/sw.json
+  PREGO_PLAN_SLOTS=$sl python bench.py --full --steps 10 --warmup 3 --workload synth512 --no-cpu-baseline 2>/dev/null > /tmp/sw.json
   python - "$sl" <<'PY'
 import json, sys
 sl = int(sys.argv[1])

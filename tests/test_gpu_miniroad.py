@@ -537,3 +537,41 @@ def test_other_dimensions_many_clips_and_rejections():
         _model(assembly101_cfg(num_layers=2), W.miniroad_state_dict(assembly101_cfg(num_layers=2), 20), "fp16x2").engine()
     with pytest.raises(PregoError, match="hidden_dim 768"):
         _model(assembly101_cfg(hidden_dim=768), W.miniroad_state_dict(assembly101_cfg(hidden_dim=768), 20), "fp16").engine()
+
+
+def test_bench_plain_run_dumps_what_its_last_timed_step_returned(tmp_path):
+    """`bench.py --dump-outputs DIR` (a fresh child process, small slice of the bench workload): the plain line carries the headline
+    fields for the steps asked for, and the dumped sample is what the eval path returns for the bench's seeded inputs and weights"""
+    import json
+    import subprocess
+    import sys
+    from prego_amd.registry import build_model
+    import prego_amd.model  # noqa: F401
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--clips", "8",
+                        "--len-scale", "0.05", "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + "\n" + r.stderr[-4000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["unit"] == "frames/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "fp16" and line["value"] > 0 and line["ms_per_step"] > 0
+    rows, probs, arg = (np.load(out_dir / f"{n}.npy") for n in ("rows", "probs", "argmax"))
+    assert rows.dtype == np.float64 and probs.dtype == np.float32 and arg.dtype == np.float32
+    frames = line["config"]["frames_per_gpu"]
+    assert len(rows) == min(frames, 131072) and probs.shape == (len(rows), 86) and arg.shape == (len(rows),)
+    # the bench's inputs, regenerated: lengths, weights and device generator as bench.py seeds them
+    from prego_amd.workloads import assembly101_eval_lengths
+    lens = [max(1, int(l * 0.05)) for l in assembly101_eval_lengths(seed=20)[:8]]
+    assert sum(lens) == frames
+    cfg = assembly101_cfg(compute_dtype="fp16")
+    eng = _model(cfg, W.miniroad_state_dict(cfg, 20, head_gain=8.0), "fp16").engine()
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(1234)
+    rgb = [torch.randn((T, 2048), device="cuda", generator=gen).clamp_(min=0) for T in lens]
+    flow = [torch.randn((T, 2048), device="cuda", generator=gen).clamp_(min=0) for T in lens]
+    outs, args, _ = eng.forward_ragged(rgb, flow, softmax=True, want_out=True, want_argmax=True)
+    eng.check()
+    idx = torch.from_numpy(rows.astype(np.int64)).cuda()
+    want_p = torch.cat(outs)[idx].cpu().numpy()
+    assert float(np.abs(probs - want_p).max()) < 1e-5
+    assert np.array_equal(arg, torch.cat(args)[idx].float().cpu().numpy()) and np.array_equal(arg, probs.argmax(1).astype(np.float32))
