@@ -155,6 +155,29 @@ int prego_miniroad_forward(prego_miniroad* h, int n_clips, const int32_t* lens, 
                            float* h_last, int flags, void* workspace, size_t workspace_bytes,
                            prego_stream_t stream);
 
+/* ---- MiniROADA (MROADA, registry name "MiniROADA"): step_recognition/model/rnn/rnn.py:73-136 ------------------------------------------
+ * The MiniROAD trunk plus an anticipation head on every frame: A_l = relu(relu(h_t) W_a[l]^T + b_a[l]) for l < L, where W_a[l] is rows
+ * l*hid .. l*hid + hid - 1 of anticipation_layer.0.weight (the .view(B, S, L, H) of rnn.py:125), and logits_l = A_l W_c^T + b_c with the SAME
+ * f_classification weights as the frame's own logits (rnn.py:126).
+ *
+ * set_anticipation: load_state_dict of the head, device fp32 tensors with the reference's state_dict shapes
+ *   anticipation_layer.0.weight [ant_len * hid, hid]   anticipation_layer.0.bias [ant_len * hid]
+ * ant_len = cfg['anticipation_length'], 1..32.  The handle keeps converted copies (the handle's operand type): call again after the weights
+ * change, like set_weights.  May allocate (and then synchronises `stream`) when ant_len grows.  Refused with a message on fp16x2 handles and
+ * on num_layers 2 (the reference's own h0 is (1, B, H), rnn.py:122).  f_actionness is built by the reference but never used in forward. */
+int prego_miniroad_set_anticipation(prego_miniroad* h, int ant_len, const float* w_a, const float* b_a, prego_stream_t stream);
+/* MROADA.forward for a ragged batch: prego_miniroad_forward's arguments and behaviour (out / argmax are MROAD's logits / argmax, bit for bit
+ * the same as prego_miniroad_forward's; h0 / h_last, passes, workspace_bytes / resident_bytes sizes, no device allocation, no host wait
+ * beyond forward's) plus
+ *   ant_out[i]       device fp32 [lens[i], ant_len, n_classes]: per-step probabilities (PREGO_FWD_SOFTMAX, rnn.py:131-134) or logits; nullable
+ *   ant_argmax[i]    device int32 [lens[i], ant_len]: argmax over classes per step, first max wins; nullable
+ * The head never materialises the [frames, ant_len * hid] intermediate; its sums are in a fixed order (repeat calls are bit-identical, and
+ * which pass ran changes no bit).  Inference only (PREGO_FWD_KEEP is refused); call set_anticipation first. */
+int prego_miniroad_forward_anticipation(prego_miniroad* h, int n_clips, const int32_t* lens, const float* const* rgb,
+                                        const float* const* flow, float* const* out, int32_t* const* argmax,
+                                        float* const* ant_out, int32_t* const* ant_argmax, const float* h0, float* h_last,
+                                        int flags, void* workspace, size_t workspace_bytes, prego_stream_t stream);
+
 /* Streaming inference, the online use of the model: ONE new frame for each of n_streams <= 16 independent streams -
  * MROAD.forward (rnn.py:51-71) with T = 1 and h0 = the state the previous call left.
  *   rgb / flow     device fp32 [n_streams, d_rgb] / [n_streams, d_flow], one frame per stream; flow == NULL = zero flow half

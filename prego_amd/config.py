@@ -56,3 +56,11 @@ def epic_tent_cfg(**over) -> dict:
     )
     cfg.update(over)
     return cfg
+
+
+def anticipation_cfg(cfg: dict, anticipation_length: int = 8, actionness: bool = False, **over) -> dict:
+    """A MiniROAD cfg turned into a MiniROADA one (model/rnn/rnn.py:73-110): the two keys MROADA reads beside MROAD's
+    (cfg['anticipation_length'], cfg['actionness']) and model = 'MiniROADA'."""
+    out = dict(cfg, model="MiniROADA", anticipation_length=int(anticipation_length), actionness=bool(actionness))
+    out.update(over)
+    return out

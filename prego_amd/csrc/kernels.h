@@ -222,6 +222,11 @@ int gru_max_tiles();
 int launch_head_softmax(bool bf16, const void* Hrelu, const void* Wc, const float* bc, const SlotPlan& plan,
                         int row0, int nrows, int hid, int C, int apply_softmax,
                         float* const* out_ptrs, int* const* argmax_ptrs, hipStream_t s, const void* rowmap = nullptr, bool f16 = false);
+// anticipation head of MiniROADA (ant_head.hip): per row, for l < L, softmax / logits of relu(relu(h) W_a[l]^T + b_a[l]) W_c^T + b_c into
+// out_ptrs[clip] [T][L][C] and argmax_ptrs[clip] [T][L]; rows and destinations as launch_head_softmax.  -1 = unsupported shape
+int launch_ant_head(bool bf16, bool f16, const void* Hrelu, const void* Wa, const float* ba, const void* Wc, const float* bc,
+                    const SlotPlan& plan, int row0, int nrows, int hid, int L, int C, int apply_softmax, float* const* out_ptrs,
+                    int* const* argmax_ptrs, const void* rowmap, hipStream_t s);
 void launch_permute_rows(const float* src, float* dst, const int* sorted_clip, int n, int width, int to_sorted,
                          hipStream_t s);
 void launch_add_vec(const float* a, const float* b, float* out, int n, int n_add, hipStream_t s);

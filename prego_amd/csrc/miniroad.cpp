@@ -90,6 +90,8 @@ struct prego_miniroad {
   void* w_c = nullptr;          // [ncls_pad][H] WT zero padded
   float* b_c = nullptr;         // [ncls_pad]
   bool have_weights = false;
+  // MiniROADA anticipation head (prego_miniroad_set_anticipation): anticipation_layer.0.weight [L*H][H] in the operand type, its bias fp32
+  int ant_len = 0; void* w_a = nullptr; float* b_a = nullptr; size_t w_a_cap = 0;
   // nn.GRU(embedding_dim, hidden_dim, num_layers) with num_layers == 2 (rnn.py:32,38): layer 1's operands (gru.*_l1; its input is layer 0's
   // h_t, so weight_ih_l1 is [3H][H]).  Inference only; hidden state [layers][slots][H]
   int layers = 1;
@@ -129,7 +131,7 @@ struct prego_miniroad {
   int* d_seg_off = nullptr; int* d_seg_clip = nullptr; int* d_seg_start = nullptr;
   size_t cap_t = 0, cap_c = 0;
   // per-call pointer tables (device)
-  void** d_ptrs = nullptr;      // [4][max_clips]
+  void** d_ptrs = nullptr;      // [6][max_clips]: rgb, flow, out, argmax, anticipation out, anticipation argmax
   // pinned host staging for the per-call tables (pointer table, plan arrays): the async H2D copies read it after the call
   // returns, so it is handle-owned and fenced by an event (never a stack or pageable buffer)
   char* pin = nullptr; size_t pin_bytes = 0; hipEvent_t pin_ev = nullptr; bool pin_busy = false;
@@ -274,7 +276,7 @@ extern "C" int prego_miniroad_create_layers(prego_miniroad** out, int d_rgb, int
     A(&h->l2_w_ih, (size_t)3 * H * H * es); A(&h->l2_w_hh, (size_t)3 * H * H * es);
     A((void**)&h->l2_bias2, 3 * H * 4); A((void**)&h->l2_b_hn, H * 4);
   }
-  A((void**)&h->d_ptrs, (size_t)4 * max_clips_of(h) * sizeof(void*));
+  A((void**)&h->d_ptrs, (size_t)6 * max_clips_of(h) * sizeof(void*));
   // plan tables pre-sized here so that forward() allocates nothing: 131 072 steps (a 72-minute clip at 30 frames/s; the longest
   // Epic-tent-O video has 31 114 frames) and max_clips clips; only a longer clip than that makes forward() grow them
   h->cap_t = (size_t)131072 + 1;
@@ -284,7 +286,7 @@ extern "C" int prego_miniroad_create_layers(prego_miniroad** out, int d_rgb, int
   A((void**)&h->d_seg_clip, h->cap_c * 4); A((void**)&h->d_seg_start, h->cap_c * 4);
   h->cap_b = (size_t)1 << 19;                    // 16.7 M packed rows per call before the table has to grow
   A((void**)&h->d_blkstep, h->cap_b * 4);
-  h->pin_bytes = (size_t)4 * max_clips_of(h) * sizeof(void*) + 2 * h->cap_t * 4 + 4 * (h->cap_c + 1) * 4 + h->cap_b * 4 + 1024;
+  h->pin_bytes = (size_t)6 * max_clips_of(h) * sizeof(void*) + 2 * h->cap_t * 4 + 4 * (h->cap_c + 1) * 4 + h->cap_b * 4 + 1024;
   if (e == hipSuccess) e = hipHostMalloc((void**)&h->pin, h->pin_bytes, hipHostMallocDefault);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&h->pin_ev, hipEventDisableTiming);
   h->no_local = getenv("PREGO_GRU_NO_LOCAL") != nullptr;
@@ -341,7 +343,8 @@ extern "C" void prego_miniroad_destroy(prego_miniroad* h) {
   if (h->side) { PREGO_TEARDOWN(hipStreamSynchronize(h->side)); PREGO_TEARDOWN(hipStreamDestroy(h->side)); }
   void* ptrs[] = {h->w1, h->b1, h->ln_g, h->ln_b, h->w_ih, h->w_hh, h->bias2, h->b_hn, h->w_c, h->b_c, h->hx,
                   h->flags, h->h_state, h->stamps, h->tile_ctr, h->d_rowoff, h->d_nact, h->d_sorted, h->d_seg_off, h->d_seg_clip,
-                  h->d_seg_start, h->d_ptrs, h->d_blkstep, h->st_scratch, h->x2_scale, h->l2_w_ih, h->l2_w_hh, h->l2_bias2, h->l2_b_hn, h->w_ih_perm, h->bias2_perm};
+                  h->d_seg_start, h->d_ptrs, h->d_blkstep, h->st_scratch, h->x2_scale, h->l2_w_ih, h->l2_w_hh, h->l2_bias2, h->l2_b_hn, h->w_ih_perm, h->bias2_perm,
+                  h->w_a, h->b_a};
   for (size_t i = 0; i < sizeof ptrs / sizeof ptrs[0]; ++i)
     if (ptrs[i]) {
 #ifdef PREGO_DEBUG_ABI
@@ -637,7 +640,7 @@ static int stage_tables(prego_miniroad* h, const void* const* tab4, size_t tab_c
     }
     (void)hipHostFree(h->pin);
     h->pin = nullptr;
-    h->pin_bytes = (size_t)4 * max_clips_of(h) * sizeof(void*) + 2 * h->cap_t * 4 + 4 * (h->cap_c + 1) * 4 + h->cap_b * 4 + 1024;
+    h->pin_bytes = (size_t)6 * max_clips_of(h) * sizeof(void*) + 2 * h->cap_t * 4 + 4 * (h->cap_c + 1) * 4 + h->cap_b * 4 + 1024;
     HIPCHK(hipHostMalloc((void**)&h->pin, h->pin_bytes, hipHostMallocDefault));
   }
   char* p = h->pin;
@@ -875,7 +878,27 @@ static hipEvent_t g_split_last[64] = {};
 
 // *fell_back = true (with PREGO_OK): the start handshake of the two launches failed - they left without writing anything, the caller
 // runs the chunked pass for this call.
-static int forward_split(prego_miniroad* h, int R, int flags, bool with_flow, bool in16, int kx, const SlotPlan& plan,
+// the anticipation head of a forward_anticipation call over packed rows [row0, row0 + nrows) of the plan, relu(h) rows at HR (chunk-relative);
+// the destinations come from the plan (the same lookup in every pass: which pass ran changes no bit)
+// AntOut: the anticipation outputs of a forward_anticipation call (host pointer arrays; their device tables are d_ptrs rows 4 and 5)
+struct AntOut {
+  bool call = false;                   // forward_anticipation (rather than forward)
+  float* const* out = nullptr;         // per clip [T][L][C], nullable
+  int32_t* const* arg = nullptr;       // per clip [T][L], nullable
+  bool wanted() const { return call && (out || arg); }
+};
+static int ant_head(prego_miniroad* h, const AntOut& ao, const void* HR, const SlotPlan& plan, int row0, int nrows, int flags, hipStream_t s) {
+  if (!ao.wanted()) return PREGO_OK;
+  const int MC = max_clips_of(h);
+  float* const* d_ao = ao.out ? (float* const*)(h->d_ptrs + 4 * MC) : nullptr;
+  int* const* d_aa = ao.arg ? (int* const*)(h->d_ptrs + 5 * MC) : nullptr;
+  if (launch_ant_head(h->bf16, h->f16, HR, h->w_a, h->b_a, h->w_c, h->b_c, plan, row0, nrows, h->hid, h->ant_len, h->ncls,
+                      (flags & PREGO_FWD_SOFTMAX) ? 1 : 0, d_ao, d_aa, nullptr, s))
+    return fail(PREGO_EINVAL, "anticipation head: unsupported shape (hid %d, L %d, num_classes %d)", h->hid, h->ant_len, h->ncls);
+  return PREGO_OK;
+}
+
+static int forward_split(prego_miniroad* h, const AntOut& ao, int R, int flags, bool with_flow, bool in16, int kx, const SlotPlan& plan,
                          const float* const* d_rgb_ptrs, const float* const* d_flow_ptrs, float* const* d_out_ptrs, int* const* d_arg_ptrs,
                          void* workspace, size_t workspace_bytes, hipStream_t s, bool* fell_back) {
   *fell_back = false;
@@ -1031,18 +1054,20 @@ static int forward_split(prego_miniroad* h, int R, int flags, bool with_flow, bo
     }
   }
   if (h->timing) { h->gemm_flop += 2.0 * total * ((double)E * kx + 3.0 * H * E); h->split_passes++; h->split_steps += h->t_max; }
-  if (launch_head_softmax(true, HR, h->w_c, h->b_c, plan, 0, total, H, h->ncls, (flags & PREGO_FWD_SOFTMAX) ? 1 : 0, d_out_ptrs, d_arg_ptrs, s,
+  if ((d_out_ptrs || d_arg_ptrs) &&
+      launch_head_softmax(true, HR, h->w_c, h->b_c, plan, 0, total, H, h->ncls, (flags & PREGO_FWD_SOFTMAX) ? 1 : 0, d_out_ptrs, d_arg_ptrs, s,
                           RM, h->f16))
     return fail(PREGO_EINVAL, "head: unsupported num_classes %d", h->ncls);
+  if (int rc_a = ant_head(h, ao, HR, plan, 0, total, flags, s)) return rc_a;
   if (h->meas_armed) { HIPCHK(hipEventRecord(h->ev_meas[1], s)); h->meas_pending = true; h->meas_armed = false; }
   HIPCHK(hipGetLastError());
   return PREGO_OK;
 }
 
-extern "C" int prego_miniroad_forward(prego_miniroad* h, int n_clips, const int32_t* lens, const float* const* rgb,
-                                      const float* const* flow, float* const* out, int32_t* const* argmax,
-                                      const float* h0, float* h_last, int flags, void* workspace,
-                                      size_t workspace_bytes, prego_stream_t stream) {
+// prego_miniroad_forward and prego_miniroad_forward_anticipation (ao.call)
+static int forward_impl(prego_miniroad* h, int n_clips, const int32_t* lens, const float* const* rgb, const float* const* flow,
+                        float* const* out, int32_t* const* argmax, const AntOut& ao, const float* h0, float* h_last, int flags,
+                        void* workspace, size_t workspace_bytes, prego_stream_t stream) {
   HandleScope scope_(h);
   if (!h) return fail(PREGO_EINVAL, "handle is NULL");
   if (!h->have_weights) return fail(PREGO_EINVAL, "forward before set_weights");
@@ -1062,6 +1087,7 @@ extern "C" int prego_miniroad_forward(prego_miniroad* h, int n_clips, const int3
   if (in16 && !h->bf16) return fail(PREGO_EINVAL, "PREGO_FWD_IN16 on an fp32-operand handle (16-bit features go with bf16 / fp16 handles)");
   if (in16 && (flags & PREGO_FWD_KEEP)) return fail(PREGO_EINVAL, "PREGO_FWD_IN16 with PREGO_FWD_KEEP: training takes fp32 features");
   const bool want_single = h0 != nullptr || h_last != nullptr || (flags & PREGO_FWD_KEEP) != 0;
+  const bool ant_wanted = ao.wanted();          // forward_anticipation with an output
   // link-fed call (prego_miniroad_set_feed_events): the feature arrays are being filled over the host link while this call runs
   const bool hostfeat = !h->feed_ev.empty();
   if (hostfeat && want_single) { h->feed_ev.clear(); return fail(PREGO_EINVAL, "feed events with h0 / h_last / PREGO_FWD_KEEP: link-fed calls are plain inference"); }
@@ -1082,7 +1108,7 @@ extern "C" int prego_miniroad_forward(prego_miniroad* h, int n_clips, const int3
     // everything but the placement (which a handle's first, chunked, call establishes)
     const bool shape_ok = h->split_env != 0 && r_try >= 1 && r_try <= 6 && h->bf16 && h->hid == 1024 && h->layers == 1 && !want_single && !hostfeat && h->G == 8 && !h->no_local &&
                           h->side != nullptr && side_queue_differs(h, s) && n_clips >= 16 * r_try && frames >= 262144 &&
-                          frames < (1ll << 31) - 65536 && (out || argmax) && split_workspace_ok(h, r_try, workspace_bytes) &&
+                          frames < (1ll << 31) - 65536 && (out || argmax || ant_wanted) && split_workspace_ok(h, r_try, workspace_bytes) &&
                           (h->d_rgb > 0 ? h->d_rgb : h->d_flow) >= 128 &&
                           (size_t)frames * (h->hid * 2 + 8) <= ((size_t)24 << 30) && split_resident_ok(h, frames);
     // a call of this class is worth one wait for the placement word of an earlier launch (the handle's second call otherwise races it)
@@ -1159,7 +1185,7 @@ extern "C" int prego_miniroad_forward(prego_miniroad* h, int n_clips, const int3
   // pointer tables -> device
   const int MC = max_clips_of(h);
   bool any_flow = false;
-  std::vector<const void*> tab((size_t)4 * MC, nullptr);
+  std::vector<const void*> tab((size_t)(ao.call ? 6 : 4) * MC, nullptr);
   for (int i = 0; i < n_clips; ++i) {
     tab[0 * MC + i] = rgb ? rgb[i] : nullptr;
     if (h->d_rgb > 0 && !tab[i]) return fail(PREGO_EINVAL, "rgb[%d] is NULL", i);
@@ -1167,6 +1193,10 @@ extern "C" int prego_miniroad_forward(prego_miniroad* h, int n_clips, const int3
     any_flow |= tab[1 * MC + i] != nullptr;
     tab[2 * MC + i] = out ? out[i] : nullptr;
     tab[3 * MC + i] = argmax ? argmax[i] : nullptr;
+    if (ao.call) {
+      tab[4 * MC + i] = ao.out ? ao.out[i] : nullptr;
+      tab[5 * MC + i] = ao.arg ? ao.arg[i] : nullptr;
+    }
   }
   rc = stage_tables(h, tab.data(), tab.size(), s);
   if (rc) return rc;
@@ -1181,7 +1211,7 @@ extern "C" int prego_miniroad_forward(prego_miniroad* h, int n_clips, const int3
   if (kx == 0) return fail(PREGO_EINVAL, "a model without rgb features (--no_rgb) needs the flow tensors");
   if (split_r > 0) {
     bool fell_back = false;
-    rc = forward_split(h, split_r, flags, with_flow, in16, kx, plan, d_rgb_ptrs, d_flow_ptrs, d_out_ptrs, d_arg_ptrs, workspace, workspace_bytes, s,
+    rc = forward_split(h, ao, split_r, flags, with_flow, in16, kx, plan, d_rgb_ptrs, d_flow_ptrs, d_out_ptrs, d_arg_ptrs, workspace, workspace_bytes, s,
                        &fell_back);
     if (rc || !fell_back) return rc;
     // The two launches could not run side by side (a profiler that serialises dispatches, another tenant on the XCDs) and left before
@@ -1190,7 +1220,7 @@ extern "C" int prego_miniroad_forward(prego_miniroad* h, int n_clips, const int3
     h->split_fails++; h->split_fallbacks++;
     if (h->split_fails >= 3) h->split_env = 0;
     else h->split_skip = 16ll << (2 * (h->split_fails - 1));
-    return prego_miniroad_forward(h, n_clips, lens, rgb, flow, out, argmax, h0, h_last, flags, workspace, workspace_bytes, stream);
+    return forward_impl(h, n_clips, lens, rgb, flow, out, argmax, ao, h0, h_last, flags, workspace, workspace_bytes, stream);
   }
   const int din = h->d_rgb + h->d_flow;
   const RowBytes rb = row_bytes(h, with_flow, flags);
@@ -1216,7 +1246,7 @@ extern "C" int prego_miniroad_forward(prego_miniroad* h, int n_clips, const int3
   // buffer, or one that is too small = per-chunk head.  Nothing is allocated and nothing is waited for here.
   bool defer_head = false;
   char* HRall = nullptr;
-  if (!(flags & PREGO_FWD_KEEP) && !hostfeat && h->layers == 1 && (out || argmax) && (long long)total_rows >= 4 * cap_rows &&
+  if (!(flags & PREGO_FWD_KEEP) && !hostfeat && h->layers == 1 && (out || argmax || ant_wanted) && (long long)total_rows >= 4 * cap_rows &&
       (size_t)total_rows * rb.hr <= ((size_t)24 << 30)) {
     const size_t need = align_up((size_t)total_rows * rb.hr, 256);
     if (h->res_buf && need <= h->res_bytes) { defer_head = true; HRall = h->res_buf; }
@@ -1446,14 +1476,18 @@ extern "C" int prego_miniroad_forward(prego_miniroad* h, int n_clips, const int3
                               (flags & PREGO_FWD_SOFTMAX) ? 1 : 0, d_out_ptrs, d_arg_ptrs, s, RM + (size_t)(ci & 1) * cap_rows * 8, h->f16))
         return fail(PREGO_EINVAL, "head: unsupported num_classes %d", h->ncls);
     }
+    if (ant_wanted && !defer_head) {
+      if (int rc_a = ant_head(h, ao, HR, plan, base, rows, flags, s)) return rc_a;
+    }
     if (packed) { HIPCHK(hipStreamWaitEvent(s, h->ev_join, 0)); side_join.pending = false; }
     t0 = t1;
     ++ci;
   }
   if (defer_head) {                      // the classifier of the whole call, once (16-bit operands: no row map at hand - the kernel looks rows up in the plan)
-    if (launch_head_softmax(h->bf16, HRall, h->w_c, h->b_c, plan, 0, total_rows, H, h->ncls, (flags & PREGO_FWD_SOFTMAX) ? 1 : 0, d_out_ptrs,
+    if ((out || argmax) && launch_head_softmax(h->bf16, HRall, h->w_c, h->b_c, plan, 0, total_rows, H, h->ncls, (flags & PREGO_FWD_SOFTMAX) ? 1 : 0, d_out_ptrs,
                             d_arg_ptrs, s, nullptr, h->f16))
       return fail(PREGO_EINVAL, "head: unsupported num_classes %d", h->ncls);
+    if (int rc_a = ant_head(h, ao, HRall, plan, 0, total_rows, flags, s)) return rc_a;
   }
   if (h_last)
     for (int l = 0; l < h->layers; ++l) launch_permute_rows(h->h_state + l * slot_stride, h_last + (size_t)l * n_clips * H, h->d_sorted, n_slots, H, 0, s);
@@ -1462,6 +1496,57 @@ extern "C" int prego_miniroad_forward(prego_miniroad* h, int n_clips, const int3
   if (h->meas_armed) { HIPCHK(hipEventRecord(h->ev_meas[1], s)); h->meas_pending = true; h->meas_armed = false; }
   HIPCHK(hipGetLastError());
   return PREGO_OK;
+}
+
+extern "C" int prego_miniroad_forward(prego_miniroad* h, int n_clips, const int32_t* lens, const float* const* rgb,
+                                      const float* const* flow, float* const* out, int32_t* const* argmax,
+                                      const float* h0, float* h_last, int flags, void* workspace,
+                                      size_t workspace_bytes, prego_stream_t stream) {
+  return forward_impl(h, n_clips, lens, rgb, flow, out, argmax, AntOut{}, h0, h_last, flags, workspace, workspace_bytes, stream);
+}
+
+// ---- MiniROADA (MROADA, registry name "MiniROADA"): the anticipation head (rnn.py:113-136; csrc/ant_head.hip) -----------------------
+extern "C" int prego_miniroad_set_anticipation(prego_miniroad* h, int ant_len, const float* w_a, const float* b_a, prego_stream_t stream) {
+  HandleScope scope_(h);
+  if (!h) return fail(PREGO_EINVAL, "handle is NULL");
+  if (h->x2) return fail(PREGO_EINVAL, "set_anticipation: fp16x2 (split-operand) handles have no anticipation head; use fp32, bf16 or fp16");
+  if (h->layers != 1)
+    return fail(PREGO_EINVAL, "set_anticipation: num_layers %d - MiniROADA runs one GRU layer (its h0 is (1, B, H), rnn.py:122)", h->layers);
+  if (ant_len < 1 || ant_len > 32) return fail(PREGO_EINVAL, "set_anticipation: anticipation_length %d must be in 1..32", ant_len);
+  if (!w_a || !b_a) return fail(PREGO_EINVAL, "set_anticipation: NULL tensor");
+  hipStream_t s = (hipStream_t)stream;
+  const int H = h->hid;
+  const size_t es = h->bf16 ? 2 : 4, need = (size_t)ant_len * H * H * es;
+  if (need > h->w_a_cap || ant_len > h->ant_len) {
+    // setup call, not a hot one: the old copies may still be read by enqueued work of this stream
+    HIPCHK(hipStreamSynchronize(s));
+    if (h->w_a) { HIPCHK(hipFree(h->w_a)); h->w_a = nullptr; }
+    if (h->b_a) { HIPCHK(hipFree(h->b_a)); h->b_a = nullptr; }
+    h->w_a_cap = 0;
+    HIPCHK(hipMalloc(&h->w_a, need));
+    HIPCHK(hipMalloc((void**)&h->b_a, (size_t)ant_len * H * 4));
+    h->w_a_cap = need;
+  }
+  launch_pad_convert(h->bf16, w_a, ant_len * H, H, H, h->w_a, ant_len * H, H, s, h->f16);
+  HIPCHK(hipMemcpyAsync(h->b_a, b_a, (size_t)ant_len * H * 4, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipGetLastError());
+  h->ant_len = ant_len;
+  return PREGO_OK;
+}
+
+extern "C" int prego_miniroad_forward_anticipation(prego_miniroad* h, int n_clips, const int32_t* lens, const float* const* rgb,
+                                                   const float* const* flow, float* const* out, int32_t* const* argmax,
+                                                   float* const* ant_out, int32_t* const* ant_argmax, const float* h0, float* h_last,
+                                                   int flags, void* workspace, size_t workspace_bytes, prego_stream_t stream) {
+  {
+    HandleScope scope_(h);
+    if (!h) return fail(PREGO_EINVAL, "handle is NULL");
+    if (h->ant_len <= 0 || !h->w_a) return fail(PREGO_EINVAL, "forward_anticipation before set_anticipation");
+    if (flags & PREGO_FWD_KEEP) return fail(PREGO_EINVAL, "forward_anticipation: PREGO_FWD_KEEP (MiniROADA training) is not supported");
+  }
+  AntOut ao;
+  ao.call = true; ao.out = ant_out; ao.arg = ant_argmax;
+  return forward_impl(h, n_clips, lens, rgb, flow, out, argmax, ao, h0, h_last, flags, workspace, workspace_bytes, stream);
 }
 
 // streaming step: one frame for each of n <= 16 streams (stream_step.hip)

@@ -199,3 +199,70 @@ def shard_clips(lengths, world_size: int, rank: int):
         owner[i] = r
         load[r] += int(lengths[i])
     return [i for i in range(len(lengths)) if owner[i] == rank]
+
+
+class AnticipationDataset(data.Dataset):
+    """`THUMOS_ANTICIPATION` / `TVSERIES_ANTICIPATION` (datasets/dataset.py:138-231): items (rgb [W, D] f32, flow [W, D] f32,
+    target [W, C] f32, ant_target f32).  Same files and video lists as the reference, same windowing:
+      train: features and targets front-padded with window_size - 1 zero rows; windows [start, end) with start from a random phase
+             (np.random.randint(stride), re-drawn by `_init_features`) in steps of stride, end = start + window_size < T - L;
+             ant_target = target[end : end + L]  [L, C]
+      test:  one item per video cut to its first T - L frames, ant_target[s] = target[s : s + L]  [T - L, L, C]
+    Differences on purpose: pads are float32, a video of at most L frames yields an empty [0, L, C] ant_target instead of a
+    shape-(0,) array, and the test-mode ant_target is one strided view instead of a Python list of T - L slices."""
+
+    def __init__(self, cfg, mode="train"):
+        self.root_path = cfg["root_path"]
+        self.mode = mode
+        self.training = mode == "train"
+        self.window_size = cfg["window_size"]
+        self.stride = cfg["stride"]
+        self.anticipation_length = int(cfg["anticipation_length"])
+        data_name = cfg["data_name"].split("_")[0]
+        self.vids = json.load(open(cfg["video_list_path"]))[data_name][mode + "_session_set"]
+        self.num_classes = cfg["num_classes"]
+        self.target_all, self.rgb_inputs, self.flow_inputs = {}, {}, {}
+        W = self.window_size - 1
+        for vid in self.vids:
+            target = np.load(osp.join(self.root_path, cfg["annotation_type"], vid + ".npy")).astype(np.float32)
+            rgb = np.load(osp.join(self.root_path, cfg["rgb_type"], vid + ".npy")).astype(np.float32)
+            flow = np.load(osp.join(self.root_path, cfg["flow_type"], vid + ".npy")).astype(np.float32)
+            if self.training:
+                target = np.concatenate((np.zeros((W, target.shape[1]), np.float32), target), 0)
+                rgb = np.concatenate((np.zeros((W, rgb.shape[1]), np.float32), rgb), 0)
+                flow = np.concatenate((np.zeros((W, flow.shape[1]), np.float32), flow), 0)
+            self.target_all[vid], self.rgb_inputs[vid], self.flow_inputs[vid] = target, rgb, flow
+        self.inputs = []
+        self._init_features()
+
+    def _init_features(self):
+        L = self.anticipation_length
+        self.inputs = []
+        for vid in self.vids:
+            target = self.target_all[vid]
+            T = target.shape[0]
+            if self.training:
+                seed = np.random.randint(self.stride)
+                for start, end in zip(range(seed, T, self.stride), range(seed + self.window_size, T - L, self.stride)):
+                    self.inputs.append([vid, start, end, target[start:end], target[end:end + L]])
+            else:
+                end = max(T - L, 0)
+                if end > 0:
+                    ant = np.lib.stride_tricks.sliding_window_view(target[:end + L - 1] if L > 1 else target[:end], L, axis=0)
+                    ant = np.ascontiguousarray(np.moveaxis(ant[:end], -1, 1))        # [end, L, C]
+                else:
+                    ant = np.zeros((0, L, target.shape[1]), np.float32)
+                self.inputs.append([vid, 0, end, target[:end], ant])
+
+    def __getitem__(self, index):
+        vid, start, end, target, ant_target = self.inputs[index]
+        return (torch.from_numpy(np.ascontiguousarray(self.rgb_inputs[vid][start:end])),
+                torch.from_numpy(np.ascontiguousarray(self.flow_inputs[vid][start:end])),
+                torch.from_numpy(np.ascontiguousarray(target)), torch.from_numpy(ant_target.astype(np.float32)))
+
+    def __len__(self):
+        return len(self.inputs)
+
+
+for _name in ("THUMOS_ANTICIPATION", "TVSERIES_ANTICIPATION"):
+    DATA_LAYERS.register(_name, AnticipationDataset)

@@ -114,6 +114,25 @@ class MiniRoadEngine:
                 ts += tl
         self._keep = ts   # alive until the stream has consumed them
 
+    def set_anticipation(self, weight: torch.Tensor, bias: torch.Tensor, ant_len: int):
+        """MiniROADA's anticipation_layer.0.weight [ant_len * hid, hid] / .bias [ant_len * hid] (rnn.py:108-110); call again after
+        the weights change, like set_weights"""
+        ts = []
+        for t in (weight, bias):
+            t = t.detach()
+            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
+                t = t.to(self.device, torch.float32).contiguous()
+            ts.append(t)
+        hid = self.dims[3]
+        if tuple(ts[0].shape) != (ant_len * hid, hid) or tuple(ts[1].shape) != (ant_len * hid,):
+            raise PregoError(f"anticipation_layer: weight {tuple(ts[0].shape)} / bias {tuple(ts[1].shape)}, expected "
+                             f"({ant_len * hid}, {hid}) / ({ant_len * hid},)")
+        with torch.cuda.device(self.device):
+            check(self.lib.prego_miniroad_set_anticipation(self.h, int(ant_len), C.c_void_p(ts[0].data_ptr()), C.c_void_p(ts[1].data_ptr()),
+                                                           C.c_void_p(_stream_ptr(self.device))))
+        self.ant_len = int(ant_len)
+        self._keep_ant = ts
+
     # -- forward ---------------------------------------------------------------------------
     def _workspace(self, n_clips, lens_arr, flags):
         need = self.lib.prego_miniroad_workspace_bytes(self.h, n_clips, lens_arr, self.rows_per_chunk, flags)
@@ -137,9 +156,17 @@ class MiniRoadEngine:
 
     def forward_ragged(self, rgb: Sequence[torch.Tensor], flow: Optional[Sequence[Optional[torch.Tensor]]],
                        softmax: bool = True, want_out: bool = True, want_argmax: bool = False,
-                       h0: Optional[torch.Tensor] = None, want_h_last: bool = False):
+                       h0: Optional[torch.Tensor] = None, want_h_last: bool = False, want_ant: bool = False,
+                       want_ant_argmax: Optional[bool] = None):
         """rgb[i]: fp32 cuda (or pinned host, see _dev_readable) [T_i, d_rgb] contiguous; flow[i] likewise or None (= zeros).
-        Returns (outs list of [T_i, C] or None, argmax list of int32 [T_i] or None, h_last or None)."""
+        Returns (outs list of [T_i, C] or None, argmax list of int32 [T_i] or None, h_last or None).
+        want_ant (MiniROADA, after set_anticipation): the anticipation head as well - returns (outs, argmax, h_last, ant_outs list of
+        [T_i, L, C] (probabilities / logits as `softmax`), ant_argmax list of int32 [T_i, L] or None (want_ant_argmax, default
+        want_argmax))."""
+        if want_ant_argmax is None:
+            want_ant_argmax = want_argmax
+        if want_ant and not getattr(self, "ant_len", 0):
+            raise PregoError("forward_ragged(want_ant=True) before set_anticipation")
         d_rgb, d_flow, emb, hid, ncls = self.dims
         if d_rgb == 0:                  # --no_rgb (rnn.py:23-29,54-57): the model's only input is the flow stream
             if flow is None or any(f is None for f in flow):
@@ -148,9 +175,11 @@ class MiniRoadEngine:
         src_list = rgb if rgb is not None else flow
         n = len(src_list)
         if n == 0:                      # empty clip list: nothing to do (the reference's loader simply yields nothing)
-            return ([] if want_out else None), ([] if want_argmax else None), (torch.empty((0, hid), device=self.device) if want_h_last else None)
+            res = ([] if want_out else None), ([] if want_argmax else None), (torch.empty((0, hid), device=self.device) if want_h_last else None)
+            return res + ([], [] if want_ant_argmax else None) if want_ant else res
         outs = [None] * n
         args = [None] * n
+        ant = ([None] * n, [None] * n if want_ant_argmax else None) if want_ant else None
         # GRU state: [n, hid]; a two-layer engine takes / returns nn.GRU's [layers, n, hid]
         L = self.num_layers
         st_shape = (lambda m: (m, hid) if L == 1 else (L, m, hid))
@@ -163,13 +192,19 @@ class MiniRoadEngine:
             sub_h0 = None if h0 is None else h0[..., idx, :].to(torch.float32).contiguous()
             sub_hl = None if h_last is None else torch.empty(st_shape(len(idx)), dtype=torch.float32, device=self.device)
             sub_out, sub_arg = [None] * len(idx), [None] * len(idx)
+            sub_ant = ([None] * len(idx), [None] * len(idx) if want_ant_argmax else None) if want_ant else None
             self._forward_pass(None if rgb is None else [rgb[i] for i in idx], None if flow is None else [flow[i] for i in idx], softmax,
-                               want_out, want_argmax, sub_h0, sub_hl, sub_out, sub_arg, 0)
+                               want_out, want_argmax, sub_h0, sub_hl, sub_out, sub_arg, 0, ant=sub_ant)
             for k, i in enumerate(idx):
                 outs[i], args[i] = sub_out[k], sub_arg[k]
+                if ant is not None:
+                    ant[0][i] = sub_ant[0][k]
+                    if ant[1] is not None:
+                        ant[1][i] = sub_ant[1][k]
             if h_last is not None:
                 h_last[..., idx, :] = sub_hl
-        return (outs if want_out else None), (args if want_argmax else None), h_last
+        res = (outs if want_out else None), (args if want_argmax else None), h_last
+        return res + ant if want_ant else res
 
     # -- link-fed inference (Evaluate: the H2D copy of a batch under its forward) ------------------------------------------
     def plan_starts(self, lens: Sequence[int], link_row_bytes: int):
@@ -190,7 +225,7 @@ class MiniRoadEngine:
         check(self.lib.prego_miniroad_set_feed_events(self.h, n, up, ev, int(link_row_bytes)))
         self._link_fed_next = True          # a link-fed call keeps the per-chunk classifier: it needs no resident buffer
 
-    def _forward_pass(self, rgb, flow, softmax, want_out, want_argmax, h0, h_last, outs, args, base):
+    def _forward_pass(self, rgb, flow, softmax, want_out, want_argmax, h0, h_last, outs, args, base, ant=None):
         d_rgb, d_flow, emb, hid, ncls = self.dims
         n = len(rgb) if rgb is not None else len(flow)
         lens = []
@@ -241,6 +276,30 @@ class MiniRoadEngine:
                 ptrs.append(p0 + o * 4)
                 o += lens[i]
             arg_p = ptr_array(ptrs)
+        if ant is not None:             # MiniROADA: [T_i, L, C] / [T_i, L] per clip, one allocation per kind
+            L = self.ant_len
+            flat = torch.empty((total, L, ncls), dtype=torch.float32, device=self.device)
+            o, p0, ptrs = 0, flat.data_ptr(), []
+            for i in range(n):
+                ant[0][base + i] = flat[o:o + lens[i]]
+                ptrs.append(p0 + o * L * ncls * 4)
+                o += lens[i]
+            ant_out_p, ant_arg_p = ptr_array(ptrs), None
+            if ant[1] is not None:
+                flat_a = torch.empty((total, L), dtype=torch.int32, device=self.device)
+                o, p0, ptrs = 0, flat_a.data_ptr(), []
+                for i in range(n):
+                    ant[1][base + i] = flat_a[o:o + lens[i]]
+                    ptrs.append(p0 + o * L * 4)
+                    o += lens[i]
+                ant_arg_p = ptr_array(ptrs)
+            with torch.cuda.device(self.device):
+                check(self.lib.prego_miniroad_forward_anticipation(
+                    self.h, n, lens_arr, rgb_p, flow_p, out_p, arg_p, ant_out_p, ant_arg_p,
+                    C.c_void_p(h0.data_ptr()) if h0 is not None else None,
+                    C.c_void_p(h_last.data_ptr()) if h_last is not None else None,
+                    flags, C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(_stream_ptr(self.device))))
+            return
         with torch.cuda.device(self.device):
             check(self.lib.prego_miniroad_forward(
                 self.h, n, lens_arr, rgb_p, flow_p, out_p, arg_p,

@@ -565,3 +565,91 @@ class Evaluate(nn.Module):
 
     def forward(self, model, dataloader, logger, device):
         return self.eval(model, dataloader, logger, device)
+
+
+@EVAL.register("ANTICIPATION")
+class AntEvaluate(nn.Module):
+    """`ANT_Evaluate` (trainer/eval.py:87-161): `AntEvaluate(cfg)(model, dataloader, logger[, device])` runs the anticipation eval set
+    (items (rgb, flow, target [T, C], ant_target [T, L, C]) of the *_ANTICIPATION data layers) and returns the mean over the L steps of
+    the per-step mAP.  `self.result` holds what the reference's `result` holds: the OAD report (`mean_AP`, per class) and
+    `anticipation_{l+1}` = the report of step l.
+    A model with `forward_clips` on a GPU (MiniROADA) is fed whole videos in batches (one ragged forward per batch, anticipation head
+    included) and metric 'AP' is computed on the device (`prego_perframe_ap`); metric 'cAP' uses the host path, and so does a stand-in
+    model without `forward_clips` (called per loader batch, as the reference does)."""
+
+    def __init__(self, cfg):
+        super().__init__()
+        data_name = cfg["data_name"].split("_")[0]
+        if data_name == "THUMOS":
+            raise NotImplementedError("THUMOS post-processing is outside the PREGO datasets")
+        self.metric = cfg["metric"]
+        if self.metric not in ("AP", "cAP"):
+            raise RuntimeError(f"Unknown metrics: {self.metric}")
+        self.all_class_names = json.load(open(cfg["video_list_path"]))[data_name]["class_index"]
+        self.max_frames_per_batch = int(cfg.get("eval_frames_per_batch", 4_000_000))
+        self.result = None
+        self.last_fps = None
+
+    def _metric(self, pred, gt):
+        if self.metric == "AP" and pred.is_cuda:
+            return perframe_average_precision_device(pred, gt.to(pred.device, torch.float32), self.all_class_names)
+        return perframe_average_precision(pred.cpu().numpy(), gt.cpu().numpy(), self.all_class_names, None, self.metric)
+
+    def eval(self, model, dataloader, logger, device=None):
+        dev = torch.device(device) if device is not None else (torch.device("cuda:0") if torch.cuda.is_available() else torch.device("cpu"))
+        model.eval()
+        batched = hasattr(model, "forward_clips") and dev.type == "cuda"
+        preds, gts, apreds, agts = [], [], [], []
+        pend, pend_frames = [], 0
+
+        def flush():
+            nonlocal pend, pend_frames
+            if not pend:
+                return
+            rgb = [p[0] for p in pend] if model.use_rgb else None
+            flow = [p[1] for p in pend] if model.use_flow else None
+            outs, _, _, ants, _ = model.forward_clips(rgb, flow, want_argmax=False, want_ant=True)
+            for (_, _, t, a), o, x in zip(pend, outs, ants):
+                preds.append(o); gts.append(t); apreds.append(x); agts.append(a)
+            pend, pend_frames = [], 0
+
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            for rgb_input, flow_input, target, ant_target in dataloader:
+                C = target.shape[-1]
+                if batched:
+                    for b in range(rgb_input.shape[0]):
+                        T = int(target.shape[1])
+                        if T == 0:
+                            continue
+                        pend.append((rgb_input[b].to(dev, torch.float32).contiguous(), flow_input[b].to(dev, torch.float32).contiguous(),
+                                     target[b].to(dev), ant_target[b].to(dev)))
+                        pend_frames += T
+                        if pend_frames >= self.max_frames_per_batch or len(pend) >= model.max_clips:
+                            flush()
+                else:
+                    out = model(rgb_input.to(dev), flow_input.to(dev))
+                    preds.append(out["logits"].reshape(-1, C)); gts.append(target.to(dev).reshape(-1, C))
+                    L = out["anticipation_logits"].shape[-2]
+                    apreds.append(out["anticipation_logits"].reshape(-1, L, C)); agts.append(ant_target.to(dev).reshape(-1, L, C))
+            if batched:
+                flush()
+        n_frames = sum(int(p.shape[0]) for p in preds)
+        pred, gt = torch.cat(preds).to(torch.float32), torch.cat(gts).to(torch.float32)
+        apred, agt = torch.cat(apreds).to(torch.float32), torch.cat(agts).to(torch.float32)
+        result = self._metric(pred, gt)
+        logger.info(f'OAD mAP: {result["mean_AP"] * 100:.2f}')
+        maps = []
+        for step in range(agt.shape[1]):
+            result[f"anticipation_{step + 1}"] = self._metric(apred[:, step, :].contiguous(), agt[:, step, :].contiguous())
+            maps.append(result[f"anticipation_{step + 1}"]["mean_AP"])
+            logger.info(f"Anticipation at step {step + 1}: {maps[-1] * 100:.2f}")
+        logger.info(f"Mean Anticipation mAP: {np.mean(maps) * 100:.2f}")
+        dt = time.perf_counter() - t0
+        self.last_fps = n_frames / dt if dt > 0 else None
+        logger.info(f"Processed {n_frames} frames in {dt:.1f} seconds ({(self.last_fps or 0):.1f} FPS)")
+        self.result = result
+        return np.mean(maps)
+
+    def forward(self, model, dataloader, logger, device=None):
+        return self.eval(model, dataloader, logger, device)

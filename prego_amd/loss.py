@@ -20,3 +20,23 @@ class OadLoss(nn.Module):
 
     def forward(self, out_dict, target):
         return oad_loss_autograd(out_dict["logits"], target, self.reduction)
+
+
+@CRITERIONS.register("ANTICIPATION")
+class OadAntLoss(nn.Module):
+    """`OadAntLoss` (criterions/loss.py:40-79): the multi-label cross entropy of OadLoss on the LAST frame's anticipation logits,
+    anticipation_logits[:, -1] [B, L, C] taken as B * L one-frame rows against ant_target.view(-1, C); reduction 'sum' by default.
+    Value and dloss/dlogits come from the same HIP kernel as OadLoss (prego_oad_loss_reduce); autograd carries the gradient back
+    through the slice to anticipation_logits."""
+
+    def __init__(self, cfg, reduction="sum"):
+        super().__init__()
+        if reduction not in ("mean", "sum"):
+            raise ValueError(f"OadAntLoss: reduction {reduction!r}: expected 'mean' or 'sum'")
+        self.reduction = reduction
+        self.num_classes = cfg["num_classes"]
+
+    def forward(self, out_dict, target, ant_target):
+        C = self.num_classes
+        last = out_dict["anticipation_logits"][:, -1, :, :].reshape(-1, 1, C)
+        return oad_loss_autograd(last, ant_target.reshape(-1, 1, C), self.reduction)

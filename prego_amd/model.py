@@ -77,9 +77,13 @@ class MROAD(nn.Module):
             self._engines[key] = ent
         vers = tuple((p.data_ptr(), p._version) for p in self.parameters())
         if vers != ent[1]:
-            ent[0].set_weights(dict(self.named_parameters()))
+            self._ingest(ent[0])
             ent[1] = vers
         return ent[0]
+
+    def _ingest(self, eng: MiniRoadEngine):
+        """hand the current parameters to the engine (it keeps converted copies)"""
+        eng.set_weights(dict(self.named_parameters()))
 
     def _mark_ingested(self, train: bool = True):
         """the engine's operand copies were refreshed in place (fused AdamW): record the current parameter versions as theirs"""
@@ -125,3 +129,87 @@ class MROAD(nn.Module):
         rgb [n, d_rgb] / flow [n, d_flow] (None = zeros), h [n, hidden_dim] = the GRU state, updated in place.  Returns
         (probabilities [n, C], argmax int32 [n]) - the eval branch of MROAD.forward (rnn.py:66-70) at T = 1 with h0 = h."""
         return self.engine().step(rgb, flow, h, softmax=True)
+
+
+@META_ARCHITECTURES.register("MiniROADA")
+class MROADA(MROAD):
+    """`MiniROADA` (rnn.py:73-136): the MiniROAD trunk plus an anticipation head on every frame, anticipation_length steps ahead, through
+    the SAME f_classification weights.  Eval forward returns {'logits': [B, T, C], 'anticipation_logits': [B, T, L, C]}, both as
+    probabilities (rnn.py:131-134); the head is the fused kernel of csrc/ant_head.hip (the [frames, L * H] intermediate is never
+    materialised).  Parameter containers are built in the reference's order (layer1, f_actionness when cfg['actionness'], gru,
+    f_classification, anticipation_layer), so a given torch seed gives the reference's initial weights and state_dict keys match
+    (f_actionness.0.* included, which the reference builds but never uses in forward).  Training, `step` streaming and fp16x2 handles are
+    not built for this model."""
+
+    def __init__(self, cfg):
+        nn.Module.__init__(self)
+        self.use_flow = not cfg["no_flow"]
+        self.use_rgb = not cfg["no_rgb"]
+        self.d_rgb = FEATURE_SIZES[cfg["rgb_type"]] if self.use_rgb else 0
+        self.d_flow = FEATURE_SIZES[cfg["flow_type"]] if self.use_flow else 0
+        self.input_dim = self.d_rgb + self.d_flow
+        self.embedding_dim = cfg["embedding_dim"]
+        self.hidden_dim = cfg["hidden_dim"]
+        self.num_layers = cfg["num_layers"]
+        self.anticipation_length = cfg["anticipation_length"]
+        self.out_dim = cfg["num_classes"]
+        self.window_size = cfg.get("window_size")
+        if self.num_layers != 1:
+            raise PregoError(f"prego_amd MiniROADA runs one GRU layer (its h0 is (1, B, H), rnn.py:122; cfg['num_layers'] = {self.num_layers})")
+        if not 1 <= int(self.anticipation_length) <= 32:
+            raise PregoError(f"prego_amd MiniROADA: anticipation_length {self.anticipation_length} must be in 1..32")
+        # parameter containers, reference construction order (rnn.py:93-110)
+        self.layer1 = nn.Sequential(
+            nn.Linear(self.input_dim, self.embedding_dim),
+            nn.LayerNorm(self.embedding_dim),
+            nn.ReLU(),
+            nn.Dropout(p=cfg["dropout"]),
+        )
+        self.actionness = cfg["actionness"]
+        if self.actionness:
+            self.f_actionness = nn.Sequential(nn.Linear(self.hidden_dim, 1))
+        self.relu = nn.ReLU()
+        self.gru = nn.GRU(self.embedding_dim, self.hidden_dim, self.num_layers, batch_first=True)
+        self.f_classification = nn.Sequential(nn.Linear(self.hidden_dim, self.out_dim))
+        self.anticipation_layer = nn.Sequential(nn.Linear(self.hidden_dim, self.anticipation_length * self.hidden_dim))
+        self.compute_dtype = cfg.get("compute_dtype", "fp16")
+        self.assume_zero_flow = bool(cfg.get("assume_zero_flow", False))
+        self.grad_compress = None
+        self._engines = {}
+
+    def _engine_dtype(self, train: bool) -> str:
+        return self.compute_dtype
+
+    def _ingest(self, eng: MiniRoadEngine):
+        eng.set_weights(dict(self.named_parameters()))
+        eng.set_anticipation(self.anticipation_layer[0].weight, self.anticipation_layer[0].bias, self.anticipation_length)
+
+    def _inputs(self, rgb_input, flow_input):
+        src = rgb_input if self.use_rgb else flow_input
+        B = src.shape[0]
+        rgb = [rgb_input[b].contiguous() for b in range(B)] if self.use_rgb else None
+        if self.use_flow and (not self.assume_zero_flow or not self.use_rgb):
+            flow = [flow_input[b].contiguous() for b in range(B)]
+        else:
+            flow = None
+        return rgb, flow
+
+    def forward(self, rgb_input, flow_input):
+        if self.training:
+            raise PregoError("MiniROADA training is not built yet in prego_amd (the anticipation head has an inference kernel only): "
+                             "call .eval() for inference")
+        rgb, flow = self._inputs(rgb_input, flow_input)
+        outs, _, _, ant, _ = self.engine().forward_ragged(rgb, flow, softmax=True, want_ant=True, want_ant_argmax=False)
+        return {"logits": torch.stack(outs, 0), "anticipation_logits": torch.stack(ant, 0)}
+
+    @torch.no_grad()
+    def forward_clips(self, rgb_list, flow_list=None, want_probs=True, want_argmax=True, want_ant=False):
+        """Ragged batched inference.  want_ant=False: as MROAD.forward_clips (outs, argmax, None).  want_ant=True: (outs [T_i, C],
+        argmax [T_i], None, anticipation probabilities [T_i, L, C], anticipation argmax int32 [T_i, L] (with want_argmax))."""
+        return self.engine().forward_ragged(rgb_list, flow_list, softmax=True, want_out=want_probs, want_argmax=want_argmax,
+                                            want_ant=want_ant)
+
+    link_fed_eval = False
+
+    def step(self, rgb, flow, h):
+        raise PregoError("MiniROADA streaming (step) is not built yet in prego_amd: use forward_clips with h0 / h_last chaining")

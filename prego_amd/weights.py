@@ -99,6 +99,22 @@ def miniroad_state_dict(cfg: dict, seed: int = 20, head_gain: float = 1.0) -> di
     return sd
 
 
+def miniroad_a_state_dict(cfg: dict, seed: int = 20, head_gain: float = 1.0, ant_gain: float = 1.0) -> dict:
+    """state_dict (numpy, fp32) of MROADA (model/rnn/rnn.py:73-110): MROAD's keys plus anticipation_layer.0.* [L*H, H] / [L*H]
+    and, with cfg['actionness'], f_actionness.0.* [1, H] / [1].  ant_gain scales anticipation_layer.0.weight: with random-init
+    weights A_l = relu(relu(h) W_a[l]^T + b_a[l]) is small and the anticipation softmaxes are flat, so argmax checks would be coin
+    tosses; together with head_gain (which scales f_classification, shared by both heads) it makes them as peaked as a trained model's."""
+    sd = miniroad_state_dict(cfg, seed, head_gain)
+    h, L = cfg["hidden_dim"], int(cfg["anticipation_length"])
+    bh = 1.0 / np.sqrt(h)
+    sd["anticipation_layer.0.weight"] = (ant_gain * uniform((L * h, h), -bh, bh, seed, "anticipation_layer.0.weight")).astype(np.float32)
+    sd["anticipation_layer.0.bias"] = uniform((L * h,), -bh, bh, seed, "anticipation_layer.0.bias")
+    if cfg.get("actionness", False):
+        sd["f_actionness.0.weight"] = uniform((1, h), -bh, bh, seed, "f_actionness.0.weight")
+        sd["f_actionness.0.bias"] = uniform((1,), -bh, bh, seed, "f_actionness.0.bias")
+    return sd
+
+
 def _lin(shape_out_in, seed, name):
     fan_in = shape_out_in[1]
     b = 1.0 / np.sqrt(fan_in)
