@@ -172,7 +172,10 @@ int prego_miniroad_set_anticipation(prego_miniroad* h, int ant_len, const float*
  *   ant_out[i]       device fp32 [lens[i], ant_len, n_classes]: per-step probabilities (PREGO_FWD_SOFTMAX, rnn.py:131-134) or logits; nullable
  *   ant_argmax[i]    device int32 [lens[i], ant_len]: argmax over classes per step, first max wins; nullable
  * The head never materialises the [frames, ant_len * hid] intermediate; its sums are in a fixed order (repeat calls are bit-identical, and
- * which pass ran changes no bit).  Inference only (PREGO_FWD_KEEP is refused); call set_anticipation first. */
+ * which pass ran changes no bit).  Call set_anticipation first.
+ * Training (PREGO_FWD_KEEP, bf16 / fp32 handles; fp16 / fp16x2 are refused, and so is PREGO_FWD_SOFTMAX with it): out and ant_out hold raw
+ * logits (rnn.py:128-130).  Nothing beyond the trunk's kept activations is kept (the backward recomputes A_l with the forward's bits for the
+ * rows that carry gradient), so workspace_bytes is the trunk's; the backward needs prego_miniroad_set_anticipation_grads. */
 int prego_miniroad_forward_anticipation(prego_miniroad* h, int n_clips, const int32_t* lens, const float* const* rgb,
                                         const float* const* flow, float* const* out, int32_t* const* argmax,
                                         float* const* ant_out, int32_t* const* ant_argmax, const float* h0, float* h_last,
@@ -257,6 +260,16 @@ int prego_miniroad_backward_callback(prego_miniroad* h, prego_bucket_fn fn, void
  * gru.weight_hh_l1 [3H, H], gru.bias_ih_l1 [3H], gru.bias_hh_l1 [3H] go (device fp32, OVERWRITTEN by every following
  * prego_miniroad_backward; layer 0's are that call's own arguments).  Required before the backward of a 2-layer handle. */
 int prego_miniroad_set_gru_layer_grads(prego_miniroad* h, int layer, float* g_w_ih, float* g_w_hh, float* g_b_ih, float* g_b_hh);
+/* MiniROADA under loss.backward() (ABI 7 addition): what the NEXT prego_miniroad_backward takes for the anticipation head, after a
+ * prego_miniroad_forward_anticipation with PREGO_FWD_KEEP (required then: that backward is refused without it; one backward only).
+ *   d_ant[i]      device fp32 [lens[i], ant_len, n_classes]: the gradient of that forward's ant_out[i]; d_ant == NULL = zero gradient:
+ *                 nothing of the head's backward runs, g_w_a / g_b_a are written as zeros and every other gradient is bit-identical to
+ *                 MiniROAD's backward for the same dlogits
+ *   g_w_a, g_b_a  device fp32 anticipation_layer.0.weight [ant_len * hid, hid] / .bias [ant_len * hid] gradients, OVERWRITTEN
+ * The head's terms are added to g_fc_w / g_fc_b and to d relu(h) before the BPTT; g_w_a / g_b_a are final at the f_classification event
+ * and callback (bucket 0).  The head's products touch only the span of packed rows that hold a non-zero d_ant value, found on the
+ * device (no host wait); the backward workspace of a handle with set_anticipation holds the whole-range worst case. */
+int prego_miniroad_set_anticipation_grads(prego_miniroad* h, const float* const* d_ant, float* g_w_a, float* g_b_a);
 size_t prego_miniroad_backward_workspace_bytes(const prego_miniroad* h, int n_clips, const int32_t* lens);
 int prego_miniroad_backward(prego_miniroad* h, int n_clips, const int32_t* lens, const float* const* dlogits,
                             float* g_layer1_w, float* g_layer1_b, float* g_ln_w, float* g_ln_b, float* g_w_ih,
@@ -323,6 +336,12 @@ int prego_miniroad_adamw_step(prego_miniroad* h, float* const* params, const flo
  *   set_peer_guard: the address of that element (after the reduction it is non-zero iff ANY rank gave up), NULL = none.  While it
  *                  holds a non-zero value prego_miniroad_adamw_step changes nothing AND raises this handle's own timeout word, so the
  *                  following steps are skipped as well and prego_miniroad_check reports PREGO_ETIMEOUT on every rank at the same step. */
+/* prego_miniroad_adamw_step for MiniROADA's anticipation_layer.0.{weight, bias} (params[0] [ant_len * hid, hid], params[1] [ant_len * hid];
+ * grads / exp_avg / exp_avg_sq likewise), rewriting the handle's anticipation operand copies in the same pass (ABI 7 addition).  Guarded on
+ * the device by the same timeout word and peer guard: whenever prego_miniroad_adamw_step changes nothing, neither does this one. */
+int prego_miniroad_adamw_step_anticipation(prego_miniroad* h, float* const* params, const float* const* grads, float* const* exp_avg,
+                                           float* const* exp_avg_sq, int64_t step, float lr, float beta1, float beta2, float eps,
+                                           float weight_decay, prego_stream_t stream);
 int prego_miniroad_guard_publish(prego_miniroad* h, float* dst, prego_stream_t stream);
 int prego_miniroad_set_peer_guard(prego_miniroad* h, const float* reduced_word);
 

@@ -46,6 +46,9 @@ int prego_debug_set_abort(prego_miniroad* h, unsigned value, prego_stream_t stre
  * this process (prego_miniroad_check's own synchronisation counts).  A test calls it around a hot call to hold "forward() allocates
  * nothing and waits for nothing" to zero (include/prego_amd.h, conventions). */
 int prego_debug_alloc_count(int64_t* device_mallocs, int64_t* host_waits);
+/* A/B switch: on != 0 makes every following MiniROADA backward of this library run the anticipation head's backward over every packed row
+ * instead of the device-side span of rows with gradient (prego_miniroad_set_anticipation_grads).  Process-wide. */
+int prego_debug_ant_full_span(int on);
 /* probe: a synthetic neighbour on XCDs >= xcd_lo for `ms` milliseconds - kind 1: back-to-back MFMAs on registers, no
  * memory traffic; kind 2: streaming reads of read_buf (+ one write per eight reads into write_buf), no matrix work; kind 3: both.
  * Launched on its own stream beside a replayed recurrence launch (prego_debug_split_fault mode 4) it separates what that launch loses to

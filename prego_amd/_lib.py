@@ -39,11 +39,13 @@ SYMBOLS = [
     "prego_miniroad_resident_bytes", "prego_miniroad_set_resident", "prego_miniroad_guard_publish", "prego_miniroad_set_peer_guard",
     "prego_miniroad_set_gru_layer_grads",
     "prego_miniroad_set_anticipation", "prego_miniroad_forward_anticipation",
+    "prego_miniroad_set_anticipation_grads", "prego_miniroad_adamw_step_anticipation",
 ]
 # include/prego_amd_debug.h: only in libprego_amd_debug.so
 DEBUG_SYMBOLS = ["prego_miniroad_debug_stamps", "prego_debug_gemm_bf16", "prego_debug_attention_bwd", "prego_debug_attention_fwd",
                  "prego_debug_recurrence_only", "prego_debug_gemm_worker", "prego_debug_head_only",
-                 "prego_debug_split_fault", "prego_debug_split_state", "prego_debug_set_abort", "prego_debug_alloc_count", "prego_debug_hog"]
+                 "prego_debug_split_fault", "prego_debug_split_state", "prego_debug_set_abort", "prego_debug_alloc_count", "prego_debug_hog",
+                 "prego_debug_ant_full_span"]
 
 
 class PregoError(RuntimeError):
@@ -87,6 +89,7 @@ def _open(path: str, debug: bool) -> C.CDLL:
     lib.prego_miniroad_set_anticipation.argtypes = [vp, i32, vp, vp, vp]
     lib.prego_miniroad_forward_anticipation.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(vp),
                                                         C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, i32, vp, sz, vp]
+    lib.prego_miniroad_set_anticipation_grads.argtypes = [vp, C.POINTER(vp), vp, vp]
     lib.prego_miniroad_step.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp]
     lib.prego_miniroad_check.argtypes = [vp, vp]
     lib.prego_miniroad_timing_enable.argtypes = [vp, i32]
@@ -116,6 +119,7 @@ def _open(path: str, debug: bool) -> C.CDLL:
     f32 = C.c_float
     lib.prego_adamw_step.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), i64, f32, f32, f32, f32, f32, vp]
     lib.prego_miniroad_adamw_step.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i64, f32, f32, f32, f32, f32, vp]
+    lib.prego_miniroad_adamw_step_anticipation.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i64, f32, f32, f32, f32, f32, vp]
     lib.prego_vit_adamw_step.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32, i64, f32, f32, f32, f32, f32, vp]
     lib.prego_vit_create.argtypes = [C.POINTER(vp)] + [i32] * 8
     lib.prego_vit_destroy.argtypes = [vp]
@@ -165,6 +169,7 @@ def _open(path: str, debug: bool) -> C.CDLL:
         lib.prego_debug_set_abort.argtypes = [vp, C.c_uint32, vp]
         lib.prego_debug_alloc_count.argtypes = [C.POINTER(i64), C.POINTER(i64)]
         lib.prego_debug_hog.argtypes = [i32, i32, i32, vp, vp, sz, vp, vp]
+        lib.prego_debug_ant_full_span.argtypes = [i32]
     return lib
 
 

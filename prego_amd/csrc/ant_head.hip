@@ -12,6 +12,7 @@
 // row's result does not depend on where in the call it sits (the chunked pass and the split pass give the same bits).
 // Traffic: W_a block nb of step l is read by every resident workgroup at about the same time (one L2 copy per XCD),
 // the relu(h) tile of a workgroup is re-read once per (l, nb) block.
+#include <type_traits>
 #include "common.h"
 #include "kernels.h"
 
@@ -46,7 +47,10 @@ __device__ __forceinline__ f32x4 mma(const typename AntOps<WT>::vec& a, const ty
 }
 }  // namespace
 
-template <typename WT, int NTC, int NB>
+// STORE_A (training backward, ant_head_bwd.hip): the first product only, for the 128-row blocks that meet the device-side packed-row span
+// [span[0], span[1]): A_l of those rows goes to a_out [rows][L * HID] in the operand type, with the bits of the forward (same k order,
+// same epilogue).  The inference instantiations (STORE_A = false) are unchanged.
+template <typename WT, int NTC, int NB, bool STORE_A = false>
 __global__ __launch_bounds__(256) void ant_head_kernel(
     const WT* __restrict__ Hrelu,      // [nrows][HID] chunk-relative packed rows
     const WT* __restrict__ Wa,         // [L*HID][HID]
@@ -56,7 +60,8 @@ __global__ __launch_bounds__(256) void ant_head_kernel(
     SlotPlan plan, int row0, int nrows, int HID, int L, int C, int apply_softmax,
     float* const* __restrict__ out_ptrs,     // per clip [T][L][C] fp32, entries nullable
     int* const* __restrict__ argmax_ptrs,    // per clip [T][L] int32, nullable array / entries
-    const int2* __restrict__ rowmap) {       // nullable: (clip, frame) of every row of this launch (chunk-relative index)
+    const int2* __restrict__ rowmap,         // nullable: (clip, frame) of every row of this launch (chunk-relative index)
+    WT* __restrict__ a_out = nullptr, const int* __restrict__ span = nullptr) {
   typedef AntOps<WT> O;
   typedef typename O::vec vec;
   constexpr int EPV = O::EPV;
@@ -77,9 +82,14 @@ __global__ __launch_bounds__(256) void ant_head_kernel(
   const int l15 = lane & 15, l4 = lane >> 4;
   const int wr = wave >> 1, wc = wave & 1;
   const int rbase = blockIdx.x * kRB;
+  int span_lo = 0, span_hi = 0;
+  if constexpr (STORE_A) {
+    span_lo = span[0]; span_hi = span[1];
+    if (rbase >= span_hi || rbase + kRB <= span_lo) return;      // the whole workgroup: no barrier has been reached
+  }
 
   // ---- destinations of the workgroup's rows: one lookup per row, once
-  if (tid < kRB) {
+  if (!STORE_A && tid < kRB) {
     int r = rbase + tid;
     const bool live = r < nrows;
     if (!live) r = nrows - 1;
@@ -123,15 +133,19 @@ __global__ __launch_bounds__(256) void ant_head_kernel(
     a_src[i] = Hrelu + (size_t)r * HID + a_part[i] * EPV;
   }
   const int nk = HID / BK, nnb = HID / NB;
+  // STORE_A: one (step l, column block nb) per workgroup (grid.y, grid.z) - the span is a few row blocks, the steps and blocks give the
+  // launch its width; the inference kernel walks every (l, nb) itself
+  const int l_lo = STORE_A ? (int)blockIdx.y : 0, l_hi = STORE_A ? (int)blockIdx.y + 1 : L;
+  const int nb_lo = STORE_A ? (int)blockIdx.z : 0, nb_hi = STORE_A ? (int)blockIdx.z + 1 : nnb;
 
-  for (int l = 0; l < L; ++l) {
+  for (int l = l_lo; l < l_hi; ++l) {
     f32x4 acc2[2][NTC];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int j = 0; j < NTC; ++j) acc2[t][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    for (int nb = 0; nb < nnb; ++nb) {
+    for (int nb = nb_lo; nb < nb_hi; ++nb) {
       const int col0 = l * HID + nb * NB;             // first W_a row of this block
       const WT* b_src[BCH];
 #pragma unroll
@@ -184,6 +198,27 @@ __global__ __launch_bounds__(256) void ant_head_kernel(
         __syncthreads();
       }
       // epilogue of the block: bias, ReLU, operand type -> LDS.  Lane holds rows m*16 + l4*4 + e, columns j*16 + l15 of its tile
+      if constexpr (STORE_A) {
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+          const int cl = wc * (NB / 2) + j * 16 + l15;
+          const float bias = ba[col0 + cl];
+#pragma unroll
+          for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              float v = acc1[m][j][e] + bias;
+              v = v > 0.f ? v : 0.f;
+              const int r = rbase + wr * 64 + m * 16 + l4 * 4 + e;
+              if (r >= span_lo && r < span_hi && r < nrows) {
+                WT* dst = a_out + (size_t)r * L * HID + col0 + cl;
+                if constexpr (ES == 4) *dst = v;
+                else *(unsigned short*)dst = to_op<WT>(v);
+              }
+            }
+        }
+        continue;                                       // no second product: the next block's K loop starts with its own barriers
+      }
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
         const int cl = wc * (NB / 2) + j * 16 + l15;
@@ -216,6 +251,7 @@ __global__ __launch_bounds__(256) void ant_head_kernel(
       // (the next block's first LDS write of sA is behind at least two barriers of its K loop)
     }
 
+    if constexpr (STORE_A) continue;
     // step l done: softmax / argmax of each row's logits_l, rows 32 wave + 16 t + 4 l4 + e, classes 16 j + l15
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -301,4 +337,27 @@ int launch_ant_head(bool bf16, bool f16, const void* Hrelu, const void* Wa, cons
   }
 #undef AD
 #undef AL
+}
+
+// A_l = relu(relu(h) W_a[l]^T + b_a[l]) in the operand type for the packed rows [span[0], span[1]) of [0, nrows) (device-side span), into
+// a_out [nrows][L * hid]: the forward's first product and epilogue, bit for bit (ant_head_kernel<..., STORE_A>)
+int launch_ant_head_store_a(bool bf16, const void* Hrelu, const void* Wa, const float* ba, int nrows, int hid, int L, void* a_out,
+                            const int* span, hipStream_t s) {
+  if (nrows <= 0) return 0;
+  if (L < 1 || L > 32 || hid % 256 != 0) return -1;
+  auto go = [&](auto tag, auto nbc) {
+    typedef decltype(tag) WT;
+    constexpr int NB = decltype(nbc)::value;
+    constexpr int ES = sizeof(WT);
+    // the two staging buffers only: STORE_A never touches the A_l block or the destination tables behind them (61 KB on bf16: two
+    // workgroups per CU instead of one)
+    const size_t lds = (size_t)(2 * kRB * (kStageLd * 2 / ES) + 2 * NB * (kStageLd * 2 / ES)) * ES;
+    static DeviceOnce once;
+    once.run([&] { (void)hipFuncSetAttribute((const void*)ant_head_kernel<WT, 1, NB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
+    const SlotPlan plan{};
+    ant_head_kernel<WT, 1, NB, true><<<dim3((nrows + kRB - 1) / kRB, L, hid / NB), 256, lds, s>>>((const WT*)Hrelu, (const WT*)Wa, ba, nullptr, nullptr, plan, 0,
+                                                                                nrows, hid, L, 1, 0, nullptr, nullptr, nullptr, (WT*)a_out, span);
+    return 0;
+  };
+  return bf16 ? go(bf16_t{}, std::integral_constant<int, 256>{}) : go(float{}, std::integral_constant<int, 128>{});
 }

@@ -227,6 +227,16 @@ int launch_head_softmax(bool bf16, const void* Hrelu, const void* Wc, const floa
 int launch_ant_head(bool bf16, bool f16, const void* Hrelu, const void* Wa, const float* ba, const void* Wc, const float* bc,
                     const SlotPlan& plan, int row0, int nrows, int hid, int L, int C, int apply_softmax, float* const* out_ptrs,
                     int* const* argmax_ptrs, const void* rowmap, hipStream_t s);
+// training (ant_head.hip): A_l of the packed rows [span[0], span[1]) (device-side span) into a_out [nrows][L * hid], operand type, the forward's bits
+int launch_ant_head_store_a(bool bf16, const void* Hrelu, const void* Wa, const float* ba, int nrows, int hid, int L, void* a_out,
+                            const int* span, hipStream_t s);
+// the anticipation head's backward (ant_head_bwd.hip): d_ant -> packed G [R][L * C] + row flags + the device-side row span, then the
+// gradient terms of f_classification, anticipation_layer and d relu(h) over that span
+void launch_ant_gather(const float* const* d_ant, const int* rowoff, const int* sorted_clip, int t_max, int nrows, int LC, float* G, int* flags,
+                       int* span, int force_full, hipStream_t s);
+void launch_ant_head_wgrad(bool bf16, const float* G, const void* HR, const void* Wc, int R, int H, int L, int C, const int* span,
+                           const void* Abuf, void* dZ, float* g_fc_w, float* g_fc_b, float* g_w_a, float* g_b_a, hipStream_t s);
+void launch_ant_head_dgrad(bool bf16, const void* Wa, int R, int H, int L, const int* span, const void* dZ, float* part, float* dHR, hipStream_t s);
 void launch_permute_rows(const float* src, float* dst, const int* sorted_clip, int n, int width, int to_sorted,
                          hipStream_t s);
 void launch_add_vec(const float* a, const float* b, float* out, int n, int n_add, hipStream_t s);

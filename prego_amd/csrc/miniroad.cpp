@@ -92,6 +92,10 @@ struct prego_miniroad {
   bool have_weights = false;
   // MiniROADA anticipation head (prego_miniroad_set_anticipation): anticipation_layer.0.weight [L*H][H] in the operand type, its bias fp32
   int ant_len = 0; void* w_a = nullptr; float* b_a = nullptr; size_t w_a_cap = 0;
+  // MiniROADA training: the last PREGO_FWD_KEEP forward was forward_anticipation's (its backward then needs set_anticipation_grads), and
+  // what prego_miniroad_set_anticipation_grads handed to the NEXT backward (d_ant NULL = zero anticipation gradient)
+  bool ant_kept = false; bool ant_grads_set = false;
+  std::vector<const float*> ant_d; float* ant_g_w = nullptr; float* ant_g_b = nullptr;
   // nn.GRU(embedding_dim, hidden_dim, num_layers) with num_layers == 2 (rnn.py:32,38): layer 1's operands (gru.*_l1; its input is layer 0's
   // h_t, so weight_ih_l1 is [3H][H]).  Inference only; hidden state [layers][slots][H]
   int layers = 1;
@@ -1275,6 +1279,7 @@ static int forward_impl(prego_miniroad* h, int n_clips, const int32_t* lens, con
     KN = (float*)carve((size_t)cap_rows * h->hid * 4); KG = (float*)carve((size_t)cap_rows * h->hid * 4);
     STATS = (float*)carve((size_t)cap_rows * 8);
     h->kept_kx = kx; h->kept_rows = total_rows;
+    h->ant_kept = ao.call;
   }
   // two-layer training: layer 0's h_t [rows][H] (operand type: layer 1's input, and the B operand of dW_ih_l1), layer 1's raw state and gates
   void* HR0 = nullptr; float* HRAW2 = nullptr; float* KR2 = nullptr; float* KZ2 = nullptr; float* KN2 = nullptr; float* KG2 = nullptr;
@@ -1542,7 +1547,10 @@ extern "C" int prego_miniroad_forward_anticipation(prego_miniroad* h, int n_clip
     HandleScope scope_(h);
     if (!h) return fail(PREGO_EINVAL, "handle is NULL");
     if (h->ant_len <= 0 || !h->w_a) return fail(PREGO_EINVAL, "forward_anticipation before set_anticipation");
-    if (flags & PREGO_FWD_KEEP) return fail(PREGO_EINVAL, "forward_anticipation: PREGO_FWD_KEEP (MiniROADA training) is not supported");
+    if ((flags & PREGO_FWD_KEEP) && (h->f16 || h->x2))
+      return fail(PREGO_EINVAL, "forward_anticipation: PREGO_FWD_KEEP (MiniROADA training) on an fp16 / fp16x2-operand handle: training runs on bf16 / fp32 handles");
+    if ((flags & PREGO_FWD_KEEP) && (flags & PREGO_FWD_SOFTMAX))
+      return fail(PREGO_EINVAL, "forward_anticipation: PREGO_FWD_KEEP returns raw logits (rnn.py:128-130): PREGO_FWD_SOFTMAX is not taken with it");
   }
   AntOut ao;
   ao.call = true; ao.out = ant_out; ao.arg = ant_argmax;
@@ -1814,6 +1822,7 @@ extern "C" int prego_oad_loss_reduce(int n_clips, const int32_t* lens, const flo
 struct BwdLayout {
   size_t total;
   size_t dLp, dLf, dLt, HRt, WcT, dWc, dHR, carry, dhpart, WhhT, dGI, dGH, dGIop, dGHop, part, T1, T2, WihT, dE, dY, dYb, Hprev, vec, bhx, bsync;
+  size_t aG, aFlags, aSpan, aA, aDZ, aPart;        // anticipation head (handles with set_anticipation only; 0 otherwise)
 };
 static BwdLayout bwd_layout(const prego_miniroad* h, int R, int n_clips) {
   const size_t es = h->bf16 ? 2 : 4;
@@ -1838,6 +1847,14 @@ static BwdLayout bwd_layout(const prego_miniroad* h, int R, int n_clips) {
   L.Hprev = put((size_t)R * H * es);
   L.vec = put(4 * E * 4);
   L.bhx = put(gru_bptt_hx_bytes(h->bf16, h->hid, h->G)); L.bsync = put(1024 * 4);     // persistent BPTT: exchange buffers, step counters
+  if (h->ant_len > 0) {
+    // MiniROADA: packed anticipation gradient G [R][L C] fp32, row flags, the row span, A_l and dZ_l [R][L H] (operand type), and the L
+    // partial sums of d relu(h) [L][R][H].  Sized for the whole range: the span is known on the device only
+    const size_t Lh = h->ant_len;
+    L.aG = put((size_t)R * Lh * h->ncls * 4); L.aFlags = put((size_t)R * 4); L.aSpan = put(64);
+    L.aA = put((size_t)R * Lh * H * es); L.aDZ = put((size_t)R * Lh * H * es);
+    L.aPart = put(Lh > 1 ? Lh * R * H * 4 : 4);
+  }
   L.total = off;
   return L;
 }
@@ -1848,6 +1865,26 @@ extern "C" int prego_miniroad_set_gru_layer_grads(prego_miniroad* h, int layer, 
   if (layer != 1 || h->layers != 2) return fail(PREGO_EINVAL, "set_gru_layer_grads: layer %d of a %d-layer handle (layer 0's gradients are prego_miniroad_backward's own arguments)", layer, h->layers);
   if (!g_w_ih || !g_w_hh || !g_b_ih || !g_b_hh) return fail(PREGO_EINVAL, "set_gru_layer_grads: NULL tensor");
   h->g_l2[0] = g_w_ih; h->g_l2[1] = g_w_hh; h->g_l2[2] = g_b_ih; h->g_l2[3] = g_b_hh;
+  return PREGO_OK;
+}
+
+#ifdef PREGO_DEBUG_ABI
+static bool g_ant_full_span = false;     // prego_debug_ant_full_span: the head's backward runs over every packed row (A/B against the span)
+extern "C" int prego_debug_ant_full_span(int on) { g_ant_full_span = on != 0; return PREGO_OK; }
+#else
+static constexpr bool g_ant_full_span = false;
+#endif
+
+extern "C" int prego_miniroad_set_anticipation_grads(prego_miniroad* h, const float* const* d_ant, float* g_w_a, float* g_b_a) {
+  HandleScope scope_(h);
+  if (!h) return fail(PREGO_EINVAL, "handle is NULL");
+  if (h->ant_len <= 0) return fail(PREGO_EINVAL, "set_anticipation_grads before set_anticipation");
+  if (!g_w_a || !g_b_a) return fail(PREGO_EINVAL, "set_anticipation_grads: NULL gradient tensor");
+  if (!h->ant_kept || h->kept_rows == 0)
+    return fail(PREGO_EINVAL, "set_anticipation_grads must follow a forward_anticipation with PREGO_FWD_KEEP");
+  h->ant_d.clear();
+  if (d_ant) h->ant_d.assign(d_ant, d_ant + h->plan_lens.size());
+  h->ant_g_w = g_w_a; h->ant_g_b = g_b_a; h->ant_grads_set = true;
   return PREGO_OK;
 }
 
@@ -1922,6 +1959,12 @@ extern "C" int prego_miniroad_backward(prego_miniroad* h, int n_clips, const int
     KR2 = (float*)carve((size_t)cap_rows * H * 4); KZ2 = (float*)carve((size_t)cap_rows * H * 4);
     KN2 = (float*)carve((size_t)cap_rows * H * 4); KG2 = (float*)carve((size_t)cap_rows * H * 4);
   }
+  if (h->ant_kept && !h->ant_grads_set)
+    return fail(PREGO_EINVAL, "backward after a MiniROADA training forward (forward_anticipation, PREGO_FWD_KEEP) needs "
+                              "prego_miniroad_set_anticipation_grads first");
+  const bool ant = h->ant_kept;                       // the head's terms join this backward
+  const bool ant_dense = ant && !h->ant_d.empty();    // ... with a non-zero anticipation gradient
+  struct AntConsume { prego_miniroad* h; ~AntConsume() { h->ant_grads_set = false; h->ant_d.clear(); } } ant_consume{h};   // one call only
   const BwdLayout L = bwd_layout(h, R, n_clips);
   if (bwd_bytes < L.total) return fail(PREGO_EWORKSPACE, "backward workspace %zu < %zu", bwd_bytes, L.total);
   char* bw = (char*)bwd_workspace;
@@ -1929,8 +1972,12 @@ extern "C" int prego_miniroad_backward(prego_miniroad* h, int n_clips, const int
 
   // dlogits pointer table
   const int MC = max_clips_of(h);
-  std::vector<const void*> tab((size_t)MC, nullptr);
+  std::vector<const void*> tab((size_t)(ant_dense ? 2 : 1) * MC, nullptr);
   for (int i = 0; i < n_clips; ++i) { if (!dlogits[i]) return fail(PREGO_EINVAL, "dlogits[%d] is NULL", i); tab[i] = dlogits[i]; }
+  for (int i = 0; ant_dense && i < n_clips; ++i) {
+    if (!h->ant_d[i]) return fail(PREGO_EINVAL, "d_ant[%d] is NULL", i);
+    tab[MC + i] = h->ant_d[i];
+  }
   { const int rc = stage_tables(h, tab.data(), tab.size(), s); if (rc) return rc; }
   const float* const* d_dl = (const float* const*)h->d_ptrs;
 
@@ -1953,7 +2000,22 @@ extern "C" int prego_miniroad_backward(prego_miniroad* h, int n_clips, const int
     gemm_nt(h, bw + L.dLt, Rp, bw + L.HRt, Rp, nullptr, (float*)(bw + L.dWc), H, Cp, H, Rp, s);   // dWc[Cp][H]
     HIPCHK(hipMemcpyAsync(g_fc_w, bw + L.dWc, (size_t)C * H * 4, hipMemcpyDeviceToDevice, s));
   }
-  if (h->bwd_ev[0]) HIPCHK(hipEventRecord(h->bwd_ev[0], s));            // f_classification gradients are final
+  // ---- MiniROADA's anticipation head (ant_head_bwd.hip): its f_classification terms join the trunk's above, anticipation_layer's
+  // gradients are written whole, d relu(h) gets its share below; every product touches only the device-side span of rows with gradient
+  const int* a_span = (const int*)(bw + L.aSpan);
+  if (ant_dense) {
+    const int La = h->ant_len;
+    launch_ant_gather((const float* const*)(h->d_ptrs + MC), h->d_rowoff, h->d_sorted, h->t_max, R, La * C, (float*)(bw + L.aG),
+                      (int*)(bw + L.aFlags), (int*)(bw + L.aSpan), g_ant_full_span ? 1 : 0, s);
+    if (launch_ant_head_store_a(bf, HR, h->w_a, h->b_a, R, H, La, bw + L.aA, a_span, s))
+      return fail(PREGO_EINVAL, "backward: anticipation head shape (hid %d, L %d)", H, La);
+    launch_ant_head_wgrad(bf, (const float*)(bw + L.aG), HR, h->w_c, R, H, La, C, a_span, bw + L.aA, bw + L.aDZ, g_fc_w, g_fc_b,
+                          h->ant_g_w, h->ant_g_b, s);
+  } else if (ant) {                                  // zero anticipation gradient: nothing of the head's backward runs
+    HIPCHK(hipMemsetAsync(h->ant_g_w, 0, (size_t)h->ant_len * H * H * 4, s));
+    HIPCHK(hipMemsetAsync(h->ant_g_b, 0, (size_t)h->ant_len * H * 4, s));
+  }
+  if (h->bwd_ev[0]) HIPCHK(hipEventRecord(h->bwd_ev[0], s));            // f_classification (and anticipation_layer) gradients are final
   if (h->bwd_cb) h->bwd_cb(h->bwd_cb_user, 0);
   if (tn) {
     // d relu(h) [R][H] = dL [R][Cp] . Wc [ncls_pad][H]: the weight as it is stored ([K][N]); rows >= ncls_pad read as zeros
@@ -1963,6 +2025,8 @@ extern "C" int prego_miniroad_backward(prego_miniroad* h, int n_clips, const int
     launch_transpose_convert(bf, bf, h->w_c, h->ncls_pad, H, H, bw + L.WcT, Cp, s);        // [H][Cp] (rows >= ncls_pad zero)
     gemm_nt(h, bw + L.dLp, Cp, bw + L.WcT, Cp, nullptr, (float*)(bw + L.dHR), H, R, H, Cp, s);    // d relu(h)
   }
+  if (ant_dense)                                     // d relu(h) += sum_l dZ_l W_a[l] over the span's rows
+    launch_ant_head_dgrad(bf, h->w_a, R, H, h->ant_len, a_span, bw + L.aDZ, (float*)(bw + L.aPart), (float*)(bw + L.dHR), s);
   launch_relu_mask((const float*)(bw + L.dHR), h->layers == 2 ? HRAW2 : HRAW, (size_t)R * H, (float*)(bw + L.dHR), s);   // the head reads the LAST layer's relu(h)
 
   // ---- BPTT through the GRU (rnn.py:61), reverse time; a stacked GRU (num_layers 2, rnn.py:32,38) runs its layers last to first:
@@ -2207,6 +2271,29 @@ extern "C" int prego_miniroad_adamw_step(prego_miniroad* h, float* const* params
   launch_add_vec(params[6], params[7], h->bias2, (int)(3 * H), (int)(2 * H), s);      // r,z rows: b_ih + b_hh ; n rows: b_ih
   h->perm_stale = true;
   HIPCHK(hipMemcpyAsync(h->b_hn, params[7] + 2 * H, (size_t)H * 4, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+// The same step for MiniROADA's anticipation_layer.0.{weight, bias} (params[0] [L H, H], params[1] [L H]), rewriting the handle's W_a operand
+// copy and its bias in the same pass; guarded by the same timeout word and peer guard as prego_miniroad_adamw_step.
+extern "C" int prego_miniroad_adamw_step_anticipation(prego_miniroad* h, float* const* params, const float* const* grads, float* const* exp_avg,
+                                                      float* const* exp_avg_sq, int64_t step, float lr, float beta1, float beta2, float eps,
+                                                      float weight_decay, prego_stream_t stream) {
+  HandleScope scope_(h);
+  if (!h || !params || !grads || !exp_avg || !exp_avg_sq) return fail(PREGO_EINVAL, "adamw (anticipation): NULL argument");
+  if (h->ant_len <= 0 || !h->w_a) return fail(PREGO_EINVAL, "adamw (anticipation) before set_anticipation");
+  if (h->f16 || h->x2) return fail(PREGO_EINVAL, "adamw step on an fp16 / fp16x2-operand handle: training runs on bf16 / fp32 handles");
+  for (int i = 0; i < 2; ++i) if (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i]) return fail(PREGO_EINVAL, "adamw (anticipation): tensor %d is NULL", i);
+  hipStream_t s = (hipStream_t)stream;
+  const long long LH = (long long)h->ant_len * h->hid;
+  float* pw[1] = {params[0]}; const float* gw[1] = {grads[0]}; float* mw[1] = {exp_avg[0]}; float* vw[1] = {exp_avg_sq[0]};
+  void* cw[1] = {h->w_a}; const long long nw[1] = {LH * h->hid};
+  float* pb[1] = {params[1]}; const float* gb[1] = {grads[1]}; float* mb[1] = {exp_avg[1]}; float* vb[1] = {exp_avg_sq[1]};
+  void* cb[1] = {h->b_a}; const long long nb[1] = {LH};
+  if (launch_adamw(1, pw, gw, mw, vw, cw, nw, h->bf16, step, lr, beta1, beta2, eps, weight_decay, s, h->abort_word, h->peer_guard) ||
+      launch_adamw(1, pb, gb, mb, vb, cb, nb, false, step, lr, beta1, beta2, eps, weight_decay, s, h->abort_word, h->peer_guard))
+    return fail(PREGO_EINVAL, "adamw (anticipation): bad step %lld", (long long)step);
   HIPCHK(hipGetLastError());
   return PREGO_OK;
 }

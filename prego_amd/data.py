@@ -255,7 +255,12 @@ class AnticipationDataset(data.Dataset):
                 self.inputs.append([vid, 0, end, target[:end], ant])
 
     def __getitem__(self, index):
-        vid, start, end, target, ant_target = self.inputs[index]
+        # index >= len: a PAD entry of EpochWindowSampler (short last global batch of a data-parallel epoch) = window index - len with
+        # all-zero target and ant_target: zero loss and zero gradient under OadAntLoss (F.normalize of a zero row is zero)
+        pad = index >= len(self.inputs)
+        vid, start, end, target, ant_target = self.inputs[index - len(self.inputs) if pad else index]
+        if pad:
+            target, ant_target = np.zeros_like(target), np.zeros_like(ant_target)
         return (torch.from_numpy(np.ascontiguousarray(self.rgb_inputs[vid][start:end])),
                 torch.from_numpy(np.ascontiguousarray(self.flow_inputs[vid][start:end])),
                 torch.from_numpy(np.ascontiguousarray(target)), torch.from_numpy(ant_target.astype(np.float32)))

@@ -17,6 +17,7 @@ _PARAM_ORDER = [
     "f_classification.0.weight", "f_classification.0.bias",
 ]
 _L1_KEYS = ["gru.weight_ih_l1", "gru.weight_hh_l1", "gru.bias_ih_l1", "gru.bias_hh_l1"]       # nn.GRU(num_layers=2), rnn.py:32,38
+ANT_KEYS = ("anticipation_layer.0.weight", "anticipation_layer.0.bias")                      # MiniROADA's head (rnn.py:108-110)
 
 
 def param_order(num_layers: int = 1):
@@ -350,8 +351,11 @@ class MiniRoadEngine:
     def set_dropout(self, p: float, seed: int):
         check(self.lib.prego_miniroad_set_dropout(self.h, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF))
 
-    def forward_train(self, rgb: torch.Tensor, flow: Optional[torch.Tensor]) -> torch.Tensor:
-        """training-mode forward of a uniform batch [B,T,D]: raw logits [B,T,C]; keeps activations for backward()."""
+    def forward_train(self, rgb: torch.Tensor, flow: Optional[torch.Tensor], want_ant: bool = False):
+        """training-mode forward of a uniform batch [B,T,D]: raw logits [B,T,C]; keeps activations for backward().
+        want_ant (MiniROADA, after set_anticipation): returns (logits [B,T,C], raw anticipation logits [B,T,L,C])."""
+        if want_ant and not getattr(self, "ant_len", 0):
+            raise PregoError("forward_train(want_ant=True) before set_anticipation")
         d_rgb, d_flow, emb, hid, ncls = self.dims
         if d_rgb == 0:
             rgb = None
@@ -371,12 +375,22 @@ class MiniRoadEngine:
         rgb_p = None if rgb is None else ptr_array([rgb.data_ptr() + b * T * d_rgb * esz for b in range(B)])
         flow_p = None if flow is None else ptr_array([flow.data_ptr() + b * T * d_flow * esz for b in range(B)])
         out_p = ptr_array([out.data_ptr() + b * T * ncls * esz for b in range(B)])
+        ant = None
         with torch.cuda.device(self.device):
-            check(self.lib.prego_miniroad_forward(self.h, B, lens_arr, rgb_p, flow_p, out_p, None, None, None, flags,
-                                                  C.c_void_p(self._ws_train.data_ptr()), self._ws_train.numel(),
-                                                  C.c_void_p(_stream_ptr(self.device))))
+            if want_ant:
+                L = self.ant_len
+                ant = torch.empty((B, T, L, ncls), dtype=torch.float32, device=self.device)
+                ant_p = ptr_array([ant.data_ptr() + b * T * L * ncls * esz for b in range(B)])
+                check(self.lib.prego_miniroad_forward_anticipation(self.h, B, lens_arr, rgb_p, flow_p, out_p, None, ant_p, None, None, None,
+                                                                   flags, C.c_void_p(self._ws_train.data_ptr()), self._ws_train.numel(),
+                                                                   C.c_void_p(_stream_ptr(self.device))))
+            else:
+                check(self.lib.prego_miniroad_forward(self.h, B, lens_arr, rgb_p, flow_p, out_p, None, None, None, flags,
+                                                      C.c_void_p(self._ws_train.data_ptr()), self._ws_train.numel(),
+                                                      C.c_void_p(_stream_ptr(self.device))))
         self._train_ctx = (B, T, lens_arr, rgb, flow)
-        return out
+        self._train_ant = want_ant
+        return (out, ant) if want_ant else out
 
     _CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int)
 
@@ -398,11 +412,18 @@ class MiniRoadEngine:
         self._cb = self._CB(tramp)
         check(self.lib.prego_miniroad_backward_callback(self.h, self._cb, None))
 
-    def backward(self, dlogits: torch.Tensor) -> dict:
-        """gradients of the ten parameters (reference state_dict names) for the last forward_train()."""
+    def backward(self, dlogits: torch.Tensor, d_ant: Optional[torch.Tensor] = None) -> dict:
+        """gradients of the ten parameters (reference state_dict names) for the last forward_train().  After forward_train(want_ant=True)
+        (MiniROADA) also those of anticipation_layer.0.{weight, bias}, from d_ant [B,T,L,C] (None = zero anticipation gradient); they sit
+        in the first sub-bucket with f_classification."""
         d_rgb, d_flow, emb, hid, ncls = self.dims
         B, T, lens_arr, _, _ = self._train_ctx
+        ant = getattr(self, "_train_ant", False)
         dlogits = dlogits.to(torch.float32).contiguous()
+        if d_ant is not None:
+            if not ant:
+                raise PregoError("backward(d_ant): the last training forward had no anticipation head")
+            d_ant = d_ant.to(torch.float32).contiguous()
         need = self.lib.prego_miniroad_backward_workspace_bytes(self.h, B, lens_arr)
         if getattr(self, "_ws_bwd", None) is None or self._ws_bwd.numel() < need:
             self._ws_bwd = torch.empty(need, dtype=torch.uint8, device=self.device)
@@ -412,7 +433,9 @@ class MiniRoadEngine:
                   "f_classification.0.bias": (ncls,)}
         # one flat fp32 bucket (17.9 M elements = 71.7 MB), the ten gradients are views into it: data-parallel training
         # all-reduces the bucket in place (no gather / scatter copies around the collective)
-        order = param_order(self.num_layers)
+        order = param_order(self.num_layers) + (list(ANT_KEYS) if ant else [])
+        if ant:
+            shapes.update({ANT_KEYS[0]: (self.ant_len * hid, hid), ANT_KEYS[1]: (self.ant_len * hid,)})
         if self.num_layers == 2:
             shapes.update({"gru.weight_ih_l1": (3 * hid, hid), "gru.weight_hh_l1": (3 * hid, hid), "gru.bias_ih_l1": (3 * hid,), "gru.bias_hh_l1": (3 * hid,)})
         sizes = [int(torch.Size(shapes[k]).numel()) for k in order]
@@ -448,6 +471,10 @@ class MiniRoadEngine:
         with torch.cuda.device(self.device):
             if self.num_layers == 2:        # the second layer's gradients: handed over beside the call (ABI 7)
                 check(self.lib.prego_miniroad_set_gru_layer_grads(self.h, 1, *[C.c_void_p(grads[k].data_ptr()) for k in _L1_KEYS]))
+            if ant:                         # MiniROADA: the anticipation head's gradient and where its two gradients go
+                da_p = None if d_ant is None else ptr_array([d_ant.data_ptr() + b * T * self.ant_len * ncls * 4 for b in range(B)])
+                check(self.lib.prego_miniroad_set_anticipation_grads(self.h, da_p, C.c_void_p(grads[ANT_KEYS[0]].data_ptr()),
+                                                                     C.c_void_p(grads[ANT_KEYS[1]].data_ptr())))
             check(self.lib.prego_miniroad_backward(
                 self.h, B, lens_arr, dl_p, *[C.c_void_p(grads[k].data_ptr()) for k in _PARAM_ORDER],
                 C.c_void_p(self._ws_train.data_ptr()), self._ws_train.numel(),

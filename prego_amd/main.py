@@ -98,7 +98,10 @@ def main(argv=None):
     scaler = torch.amp.GradScaler("cuda") if args.amp else None          # main.py:75
     best_mAP, best_epoch = 0, 0
     for epoch in range(1, cfg["num_epoch"] + 1):
-        epoch_loss = train_one_epoch(trainloader, net, criterion, optimizer, scaler, epoch, device, None, scheduler=None)
+        if cfg["task"] == "ANTICIPATION":      # the reference passes `device` positionally into `writer` here (a TypeError): keywords
+            epoch_loss = train_one_epoch(trainloader, net, criterion, optimizer, scaler, epoch, writer=None, scheduler=None, device=device)
+        else:
+            epoch_loss = train_one_epoch(trainloader, net, criterion, optimizer, scaler, epoch, device, None, scheduler=None)
         trainloader.dataset._init_features()
         mAP = evaluate_fn(net, testloader, logger, device)
         if rank == 0 and mAP > best_mAP:

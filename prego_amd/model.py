@@ -138,8 +138,9 @@ class MROADA(MROAD):
     probabilities (rnn.py:131-134); the head is the fused kernel of csrc/ant_head.hip (the [frames, L * H] intermediate is never
     materialised).  Parameter containers are built in the reference's order (layer1, f_actionness when cfg['actionness'], gru,
     f_classification, anticipation_layer), so a given torch seed gives the reference's initial weights and state_dict keys match
-    (f_actionness.0.* included, which the reference builds but never uses in forward).  Training, `step` streaming and fp16x2 handles are
-    not built for this model."""
+    (f_actionness.0.* included, which the reference builds but never uses in forward).  Training mode returns both as raw logits
+    (rnn.py:128-130) through one autograd Function (csrc/ant_head_bwd.hip for the head's backward); f_actionness never gets a gradient.
+    `step` streaming and fp16x2 handles are not built for this model."""
 
     def __init__(self, cfg):
         nn.Module.__init__(self)
@@ -177,8 +178,7 @@ class MROADA(MROAD):
         self.grad_compress = None
         self._engines = {}
 
-    def _engine_dtype(self, train: bool) -> str:
-        return self.compute_dtype
+    # training follows MROAD's rule (fp16 trains on bf16, fp16x2 on fp32): MROAD._engine_dtype
 
     def _ingest(self, eng: MiniRoadEngine):
         eng.set_weights(dict(self.named_parameters()))
@@ -196,8 +196,12 @@ class MROADA(MROAD):
 
     def forward(self, rgb_input, flow_input):
         if self.training:
-            raise PregoError("MiniROADA training is not built yet in prego_amd (the anticipation head has an inference kernel only): "
-                             "call .eval() for inference")
+            src = rgb_input if self.use_rgb else flow_input
+            if not src.is_cuda:
+                raise PregoError("MiniROADA training is not built for CPU tensors: prego_amd has no CPU fallback")
+            from .autograd import miniroada_train_forward
+            logits, ant = miniroada_train_forward(self, rgb_input, flow_input)
+            return {"logits": logits, "anticipation_logits": ant}
         rgb, flow = self._inputs(rgb_input, flow_input)
         outs, _, _, ant, _ = self.engine().forward_ragged(rgb, flow, softmax=True, want_ant=True, want_ant_argmax=False)
         return {"logits": torch.stack(outs, 0), "anticipation_logits": torch.stack(ant, 0)}

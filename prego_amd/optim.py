@@ -12,7 +12,12 @@ import torch
 
 from . import _lib
 from ._lib import PregoError, check, ptr_array
-from .engine import _PARAM_ORDER, _stream_ptr
+from .engine import ANT_KEYS, _PARAM_ORDER, _stream_ptr
+
+
+def _fused_keys(model):
+    """the tensors the fused MiniROAD step updates: the ten of prego_miniroad_adamw_step, plus MiniROADA's anticipation_layer (its own launch)"""
+    return list(_PARAM_ORDER) + (list(ANT_KEYS) if hasattr(model, "anticipation_layer") else [])
 
 
 class FusedAdamW(torch.optim.Optimizer):
@@ -31,9 +36,13 @@ class FusedAdamW(torch.optim.Optimizer):
         if self._model is None or self._model is not model or len(self.param_groups) != 1:
             return False
         named = dict(model.named_parameters())
-        want = {id(named[k]) for k in _PARAM_ORDER if k in named}
-        have = {id(p) for p in self.param_groups[0]["params"]}
-        return len(want) == len(_PARAM_ORDER) and want == have and all(p.is_cuda for p in self.param_groups[0]["params"])
+        keys = _fused_keys(model)
+        want = {id(named[k]) for k in keys if k in named}
+        # MiniROADA's f_actionness (cfg['actionness']) is built but never used in forward (rnn.py:98-99): it never has a gradient, so
+        # every step skips it, as torch.optim.AdamW does
+        idle = {id(p) for k, p in named.items() if k.startswith("f_actionness.")}
+        have = {id(p) for p in self.param_groups[0]["params"]} - idle
+        return len(want) == len(keys) and want == have and all(p.is_cuda for p in self.param_groups[0]["params"])
 
     def _state(self, p):
         st = self.state[p]
@@ -70,7 +79,7 @@ class FusedAdamW(torch.optim.Optimizer):
             fused_model = False
             if m is not None:
                 named = dict(m.named_parameters())
-                want = [named[k] for k in _PARAM_ORDER]
+                want = [named[k] for k in _fused_keys(m)]
                 fused_model = len(ps) == len(want) and {id(p) for p in ps} == {id(p) for p in want}
                 if fused_model:             # the C ABI takes the ten tensors in prego_miniroad_set_weights' order
                     ps = want
@@ -101,10 +110,16 @@ class FusedAdamW(torch.optim.Optimizer):
                     self._vit._ver = tuple((p.data_ptr(), p._version) for p in sd.values())
                 elif fused_model:
                     eng = m.engine(train=True)        # weights already ingested (versions unchanged since the forward)
+                    n0 = len(_PARAM_ORDER)
                     check(lib.prego_miniroad_adamw_step(
-                        eng.h, ptr_array([p.data_ptr() for p in ps]), ptr_array([g.data_ptr() for g in grads]),
-                        ptr_array([st["exp_avg"].data_ptr() for st in states]), ptr_array([st["exp_avg_sq"].data_ptr() for st in states]),
-                        *hyper, C.c_void_p(_stream_ptr(dev))))
+                        eng.h, ptr_array([p.data_ptr() for p in ps[:n0]]), ptr_array([g.data_ptr() for g in grads[:n0]]),
+                        ptr_array([st["exp_avg"].data_ptr() for st in states[:n0]]),
+                        ptr_array([st["exp_avg_sq"].data_ptr() for st in states[:n0]]), *hyper, C.c_void_p(_stream_ptr(dev))))
+                    if len(ps) > n0:        # MiniROADA: anticipation_layer.0.{weight, bias}, same guard, W_a operand copy rewritten
+                        check(lib.prego_miniroad_adamw_step_anticipation(
+                            eng.h, ptr_array([p.data_ptr() for p in ps[n0:]]), ptr_array([g.data_ptr() for g in grads[n0:]]),
+                            ptr_array([st["exp_avg"].data_ptr() for st in states[n0:]]),
+                            ptr_array([st["exp_avg_sq"].data_ptr() for st in states[n0:]]), *hyper, C.c_void_p(_stream_ptr(dev))))
                     # the engine's operand copies are now those of the NEW values: bump the parameter versions (raw-pointer
                     # update) and record them as ingested, so model.engine() does not re-ingest
                     # the data-parallel peer guard (engine.backward) pointed into THIS step's gradient bucket: one step, one flag

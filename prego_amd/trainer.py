@@ -1,5 +1,6 @@
-"""`train_one_epoch` ("OAD") behind the reference's TRAINER registry (trainer/train.py:5-29): same signature and
-return value (sum of per-step losses).  `scheduler` is accepted and never stepped, as in the reference.
+"""`train_one_epoch` ("OAD") and `ant_train_one_epoch` ("ANTICIPATION") behind the reference's TRAINER registry (trainer/train.py:5-54):
+same signatures and return value (sum of per-step losses).  `scheduler` is accepted and never stepped, as in the reference.  One loop
+body serves both tasks; they differ in the batch layout and in how a data-parallel step is weighted.
 Data-parallel training: when torch.distributed is initialised, gradients are averaged with ONE all-reduce over a flat
 fp32 bucket per step (clip-sharded DP); with a single process this is the reference loop."""
 from __future__ import annotations
@@ -148,27 +149,27 @@ def _loss_host(dev, dtype):
     return ent[1]
 
 
-def _device_batches(trainloader, model, device):
+def _device_batches(trainloader, model, device, n_dev=3):
     """The loader's batches with rgb / flow / target on `device` (train.py:9: three `.to(device)` per step, in front of the step).
     On a GPU the copies of batch k + 1 are enqueued on a side stream BEFORE step k's kernels, from the loader's pinned tensors
     (`pin_memory=True`, data.build_data_loader), so they run under step k: a 16 x 128 x 4096 fp32 batch is 33.5 MB = 0.6 ms of link time
     per modality against a 1.2 ms step.  A model that is told the flow half is zero (`assume_zero_flow`, dataset.py:69) never reads
-    `flow_input`: it is not copied at all.  Same values, same order as the reference loop."""
+    `flow_input`: it is not copied at all.  Same values, same order as the reference loop.  n_dev: the leading tensors of a batch that
+    go to the device (3: OAD's rgb, flow, target; 4: the anticipation batch's ant_target as well)."""
     dev = torch.device(device)
     skip_flow = bool(getattr(model, "assume_zero_flow", False) and getattr(model, "use_rgb", True))
     if dev.type != "cuda" or not PREFETCH:
-        for rgb, flow, target, vid, start, end in trainloader:
-            yield rgb.to(device), (flow if skip_flow else flow.to(device)), target.to(device), vid, start, end
+        for batch in trainloader:
+            yield tuple(t if (i == 1 and skip_flow) else t.to(device) for i, t in enumerate(batch[:n_dev])) + tuple(batch[n_dev:])
         return
     side = _side_stream(dev)
 
     def move(batch):
-        rgb, flow, target, vid, start, end = batch
         with torch.cuda.stream(side):
-            moved = (rgb.to(dev, non_blocking=True), flow if skip_flow else flow.to(dev, non_blocking=True), target.to(dev, non_blocking=True))
+            moved = tuple(t if (i == 1 and skip_flow) else t.to(dev, non_blocking=True) for i, t in enumerate(batch[:n_dev]))
             ev = torch.cuda.Event()
             ev.record(side)
-        return moved + (vid, start, end), ev, batch          # `batch`: the pinned sources stay alive until their copies are done
+        return moved + tuple(batch[n_dev:]), ev, batch          # `batch`: the pinned sources stay alive until their copies are done
 
     it = iter(trainloader)
     nxt = None
@@ -179,7 +180,7 @@ def _device_batches(trainloader, model, device):
         cur, ev, _src = nxt
         main = torch.cuda.current_stream(dev)
         main.wait_event(ev)
-        for t in cur[:3]:
+        for t in cur[:n_dev]:
             if t.is_cuda:
                 t.record_stream(main)             # allocated on the side stream, read by this step's kernels
         nxt = None
@@ -193,17 +194,19 @@ CHECK_EVERY = 32       # guarded loop: steps between two timeout checks (each on
 GUARDED_LOOP = True     # False: always the per-step check + loss.item() loop (tests compare the two)
 
 
-def _guarded_epoch(trainloader, model, criterion, optimizer, device, step_weight):
+def _guarded_epoch(trainloader, model, criterion, optimizer, device, step_weight, n_dev=3, grad_weight=None):
     losses, weights, n = None, [], 0
-    for it, (rgb_input, flow_input, target, vid, start, end) in enumerate(_device_batches(trainloader, model, device)):
+    for it, batch in enumerate(_device_batches(trainloader, model, device, n_dev)):
+        rgb_input, flow_input = batch[0], batch[1]
         w = float(step_weight(it)) if step_weight is not None else 1.0
+        gw = w if grad_weight is None else grad_weight
         model.train()
         out_dict = model(rgb_input, flow_input)
-        loss = criterion(out_dict, target)
+        loss = criterion(out_dict, *batch[2:n_dev])
         optimizer.zero_grad(set_to_none=True)
-        _arm_early_allreduce(model, w)
+        _arm_early_allreduce(model, gw)
         loss.backward()
-        _allreduce_grads(model, w)
+        _allreduce_grads(model, gw)
         optimizer.step()                   # a no-op on the device if this step's recurrence / BPTT gave up
         if losses is None or n == losses.numel():
             grown = torch.empty(max(1024, 2 * n), dtype=loss.dtype, device=loss.device)
@@ -225,11 +228,41 @@ def _guarded_epoch(trainloader, model, criterion, optimizer, device, step_weight
 
 @TRAINER.register("OAD")
 def train_one_epoch(trainloader, model, criterion, optimizer, scaler, epoch, device, writer=None, scheduler=None):
-    epoch_loss = 0
     sampler = getattr(trainloader, "sampler", None)
     if hasattr(sampler, "set_epoch"):          # data-parallel runs: a different permutation every epoch
         sampler.set_epoch(epoch)
     step_weight = getattr(sampler, "step_weight", None)       # data.EpochWindowSampler: global batch / real windows of a step (1.0 but for a short last batch)
+    return _epoch(trainloader, model, criterion, optimizer, scaler, epoch, device, writer, step_weight)
+
+
+@TRAINER.register("ANTICIPATION")
+def ant_train_one_epoch(trainloader, model, criterion, optimizer, scaler, epoch, writer=None, scheduler=None, *, device=None):
+    """trainer/train.py:31-54: batches (rgb, flow, target, ant_target), loss = criterion(out, target, ant_target).  The reference moves them
+    with `.cuda()`; here `device` (default: the model's).  Data-parallel steps follow criterion.reduction: OadAntLoss's default 'sum'
+    makes the single-process step the gradient of the SUM over the global batch, so the all-reduced mean is scaled by the world size (PAD
+    windows of EpochWindowSampler carry all-zero targets: zero loss, zero gradient), and the returned epoch loss is the global sum (one
+    scalar all-reduce per epoch).  'mean', or a criterion without a `reduction` attribute, keeps OAD's step weight."""
+    if device is None:
+        device = next(model.parameters()).device
+    sampler = getattr(trainloader, "sampler", None)
+    if hasattr(sampler, "set_epoch"):
+        sampler.set_epoch(epoch)
+    world, force = _dp_state()
+    if getattr(criterion, "reduction", None) == "sum":      # no `reduction` attribute: OAD's step weight, as for 'mean'
+        loss_sum = _epoch(trainloader, model, criterion, optimizer, scaler, epoch, device, writer, None, n_dev=4, grad_weight=float(world))
+        if world > 1 or force:
+            t = torch.tensor([loss_sum], dtype=torch.float64,
+                             device=device if dist.get_backend() == "nccl" else "cpu")
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            loss_sum = float(t.item())
+        return loss_sum
+    return _epoch(trainloader, model, criterion, optimizer, scaler, epoch, device, writer, getattr(sampler, "step_weight", None), n_dev=4)
+
+
+def _epoch(trainloader, model, criterion, optimizer, scaler, epoch, device, writer, step_weight, n_dev=3, grad_weight=None):
+    """the loop body of both trainers: n_dev leading batch tensors go to the device, criterion(out, *batch[2:n_dev]); a step's gradient is
+    weighted by grad_weight (None: the step weight, which also weights the logged loss)"""
+    epoch_loss = 0
     # A FusedAdamW bound to this model steps through prego_miniroad_adamw_step, which the DEVICE skips while the engine's timeout word is
     # set: nothing has to be checked on the host in front of optimizer.step().  The loop then runs without a synchronisation per step -
     # the per-step losses go to a device buffer and are summed at the end exactly as train.py:26 sums them (fp64, in step order), the
@@ -241,9 +274,11 @@ def train_one_epoch(trainloader, model, criterion, optimizer, scaler, epoch, dev
                     # the `Transformer` entry (ViTEnc) has no persistent kernel that could give up: nothing to check, any optimizer
                     or (hasattr(model, "pre_head_ln") and getattr(model, "_engine", None) is None)))
     if guarded:
-        return _guarded_epoch(trainloader, model, criterion, optimizer, device, step_weight)
-    for it, (rgb_input, flow_input, target, vid, start, end) in enumerate(_device_batches(trainloader, model, device)):
+        return _guarded_epoch(trainloader, model, criterion, optimizer, device, step_weight, n_dev, grad_weight)
+    for it, batch in enumerate(_device_batches(trainloader, model, device, n_dev)):
+        rgb_input, flow_input, targets = batch[0], batch[1], batch[2:n_dev]
         w = float(step_weight(it)) if step_weight is not None else 1.0
+        gw = w if grad_weight is None else grad_weight
         loss_value = None
         model.train()
         if scaler is not None:
@@ -252,21 +287,21 @@ def train_one_epoch(trainloader, model, criterion, optimizer, scaler, epoch, dev
             # this hardware route, and bf16's exponent range makes the scale harmless), unscale + inf check + step by GradScaler
             with torch.autocast(device_type="cuda", enabled=torch.cuda.is_available()):
                 out_dict = model(rgb_input, flow_input)
-                loss = criterion(out_dict, target)
+                loss = criterion(out_dict, *targets)
             optimizer.zero_grad(set_to_none=True)
-            _arm_early_allreduce(model, w)
+            _arm_early_allreduce(model, gw)
             scaler.scale(loss).backward()
-            _allreduce_grads(model, w)         # enqueued behind the backward's events, BEFORE the host waits for anything
+            _allreduce_grads(model, gw)        # enqueued behind the backward's events, BEFORE the host waits for anything
             _check_engine(model)               # synchronises; only gates optimizer.step()
             scaler.step(optimizer)
             scaler.update()
         else:
             out_dict = model(rgb_input, flow_input)
-            loss = criterion(out_dict, target)
+            loss = criterion(out_dict, *targets)
             optimizer.zero_grad(set_to_none=True)
-            _arm_early_allreduce(model, w)
+            _arm_early_allreduce(model, gw)
             loss.backward()
-            _allreduce_grads(model, w)         # enqueued behind the backward's events, BEFORE the host waits for anything
+            _allreduce_grads(model, gw)        # enqueued behind the backward's events, BEFORE the host waits for anything
             # train.py:26's loss.item(): the value travels to pinned host memory in front of the check's synchronisation and is read
             # behind it - optimizer.step() is then enqueued with nothing waiting for it, and the host walks into the next step while the
             # AdamW kernel runs (a second synchronisation behind optimizer.step() cost its launch + 0.09 ms of idle host per step)

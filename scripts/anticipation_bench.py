@@ -4,6 +4,13 @@ MROADA and MROAD frames/s, the anticipation head's own time (MROADA pass - MROAD
 2.5 PFLOP/s dense bf16 spec, and which pass ran.
 
     python scripts/anticipation_bench.py [--dtype bf16] [--steps 3] [--warmup 1] [--clips N]
+
+--train: the training step instead (B 16, T 128, zero flow, FusedAdamW, the guarded loop's body: forward, OadAntLoss, backward, step) for
+MiniROADA at L = 1 / 4 / 8 and MiniROAD's step in the same process, in alternating rounds; median step time from device events after
+warm-up.  With PREGO_AMD_DEBUG_LIB=1 MiniROADA also runs with the head's backward forced over every packed row (prego_debug_ant_full_span)
+for the span / full-range A/B.
+
+    PREGO_AMD_DEBUG_LIB=1 python scripts/anticipation_bench.py --train [--steps 200] [--warmup 20] [--rounds 4]
 """
 from __future__ import annotations
 
@@ -13,6 +20,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -30,10 +38,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--warmup", type=int, default=None, help="default: 1 inference pass, 20 training steps per configuration (--train)")
     ap.add_argument("--clips", type=int, default=0, help="first N clips of the workload (0 = all)")
     ap.add_argument("--L", type=int, default=8)
+    ap.add_argument("--train", action="store_true")
+    ap.add_argument("--rounds", type=int, default=4)
     a = ap.parse_args()
+    if a.warmup is None:
+        a.warmup = 20 if a.train else 1
+    if a.train:
+        return train_bench(a)
     dev = "cuda:0"
     lens = workloads.assembly101_eval_lengths()
     if a.clips:
@@ -75,6 +89,67 @@ def main():
         "mroada_ms": dt_a * 1e3, "mroad_ms": dt_0 * 1e3, "head_ms": head * 1e3, "head_tflop": flop / 1e12,
         "head_tflops": flop / head / 1e12, "head_share_of_spec": flop / head / SPEC,
         "pass_mroada": info_a, "pass_mroad": info_0}))
+
+
+def train_bench(a):
+    from prego_amd import _lib
+    from prego_amd.loss import OadAntLoss, OadLoss
+    from prego_amd.optim import FusedAdamW
+    dev, B, T = "cuda:0", 16, 128
+    steps = max(a.steps, 200)
+    dbg = _lib.load() if _lib.LIB_PATH == _lib.DEBUG_LIB_PATH else None
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1234)
+    rgb = torch.randn((B, T, 2048), device=dev, generator=gen).clamp_(min=0)
+    flow = torch.zeros_like(rgb)
+    tgt = torch.nn.functional.one_hot(torch.randint(0, 86, (B, T), device=dev, generator=gen), 86).float()
+    runs = {}
+    base = assembly101_cfg(compute_dtype=a.dtype, assume_zero_flow=True)
+    m0 = build_model(base, dev)
+    m0.load_state_dict({k: torch.from_numpy(v) for k, v in W.miniroad_state_dict(base, 20).items()})
+    runs["miniroad"] = (m0, FusedAdamW(m0.parameters(), lr=1e-4, weight_decay=0.05, model=m0), OadLoss(base), (tgt,), False)
+    for L in (1, 4, 8):
+        cfg = anticipation_cfg(base, L)
+        m = build_model(cfg, dev)
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in W.miniroad_a_state_dict(cfg, 20).items()})
+        ant = torch.nn.functional.one_hot(torch.randint(0, 86, (B, L), device=dev, generator=gen), 86).float()
+        runs[f"mroada_L{L}"] = (m, FusedAdamW(m.parameters(), lr=1e-4, weight_decay=0.05, model=m), OadAntLoss(cfg), (tgt, ant), False)
+        if dbg is not None:
+            runs[f"mroada_L{L}_full"] = runs[f"mroada_L{L}"][:4] + (True,)
+    times = {k: [] for k in runs}
+
+    def step(m, opt, crit, targets):
+        m.train()
+        out = m(rgb, flow)
+        loss = crit(out, *targets)
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        opt.step()
+
+    for k, (m, opt, crit, targets, full) in runs.items():       # warm-up: workspaces, kernels, optimizer state
+        for _ in range(a.warmup):
+            step(m, opt, crit, targets)
+    torch.cuda.synchronize()
+    per_round = (steps + a.rounds - 1) // a.rounds
+    for _ in range(a.rounds):
+        for k, (m, opt, crit, targets, full) in runs.items():
+            if dbg is not None:
+                dbg.prego_debug_ant_full_span(1 if full else 0)
+            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(per_round)]
+            for e0, e1 in evs:
+                e0.record()
+                step(m, opt, crit, targets)
+                e1.record()
+            torch.cuda.synchronize()
+            times[k] += [e0.elapsed_time(e1) for e0, e1 in evs]
+            m.check()
+    if dbg is not None:
+        dbg.prego_debug_ant_full_span(0)
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    print(json.dumps({"metric": "training step ms (median of device-event times, B 16, T 128, zero flow, FusedAdamW)", "dtype": a.dtype,
+                      "steps_per_config": len(next(iter(times.values()))), "rounds": a.rounds, "median_ms": med,
+                      "p10_ms": {k: float(np.percentile(v, 10)) for k, v in times.items()},
+                      "p90_ms": {k: float(np.percentile(v, 90)) for k, v in times.items()}}))
 
 
 if __name__ == "__main__":
