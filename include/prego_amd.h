@@ -189,7 +189,7 @@ int prego_miniroad_forward_anticipation(prego_miniroad* h, int n_clips, const in
  *   out            device fp32 [n_streams, n_classes]: probabilities (PREGO_FWD_SOFTMAX in flags) or logits; nullable
  *   argmax         device int32 [n_streams]; nullable
  * Three kernel launches for <= 4 streams (LayerNorm inside the W_ih product), four above; no plan, no workspace, no host staging (the general forward() with n_clips = 1, lens = {1}, h0, h_last is
- * the same arithmetic in eight launches plus table staging).  bf16 handles only (PREGO_EINVAL otherwise: use forward()).
+ * the same arithmetic in eight launches plus table staging).  bf16 and fp16 handles (PREGO_EINVAL on fp32 / fp16x2 handles: use forward()).
  * Projection outputs stay fp32 here (forward()'s inference path rounds them to bf16), so the two paths agree to the operand
  * rounding, not bit for bit. */
 int prego_miniroad_step(prego_miniroad* h, int n_streams, const float* rgb, const float* flow, float* h_state, float* out,

@@ -28,7 +28,6 @@ def _newer(a, b):
 
 
 DEBUG_LIB = os.path.join(LIBDIR, "libprego_amd_debug.so")
-DEBUG_ABI_SOURCES = ("miniroad.cpp", "vit_host.cpp")       # the only files that define prego_debug_* entry points (include/prego_amd_debug.h)
 DEBUG_ONLY_SOURCES = ("debug_hog.hip",)                    # kernels of probe hooks: linked into libprego_amd_debug.so only
 
 
@@ -45,7 +44,7 @@ def _tree_hash() -> str:
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Builds libprego_amd.so (the product ABI, include/prego_amd.h) and libprego_amd_debug.so (the same objects plus the probe /
-    unit-test entry points of include/prego_amd_debug.h: the two host files compiled again with -DPREGO_DEBUG_ABI).  An object is
+    unit-test entry points of include/prego_amd_debug.h: every host file (*.cpp) compiled again with -DPREGO_DEBUG_ABI; kernels (*.hip) once).  An object is
     recompiled when it is older than its source or a header; EVERYTHING is rebuilt when the library's recorded sources_sha256 differs
     from the tree (a prebuilt library shipped with an edited tree, or clock skew between hosts, cannot pass as current)."""
     os.makedirs(LIBDIR, exist_ok=True)
@@ -68,7 +67,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         if src not in DEBUG_ONLY_SOURCES:
             objs.append(op)
         variants = [(op, [])]
-        if src in DEBUG_ABI_SOURCES:
+        if src.endswith(".cpp"):                                  # host code: prego_debug_* entry points, prego_tune_env
             dop = os.path.join(LIBDIR, src.replace(".", "_") + "_dbg.o")
             variants.append((dop, ["-DPREGO_DEBUG_ABI"]))
             dbg_objs.append(dop)

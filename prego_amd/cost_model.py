@@ -1,8 +1,8 @@
 """Host-side cost model of a MiniROAD pass / training step on one MI355X, and what it predicts for 1 / 2 / 4 / 8 GPUs.
 
 Pure Python (no GPU, no library): `bench.py` prints the table into every line (`predicted`), `DESIGN.md` section 10 quotes it, and the
-world-N dry-run test checks the sharding it is computed from.  The constants are the ones `csrc/miniroad.cpp` chooses the pass with
-(`prego_miniroad_forward`: chunked = recurrence estimate + rows x (projection flops at 1.4 PFLOP/s + 3 ns) + 30 us per chunk; split =
+world-N dry-run test checks the sharding it is computed from.  The constants are the ones `choose_pass` in
+`csrc/miniroad_forward.cpp` chooses the pass with (chunked = recurrence estimate + rows x (projection flops at 1.4 PFLOP/s + 3 ns) + 30 us per chunk; split =
 max(steps x 2.0 us, rows x (flops at 1.4 PFLOP/s + pack bytes at 5.3 TB/s + 1.5 ns) x 8 / (8 - R)) + 1.5 ms), with the measured /
 estimated ratios of round 6's devices folded in (chunked 0.98, split 0.93): a prediction, to be held against the driver's SCALE file.
 

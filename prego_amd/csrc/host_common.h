@@ -1,0 +1,20 @@
+// Shared by every host translation unit (*.cpp) of the library: error plumbing and two small helpers.
+#pragma once
+#include "../../include/prego_amd.h"
+#ifdef PREGO_DEBUG_ABI
+#include "../../include/prego_amd_debug.h"
+#endif
+#include "kernels.h"      // declares prego_tune_env (defined in miniroad.cpp: getenv in the debug library, NULL in the product library)
+
+#include <cstddef>
+
+// Records the message for prego_last_error() and, when an entry point of a MiniROAD handle is running on this thread (HandleScope,
+// miniroad_handle.h), for prego_miniroad_last_error(h) as well; returns `code`.  Defined in miniroad.cpp beside the error state.
+int prego_fail_(int code, const char* fmt, ...);
+#define HIPCHK(x)                                                                                          \
+  do {                                                                                                     \
+    hipError_t e_ = (x);                                                                                   \
+    if (e_ != hipSuccess) return prego_fail_(PREGO_EHIP, "%s failed: %s", #x, hipGetErrorString(e_));      \
+  } while (0)
+
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

@@ -1,0 +1,116 @@
+// Handle-free entry points of the C ABI (include/prego_amd.h): post-processing, metrics and label preparation around the models.
+#include "host_common.h"
+
+#include <algorithm>
+#include <thread>
+#include <vector>
+
+// ================================================================================================
+// post-processing: utils/aggregate.py:55-72 (the 200-frame majority vote) on the device
+// ================================================================================================
+extern "C" int prego_window_vote(const int32_t* argmax, int64_t n_frames, int window, int n_classes, int32_t* votes,
+                                 prego_stream_t stream) {
+  if (!argmax || !votes) return prego_fail_(PREGO_EINVAL, "window_vote: NULL argument");
+  if (launch_window_vote(argmax, n_frames, window, n_classes, votes, (hipStream_t)stream))
+    return prego_fail_(PREGO_EINVAL, "window_vote: n_frames %lld, window %d, n_classes %d (1..128)", (long long)n_frames, window, n_classes);
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+extern "C" int prego_format_ids(const int32_t* ids, int64_t n, uint32_t* text, int32_t* bad, prego_stream_t stream) {
+  if (!ids || !text) return prego_fail_(PREGO_EINVAL, "format_ids: NULL argument");
+  if (launch_format_ids(ids, n, text, bad, (hipStream_t)stream)) return prego_fail_(PREGO_EINVAL, "format_ids: n %lld", (long long)n);
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+// ================================================================================================
+// metric: utils/metrics.py:25-62 (per-class average precision of the per-frame scores) on the device
+// ================================================================================================
+extern "C" size_t prego_perframe_ap_workspace_bytes(int64_t n_frames, int n_classes) {
+  if (n_frames <= 0 || n_classes <= 0) return 0;
+  return perframe_ap_workspace_bytes(n_frames, n_classes);
+}
+static int perframe_ap_common(const float* scores, const float* target, const int32_t* labels, int64_t n_frames, int n_classes, double* ap,
+                              int64_t* n_pos, double* score_sum, void* workspace, size_t workspace_bytes, prego_stream_t stream) {
+  if (!scores || (!target && !labels) || !ap || !workspace) return prego_fail_(PREGO_EINVAL, "perframe_ap: NULL argument");
+  if (n_frames <= 0 || n_frames >= (1ll << 31) || n_classes <= 0 || n_classes > 65535)
+    return prego_fail_(PREGO_EINVAL, "perframe_ap: n_frames %lld, n_classes %d", (long long)n_frames, n_classes);
+  if (workspace_bytes < perframe_ap_workspace_bytes(n_frames, n_classes))
+    return prego_fail_(PREGO_EWORKSPACE, "perframe_ap: workspace %zu < %zu", workspace_bytes, perframe_ap_workspace_bytes(n_frames, n_classes));
+  if (launch_perframe_ap(scores, target, (const int*)labels, n_frames, n_classes, ap, (long long*)n_pos, score_sum, workspace, (hipStream_t)stream))
+    return prego_fail_(PREGO_EINVAL, "perframe_ap: bad arguments");
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+extern "C" int prego_perframe_ap(const float* scores, const float* target, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
+                                 double* score_sum, void* workspace, size_t workspace_bytes, prego_stream_t stream) {
+  return perframe_ap_common(scores, target, nullptr, n_frames, n_classes, ap, n_pos, score_sum, workspace, workspace_bytes, stream);
+}
+extern "C" int prego_perframe_ap_labels(const float* scores, const int32_t* labels, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
+                                        double* score_sum, void* workspace, size_t workspace_bytes, prego_stream_t stream) {
+  return perframe_ap_common(scores, nullptr, labels, n_frames, n_classes, ap, n_pos, score_sum, workspace, workspace_bytes, stream);
+}
+
+// The feeder's side of that: one-hot target rows (what the reference's dataset yields, dataset.py / eval.py:55 np.argmax(target)) reduced
+// to their class id on the host, in the loader's own memory, by a few threads - while the GPU is busy with the features.  HOST function.
+extern "C" int prego_onehot_labels(int n_videos, const float* const* targets, const int64_t* n_frames, int n_classes, int32_t* labels,
+                                   int32_t* onehot) {
+  if (n_videos < 0 || (n_videos && (!targets || !n_frames || !labels || !onehot)) || n_classes <= 0)
+    return prego_fail_(PREGO_EINVAL, "onehot_labels: bad argument");
+  std::vector<int64_t> off((size_t)n_videos + 1, 0);
+  for (int v = 0; v < n_videos; ++v) {
+    if (n_frames[v] < 0 || (n_frames[v] && !targets[v])) return prego_fail_(PREGO_EINVAL, "onehot_labels: video %d", v);
+    off[(size_t)v + 1] = off[(size_t)v] + n_frames[v];
+    onehot[v] = 1;
+  }
+  const int64_t total = off[(size_t)n_videos];
+  const unsigned hw = std::thread::hardware_concurrency();
+  const int nt = (int)std::min<int64_t>(std::max<int64_t>(1, total / 16384), std::min(16u, hw ? hw : 1u));
+  auto work = [&](int t) {
+    const int64_t a = total * t / nt, b = total * (t + 1) / nt;
+    int v = (int)(std::upper_bound(off.begin(), off.end(), a) - off.begin()) - 1;
+    for (int64_t i = a; i < b; ++i) {
+      while (i >= off[(size_t)v + 1]) ++v;
+      const float* row = targets[v] + (size_t)(i - off[(size_t)v]) * n_classes;
+      int nz = 0, pos = 0;
+      for (int c = 0; c < n_classes; ++c) { nz += row[c] != 0.f; pos += row[c] > 0.f; }
+      int best = 0;                                            // np.argmax: the first maximum
+      if (nz == 1 && pos == 1) { while (!(row[best] > 0.f)) ++best; }
+      else {
+        __atomic_store_n(&onehot[v], 0, __ATOMIC_RELAXED);
+        for (int c = 1; c < n_classes; ++c) if (row[c] > row[best]) best = c;
+      }
+      labels[i] = best;
+    }
+  };
+  std::vector<std::thread> th;
+  for (int t = 1; t < nt; ++t) th.emplace_back(work, t);
+  if (total > 0) work(0);
+  for (auto& x : th) x.join();
+  return PREGO_OK;
+}
+#ifdef PREGO_DEBUG_ABI
+// probe: the ping-pong GEMM as a persistent worker that only runs on XCDs >= xcd_lo and claims tiles from `counter`
+// (device word, zeroed by the caller in stream order); grid = workgroups launched (256 = one per CU)
+extern "C" int prego_debug_gemm_worker(const void* A, const void* B, const float* bias, float* C, int M, int N, int K, int xcd_lo,
+                                       unsigned* counter, int grid, prego_stream_t stream) {
+  if (!A || !B || !bias || !C || !counter || M <= 0 || grid <= 0) return prego_fail_(PREGO_EINVAL, "debug gemm worker: bad arguments");
+  if (launch_gemm_bf16_pingpong_worker(A, K, B, K, bias, C, N, M, N, K, xcd_lo, counter, grid, (hipStream_t)stream))
+    return prego_fail_(PREGO_EINVAL, "debug gemm worker: unsupported shape");
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+// debug / microbenchmark: C[M,N] (fp32) = A[M,K] . B[N,K]^T + bias with a chosen bf16 kernel variant
+// (0 = 128x128 two-stage, 1 = 256x128 three-stage counted-vmcnt, 9 = 256x256 two-stage, 12 = ping-pong), scripts/gemm_bench.py
+void launch_gemm_bf16_variant(int variant, const void* A, int lda, const void* B, int ldb, const float* bias, float* C, int ldc,
+                              int M, int N, int K, hipStream_t s);
+extern "C" int prego_debug_gemm_bf16(int variant, const void* A, const void* B, const float* bias, float* C, int M, int N, int K,
+                                     prego_stream_t stream) {
+  if (!A || !B || !C || M <= 0 || N % 128 || K % 64) return prego_fail_(PREGO_EINVAL, "debug gemm: bad arguments");
+  launch_gemm_bf16_variant(variant, A, K, B, K, bias, C, N, M, N, K, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+#endif  // PREGO_DEBUG_ABI

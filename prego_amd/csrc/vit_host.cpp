@@ -1,10 +1,6 @@
 // C ABI of the "Transformer" (ViTEnc) path and of the causal AttentionLayer op (include/prego_amd.h).
 // bf16 (or, inference only, IEEE fp16) MFMA operands, fp32 accumulation / residual stream / LayerNorm / softmax.
-#include "../../include/prego_amd.h"
-#ifdef PREGO_DEBUG_ABI
-#include "../../include/prego_amd_debug.h"
-#endif
-#include "kernels.h"
+#include "host_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -14,14 +10,6 @@
 #include <vector>
 
 extern "C" const char* prego_last_error(void);
-// error plumbing shared with miniroad.cpp
-int prego_fail_(int code, const char* fmt, ...);
-#define HIPCHK(x)                                                                                          \
-  do {                                                                                                     \
-    hipError_t e_ = (x);                                                                                   \
-    if (e_ != hipSuccess) return prego_fail_(PREGO_EHIP, "%s failed: %s", #x, hipGetErrorString(e_));      \
-  } while (0)
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct VitLayer {
   float *ln1_w, *ln1_b, *proj_b, *ln2_w, *ln2_b, *ff1_b, *ff2_b;

@@ -32,7 +32,7 @@ def param_order(num_layers: int = 1):
 
 def plan_passes(lens, max_clips: int, single: bool = False, max_slots: int = 512):
     """Split a clip list into forward() calls.  The C ABI packs up to `max_clips` clips per call into its recurrence
-    slots itself (continuous batching: longest-first bin packing, see csrc/miniroad.cpp::build_plan); only calls that
+    slots itself (continuous batching: longest-first bin packing, see csrc/miniroad_plan.cpp::build_plan); only calls that
     need one clip per slot (h0 / h_last) are limited to `max_slots` clips.  Returns lists of clip indices."""
     n = len(lens)
     cap = max_slots if single else max_clips
@@ -448,7 +448,7 @@ class MiniRoadEngine:
             total += (n + 63) // 64 * 64            # 256-byte aligned views
         self._grad_flat = torch.empty(total, dtype=torch.float32, device=self.device)   # every gradient tensor is overwritten by backward
         grads = {k: self._grad_flat[o:o + n].view(shapes[k]) for k, o, n in zip(order, offs, sizes)}
-        # buckets of the flat tensor in the order the backward finishes them (csrc/miniroad.cpp: head, GRU, then LayerNorm / layer1):
+        # buckets of the flat tensor in the order the backward finishes them (csrc/miniroad_train.cpp: head, GRU, then LayerNorm / layer1):
         # the first two are announced by events recorded inside the backward, the last one is final when backward returns
         o_ih, o_fc = offs[order.index("gru.weight_ih_l0")], offs[order.index("f_classification.0.weight")]
         self._grad_bounds = [(o_fc, total), (o_ih, o_fc), (0, o_ih)]       # bucket 2 ends with the guard slot

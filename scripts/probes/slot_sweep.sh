@@ -1,6 +1,6 @@
 #!/bin/bash
 export PREGO_AMD_DEBUG_LIB=1   # tuning knobs (PREGO_SPLIT_LAG*, PREGO_PLAN_SLOTS, PREGO_ATTN_NW, ...) are read by the debug library only (csrc/kernels.h: prego_tune_env)
-# recurrence cost per time step by live tiles per group (calibrates kStepCost in csrc/miniroad.cpp): synth512 workload,
+# recurrence cost per time step by live tiles per group (calibrates kStepCost in csrc/miniroad_plan.cpp): synth512 workload,
 # slots forced to 128 / 256 / 512 = 1 / 2 / 4 tiles per group
 for sl in 128 256 512; do
   PREGO_PLAN_SLOTS=$sl python bench.py --full --steps 10 --warmup 3 --workload synth512 --no-cpu-baseline 2>/dev/null > /tmp/sw.json

@@ -51,7 +51,7 @@ def main(out_dir, out_json):
         if not bptt or not any("gru_bptt" in r["Kernel_Name"] for r in seg):
             continue
         bk = [r for r in seg if "gru_bptt" in r["Kernel_Name"]][-1]
-        # the backward's last kernel = the last GEMM on the main stream before AdamW (layer1's wgrad, miniroad.cpp: prego_miniroad_backward)
+        # the backward's last kernel = the last GEMM on the main stream before AdamW (layer1's wgrad, miniroad_train.cpp: prego_miniroad_backward)
         mains = [r for r in seg if r[skey] == main_stream and r["s"] >= bptt[0]["s"] and "gemm" in r["Kernel_Name"]]
         last_bwd = max(mains, key=lambda r: r["e"])
         comm = [r for r in seg if r[skey] != main_stream and r["s"] >= bptt[0]["s"]]
