@@ -1,6 +1,6 @@
 /* Probe / unit-test entry points of the MI355X PREGO library - NOT part of the product ABI (include/prego_amd.h).
  * They exist only in libprego_amd_debug.so = the same sources built with -DPREGO_DEBUG_ABI (python -m prego_amd.build builds both),
- * and serve the kernel-level GPU tests (tests/test_gpu_gemm.py, the attention kernel tests) and the measurement scripts under
+ * and serve the kernel-level GPU tests (tests/test_gpu_gemm.py, tests/test_gpu_gemm_tn.py, the attention kernel tests) and the measurement scripts under
  * scripts/.  Nothing under prego_amd/ calls them. */
 #ifndef PREGO_AMD_DEBUG_H
 #define PREGO_AMD_DEBUG_H
@@ -59,6 +59,20 @@ int prego_debug_hog(int kind, int xcd_lo, int ms, const void* read_buf, void* wr
  * (0 = 128x128, 1 = 256x128 three-stage, 9 = 256x256 two-stage, 12 = the ping-pong kernel = the production kernel of the projections; scripts/gemm_bench.py).  N % 128 == 0 (256 for variants >= 9), K % 64 == 0. */
 int prego_debug_gemm_bf16(int variant, const void* A, const void* B, const float* bias, float* C, int M, int N, int K,
                           prego_stream_t stream);
+
+/* Unit test only (tests/test_gpu_gemm_tn.py): the training GEMMs on k-major operands exactly as the training steps launch them
+ * (launch_gemm_bf16_tn chooses between the split-K and the plain kernel itself).  C[M,N] = op(A) . op(B) (+ bias[n]); ta: A is stored
+ * [K][M] with lda elements per k row, else [M][K]; tb: B is stored [K][N], else [N][K]; 16-bit operands are bf16.  k_valid <= K: the
+ * contraction rows of a k-major operand that exist.  C16 (nullable): device bf16 [M][ldc], written INSTEAD of the fp32 C.  colsum_out
+ * (nullable, ta only): fp32 [M] column sums of A over k.  PREGO_EINVAL, nothing launched, for a shape the launcher refuses. */
+int prego_debug_gemm_tn(int ta, int tb, const void* A, int lda, const void* B, int ldb, const float* bias, float* C, void* C16, int ldc,
+                        int M, int N, int K, int k_valid, float* colsum_out, prego_stream_t stream);
+
+/* Unit test only (tests/test_gpu_gemm.py): the production dispatcher of the projections, launch_gemm_bf16_nt: C[M,N] fp32 = A[M,K] .
+ * B[N,K]^T + bias, operands bf16 or (f16 != 0) IEEE fp16; train_splitk: the keeping training forward's flag.  N % 128 == 0, K % 64 == 0,
+ * M > 0, lda, ldb >= K, ldc >= N. */
+int prego_debug_gemm_nt(int f16, int train_splitk, const void* A, int lda, const void* B, int ldb, const float* bias, float* C, int ldc,
+                        int M, int N, int K, prego_stream_t stream);
 
 /* Debug / unit test only: the attention backward kernels alone.  qs (= q * dh^-0.5), k, v: device bf16 [batch, heads, len, dh];
  * o, dout: device bf16 [batch, len, heads*dh]; lse: device fp32 [batch, heads, len] log-sum-exp of the scaled scores;

@@ -282,10 +282,19 @@ __global__ __launch_bounds__(SPLITK ? 512 : 256, SPLITK ? 1 : 2) void gemm_bf16_
 // only with !ta and at most 256 tiles - the split-K form).
 // k_valid <= K: contraction rows that exist in memory (the rest reads as zeros; K itself a multiple of 64).  colsum_out (ta only,
 // nullable): [M] column sums of A over k = the bias gradient of a wgrad.  C16 (nullable): store C as bf16 there instead of fp32 into C.
-// Returns -1 for an unsupported shape.
+// Caller contract: a k-major operand is read in rows [0, k_valid) only - rows k_valid .. K-1 need not exist.  A ROW-MAJOR A (dgrad) is
+// read in all K columns: columns k_valid .. K-1 meet zero-filled B rows, so they must hold finite values (production: zeros).
+// Returns -1 for an unsupported shape, before any launch.
 int launch_gemm_bf16_tn(bool ta, bool tb, const void* A, int lda, const void* B, int ldb, const float* bias, float* C, int ldc, int M, int N,
                         int K, int k_valid, float* colsum_out, hipStream_t s, void* C16) {
   if (K % TBK || K <= 0 || M <= 0 || N <= 0 || (!tb && ta) || (colsum_out && !ta) || (lda % 8) || (ldb % 8)) return -1;
+  // The kernel builds num_records and its byte offsets in 32 bits.  k-major operand: num_records = k_valid * ld * 2 and the tile offset
+  // kt * 64 * ld * 2 stay below K * ld * 2; row-major operand: num_records and the lane offsets stay below 128 * ld * 2, the tile offset
+  // below K * 2.  A shape past these fails here instead of wrapping.
+  const long long ldmax = lda > ldb ? lda : ldb;
+  if (lda <= 0 || ldb <= 0 || (long long)K * ldmax * 2 > 0x7fffffffll || (long long)M * lda * 2 > 0x7fffffffll ||
+      (long long)(TBM + 1) * ldmax * 2 + (long long)K * 2 > 0x7fffffffll)
+    return -1;
   const int ntm = (M + TBM - 1) / TBM, ntn = (N + TBN - 1) / TBN;
   const bf16_t* a = (const bf16_t*)A; const bf16_t* b = (const bf16_t*)B;
   const size_t lds = 65536;

@@ -113,4 +113,25 @@ extern "C" int prego_debug_gemm_bf16(int variant, const void* A, const void* B, 
   HIPCHK(hipGetLastError());
   return PREGO_OK;
 }
+
+// unit test (tests/test_gpu_gemm_tn.py): launch_gemm_bf16_tn as the training steps call it - the launcher's own choice of kernel runs
+extern "C" int prego_debug_gemm_tn(int ta, int tb, const void* A, int lda, const void* B, int ldb, const float* bias, float* C, void* C16,
+                                   int ldc, int M, int N, int K, int k_valid, float* colsum_out, prego_stream_t stream) {
+  if (!A || !B || (!C && !C16)) return prego_fail_(PREGO_EINVAL, "debug gemm tn: NULL argument");
+  if (launch_gemm_bf16_tn(ta != 0, tb != 0, A, lda, B, ldb, bias, C, ldc, M, N, K, k_valid, colsum_out, (hipStream_t)stream, C16))
+    return prego_fail_(PREGO_EINVAL, "debug gemm tn: unsupported shape (ta %d, tb %d, M %d, N %d, K %d, k_valid %d, lda %d, ldb %d)", ta, tb, M,
+                       N, K, k_valid, lda, ldb);
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+// unit test (tests/test_gpu_gemm.py): the production dispatcher of the NT projections, with the argument checks its callers guarantee
+extern "C" int prego_debug_gemm_nt(int f16, int train_splitk, const void* A, int lda, const void* B, int ldb, const float* bias, float* C,
+                                   int ldc, int M, int N, int K, prego_stream_t stream) {
+  if (!A || !B || !C || M <= 0 || N <= 0 || N % 128 || K <= 0 || K % 64 || lda < K || ldb < K || ldc < N)
+    return prego_fail_(PREGO_EINVAL, "debug gemm nt: bad arguments (M %d, N %d, K %d, lda %d, ldb %d, ldc %d)", M, N, K, lda, ldb, ldc);
+  launch_gemm_bf16_nt(A, lda, B, ldb, bias, C, ldc, M, N, K, (hipStream_t)stream, f16 != 0, train_splitk != 0);
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
 #endif  // PREGO_DEBUG_ABI

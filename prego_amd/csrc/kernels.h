@@ -264,6 +264,15 @@ int launch_ln_relu_bwd(const float* dE, const float* Y, const float* stats, cons
                        int relu = 1, int accumulate = 0, void* dYb = nullptr /* bf16 copy of dY (wgrad operand), nullable */);
 // training GEMMs on k-major operands (gemm_tn.hip): C[M,N] fp32 = op(A) . op(B) + bias; ta: A stored [K][M]; tb (required): B stored [K][N];
 // colsum_out (ta only): [M] column sums of A = the bias gradient of a wgrad; k_valid: contraction rows present in memory
+// Caller contract (tests/test_gpu_gemm_tn.py holds the kernel to it with NaN-filled surroundings):
+//   * a k-major operand (A with ta, B with tb) is read in rows [0, k_valid) only; rows k_valid .. K-1 need not exist.  Its columns past
+//     M (A) / N (B) up to the leading dimension are read but reach only output rows / columns that are never stored
+//   * a ROW-MAJOR A (!ta: the dgrads) is read in rows [0, M) and in ALL K columns: with k_valid < K its columns k_valid .. K-1 are
+//     multiplied by zero-filled B rows, so the CALLER must keep them finite (the head dgrad's dlogits hold zeros in their pad
+//     columns) - a NaN or Inf there would reach every output of its row
+//   * lda, ldb multiples of 8, K a multiple of 64; -1 (nothing launched) for anything else, for !tb with ta / K < 128 / more than 256
+//     tiles / k_valid != K, and for operands whose byte offsets do not fit 31 bits (K * max(lda, ldb) * 2, M * lda * 2)
+//   * exactly the M x N block of C (or C16) and colsum_out[0, M) are written
 int launch_gemm_bf16_tn(bool ta, bool tb, const void* A, int lda, const void* B, int ldb, const float* bias, float* C, int ldc, int M, int N,
                         int K, int k_valid, float* colsum_out, hipStream_t s, void* C16 = nullptr /* bf16 C instead of fp32 */);
 
