@@ -325,7 +325,9 @@ def test_chunking_and_streaming_are_bit_exact(dtype):
 @pytest.mark.parametrize("dtype", ALL_DT)
 def test_continuous_batching_matches_per_clip_results(dtype):
     """more clips than recurrence slots: several clips share a slot back to back (h restarts at 0 at every clip
-    boundary, chunk boundaries fall anywhere).  Every clip must come out exactly as when it is run alone."""
+    boundary, chunk boundaries fall anywhere).  Every clip must come out exactly as when it is run alone.
+    (Six clips are compared here; the check of EVERY frame of EVERY clip of such a call, against a reference with one right answer, lives in
+    tests/test_gpu_automaton.py::test_clip_counts_and_chunk_sizes.)"""
     cfg = epic_tent_cfg()
     sd = W.miniroad_state_dict(cfg, 20, head_gain=8.0)
     m = _model(cfg, sd, dtype)
