@@ -191,9 +191,19 @@ int prego_miniroad_forward_anticipation(prego_miniroad* h, int n_clips, const in
  * Three kernel launches for <= 4 streams (LayerNorm inside the W_ih product), four above; no plan, no workspace, no host staging (the general forward() with n_clips = 1, lens = {1}, h0, h_last is
  * the same arithmetic in eight launches plus table staging).  bf16 and fp16 handles (PREGO_EINVAL on fp32 / fp16x2 handles: use forward()).
  * Projection outputs stay fp32 here (forward()'s inference path rounds them to bf16), so the two paths agree to the operand
- * rounding, not bit for bit. */
+ * rounding, not bit for bit.  hidden_dim 1024, one GRU layer.  MiniROADA: prego_miniroad_step_anticipation below. */
 int prego_miniroad_step(prego_miniroad* h, int n_streams, const float* rgb, const float* flow, float* h_state, float* out,
                         int32_t* argmax, int flags, prego_stream_t stream);
+/* MiniROADA streaming - MROADA.forward (rnn.py:113-136) with T = 1 and h0 = the previous call's state: prego_miniroad_step plus
+ *   ant_out        device fp32 [n_streams, ant_len, n_classes]: per-step probabilities (PREGO_FWD_SOFTMAX) or logits; nullable
+ *   ant_argmax     device int32 [n_streams, ant_len]: first max wins; nullable
+ * out, argmax and h_state are bit for bit prego_miniroad_step's (the same launches with the same arguments); the anticipation head follows
+ * on the same stream in two more launches (csrc/stream_ant.hip) that read the new state, and none when both of its outputs are NULL.  Sums
+ * in a fixed order: repeat calls are bit-identical.  No device allocation, no workspace, no host wait (set_anticipation holds the one
+ * intermediate buffer, one per handle, as prego_miniroad_step's scratch: like every entry point of a handle, not to be called on one
+ * handle from two streams at once).  prego_miniroad_step's refusals, and PREGO_EINVAL before set_anticipation. */
+int prego_miniroad_step_anticipation(prego_miniroad* h, int n_streams, const float* rgb, const float* flow, float* h_state,
+                                     float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax, int flags, prego_stream_t stream);
 
 /* Synchronises `stream` and reports a recurrence timeout (PREGO_ETIMEOUT) or HIP error since the last check. */
 int prego_miniroad_check(prego_miniroad* h, prego_stream_t stream);

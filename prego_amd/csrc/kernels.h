@@ -349,3 +349,10 @@ struct StreamGemv {
 int launch_stream_gemv(int nprob, const StreamGemv* pr, int n, hipStream_t s, bool f16 = false);
 int launch_stream_gates_head(const float* gi, const float* gh, const float* b_hn, float* h_state, const void* wc, const float* bc, int n,
                               int H, int C, int softmax, float* out, int* argmax, hipStream_t s, bool f16 = false);
+
+// MiniROADA streaming (stream_ant.hip): the anticipation head behind the streaming step, two launches for n <= 16 streams.  H == 1024.
+// A [n][L * H] 16-bit = op16(relu(op16(relu(h_state)) W_a^T + b_a)) from the fp32 state the step has just written
+int launch_stream_ant_hidden(const void* wa, const float* ba, const float* h_state, void* A, int n, int H, int L, hipStream_t s, bool f16 = false);
+// ant_out [n][L][C] / ant_argmax [n][L] (each nullable) = softmax or logits / first argmax of A_l W_c^T + b_c
+int launch_stream_ant_head(const void* A, const void* wc, const float* bc, int n, int H, int L, int C, int softmax, float* ant_out,
+                           int* ant_argmax, hipStream_t s, bool f16 = false);

@@ -104,7 +104,7 @@ extern "C" int prego_miniroad_create_layers(prego_miniroad** out, int d_rgb, int
   A(&h->w1, (size_t)emb * din * es); A((void**)&h->b1, emb * 4); A((void**)&h->ln_g, emb * 4); A((void**)&h->ln_b, emb * 4);
   A(&h->w_ih, (size_t)3 * H * emb * es); A(&h->w_hh, (size_t)3 * H * H * es);
   A((void**)&h->bias2, 3 * H * 4); A((void**)&h->b_hn, H * 4);
-  if (h->bf16 && H == 1024 && h->layers == 1) { A(&h->w_ih_perm, (size_t)3 * H * emb * es); A((void**)&h->bias2_perm, 3 * H * 4); }
+  if (h->bf16 && H == 1024) { A(&h->w_ih_perm, (size_t)3 * H * emb * es); A((void**)&h->bias2_perm, 3 * H * 4); }
   A(&h->w_c, (size_t)h->ncls_pad * H * es); A((void**)&h->b_c, h->ncls_pad * 4);
   A(&h->hx, h->x2 ? gru_x2_hx_bytes(H, h->G) : gru_hx_bytes(h->bf16, H, h->G));
   if (h->x2) A((void**)&h->x2_scale, 6 * sizeof(float));
@@ -182,7 +182,7 @@ extern "C" void prego_miniroad_destroy(prego_miniroad* h) {
   void* ptrs[] = {h->w1, h->b1, h->ln_g, h->ln_b, h->w_ih, h->w_hh, h->bias2, h->b_hn, h->w_c, h->b_c, h->hx,
                   h->flags, h->h_state, h->stamps, h->tile_ctr, h->d_rowoff, h->d_nact, h->d_sorted, h->d_seg_off, h->d_seg_clip,
                   h->d_seg_start, h->d_ptrs, h->d_blkstep, h->st_scratch, h->x2_scale, h->l2_w_ih, h->l2_w_hh, h->l2_bias2, h->l2_b_hn, h->w_ih_perm, h->bias2_perm,
-                  h->w_a, h->b_a};
+                  h->w_a, h->b_a, h->st_ant};
   for (size_t i = 0; i < sizeof ptrs / sizeof ptrs[0]; ++i)
     if (ptrs[i]) {
 #ifdef PREGO_DEBUG_ABI
@@ -273,9 +273,13 @@ extern "C" int prego_miniroad_set_anticipation(prego_miniroad* h, int ant_len, c
     HIPCHK(hipStreamSynchronize(s));
     if (h->w_a) { HIPCHK(hipFree(h->w_a)); h->w_a = nullptr; }
     if (h->b_a) { HIPCHK(hipFree(h->b_a)); h->b_a = nullptr; }
+    if (h->st_ant) { HIPCHK(hipFree(h->st_ant)); h->st_ant = nullptr; }
     h->w_a_cap = 0;
     HIPCHK(hipMalloc(&h->w_a, need));
     HIPCHK(hipMalloc((void**)&h->b_a, (size_t)ant_len * H * 4));
+    // streaming step (prego_miniroad_step_anticipation; 16-bit handles of hidden_dim 1024): its 16-bit intermediate, allocated
+    // here so that the step itself never allocates
+    if (h->bf16 && H == 1024) HIPCHK(hipMalloc(&h->st_ant, (size_t)16 * ant_len * H * 2));
     h->w_a_cap = need;
   }
   launch_pad_convert(h->bf16, w_a, ant_len * H, H, H, h->w_a, ant_len * H, H, s, h->f16);

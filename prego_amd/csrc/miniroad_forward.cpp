@@ -505,9 +505,10 @@ extern "C" int prego_miniroad_forward_anticipation(prego_miniroad* h, int n_clip
   return forward_impl(h, FwdCall{n_clips, lens, rgb, flow, out, argmax, ao, h0, h_last, flags, workspace, workspace_bytes, (hipStream_t)stream});
 }
 
-// streaming step: one frame for each of n <= 16 streams (stream_step.hip)
-extern "C" int prego_miniroad_step(prego_miniroad* h, int n_streams, const float* rgb, const float* flow, float* h_state, float* out,
-                                   int32_t* argmax, int flags, prego_stream_t stream) {
+// streaming step: one frame for each of n <= 16 streams (stream_step.hip); ant = prego_miniroad_step_anticipation, whose trunk launches
+// and their arguments are these very ones, followed by the anticipation head's two (stream_ant.hip) when an output is wanted
+static int step_impl(prego_miniroad* h, int n_streams, const float* rgb, const float* flow, float* h_state, float* out, int32_t* argmax,
+                     bool ant, float* ant_out, int32_t* ant_argmax, int flags, prego_stream_t stream) {
   HandleScope scope_(h);
   if (!h) return prego_fail_(PREGO_EINVAL, "handle is NULL");
   if (!h->have_weights) return prego_fail_(PREGO_EINVAL, "step before set_weights");
@@ -518,6 +519,7 @@ extern "C" int prego_miniroad_step(prego_miniroad* h, int n_streams, const float
   if (!h_state) return prego_fail_(PREGO_EINVAL, "step: h_state is NULL");
   if (h->d_rgb > 0 && !rgb) return prego_fail_(PREGO_EINVAL, "step: rgb is NULL");
   if (h->d_rgb == 0 && !flow) return prego_fail_(PREGO_EINVAL, "a model without rgb features (--no_rgb) needs the flow frame");
+  if (ant && (h->ant_len <= 0 || !h->w_a || !h->st_ant)) return prego_fail_(PREGO_EINVAL, "step_anticipation before set_anticipation");
   hipStream_t s = (hipStream_t)stream;
   const int E = h->emb, H = h->hid, din = h->d_rgb + h->d_flow;
   float* Y = (float*)h->st_scratch;
@@ -538,8 +540,26 @@ extern "C" int prego_miniroad_step(prego_miniroad* h, int n_streams, const float
   if (launch_stream_gemv(2, g2, n_streams, s, h->f16)) return prego_fail_(PREGO_EINVAL, "step: unsupported GRU shape %d / %d", E, H);
   if (launch_stream_gates_head(GI, GH, h->b_hn, h_state, h->w_c, h->b_c, n_streams, H, h->ncls, (flags & PREGO_FWD_SOFTMAX) ? 1 : 0, out,
                                (int*)argmax, s, h->f16)) return prego_fail_(PREGO_EINVAL, "step: unsupported head shape %d x %d", h->ncls, H);
+  if (ant && (ant_out || ant_argmax)) {
+    // the head reads the state the launch above has just written: relu + rounding on load is the classifier's own operand
+    if (launch_stream_ant_hidden(h->w_a, h->b_a, h_state, h->st_ant, n_streams, H, h->ant_len, s, h->f16) ||
+        launch_stream_ant_head(h->st_ant, h->w_c, h->b_c, n_streams, H, h->ant_len, h->ncls, (flags & PREGO_FWD_SOFTMAX) ? 1 : 0, ant_out,
+                               (int*)ant_argmax, s, h->f16))
+      return prego_fail_(PREGO_EINVAL, "step_anticipation: unsupported head shape %d x %d x %d", h->ant_len, h->ncls, H);
+  }
   HIPCHK(hipGetLastError());
   return PREGO_OK;
+}
+
+extern "C" int prego_miniroad_step(prego_miniroad* h, int n_streams, const float* rgb, const float* flow, float* h_state, float* out,
+                                   int32_t* argmax, int flags, prego_stream_t stream) {
+  return step_impl(h, n_streams, rgb, flow, h_state, out, argmax, false, nullptr, nullptr, flags, stream);
+}
+
+extern "C" int prego_miniroad_step_anticipation(prego_miniroad* h, int n_streams, const float* rgb, const float* flow, float* h_state,
+                                                float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax, int flags,
+                                                prego_stream_t stream) {
+  return step_impl(h, n_streams, rgb, flow, h_state, out, argmax, true, ant_out, ant_argmax, flags, stream);
 }
 
 #ifdef PREGO_DEBUG_ABI

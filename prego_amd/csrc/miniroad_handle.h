@@ -3,7 +3,7 @@
 //   miniroad.cpp          error state (g_err, g_cur), create / destroy, weight setters, check, timing (ev_begin / ev_end), pass_info,
 //                         the debug library's allocation / wait counters (g_dbg_mallocs, g_dbg_syncs)
 //   miniroad_plan.cpp     build_plan, device_plan, stage_tables, feed events, row_bytes / fwd_layout and the workspace size
-//   miniroad_forward.cpp  validate_forward, choose_pass, run_chunked_pass, the forward entry points, prego_miniroad_step, ant_head
+//   miniroad_forward.cpp  validate_forward, choose_pass, run_chunked_pass, the forward entry points, prego_miniroad_step (_anticipation), ant_head
 //   miniroad_split.cpp    ring / resident-buffer sizing, forward_split; the per-device order of split passes (g_split_mu, g_split_last)
 //   miniroad_train.cpp    dropout, loss, bwd_layout, backward, AdamW; the debug library's g_ant_full_span
 #pragma once
@@ -52,6 +52,7 @@ struct prego_miniroad {
   bool have_weights = false;
   // MiniROADA anticipation head (prego_miniroad_set_anticipation): anticipation_layer.0.weight [L*H][H] in the operand type, its bias fp32
   int ant_len = 0; void* w_a = nullptr; float* b_a = nullptr; size_t w_a_cap = 0;
+  void* st_ant = nullptr;       // streaming step with anticipation: A [16][ant_len * H] in the operand type (16-bit handles; set_anticipation)
   // MiniROADA training: the last PREGO_FWD_KEEP forward was forward_anticipation's (its backward then needs set_anticipation_grads), and
   // what prego_miniroad_set_anticipation_grads handed to the NEXT backward (d_ant NULL = zero anticipation gradient)
   bool ant_kept = false; bool ant_grads_set = false;

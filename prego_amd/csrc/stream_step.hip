@@ -14,6 +14,7 @@
 // (lanes whose stream index is >= n load nothing), the four partial tiles meet in LDS and are added in K order.
 #include "common.h"
 #include "kernels.h"
+#include "stream_head.h"
 
 #define SG_MAXKS 32            // k-steps of 32 per wave: K <= 4096
 
@@ -235,32 +236,10 @@ __global__ __launch_bounds__(256, 1) void stream_gates_head_kernel(const float* 
     for (int ct = 0; ct < NT; ++ct) redh[q][ct][g] = acc[ct];
   }
   __syncthreads();
-  if (tid < C) {                                              // class c = tile c / 16, row c % 16 = 4 g + e
-    const int ct = tid >> 4, r = tid & 15, gg = r >> 2, e = r & 3;
-    sl[tid] = ((redh[0][ct][gg][e] + redh[1][ct][gg][e]) + (redh[2][ct][gg][e] + redh[3][ct][gg][e])) + bc_t;
-  }
+  stream_head_logits<NT>(redh, sl, tid, C, bc_t);
   __syncthreads();
-  if (q == 0) {
-    // C <= 128: two classes per lane
-    const float v0 = lane < C ? sl[lane] : -INFINITY, v1 = lane + 64 < C ? sl[lane + 64] : -INFINITY;
-    const float mx = wave_max(fmaxf(v0, v1));
-    // first index holding the maximum (np.argmax)
-    int cand = v0 == mx ? lane : (v1 == mx ? lane + 64 : 0x7fffffff);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int other = __shfl_xor(cand, o, 64); cand = other < cand ? other : cand; }
-    if (argmax != nullptr && lane == 0) argmax[s] = cand;
-    if (out != nullptr) {
-      if (softmax) {
-        const float e0 = lane < C ? __expf(v0 - mx) : 0.f, e1 = lane + 64 < C ? __expf(v1 - mx) : 0.f;
-        const float inv = 1.0f / wave_sum(e0 + e1);
-        if (lane < C) out[(size_t)s * C + lane] = e0 * inv;
-        if (lane + 64 < C) out[(size_t)s * C + lane + 64] = e1 * inv;
-      } else {
-        if (lane < C) out[(size_t)s * C + lane] = v0;
-        if (lane + 64 < C) out[(size_t)s * C + lane + 64] = v1;
-      }
-    }
-  }
+  if (q == 0)
+    stream_head_finish(sl, lane, C, softmax, out != nullptr ? out + (size_t)s * C : nullptr, argmax != nullptr ? argmax + s : nullptr);
 }
 
 // y[n][Nout] = x[n][K] W^T + bias for one or two problems in one launch.  Returns -1 on an unsupported shape.

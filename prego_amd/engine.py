@@ -310,12 +310,18 @@ class MiniRoadEngine:
 
     # -- streaming (online use) ------------------------------------------------
     def step(self, rgb: Optional[torch.Tensor], flow: Optional[torch.Tensor], h: torch.Tensor, softmax: bool = True,
-             out: Optional[torch.Tensor] = None, argmax: Optional[torch.Tensor] = None):
+             out: Optional[torch.Tensor] = None, argmax: Optional[torch.Tensor] = None, want_ant: bool = False,
+             ant_out: Optional[torch.Tensor] = None, ant_argmax: Optional[torch.Tensor] = None):
         """One new frame for each of n <= 16 independent streams: rgb [n, d_rgb] / flow [n, d_flow] (None = zero flow) fp32 cuda
         contiguous, h [n, hid] fp32 cuda = the GRU state, UPDATED IN PLACE (zeros before a stream's first frame).
         Returns (probabilities or logits [n, C], argmax int32 [n]); pass `out` / `argmax` to reuse buffers.  bf16 / fp16 engines run
         the three / four-launch fast path (prego_miniroad_step); fp32 / fp16x2 engines, hidden sizes other than 1024 and two-layer models
-        (h: [layers, n, hid]) the general forward with h0 / h_last."""
+        (h: [layers, n, hid]) the general forward with h0 / h_last.
+        want_ant (MiniROADA, after set_anticipation): the anticipation head on the new state as well (prego_miniroad_step_anticipation, two
+        more launches; the general forward where the fast path does not apply) - returns (out, argmax, ant_out [n, L, C] probabilities
+        or logits as `softmax`, ant_argmax int32 [n, L]); pass `ant_out` / `ant_argmax` to reuse buffers."""
+        if want_ant and not getattr(self, "ant_len", 0):
+            raise PregoError("step(want_ant=True) before set_anticipation")
         d_rgb, d_flow, emb, hid, ncls = self.dims
         src = rgb if d_rgb > 0 else flow
         if src is None:
@@ -332,14 +338,37 @@ class MiniRoadEngine:
             out = torch.empty((n, ncls), dtype=torch.float32, device=self.device)
         if argmax is None:
             argmax = torch.empty((n,), dtype=torch.int32, device=self.device)
+        if want_ant:
+            L = self.ant_len
+            if ant_out is None:
+                ant_out = torch.empty((n, L, ncls), dtype=torch.float32, device=self.device)
+            if ant_argmax is None:
+                ant_argmax = torch.empty((n, L), dtype=torch.int32, device=self.device)
+            for t, shape, dt in ((ant_out, (n, L, ncls), torch.float32), (ant_argmax, (n, L), torch.int32)):
+                if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape:
+                    raise PregoError(f"step: expected a contiguous {dt} cuda {list(shape)} anticipation buffer, got {tuple(t.shape)} {t.dtype} on {t.device}")
         if general:
             rl = [rgb[i:i + 1] for i in range(n)] if d_rgb > 0 else None
             fl = [flow[i:i + 1] for i in range(n)] if flow is not None else None
-            o, a, hl = self.forward_ragged(rl, fl, softmax=softmax, want_out=True, want_argmax=True, h0=h, want_h_last=True)
+            if want_ant:
+                o, a, hl, ao, aa = self.forward_ragged(rl, fl, softmax=softmax, want_out=True, want_argmax=True, h0=h, want_h_last=True,
+                                                       want_ant=True)
+                ant_out.copy_(torch.cat(ao))
+                ant_argmax.copy_(torch.cat(aa))
+            else:
+                o, a, hl = self.forward_ragged(rl, fl, softmax=softmax, want_out=True, want_argmax=True, h0=h, want_h_last=True)
             h.copy_(hl)
             out.copy_(torch.cat(o))
             argmax.copy_(torch.cat(a))
-            return out, argmax
+            return (out, argmax, ant_out, ant_argmax) if want_ant else (out, argmax)
+        if want_ant:
+            with torch.cuda.device(self.device):
+                check(self.lib.prego_miniroad_step_anticipation(
+                    self.h, n, C.c_void_p(rgb.data_ptr()) if (rgb is not None and d_rgb > 0) else None,
+                    C.c_void_p(flow.data_ptr()) if flow is not None else None, C.c_void_p(h.data_ptr()), C.c_void_p(out.data_ptr()),
+                    C.c_void_p(argmax.data_ptr()), C.c_void_p(ant_out.data_ptr()), C.c_void_p(ant_argmax.data_ptr()),
+                    _lib.FWD_SOFTMAX if softmax else 0, C.c_void_p(_stream_ptr(self.device))))
+            return out, argmax, ant_out, ant_argmax
         with torch.cuda.device(self.device):
             check(self.lib.prego_miniroad_step(
                 self.h, n, C.c_void_p(rgb.data_ptr()) if (rgb is not None and d_rgb > 0) else None,

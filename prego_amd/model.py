@@ -140,7 +140,8 @@ class MROADA(MROAD):
     f_classification, anticipation_layer), so a given torch seed gives the reference's initial weights and state_dict keys match
     (f_actionness.0.* included, which the reference builds but never uses in forward).  Training mode returns both as raw logits
     (rnn.py:128-130) through one autograd Function (csrc/ant_head_bwd.hip for the head's backward); f_actionness never gets a gradient.
-    `step` streaming and fp16x2 handles are not built for this model."""
+    `step` is the online use: one frame per stream, with the head on the new state (csrc/stream_ant.hip).  fp16x2 handles are not built
+    for this model."""
 
     def __init__(self, cfg):
         nn.Module.__init__(self)
@@ -215,5 +216,10 @@ class MROADA(MROAD):
 
     link_fed_eval = False
 
+    @torch.no_grad()
     def step(self, rgb, flow, h):
-        raise PregoError("MiniROADA streaming (step) is not built yet in prego_amd: use forward_clips with h0 / h_last chaining")
+        """Online inference: one new frame per stream, as MROAD.step, with the anticipation head on the new state.  Returns (probabilities
+        [n, C], argmax int32 [n], anticipation probabilities [n, L, C], anticipation argmax int32 [n, L]) - the eval branch of
+        MROADA.forward (rnn.py:131-135) at T = 1 with h0 = h; h is updated in place.  bf16 / fp16 models of hidden_dim 1024 run the
+        streaming kernels (csrc/stream_step.hip, csrc/stream_ant.hip), the others the general forward."""
+        return self.engine().step(rgb, flow, h, softmax=True, want_ant=True)

@@ -11,6 +11,14 @@ warm-up.  With PREGO_AMD_DEBUG_LIB=1 MiniROADA also runs with the head's backwar
 for the span / full-range A/B.
 
     PREGO_AMD_DEBUG_LIB=1 python scripts/anticipation_bench.py --train [--steps 200] [--warmup 20] [--rounds 4]
+
+--step: the online use, one frame per call for n = 1 / 4 / 16 streams at L = 1 / 4 / 8 (zero flow): (a) MROAD.step, (b) MROADA.step
+(csrc/stream_ant.hip behind the streaming step), (c) the general forward at T = 1 with h0 / h_last and the anticipation head - what
+MiniROADA streaming cost before (b) existed.  The --train protocol: warm-up, alternating rounds, a device-event pair around every frame,
+median over all rounds (at least 200 frames per path and round); `round_us` is the whole round between two events divided by its frames
+(what a caller that issues frames back to back sees, host issue rate included).
+
+    python scripts/anticipation_bench.py --step [--steps 200] [--warmup 20] [--rounds 4]
 """
 from __future__ import annotations
 
@@ -42,12 +50,15 @@ def main():
     ap.add_argument("--clips", type=int, default=0, help="first N clips of the workload (0 = all)")
     ap.add_argument("--L", type=int, default=8)
     ap.add_argument("--train", action="store_true")
+    ap.add_argument("--step", action="store_true")
     ap.add_argument("--rounds", type=int, default=4)
     a = ap.parse_args()
     if a.warmup is None:
-        a.warmup = 20 if a.train else 1
+        a.warmup = 20 if (a.train or a.step) else 1
     if a.train:
         return train_bench(a)
+    if a.step:
+        return step_bench(a)
     dev = "cuda:0"
     lens = workloads.assembly101_eval_lengths()
     if a.clips:
@@ -150,6 +161,69 @@ def train_bench(a):
                       "steps_per_config": len(next(iter(times.values()))), "rounds": a.rounds, "median_ms": med,
                       "p10_ms": {k: float(np.percentile(v, 10)) for k, v in times.items()},
                       "p90_ms": {k: float(np.percentile(v, 90)) for k, v in times.items()}}))
+
+
+def step_bench(a):
+    dev, H, C = "cuda:0", 1024, 86
+    frames = max(a.steps, 200)
+    base = assembly101_cfg(compute_dtype=a.dtype, assume_zero_flow=True)
+    m0 = build_model(base, dev)
+    m0.load_state_dict({k: torch.from_numpy(v) for k, v in W.miniroad_state_dict(base, 20).items()})
+    m0.eval()
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1234)
+    x = torch.randn((64, 16, 2048), device=dev, generator=gen).clamp_(min=0)
+    table = {}
+    for L in (1, 4, 8):
+        cfg = anticipation_cfg(base, L)
+        m = build_model(cfg, dev)
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in W.miniroad_a_state_dict(cfg, 20, head_gain=8.0, ant_gain=4.0).items()})
+        m.eval()
+        e0, ea = m0.engine(), m.engine()
+        for n in (1, 4, 16):
+            xs = [x[i, :n].contiguous() for i in range(64)]
+            rows = [xs[i][k:k + 1] for i in range(64) for k in range(n)]
+            rows = [rows[i * n:(i + 1) * n] for i in range(64)]
+            out, arg = torch.empty((n, C), device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
+            ao, aa = torch.empty((n, L, C), device=dev), torch.empty((n, L), dtype=torch.int32, device=dev)
+            hs = {k: torch.zeros((n, H), device=dev) for k in "abc"}
+
+            def fa(i):
+                e0.step(xs[i & 63], None, hs["a"], out=out, argmax=arg)
+
+            def fb(i):
+                ea.step(xs[i & 63], None, hs["b"], out=out, argmax=arg, want_ant=True, ant_out=ao, ant_argmax=aa)
+
+            def fc(i):
+                r = ea.forward_ragged(rows[i & 63], None, softmax=True, want_out=True, want_argmax=True, h0=hs["c"], want_h_last=True, want_ant=True)
+                hs["c"] = r[2]
+            paths = {"a_mroad_step": fa, "b_mroada_step": fb, "c_general_T1": fc}
+            times, rounds = {k: [] for k in paths}, {k: [] for k in paths}
+            for f in paths.values():
+                for i in range(a.warmup):
+                    f(i)
+            torch.cuda.synchronize()
+            for _ in range(a.rounds):
+                for k, f in paths.items():
+                    evs = [torch.cuda.Event(enable_timing=True) for _ in range(2 * frames)]
+                    r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    r0.record()
+                    for i in range(frames):
+                        evs[2 * i].record()
+                        f(i)
+                        evs[2 * i + 1].record()
+                    r1.record()
+                    torch.cuda.synchronize()
+                    times[k] += [evs[2 * i].elapsed_time(evs[2 * i + 1]) * 1e3 for i in range(frames)]
+                    rounds[k].append(r0.elapsed_time(r1) * 1e3 / frames)
+            e0.check(); ea.check()
+            table[f"n{n}_L{L}"] = {k: {"median_us": float(np.median(v)), "p10_us": float(np.percentile(v, 10)), "p90_us": float(np.percentile(v, 90)),
+                                       "round_us": float(np.median(rounds[k]))} for k, v in times.items()}
+            t = table[f"n{n}_L{L}"]
+            t["b_minus_a_us"] = t["b_mroada_step"]["median_us"] - t["a_mroad_step"]["median_us"]
+        del m
+    print(json.dumps({"metric": "per-frame device time, us (median of device-event pairs around every frame; zero flow)", "dtype": a.dtype,
+                      "frames_per_path_and_round": frames, "rounds": a.rounds, "table": table}))
 
 
 if __name__ == "__main__":
