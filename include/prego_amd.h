@@ -204,6 +204,25 @@ int prego_miniroad_step(prego_miniroad* h, int n_streams, const float* rgb, cons
  * handle from two streams at once).  prego_miniroad_step's refusals, and PREGO_EINVAL before set_anticipation. */
 int prego_miniroad_step_anticipation(prego_miniroad* h, int n_streams, const float* rgb, const float* flow, float* h_state,
                                      float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax, int flags, prego_stream_t stream);
+/* Wide streaming step: prego_miniroad_step / prego_miniroad_step_anticipation for 1 <= n_streams <= 256, the array shapes following
+ * n_streams.  The weights cross the memory system once per call whatever n_streams is (csrc/stream_wide.hip): every product holds its weight
+ * fragments in registers and walks the streams in tiles of 16, and the anticipation classifier takes 16 rows per workgroup.
+ * Bits: a stream's out, argmax, new h_state, ant_out and ant_argmax are bit for bit what prego_miniroad_step (_anticipation) writes for that
+ * stream in a call of 5..16 streams (every sum keeps that order), whatever n_streams is and wherever the stream stands in the call; repeat
+ * calls are bit-identical.  With n_streams <= 16 the call IS prego_miniroad_step (_anticipation): its launches on the handle's own scratch
+ * (the fused LayerNorm up to 4 streams included); the workspace may then be NULL and the query returns 0.
+ *   workspace      device memory, 256-byte aligned, of at least prego_miniroad_step_wide_workspace_bytes(h, n_streams) bytes: the
+ *                  intermediates that grow with the call (16-bit copies of the frame and the state, y, e, gi, gh and, once set_anticipation
+ *                  has run, A [n_streams, ant_len * hid]; one size serves both entry points).  Query again after set_anticipation.
+ * Every output is nullable as in prego_miniroad_step (_anticipation); with ant_out and ant_argmax both NULL the anticipation head is not
+ * launched.  No device allocation, no host wait.  PREGO_EINVAL with a message, nothing written: n_streams outside 1..256, a NULL, unaligned
+ * or too small workspace above 16 streams, everything prego_miniroad_step refuses, and _anticipation before set_anticipation. */
+size_t prego_miniroad_step_wide_workspace_bytes(const prego_miniroad* h, int n_streams);
+int prego_miniroad_step_wide(prego_miniroad* h, int n_streams, const float* rgb, const float* flow, float* h_state, float* out,
+                             int32_t* argmax, int flags, void* workspace, size_t workspace_bytes, prego_stream_t stream);
+int prego_miniroad_step_wide_anticipation(prego_miniroad* h, int n_streams, const float* rgb, const float* flow, float* h_state,
+                                          float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax, int flags, void* workspace,
+                                          size_t workspace_bytes, prego_stream_t stream);
 
 /* Synchronises `stream` and reports a recurrence timeout (PREGO_ETIMEOUT) or HIP error since the last check. */
 int prego_miniroad_check(prego_miniroad* h, prego_stream_t stream);

@@ -41,6 +41,7 @@ SYMBOLS = [
     "prego_miniroad_set_anticipation", "prego_miniroad_forward_anticipation",
     "prego_miniroad_set_anticipation_grads", "prego_miniroad_adamw_step_anticipation",
     "prego_miniroad_step_anticipation",
+    "prego_miniroad_step_wide_workspace_bytes", "prego_miniroad_step_wide", "prego_miniroad_step_wide_anticipation",
 ]
 # include/prego_amd_debug.h: only in libprego_amd_debug.so
 DEBUG_SYMBOLS = ["prego_miniroad_debug_stamps", "prego_debug_gemm_bf16", "prego_debug_attention_bwd", "prego_debug_attention_fwd",
@@ -93,6 +94,10 @@ def _open(path: str, debug: bool) -> C.CDLL:
     lib.prego_miniroad_set_anticipation_grads.argtypes = [vp, C.POINTER(vp), vp, vp]
     lib.prego_miniroad_step.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp]
     lib.prego_miniroad_step_anticipation.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.prego_miniroad_step_wide_workspace_bytes.argtypes = [vp, i32]
+    lib.prego_miniroad_step_wide_workspace_bytes.restype = sz
+    lib.prego_miniroad_step_wide.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, sz, vp]
+    lib.prego_miniroad_step_wide_anticipation.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]
     lib.prego_miniroad_check.argtypes = [vp, vp]
     lib.prego_miniroad_timing_enable.argtypes = [vp, i32]
     lib.prego_miniroad_timing_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double),

@@ -356,3 +356,14 @@ int launch_stream_ant_hidden(const void* wa, const float* ba, const float* h_sta
 // ant_out [n][L][C] / ant_argmax [n][L] (each nullable) = softmax or logits / first argmax of A_l W_c^T + b_c
 int launch_stream_ant_head(const void* A, const void* wc, const float* bc, int n, int H, int L, int C, int softmax, float* ant_out,
                            int* ant_argmax, hipStream_t s, bool f16 = false);
+
+// wide streaming step (stream_wide.hip): the same arithmetic per output element for n <= 256 streams, weights read once per call.
+// xb [n][d_rgb + d_flow] / hb [n][H] = the fp32 frame (a NULL rgb / flow half: zeros) and state in the operand type (pack2_sat)
+int launch_wide_cast(const float* rgb, const float* flow, const float* h_state, void* xb, void* hb, int n, int d_rgb, int d_flow, int H,
+                     hipStream_t s, bool f16 = false);
+// launch_stream_gemv over ceil(n / 16) stream tiles; every problem takes 16-bit input rows in one piece (x_bf16, kx1 == K), no LayerNorm fusion
+int launch_wide_gemv(int nprob, const StreamGemv* pr, int n, hipStream_t s, bool f16 = false);
+// launch_stream_ant_hidden over the stream tiles / launch_stream_ant_head with 16 rows of the [n L] row list per workgroup
+int launch_wide_ant_hidden(const void* wa, const float* ba, const float* h_state, void* A, int n, int H, int L, hipStream_t s, bool f16 = false);
+int launch_wide_ant_head(const void* A, const void* wc, const float* bc, int n, int H, int L, int C, int softmax, float* ant_out,
+                         int* ant_argmax, hipStream_t s, bool f16 = false);

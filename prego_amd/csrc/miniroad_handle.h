@@ -3,7 +3,7 @@
 //   miniroad.cpp          error state (g_err, g_cur), create / destroy, weight setters, check, timing (ev_begin / ev_end), pass_info,
 //                         the debug library's allocation / wait counters (g_dbg_mallocs, g_dbg_syncs)
 //   miniroad_plan.cpp     build_plan, device_plan, stage_tables, feed events, row_bytes / fwd_layout and the workspace size
-//   miniroad_forward.cpp  validate_forward, choose_pass, run_chunked_pass, the forward entry points, prego_miniroad_step (_anticipation), ant_head
+//   miniroad_forward.cpp  validate_forward, choose_pass, run_chunked_pass, the forward entry points, prego_miniroad_step (_anticipation), prego_miniroad_step_wide (_anticipation), ant_head
 //   miniroad_split.cpp    ring / resident-buffer sizing, forward_split; the per-device order of split passes (g_split_mu, g_split_last)
 //   miniroad_train.cpp    dropout, loss, bwd_layout, backward, AdamW; the debug library's g_ant_full_span
 #pragma once

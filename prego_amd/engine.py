@@ -376,6 +376,53 @@ class MiniRoadEngine:
                 C.c_void_p(argmax.data_ptr()), _lib.FWD_SOFTMAX if softmax else 0, C.c_void_p(_stream_ptr(self.device))))
         return out, argmax
 
+    def step_wide(self, rgb: Optional[torch.Tensor], flow: Optional[torch.Tensor], h: torch.Tensor, softmax: bool = True,
+                  out: Optional[torch.Tensor] = None, argmax: Optional[torch.Tensor] = None, want_ant: bool = False,
+                  ant_out: Optional[torch.Tensor] = None, ant_argmax: Optional[torch.Tensor] = None):
+        """`step` for n <= 256 streams in one call (prego_miniroad_step_wide / _anticipation, csrc/stream_wide.hip): the weights are read once
+        per call whatever n is, and every stream's outputs and new state are bit for bit those of a 5..16-stream `step` (n <= 16 runs `step`'s
+        own launches).  Arguments, checks and return values are `step`'s.  The engine keeps one workspace tensor for the intermediates
+        that grow with n; it is grown here, outside the C call, when a larger n arrives.  Engines the streaming kernels are not built for
+        (fp32, fp16x2, hidden sizes other than 1024, two layers) take the general forward exactly as `step` does."""
+        d_rgb, d_flow, emb, hid, ncls = self.dims
+        if self.compute_dtype in ("fp32", "fp16x2") or hid != 1024 or self.num_layers != 1:
+            return self.step(rgb, flow, h, softmax=softmax, out=out, argmax=argmax, want_ant=want_ant, ant_out=ant_out, ant_argmax=ant_argmax)
+        if want_ant and not getattr(self, "ant_len", 0):
+            raise PregoError("step_wide(want_ant=True) before set_anticipation")
+        src = rgb if d_rgb > 0 else flow
+        if src is None:
+            raise PregoError("step_wide: a --no_rgb model needs the flow frame" if d_rgb == 0 else "step_wide: rgb is None")
+        n = src.shape[0]
+        L = self.ant_len if want_ant else 0
+        if out is None:
+            out = torch.empty((n, ncls), dtype=torch.float32, device=self.device)
+        if argmax is None:
+            argmax = torch.empty((n,), dtype=torch.int32, device=self.device)
+        if want_ant and ant_out is None:
+            ant_out = torch.empty((n, L, ncls), dtype=torch.float32, device=self.device)
+        if want_ant and ant_argmax is None:
+            ant_argmax = torch.empty((n, L), dtype=torch.int32, device=self.device)
+        checks = [(rgb if d_rgb > 0 else None, (n, d_rgb), torch.float32, "rgb"), (flow, (n, d_flow), torch.float32, "flow"),
+                  (h, (n, hid), torch.float32, "GRU state"), (out, (n, ncls), torch.float32, "out"), (argmax, (n,), torch.int32, "argmax")]
+        if want_ant:
+            checks += [(ant_out, (n, L, ncls), torch.float32, "anticipation out"), (ant_argmax, (n, L), torch.int32, "anticipation argmax")]
+        for t, shape, dt, what in checks:
+            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
+                raise PregoError(f"step_wide: expected {what} as contiguous {dt} cuda {list(shape)}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        need = self.lib.prego_miniroad_step_wide_workspace_bytes(self.h, n)
+        if need and (getattr(self, "_ws_wide", None) is None or self._ws_wide.numel() < need):
+            self._ws_wide = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._ws_wide if need else None
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        tail = (_lib.FWD_SOFTMAX if softmax else 0, p(ws), ws.numel() if ws is not None else 0, C.c_void_p(_stream_ptr(self.device)))
+        with torch.cuda.device(self.device):
+            if want_ant:
+                check(self.lib.prego_miniroad_step_wide_anticipation(self.h, n, p(rgb if d_rgb > 0 else None), p(flow), p(h), p(out), p(argmax),
+                                                                     p(ant_out), p(ant_argmax), *tail))
+                return out, argmax, ant_out, ant_argmax
+            check(self.lib.prego_miniroad_step_wide(self.h, n, p(rgb if d_rgb > 0 else None), p(flow), p(h), p(out), p(argmax), *tail))
+        return out, argmax
+
     # -- training ------------------------------------------------------------------------
     def set_dropout(self, p: float, seed: int):
         check(self.lib.prego_miniroad_set_dropout(self.h, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF))

@@ -130,6 +130,12 @@ class MROAD(nn.Module):
         (probabilities [n, C], argmax int32 [n]) - the eval branch of MROAD.forward (rnn.py:66-70) at T = 1 with h0 = h."""
         return self.engine().step(rgb, flow, h, softmax=True)
 
+    @torch.no_grad()
+    def step_wide(self, rgb, flow, h):
+        """`step` for up to 256 streams per call: the weights are read once per call whatever n is (csrc/stream_wide.hip), and every
+        stream's results are bit for bit those of a 5..16-stream `step`.  Returns what `step` returns."""
+        return self.engine().step_wide(rgb, flow, h, softmax=True)
+
 
 @META_ARCHITECTURES.register("MiniROADA")
 class MROADA(MROAD):
@@ -223,3 +229,8 @@ class MROADA(MROAD):
         MROADA.forward (rnn.py:131-135) at T = 1 with h0 = h; h is updated in place.  bf16 / fp16 models of hidden_dim 1024 run the
         streaming kernels (csrc/stream_step.hip, csrc/stream_ant.hip), the others the general forward."""
         return self.engine().step(rgb, flow, h, softmax=True, want_ant=True)
+
+    @torch.no_grad()
+    def step_wide(self, rgb, flow, h):
+        """`step` for up to 256 streams per call, the anticipation head included (csrc/stream_wide.hip).  Returns what `step` returns."""
+        return self.engine().step_wide(rgb, flow, h, softmax=True, want_ant=True)

@@ -19,6 +19,12 @@ median over all rounds (at least 200 frames per path and round); `round_us` is t
 (what a caller that issues frames back to back sees, host issue rate included).
 
     python scripts/anticipation_bench.py --step [--steps 200] [--warmup 20] [--rounds 4]
+
+--step --wide: more than 16 streams per frame time, n = 17 / 32 / 64 / 128 / 256 for MiniROAD and MiniROADA at L = 1 / 8 (zero flow), the
+same protocol: (w) step_wide (csrc/stream_wide.hip), (g) ceil(n / 16) `step` calls over 16-row views of the same tensors on one stream -
+what a caller had before (w) existed - and (c) the general forward at T = 1.  --models / --streams / --paths narrow the run.
+
+    python scripts/anticipation_bench.py --step --wide [--steps 200] [--warmup 20] [--rounds 4] [--streams 17,256] [--models L0,L8] [--paths w,g]
 """
 from __future__ import annotations
 
@@ -52,13 +58,17 @@ def main():
     ap.add_argument("--train", action="store_true")
     ap.add_argument("--step", action="store_true")
     ap.add_argument("--rounds", type=int, default=4)
+    ap.add_argument("--wide", action="store_true", help="with --step: step_wide against the loop of 16-stream steps")
+    ap.add_argument("--streams", default="17,32,64,128,256")
+    ap.add_argument("--models", default="L0,L1,L8", help="L0 = MiniROAD, Lk = MiniROADA with anticipation_length k")
+    ap.add_argument("--paths", default="w,g,c")
     a = ap.parse_args()
     if a.warmup is None:
         a.warmup = 20 if (a.train or a.step) else 1
     if a.train:
         return train_bench(a)
     if a.step:
-        return step_bench(a)
+        return step_wide_bench(a) if a.wide else step_bench(a)
     dev = "cuda:0"
     lens = workloads.assembly101_eval_lengths()
     if a.clips:
@@ -223,6 +233,76 @@ def step_bench(a):
             t["b_minus_a_us"] = t["b_mroada_step"]["median_us"] - t["a_mroad_step"]["median_us"]
         del m
     print(json.dumps({"metric": "per-frame device time, us (median of device-event pairs around every frame; zero flow)", "dtype": a.dtype,
+                      "frames_per_path_and_round": frames, "rounds": a.rounds, "table": table}))
+
+
+def step_wide_bench(a):
+    dev, H, C = "cuda:0", 1024, 86
+    frames = max(a.steps, 200)
+    base = assembly101_cfg(compute_dtype=a.dtype, assume_zero_flow=True)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1234)
+    x = torch.randn((16, 256, 2048), device=dev, generator=gen).clamp_(min=0)
+    table = {}
+    for name in a.models.split(","):
+        L = int(name[1:])
+        cfg = anticipation_cfg(base, L) if L else base
+        sd = W.miniroad_a_state_dict(cfg, 20, head_gain=8.0, ant_gain=4.0) if L else W.miniroad_state_dict(base, 20, head_gain=8.0)
+        m = build_model(cfg, dev)
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+        m.eval()
+        eng, ant = m.engine(), L > 0
+        for n in (int(s) for s in a.streams.split(",")):
+            xs = [x[i, :n].contiguous() for i in range(16)]
+            rows = [[xs[i][k:k + 1] for k in range(n)] for i in range(16)]
+            out, arg = torch.empty((n, C), device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
+            ao, aa = (torch.empty((n, L, C), device=dev), torch.empty((n, L), dtype=torch.int32, device=dev)) if ant else (None, None)
+            hs = {k: torch.zeros((n, H), device=dev) for k in "wgc"}
+            groups = [(lo, min(lo + 16, n)) for lo in range(0, n, 16)]
+            views = [[xs[i][lo:hi] for lo, hi in groups] for i in range(16)]
+            gv = [(hs["g"][lo:hi], out[lo:hi], arg[lo:hi], ao[lo:hi] if ant else None, aa[lo:hi] if ant else None) for lo, hi in groups]
+
+            def fw(i):
+                eng.step_wide(xs[i & 15], None, hs["w"], out=out, argmax=arg, want_ant=ant, ant_out=ao, ant_argmax=aa)
+
+            def fg(i):
+                for xv, (hv, ov, av, aov, aav) in zip(views[i & 15], gv):
+                    eng.step(xv, None, hv, out=ov, argmax=av, want_ant=ant, ant_out=aov, ant_argmax=aav)
+
+            def fc(i):
+                r = eng.forward_ragged(rows[i & 15], None, softmax=True, want_out=True, want_argmax=True, h0=hs["c"], want_h_last=True, want_ant=ant)
+                hs["c"] = r[2]
+            paths = {k: f for k, f in (("w", fw), ("g", fg), ("c", fc)) if k in a.paths.split(",")}
+            times, rounds = {k: [] for k in paths}, {k: [] for k in paths}
+            for f in paths.values():
+                for i in range(a.warmup):
+                    f(i)
+            torch.cuda.synchronize()
+            for _ in range(a.rounds):
+                for k, f in paths.items():
+                    evs = [torch.cuda.Event(enable_timing=True) for _ in range(2 * frames)]
+                    r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    r0.record()
+                    for i in range(frames):
+                        evs[2 * i].record()
+                        f(i)
+                        evs[2 * i + 1].record()
+                    r1.record()
+                    torch.cuda.synchronize()
+                    times[k] += [evs[2 * i].elapsed_time(evs[2 * i + 1]) * 1e3 for i in range(frames)]
+                    rounds[k].append(r0.elapsed_time(r1) * 1e3 / frames)
+            eng.check()
+            t = {k: {"median_us": float(np.median(v)), "p10_us": float(np.percentile(v, 10)), "p90_us": float(np.percentile(v, 90)),
+                     "round_us": float(np.median(rounds[k]))} for k, v in times.items()}
+            if "w" in t and "g" in t:
+                t["g_minus_w_us"] = t["g"]["median_us"] - t["w"]["median_us"]
+                t["spreads_us"] = (t["g"]["p90_us"] - t["g"]["p10_us"]) + (t["w"]["p90_us"] - t["w"]["p10_us"])
+                t["w_below_g_by_more_than_the_spreads"] = t["g_minus_w_us"] > t["spreads_us"]
+            table[f"{name}_n{n}"] = t
+            print(json.dumps({f"{name}_n{n}": t}), file=sys.stderr, flush=True)
+        del m, eng
+    print(json.dumps({"metric": "per-frame device time, us (median of device-event pairs around every frame; zero flow): w = step_wide, "
+                                "g = ceil(n / 16) step calls, c = general forward at T = 1", "dtype": a.dtype,
                       "frames_per_path_and_round": frames, "rounds": a.rounds, "table": table}))
 
 
