@@ -320,6 +320,14 @@ int prego_window_vote(const int32_t* argmax, int64_t n_frames, int window, int n
  * device int32, set to 1 when an id is out of range (its text is then "  0,": the caller must not use the text). */
 int prego_format_ids(const int32_t* ids, int64_t n, uint32_t* text, int32_t* bad, prego_stream_t stream);
 
+/* fp32 feature rows -> the 16-bit operand type, with the conversion the pack kernels apply (so a forward with
+ * PREGO_FWD_IN16 on dst gives the bits of a forward on src).  n elements, n % 8 == 0; src, dst 16-byte aligned,
+ * not overlapping; dtype PREGO_BF16 or PREGO_F16.  n == 0: nothing is launched.  Round to nearest even; PREGO_F16 saturates at
+ * +-65504.  PREGO_EINVAL with a message, nothing launched: a NULL pointer, negative n, n % 8 != 0, a misaligned pointer, overlap, any
+ * other dtype.  An addition to ABI 7 (existing signatures unchanged): what an evaluator that keeps its eval set in device memory
+ * between calls converts its fp32 features with, once. */
+int prego_cast_features(const float* src, void* dst, int64_t n, int dtype, prego_stream_t stream);
+
 /* utils/metrics.py:25-62 on the device: sklearn.metrics.average_precision_score of every class column of the per-frame score
  * matrix the eval loop collects (trainer/eval.py:48-57; main.py:101 runs it after every epoch).  scores / target: device fp32
  * [n_frames][n_classes] row-major (target != 0 marks a positive).  Thresholds are the distinct score values (ties share one),

@@ -42,6 +42,7 @@ SYMBOLS = [
     "prego_miniroad_set_anticipation_grads", "prego_miniroad_adamw_step_anticipation",
     "prego_miniroad_step_anticipation",
     "prego_miniroad_step_wide_workspace_bytes", "prego_miniroad_step_wide", "prego_miniroad_step_wide_anticipation",
+    "prego_cast_features",
 ]
 # include/prego_amd_debug.h: only in libprego_amd_debug.so
 DEBUG_SYMBOLS = ["prego_miniroad_debug_stamps", "prego_debug_gemm_bf16", "prego_debug_attention_bwd", "prego_debug_attention_fwd",
@@ -118,6 +119,7 @@ def _open(path: str, debug: bool) -> C.CDLL:
     lib.prego_miniroad_pass_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.prego_window_vote.argtypes = [vp, i64, i32, i32, vp, vp]
     lib.prego_format_ids.argtypes = [vp, i64, vp, vp, vp]
+    lib.prego_cast_features.argtypes = [vp, vp, i64, i32, vp]
     lib.prego_perframe_ap_workspace_bytes.argtypes = [i64, i32]
     lib.prego_perframe_ap_workspace_bytes.restype = sz
     lib.prego_perframe_ap.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, sz, vp]

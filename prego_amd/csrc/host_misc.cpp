@@ -25,6 +25,25 @@ extern "C" int prego_format_ids(const int32_t* ids, int64_t n, uint32_t* text, i
 }
 
 // ================================================================================================
+// Evaluate's feature cache: fp32 feature rows -> the handle's 16-bit operand type, once (feature_cache.hip)
+// ================================================================================================
+extern "C" int prego_cast_features(const float* src, void* dst, int64_t n, int dtype, prego_stream_t stream) {
+  if (!src || !dst) return prego_fail_(PREGO_EINVAL, "cast_features: NULL argument");
+  if (dtype != PREGO_BF16 && dtype != PREGO_F16) return prego_fail_(PREGO_EINVAL, "cast_features: dtype %d (PREGO_BF16 or PREGO_F16)", dtype);
+  if (n < 0 || n % 8) return prego_fail_(PREGO_EINVAL, "cast_features: n %lld (>= 0, a multiple of 8)", (long long)n);
+  const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst;
+  if (s0 % 16 || d0 % 16) return prego_fail_(PREGO_EINVAL, "cast_features: src and dst must be 16-byte aligned");
+  if (s0 < d0 + (uintptr_t)n * 2 && d0 < s0 + (uintptr_t)n * 4) return prego_fail_(PREGO_EINVAL, "cast_features: src and dst overlap");
+  if (n == 0) return PREGO_OK;
+  int dev = 0, n_cu = 0;
+  HIPCHK(hipGetDevice(&dev));
+  HIPCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+  launch_cast_features(dtype == PREGO_F16, src, dst, n, n_cu, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+// ================================================================================================
 // metric: utils/metrics.py:25-62 (per-class average precision of the per-frame scores) on the device
 // ================================================================================================
 extern "C" size_t prego_perframe_ap_workspace_bytes(int64_t n_frames, int n_classes) {

@@ -285,6 +285,9 @@ size_t perframe_ap_workspace_bytes(long long n_frames, int n_classes);
 int launch_perframe_ap(const float* scores, const float* target, const int* labels, long long n_frames, int n_classes, double* ap, long long* n_pos,
                        double* score_sum, void* workspace, hipStream_t s);
 
+// Evaluate's feature cache (feature_cache.hip): n fp32 values -> bf16 / fp16 (f16) with the pack kernels' conversion; n % 8 == 0, n > 0
+void launch_cast_features(bool f16, const float* src, void* dst, long long n, int n_cu, hipStream_t s);
+
 // split pass (round 6): rows gate * H + u of a 16-bit [3H][E] matrix and an fp32 [3H] vector -> rows (u / 2) * 6 + 2 * gate + u % 2 (rowwise.hip)
 void launch_permute_gi_rows(const void* w, const float* bias, void* w_perm, float* bias_perm, int H, int E, hipStream_t s);
 

@@ -19,6 +19,7 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from .eval_cache import EvalFeatureCache
 from .metrics import (perframe_ap_raw, perframe_ap_raw_device, perframe_average_precision, perframe_average_precision_device,
                       report_from_raw)
 from .registry import EVAL
@@ -47,6 +48,9 @@ class Evaluate(nn.Module):
         self.last_fps = None
         self._copy_stream = None             # side stream for the H2D feature copies (double buffering against the compute stream)
         self._ap_stream = None               # side stream of the metric's kernels (enqueued behind the last forward)
+        # cfg['eval_cache_device'] (not a reference key): the eval set's features stay in device memory between calls (eval_cache.py)
+        self._cache = EvalFeatureCache(cfg.get("eval_cache_max_bytes")) if cfg.get("eval_cache_device", False) else None
+        self.last_source = None              # "loader" | "cache": where the last call took its features from
 
     @staticmethod
     def _new_copy_stream(dev):
@@ -166,7 +170,17 @@ class Evaluate(nn.Module):
             flow = None if flows is None else [None if f is None else f.to(device) for f in flows]
             tgt = self._targets_to_device([b[2] for b in sub], dev)
         probs, args, _ = model.forward_clips(rgb, flow, want_probs=True, want_argmax=True)
-        return probs, args, tgt
+        return probs, args, tgt, rgb, flow
+
+    @staticmethod
+    def _enqueue_resident(model, batch):
+        """a batch cut from the feature cache: ONE forward on the resident tensors, whatever the batch's size - nothing to copy, so nothing
+        to hide behind a first part (forward_ragged provides the resident buffer and the library picks the pass, as for any
+        device-resident call)"""
+        flow = [b[1] for b in batch]
+        probs, args, _ = model.forward_clips([b[0] for b in batch], None if all(f is None for f in flow) else flow, want_probs=True,
+                                             want_argmax=True)
+        return probs, args, [b[2] for b in batch]
 
     # link-fed eval: frames per H2D piece; one feed event per ~EVENT_BYTES copied.  A copy costs ~10 us of fixed time whatever its size, so
     # large pieces keep the link busier (182-video set, 16-bit features: 2 048 frames 226 ms to the last id, 4 096: 220, 8 192: 215.5) -
@@ -242,10 +256,11 @@ class Evaluate(nn.Module):
         for t in tgt:
             t.record_stream(cur)
         cur.wait_event(ready)
-        return probs, args, tgt
+        return probs, args, tgt, rgb, flow
 
-    def _flush(self, model, batch, device):
-        """enqueue one batch (H2D + forward + argmax ids D2H): nothing here waits for the GPU.  Returns the record _collect finishes."""
+    def _flush(self, model, batch, device, resident=False):
+        """enqueue one batch (H2D + forward + argmax ids D2H): nothing here waits for the GPU.  Returns the record _collect finishes.
+        resident: the batch comes from the feature cache (device tensors, targets in their device form)."""
         if not batch:
             return None
         # Pinned host features + a model that can be fed while it runs: ONE link-fed forward (_enqueue_link_fed).  Otherwise a batch
@@ -258,7 +273,7 @@ class Evaluate(nn.Module):
         on_gpu = torch.device(device).type == "cuda"
         link_fed = on_gpu and bool(getattr(model, "link_fed_eval", False)) and bool(self.cfg.get("eval_link_fed", True)) and len(batch) >= 2 and \
             all(b[0].device.type == "cpu" and b[0].is_pinned() and (b[1] is None or (b[1].device.type == "cpu" and b[1].is_pinned())) for b in batch)
-        if len(batch) >= 16 and on_gpu and not link_fed and self.cfg.get("eval_split_by_length", True):
+        if len(batch) >= 16 and on_gpu and not link_fed and not resident and self.cfg.get("eval_split_by_length", True):
             order.sort(key=lambda i: -frames[i])
             # share of the frames in the first part: its forward should last about as long as the second part's copy.  Measured on
             # the 60-video bench set (scripts/eval_e2e_bench.py): fp32 features 0.2: 4.23, 0.5: 4.72, 0.6: 4.41 M frames/s;
@@ -273,21 +288,27 @@ class Evaluate(nn.Module):
             if k >= 1:
                 parts = [order[:k], order[k:]]
         res = {}
-        if link_fed:
-            probs, args, tgt = self._enqueue_link_fed(model, batch, device)
+        fed = {}                             # batch index -> (rgb, flow or None) as the forward read them on the device: what the cache keeps
+        if resident:
+            for i, (p, a, t) in enumerate(zip(*self._enqueue_resident(model, batch))):
+                res[i] = (p, a, t)
+        elif link_fed:
+            probs, args, tgt, rgb, flow = self._enqueue_link_fed(model, batch, device)
             for i, (p, a, t) in enumerate(zip(probs, args, tgt)):
                 res[i] = (p, a, t)
+                fed[i] = (rgb[i], None if flow is None else flow[i])
         else:
             for part in parts:
-                probs, args, tgt = self._enqueue(model, [batch[i] for i in part], device)
-                for i, p, a, t in zip(part, probs, args, tgt):
+                probs, args, tgt, rgb, flow = self._enqueue(model, [batch[i] for i in part], device)
+                for k, (i, p, a, t) in enumerate(zip(part, probs, args, tgt)):
                     res[i] = (p, a, t)
+                    fed[i] = (rgb[k], None if flow is None else flow[k])
         want_json = self.cfg["eval"] is not None
         # np.argmax of the one-hot targets (eval.py:55) on the device, where they are anyway for the AP kernel (on the host it reads
         # frames x classes floats through one core: 25 ms for the bench set); ONE device -> host copy of the whole batch's pred and gt
         # ids is ENQUEUED here (into pinned memory, behind the forward) and waited for in _collect - one batch later, so that the next
         # batch's copies and forward are already running while the host waits for these ids and formats their text
-        rec = {"items": [(vid, res[i]) for i, (r, f, target, vid) in enumerate(batch)], "ids": None, "ev": None, "link_fed": link_fed,
+        rec = {"items": [(b[3], res[i]) for i, b in enumerate(batch)], "ids": None, "ev": None, "link_fed": link_fed,
                "src": list(batch), "feed": getattr(self, "_feed_events", None)}       # the loader's tensors / the feed events stay alive until _collect
         if want_json:
             pred_ids = torch.cat([res[i][1] for i in range(len(batch))])
@@ -320,6 +341,12 @@ class Evaluate(nn.Module):
                 rec["ids"], rec["ev"], rec["_keep"] = ids_host, ev, ids_dev
             else:                                  # a stand-in model on a CPU box (the gloo tests of the sharding logic)
                 rec["ids"] = ids_dev
+        if self._cache is not None and self._cache.filling:
+            # behind everything this batch's ids wait for: the features (fp32 ones of a 16-bit engine converted by prego_cast_features, on
+            # this stream, behind the forward that read them) and the device targets stay; an fp32 source lives until _collect drops rec
+            n = range(len(batch))
+            self._cache.retain(batch, [fed[i][0] for i in n], [fed[i][1] for i in n], [res[i][2] for i in n], torch.device(device))
+            rec["fed"] = fed
         batch.clear()
         return rec
 
@@ -352,8 +379,11 @@ class Evaluate(nn.Module):
                         json_parts += [json.dumps(str(vid)).encode() + b': {"pred": [', tp, b', "gt": [', tg, b"}"]
                     else:
                         json_parts += self._json_int_lists({vid: output[vid]}, as_parts=True)
+                if self._cache is not None and self._cache.filling:
+                    self._cache.gt_ids[vid] = output[vid]["gt"].copy()
                 o += n
                 self.last_device_argmax[vid] = a          # int32 on the device: input of aggregate_device (utils/aggregate.py)
+        rec.pop("fed", None)                 # a filling call's device features: what the cache does not keep (fp32 sources of its 16-bit copies) goes now
 
     def _cat_targets(self, gt_targets, matrix=False):
         """the eval set's ground truth: one class-id vector [frames] when every video came as class ids (and the caller takes them), else
@@ -372,16 +402,73 @@ class Evaluate(nn.Module):
                 pred_scores.append(p)
                 gt_targets.append(t)
 
+    def _loader_videos(self, model, dataloader, world, rank, skip_flow):
+        """this rank's videos as the loop below batches them, one list per loader item: (features, flow or None, target rows, name,
+        position in the loader's order, loader item)"""
+        pos = 0
+        for item, (rgb_input, flow_input, target, vid, start, end) in enumerate(dataloader):
+            group = []
+            # loader items carry a leading batch dim of test_batch_size == 1 (dataset_builder.py:19)
+            for b in range(rgb_input.shape[0]):
+                mine = (pos % world) == rank
+                pos += 1
+                if not mine:
+                    continue
+                name = vid[b] if isinstance(vid, (list, tuple)) else vid
+                fl = None if (skip_flow or self._flow_zero(model, flow_input[b])) else self._features(model, flow_input[b])
+                group.append((self._features(model, rgb_input[b]), fl, target[b], name, pos - 1, item))
+            yield group
+
     def eval(self, model, dataloader, logger, device):
+        """One pass over the eval set.  With cfg['eval_cache_device'] (off by default; eval_cache.py) the first call on a loader also
+        leaves its features in device memory - at most cfg['eval_cache_max_bytes'], by default half of what is free at the first batch;
+        a set that does not fit is not cached, which is no error - and later calls on the same dataset object, feature signature and
+        (world, rank) take them from there: the loader is not iterated, the results are bit for bit the first call's for the same
+        weights.  Features changed IN PLACE inside the same dataset object are not detected: call drop_cache().  `last_source` says
+        where a call's features came from ("loader" | "cache"), `cache_info()` what is held."""
         model.eval()
-        output = {}
-        self.last_device_argmax = {}
-        max_clips = model.max_clips          # MROAD: the engine's clip capacity; ViTEnc (`model: 'Transformer'`): its own bound
         # data-parallel eval: videos are independent, so under torch.distributed rank r takes every world-th video of
         # the loader's order (no data-path collective); rank 0 gathers the per-video results once at the end
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         rank = dist.get_rank() if world > 1 else 0
         skip_flow = self._zero_flow(model, dataloader)
+        cache = self._cache
+        self.last_source = "loader"
+        if cache is None:
+            return self._eval_pass(model, self._loader_videos(model, dataloader, world, rank, skip_flow), logger, device, world, rank)
+        op16 = {"fp16": torch.float16, "bf16": torch.bfloat16}.get(getattr(model, "compute_dtype", None)) if hasattr(model, "engine") else None
+        keep = op16 or torch.float32         # a 16-bit engine reads 16-bit operands; every other model what _features ships
+        sig = (getattr(model, "d_rgb", None), getattr(model, "d_flow", None), keep, skip_flow, world, rank, str(torch.device(device)))
+        if cache.begin(getattr(dataloader, "dataset", dataloader), sig, torch.device(device), keep, logger):
+            self.last_source = "cache"
+            videos = cache.videos()
+        else:
+            videos = self._loader_videos(model, dataloader, world, rank, skip_flow)
+        try:
+            result = self._eval_pass(model, videos, logger, device, world, rank)
+        except BaseException:
+            cache.abort()
+            raise
+        cache.commit()
+        return result
+
+    def drop_cache(self):
+        """release the cached eval set (cfg['eval_cache_device']); the next call iterates the loader and fills the cache again"""
+        if self._cache is not None:
+            self._cache.drop()
+
+    def cache_info(self) -> dict:
+        """enabled, state ("empty" | "filled" | "disabled"), reason (why disabled), videos, frames, bytes (device memory), dtype"""
+        if self._cache is None:
+            return dict(enabled=False, state="disabled", reason="cfg['eval_cache_device'] is off", videos=0, frames=0, bytes=0, dtype=None)
+        return self._cache.info()
+
+    def _eval_pass(self, model, videos, logger, device, world, rank):
+        """`videos`: _loader_videos, or the feature cache's record of them (device tensors: every batch is one resident forward)"""
+        output = {}
+        self.last_device_argmax = {}
+        max_clips = model.max_clips          # MROAD: the engine's clip capacity; ViTEnc (`model: 'Transformer'`): its own bound
+        resident = self.last_source == "cache"
         with torch.no_grad():
             pred_scores, gt_targets = [], []
             per_video = []                       # (loader position, n_frames) to restore the loader's order on rank 0
@@ -389,24 +476,17 @@ class Evaluate(nn.Module):
             t0_ = time.perf_counter()
             self.phase_log = []                  # (phase, host seconds since the start of this eval): where an end-to-end eval spends its time
             mark = lambda name: self.phase_log.append((name, time.perf_counter() - t0_))
-            batch, frames, pos = [], 0, 0
+            batch, frames = [], 0
             pending = None                       # the batch whose launch is out and whose host half (_collect) is still due
             json_parts = [] if (self.cfg["eval"] is not None and world == 1) else None      # per-video JSON text, formatted batch by batch
-            for rgb_input, flow_input, target, vid, start, end in dataloader:
-                # loader items carry a leading batch dim of test_batch_size == 1 (dataset_builder.py:19)
-                for b in range(rgb_input.shape[0]):
-                    mine = (pos % world) == rank
-                    pos += 1
-                    if not mine:
-                        continue
-                    name = vid[b] if isinstance(vid, (list, tuple)) else vid
-                    fl = None if (skip_flow or self._flow_zero(model, flow_input[b])) else self._features(model, flow_input[b])
-                    batch.append((self._features(model, rgb_input[b]), fl, target[b], name))
-                    per_video.append((pos - 1, int(rgb_input.shape[1])))
-                    frames += rgb_input.shape[1]
+            for group in videos:
+                for it in group:
+                    batch.append(it)
+                    per_video.append((it[4], int(it[0].shape[0])))
+                    frames += int(it[0].shape[0])
                 if len(batch) >= max_clips or frames >= self.max_frames_per_batch:
                     mark("loader")
-                    rec = self._flush(model, batch, device)                 # batch k: enqueued ...
+                    rec = self._flush(model, batch, device, resident)       # batch k: enqueued ...
                     self._scores(rec, pred_scores, gt_targets)
                     mark("launch")
                     self._collect(pending, pred_scores, gt_targets, output, json_parts)      # ... while the host finishes batch k - 1
@@ -414,7 +494,7 @@ class Evaluate(nn.Module):
                     pending = rec
                     frames = 0
             mark("loader")
-            rec = self._flush(model, batch, device)
+            rec = self._flush(model, batch, device, resident)
             self._scores(rec, pred_scores, gt_targets)
             finish_ap = None
             if world == 1 and torch.device(device).type == "cuda" and self.metric == "AP" and pred_scores:
