@@ -224,6 +224,57 @@ int prego_miniroad_step_wide_anticipation(prego_miniroad* h, int n_streams, cons
                                           float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax, int flags, void* workspace,
                                           size_t workspace_bytes, prego_stream_t stream);
 
+/* Stream pool (an addition to ABI 7, existing signatures unchanged): the online detector for a host whose streams open and close at
+ * different times and of which only some have a new frame at any tick.  Every live video owns a SLOT of one device block: its GRU state
+ * row (rnn.py:58-62 with h0 = the previous frame's state) and its running aggregation record - utils/aggregate.py:55-78 fed one id at a
+ * time: the votes of the unfinished `window`-frame window and the list of (step id, first frame) events so far.  The pool object is host
+ * memory (geometry, the addresses inside the caller's block); it owns no device memory.
+ *   block           device memory, 256-byte aligned, at least prego_stream_pool_bytes(h, capacity, max_events) bytes, the caller's:
+ *                   h [capacity][hid] fp32 at offset 0, then the records.  create enqueues its zeroing on `stream`; an all-zero slot is an
+ *                   empty stream (zero state, no frames), so opening a stream needs no call.
+ *   record of a slot (prego_stream_pool_record gives its address and size for ONE D2H copy), int32 words:
+ *                   [0] frames  [1] last vote + 1 (0 = none yet)  [2] n_events  [3] overflow  [4 ..) counts[n_classes rounded up to 4]
+ *                   event_id[max_events]  event_start[max_events]
+ *                   aggregate.py:75-78's results follow as pred = event_id[0 .. n_events) and
+ *                   changes_pred = event_start[1 .. n_events) + {frames} (after a flush; before it the last finished window ends at
+ *                   frames - frames % window).
+ *   update rule     one id of a slot: counts[id]++, frames++; when frames % window == 0 the window votes for the lowest id with the
+ *                   maximal count (np.argmax(np.bincount(.)), aggregate.py:60), the counts are cleared, and when the vote differs from
+ *                   the previous window's (or is the first) the event (vote, frame at which the window began) is appended.  A full
+ *                   record sets bit 0 of overflow and drops the event (nothing is written past max_events); an id outside
+ *                   [0, n_classes) sets bit 1 and counts nothing (np.bincount raises there; prego_window_vote marks it with -1).
+ *   slots           HOST int32 [n]: which slots a call addresses, 1 <= n <= min(256, capacity), each in [0, capacity) and named once.
+ *                   The list travels in the kernel arguments: it may be freed or reused as soon as the call returns.
+ * prego_miniroad_step_pool: one new frame for the slots named, in three steps on `stream` - the slots' state rows are gathered into a dense
+ * [n_active, hid] copy in the workspace, prego_miniroad_step_wide (_anticipation when ant_out or ant_argmax is non-NULL) runs on it
+ * through its own entry point, the new rows go back to their slots and every slot's record takes its argmax.  rgb, flow, out, argmax,
+ * ant_out, ant_argmax: dense, row i belongs to slots[i], with prego_miniroad_step_wide's shapes and nullability (a NULL argmax: the ids
+ * go through the workspace).  Bits: a stream's outputs and its new state in the pool are bit for bit what prego_miniroad_step_wide writes
+ * for a dense call of the same n_active streams; they depend neither on the slot numbers nor on the order of `slots` (the pool adds
+ * no arithmetic).  Two launches more than prego_miniroad_step_wide; no device allocation, no host wait.
+ *   workspace       device memory, 256-byte aligned, prego_miniroad_step_pool_workspace_bytes(h, n_active) bytes: the dense state, the
+ *                   argmax vector and prego_miniroad_step_wide's workspace.  Query again after set_anticipation.
+ * prego_stream_pool_vote: the record update alone, ids device int32 [n] from anywhere (the Transformer path, a general forward).
+ * prego_stream_pool_flush: votes the unfinished window of each slot, the reference's shorter last window (aggregate.py:57-58); a slot
+ * whose frames are a multiple of `window`, or that was flushed already, is left as it is.  prego_stream_pool_reset: zeroes state and record.
+ * PREGO_EINVAL with a message, nothing launched: n outside 1..min(256, capacity), a slot outside [0, capacity), a slot named twice, a
+ * NULL, unaligned or too small block or workspace, window < 1, max_events < 1, capacity or max_events above 1 048 576, a pool created for
+ * another hidden size or class count, and everything prego_miniroad_step_wide refuses (fp32 / fp16x2 handles, hidden_dim != 1024, two
+ * layers; ant_out / ant_argmax before set_anticipation).  A pool belongs to one stream at a time, as a handle does. */
+typedef struct prego_stream_pool prego_stream_pool;
+size_t prego_stream_pool_bytes(const prego_miniroad* h, int capacity, int max_events);
+int prego_stream_pool_create(prego_stream_pool** out, const prego_miniroad* h, int capacity, int window, int max_events, void* device_block,
+                             size_t bytes, prego_stream_t stream);
+void prego_stream_pool_destroy(prego_stream_pool* p);
+size_t prego_miniroad_step_pool_workspace_bytes(const prego_miniroad* h, int n_active);
+int prego_miniroad_step_pool(prego_miniroad* h, prego_stream_pool* p, int n_active, const int32_t* slots, const float* rgb, const float* flow,
+                             float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax, int flags, void* workspace,
+                             size_t workspace_bytes, prego_stream_t stream);
+int prego_stream_pool_vote(prego_stream_pool* p, int n, const int32_t* slots, const int32_t* ids, prego_stream_t stream);
+int prego_stream_pool_flush(prego_stream_pool* p, int n, const int32_t* slots, prego_stream_t stream);
+int prego_stream_pool_reset(prego_stream_pool* p, int n, const int32_t* slots, prego_stream_t stream);
+int prego_stream_pool_record(const prego_stream_pool* p, int slot, const void** device_record, size_t* bytes);
+
 /* Synchronises `stream` and reports a recurrence timeout (PREGO_ETIMEOUT) or HIP error since the last check. */
 int prego_miniroad_check(prego_miniroad* h, prego_stream_t stream);
 

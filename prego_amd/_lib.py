@@ -43,6 +43,8 @@ SYMBOLS = [
     "prego_miniroad_step_anticipation",
     "prego_miniroad_step_wide_workspace_bytes", "prego_miniroad_step_wide", "prego_miniroad_step_wide_anticipation",
     "prego_cast_features",
+    "prego_stream_pool_bytes", "prego_stream_pool_create", "prego_stream_pool_destroy", "prego_miniroad_step_pool_workspace_bytes",
+    "prego_miniroad_step_pool", "prego_stream_pool_vote", "prego_stream_pool_flush", "prego_stream_pool_reset", "prego_stream_pool_record",
 ]
 # include/prego_amd_debug.h: only in libprego_amd_debug.so
 DEBUG_SYMBOLS = ["prego_miniroad_debug_stamps", "prego_debug_gemm_bf16", "prego_debug_attention_bwd", "prego_debug_attention_fwd",
@@ -99,6 +101,18 @@ def _open(path: str, debug: bool) -> C.CDLL:
     lib.prego_miniroad_step_wide_workspace_bytes.restype = sz
     lib.prego_miniroad_step_wide.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, sz, vp]
     lib.prego_miniroad_step_wide_anticipation.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]
+    lib.prego_stream_pool_bytes.argtypes = [vp, i32, i32]
+    lib.prego_stream_pool_bytes.restype = sz
+    lib.prego_stream_pool_create.argtypes = [C.POINTER(vp), vp, i32, i32, i32, vp, sz, vp]
+    lib.prego_stream_pool_destroy.argtypes = [vp]
+    lib.prego_stream_pool_destroy.restype = None
+    lib.prego_miniroad_step_pool_workspace_bytes.argtypes = [vp, i32]
+    lib.prego_miniroad_step_pool_workspace_bytes.restype = sz
+    lib.prego_miniroad_step_pool.argtypes = [vp, vp, i32, C.POINTER(C.c_int32), vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]
+    lib.prego_stream_pool_vote.argtypes = [vp, i32, C.POINTER(C.c_int32), vp, vp]
+    lib.prego_stream_pool_flush.argtypes = [vp, i32, C.POINTER(C.c_int32), vp]
+    lib.prego_stream_pool_reset.argtypes = [vp, i32, C.POINTER(C.c_int32), vp]
+    lib.prego_stream_pool_record.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz)]
     lib.prego_miniroad_check.argtypes = [vp, vp]
     lib.prego_miniroad_timing_enable.argtypes = [vp, i32]
     lib.prego_miniroad_timing_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double),

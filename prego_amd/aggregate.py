@@ -1,7 +1,9 @@
 """Per-frame argmax -> 200-frame majority vote -> step sequence (utils/aggregate.py:46-90), the wire format
 into step_anticipation.  `aggregate` is the host (numpy) form over the JSON the eval loop wrote;
 `aggregate_device` takes the int32 per-frame argmax tensors the head kernel left in HBM and runs the majority vote there
-(`prego_window_vote`, csrc/postproc.hip): one int32 per 200-frame window crosses PCIe instead of one per frame."""
+(`prego_window_vote`, csrc/postproc.hip): one int32 per 200-frame window crosses PCIe instead of one per frame.
+`aggregate_online` / `OnlineRecord` is the same rule fed one id at a time: the host model of the record a stream pool keeps per slot
+(prego_amd/stream_pool.py, csrc/stream_pool.hip)."""
 from __future__ import annotations
 
 import json
@@ -38,6 +40,66 @@ def aggregate(data: dict, output_path: str | None = None, window_size: int = 200
         with open(output_path, "w") as fp:
             json.dump(out, fp)
     return out
+
+
+OVERFLOW_FULL, OVERFLOW_BAD_ID = 1, 2          # bits of a stream-pool record's `overflow` word (csrc/stream_pool.hip)
+
+
+class OnlineRecord:
+    """Host model of one slot's vote record in a stream pool (csrc/stream_pool.hip: pool_vote_update / pool_flush), fed one id at a time:
+    utils/aggregate.py:55-78 without the per-frame list.  `counts` holds the votes of the unfinished window, an event is (id, frame at
+    which its window began); a full record or an id outside [0, n_classes) sets a bit of `overflow` instead of writing."""
+
+    def __init__(self, window: int = 200, n_classes: int = 128, max_events: int = 1024):
+        if window < 1 or max_events < 1 or not 1 <= n_classes <= 128:
+            raise ValueError(f"OnlineRecord: window {window}, n_classes {n_classes} (1..128), max_events {max_events}")
+        self.window, self.n_classes, self.max_events = int(window), int(n_classes), int(max_events)
+        self.frames, self.counts, self.last_vote, self.overflow = 0, [0] * self.n_classes, None, 0
+        self.event_id, self.event_start, self.voted_to = [], [], 0
+
+    def _close_window(self, start: int):
+        vote = max(range(self.n_classes), key=lambda c: (self.counts[c], -c))        # np.argmax(np.bincount(.)): the lowest id wins a tie
+        self.counts = [0] * self.n_classes
+        if vote != self.last_vote:
+            if len(self.event_id) < self.max_events:
+                self.event_id.append(vote)
+                self.event_start.append(start)
+            else:
+                self.overflow |= OVERFLOW_FULL
+        self.last_vote, self.voted_to = vote, self.frames
+
+    def push(self, idx: int):
+        idx = int(idx)
+        if not 0 <= idx < self.n_classes:
+            self.overflow |= OVERFLOW_BAD_ID
+            return
+        self.counts[idx] += 1
+        self.frames += 1
+        if self.frames % self.window == 0:
+            self._close_window(self.frames - self.window)
+
+    def flush(self):
+        """the reference's shorter last window (aggregate.py:57-58: e = min(s + window, len))"""
+        rest = self.frames % self.window
+        if rest and any(self.counts):
+            self._close_window(self.frames - rest)
+
+    def result(self) -> dict:
+        """{'pred', 'changes_pred'} of the windows voted so far (an unfinished window counts once flushed) and the frames fed"""
+        return {"pred": list(self.event_id), "changes_pred": list(self.event_start[1:]) + [self.voted_to], "frames": self.frames}
+
+
+def aggregate_online(ids, window: int = 200, n_classes: int = 128, max_events: int = 1 << 30) -> dict:
+    """`aggregate`'s 'pred' / 'changes_pred' of one stream from its per-frame ids, fed one id at a time through the record a stream pool
+    keeps per slot and flushed at the end."""
+    rec = OnlineRecord(window, n_classes, max_events)
+    for i in ids:
+        rec.push(i)
+    rec.flush()
+    if rec.overflow:
+        raise ValueError(f"aggregate_online: overflow {rec.overflow} (1: more than {max_events} events, 2: an id outside [0, {n_classes}))")
+    r = rec.result()
+    return {"pred": r["pred"], "changes_pred": r["changes_pred"]}
 
 
 def aggregate_device(preds: dict, gts: dict, output_path: str | None = None, window_size: int = 200, n_classes: int | None = None) -> dict:

@@ -288,6 +288,23 @@ int launch_perframe_ap(const float* scores, const float* target, const int* labe
 // Evaluate's feature cache (feature_cache.hip): n fp32 values -> bf16 / fp16 (f16) with the pack kernels' conversion; n % 8 == 0, n > 0
 void launch_cast_features(bool f16, const float* src, void* dst, long long n, int n_cu, hipStream_t s);
 
+// stream pool (stream_pool.hip): slot-addressed GRU state rows and per-slot vote records in the caller's device block
+constexpr int kPoolMaxActive = 256;      // slots one call may name
+constexpr int kPoolRecHeader = 4;        // record words in front of the counts: frames, last vote + 1, n_events, overflow
+constexpr int kPoolOverflowFull = 1, kPoolOverflowBadId = 2;      // bits of the overflow word
+struct PoolGeom {
+  float* h;                              // [capacity][hid] fp32
+  int* rec;                              // [capacity][rec_words]: header | counts[ncls_pad] | event_id[max_events] | event_start[max_events]
+  int hid, ncls, ncls_pad, window, max_events, rec_words, capacity;
+};
+struct PoolSlots { int s[kPoolMaxActive]; };      // the slot list of one call, by value in the kernel arguments
+// slots: HOST, n in 1..256, every slot in [0, capacity) and named once (the caller checks duplicates); -1 = refused, nothing launched
+int launch_pool_gather(const PoolGeom& g, const int* slots, int n, float* h_ws, hipStream_t s);
+int launch_pool_commit(const PoolGeom& g, const int* slots, int n, const float* h_ws, const int* argmax, hipStream_t s);
+int launch_pool_vote(const PoolGeom& g, const int* slots, int n, const int* ids, hipStream_t s);
+int launch_pool_flush(const PoolGeom& g, const int* slots, int n, hipStream_t s);
+int launch_pool_reset(const PoolGeom& g, const int* slots, int n, hipStream_t s);
+
 // split pass (round 6): rows gate * H + u of a 16-bit [3H][E] matrix and an fp32 [3H] vector -> rows (u / 2) * 6 + 2 * gate + u % 2 (rowwise.hip)
 void launch_permute_gi_rows(const void* w, const float* bias, void* w_perm, float* bias_perm, int H, int E, hipStream_t s);
 

@@ -505,8 +505,8 @@ extern "C" int prego_miniroad_forward_anticipation(prego_miniroad* h, int n_clip
   return forward_impl(h, FwdCall{n_clips, lens, rgb, flow, out, argmax, ao, h0, h_last, flags, workspace, workspace_bytes, (hipStream_t)stream});
 }
 
-// what every streaming step refuses, n_max = 16 (step) or 256 (step_wide) streams per call; 0 = the call may go ahead
-static int step_refusals(prego_miniroad* h, int n_streams, int n_max, const float* rgb, const float* flow, const float* h_state, bool ant) {
+// what every streaming step refuses, n_max = 16 (step) or 256 (step_wide, step_pool) streams per call; 0 = the call may go ahead
+int step_refusals(prego_miniroad* h, int n_streams, int n_max, const float* rgb, const float* flow, const float* h_state, bool ant) {
   if (!h) return prego_fail_(PREGO_EINVAL, "handle is NULL");
   if (!h->have_weights) return prego_fail_(PREGO_EINVAL, "step before set_weights");
   if (!h->bf16) return prego_fail_(PREGO_EINVAL, "step: the streaming fast path takes bf16 / fp16 handles (fp32 / fp16x2 operands: use forward() with h0 / h_last)");

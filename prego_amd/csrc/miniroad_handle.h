@@ -4,6 +4,7 @@
 //                         the debug library's allocation / wait counters (g_dbg_mallocs, g_dbg_syncs)
 //   miniroad_plan.cpp     build_plan, device_plan, stage_tables, feed events, row_bytes / fwd_layout and the workspace size
 //   miniroad_forward.cpp  validate_forward, choose_pass, run_chunked_pass, the forward entry points, prego_miniroad_step (_anticipation), prego_miniroad_step_wide (_anticipation), ant_head
+//   stream_pool.cpp       the stream pool: prego_stream_pool_*, prego_miniroad_step_pool (kernels: stream_pool.hip)
 //   miniroad_split.cpp    ring / resident-buffer sizing, forward_split; the per-device order of split passes (g_split_mu, g_split_last)
 //   miniroad_train.cpp    dropout, loss, bwd_layout, backward, AdamW; the debug library's g_ant_full_span
 #pragma once
@@ -222,5 +223,7 @@ int forward_split(prego_miniroad* h, const AntOut& ao, int R, int flags, bool wi
 // the anticipation head of a forward_anticipation call over packed rows [row0, row0 + nrows) of the plan, relu(h) rows at HR (chunk-relative);
 // the destinations come from the plan (the same lookup in every pass: which pass ran changes no bit)
 int ant_head(prego_miniroad* h, const AntOut& ao, const void* HR, const SlotPlan& plan, int row0, int nrows, int flags, hipStream_t s);
+// what every streaming step refuses, n_max streams per call (16: step, 256: step_wide, step_pool); 0 = the call may go ahead.  Under a HandleScope
+int step_refusals(prego_miniroad* h, int n_streams, int n_max, const float* rgb, const float* flow, const float* h_state, bool ant);
 
 #pragma GCC visibility pop

@@ -1,0 +1,169 @@
+// Host side of the stream pool (include/prego_amd.h: prego_stream_pool_*, prego_miniroad_step_pool; kernels: stream_pool.hip).  The pool
+// object is host memory only: the geometry, the addresses inside the caller's device block and a stamp table for the duplicate check.
+// Every entry point validates the whole slot list before its first launch, so a refused call has launched nothing.
+#include "miniroad_handle.h"
+
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+struct prego_stream_pool {
+  PoolGeom g;
+  size_t bytes;                          // of the block, as laid out
+  std::vector<unsigned> stamp;           // [capacity]: the call that last named the slot (duplicate check without a per-call allocation)
+  unsigned call = 0;
+};
+
+namespace {
+struct PoolLayout { size_t h_bytes, rec_words, total; };
+
+// block: h [capacity][hid] fp32 | records [capacity][rec_words] int32, each part 256-byte aligned
+PoolLayout pool_layout(int hid, int ncls, int capacity, int max_events) {
+  PoolLayout l{};
+  const size_t ncls_pad = align_up((size_t)ncls, 4);
+  l.rec_words = align_up((size_t)kPoolRecHeader + ncls_pad + 2 * (size_t)max_events, 4);
+  l.h_bytes = align_up((size_t)capacity * hid * 4, 256);
+  l.total = l.h_bytes + align_up((size_t)capacity * l.rec_words * 4, 256);
+  return l;
+}
+
+bool pool_shape_ok(int capacity, int max_events) { return capacity >= 1 && capacity <= (1 << 20) && max_events >= 1 && max_events <= (1 << 20); }
+
+// the slot list of one call: n in 1..min(256, capacity), every slot inside the pool and named once
+int check_slots(prego_stream_pool* p, const char* who, int n, const int32_t* slots) {
+  const int n_max = p->g.capacity < kPoolMaxActive ? p->g.capacity : kPoolMaxActive;
+  if (n < 1 || n > n_max)
+    return prego_fail_(PREGO_EINVAL, "%s: %d slots (1..%d per call: at most %d, pool capacity %d)", who, n, n_max, kPoolMaxActive, p->g.capacity);
+  if (!slots) return prego_fail_(PREGO_EINVAL, "%s: slots is NULL", who);
+  for (int i = 0; i < n; ++i)
+    if (slots[i] < 0 || slots[i] >= p->g.capacity)
+      return prego_fail_(PREGO_EINVAL, "%s: slots[%d] = %d is outside the pool (capacity %d)", who, i, slots[i], p->g.capacity);
+  if (++p->call == 0) {                                       // the counter wrapped: old stamps could alias
+    std::fill(p->stamp.begin(), p->stamp.end(), 0u);
+    p->call = 1;
+  }
+  for (int i = 0; i < n; ++i) {
+    if (p->stamp[(size_t)slots[i]] == p->call) return prego_fail_(PREGO_EINVAL, "%s: slot %d is named twice", who, slots[i]);
+    p->stamp[(size_t)slots[i]] = p->call;
+  }
+  return 0;
+}
+
+// dense state [n][hid] fp32 | argmax [n] int32 | the wide step's own workspace, each part 256-byte aligned
+struct StepPoolLayout { size_t am, wide, wide_bytes, total; };
+StepPoolLayout step_pool_layout(const prego_miniroad* h, int n) {
+  StepPoolLayout l{};
+  l.am = align_up((size_t)n * h->hid * 4, 256);
+  l.wide = l.am + align_up((size_t)n * 4, 256);
+  l.wide_bytes = prego_miniroad_step_wide_workspace_bytes(h, n);      // 0 up to 16 streams: step's launches on the handle's scratch
+  l.total = l.wide + l.wide_bytes;
+  return l;
+}
+}  // namespace
+
+extern "C" size_t prego_stream_pool_bytes(const prego_miniroad* h, int capacity, int max_events) {
+  if (!h || !pool_shape_ok(capacity, max_events)) return 0;
+  return pool_layout(h->hid, h->ncls, capacity, max_events).total;
+}
+
+extern "C" int prego_stream_pool_create(prego_stream_pool** out, const prego_miniroad* h, int capacity, int window, int max_events,
+                                        void* device_block, size_t bytes, prego_stream_t stream) {
+  if (!out) return prego_fail_(PREGO_EINVAL, "stream_pool_create: out is NULL");
+  *out = nullptr;
+  if (!h) return prego_fail_(PREGO_EINVAL, "stream_pool_create: handle is NULL");
+  if (window < 1) return prego_fail_(PREGO_EINVAL, "stream_pool_create: window %d (>= 1)", window);
+  if (!pool_shape_ok(capacity, max_events))
+    return prego_fail_(PREGO_EINVAL, "stream_pool_create: capacity %d, max_events %d (each 1..%d)", capacity, max_events, 1 << 20);
+  const PoolLayout l = pool_layout(h->hid, h->ncls, capacity, max_events);
+  if (!device_block || bytes < l.total)
+    return prego_fail_(PREGO_EINVAL, "stream_pool_create: block %p with %zu bytes, %d slots of %d events need %zu (prego_stream_pool_bytes)",
+                       device_block, bytes, capacity, max_events, l.total);
+  if ((uintptr_t)device_block & 255) return prego_fail_(PREGO_EINVAL, "stream_pool_create: the block must be 256-byte aligned");
+  prego_stream_pool* p = new prego_stream_pool();
+  p->g = PoolGeom{(float*)device_block, (int*)((char*)device_block + l.h_bytes), h->hid, h->ncls, (int)align_up((size_t)h->ncls, 4), window,
+                  max_events, (int)l.rec_words, capacity};
+  p->bytes = l.total;
+  p->stamp.assign((size_t)capacity, 0u);
+  const hipError_t e = hipMemsetAsync(device_block, 0, l.total, (hipStream_t)stream);      // every slot empty: open launches nothing
+  if (e != hipSuccess) {
+    delete p;
+    return prego_fail_(PREGO_EHIP, "stream_pool_create: hipMemsetAsync failed: %s", hipGetErrorString(e));
+  }
+  *out = p;
+  return PREGO_OK;
+}
+
+extern "C" void prego_stream_pool_destroy(prego_stream_pool* p) { delete p; }
+
+extern "C" size_t prego_miniroad_step_pool_workspace_bytes(const prego_miniroad* h, int n_active) {
+  if (!h || n_active < 1 || n_active > kPoolMaxActive) return 0;
+  return step_pool_layout(h, n_active).total;
+}
+
+extern "C" int prego_miniroad_step_pool(prego_miniroad* h, prego_stream_pool* p, int n_active, const int32_t* slots, const float* rgb,
+                                        const float* flow, float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax, int flags,
+                                        void* workspace, size_t workspace_bytes, prego_stream_t stream) {
+  const bool ant = ant_out != nullptr || ant_argmax != nullptr;
+  StepPoolLayout l{};
+  {
+    HandleScope scope_(h);
+    if (!p) return prego_fail_(PREGO_EINVAL, "step_pool: pool is NULL");
+    // everything the wide step would refuse, before the gather is launched (the state it will be handed is the workspace's dense copy)
+    if (int rc = step_refusals(h, n_active, kPoolMaxActive, rgb, flow, p->g.h, ant)) return rc;
+    if (p->g.hid != h->hid || p->g.ncls != h->ncls)
+      return prego_fail_(PREGO_EINVAL, "step_pool: the pool was created for hidden_dim %d / %d classes, the handle has %d / %d", p->g.hid,
+                         p->g.ncls, h->hid, h->ncls);
+    if (int rc = check_slots(p, "step_pool", n_active, slots)) return rc;
+    l = step_pool_layout(h, n_active);
+    if (!workspace || workspace_bytes < l.total)
+      return prego_fail_(PREGO_EINVAL, "step_pool: workspace %p with %zu bytes, %d active streams need %zu (prego_miniroad_step_pool_workspace_bytes)",
+                         workspace, workspace_bytes, n_active, l.total);
+    if ((uintptr_t)workspace & 255) return prego_fail_(PREGO_EINVAL, "step_pool: the workspace must be 256-byte aligned");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  float* h_ws = (float*)ws;
+  int32_t* am = argmax ? argmax : (int32_t*)(ws + l.am);      // the vote always has its ids
+  if (launch_pool_gather(p->g, slots, n_active, h_ws, s)) return prego_fail_(PREGO_EINVAL, "step_pool: gather refused its arguments");
+  // the dense call a caller without a pool would make, through the same entry point: the pool adds no arithmetic
+  const int rc = ant ? prego_miniroad_step_wide_anticipation(h, n_active, rgb, flow, h_ws, out, am, ant_out, ant_argmax, flags, ws + l.wide,
+                                                             l.wide_bytes, stream)
+                     : prego_miniroad_step_wide(h, n_active, rgb, flow, h_ws, out, am, flags, ws + l.wide, l.wide_bytes, stream);
+  if (rc) return rc;                                          // the pool itself is untouched: only the commit writes it
+  if (launch_pool_commit(p->g, slots, n_active, h_ws, am, s)) return prego_fail_(PREGO_EINVAL, "step_pool: commit refused its arguments");
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+extern "C" int prego_stream_pool_vote(prego_stream_pool* p, int n, const int32_t* slots, const int32_t* ids, prego_stream_t stream) {
+  if (!p) return prego_fail_(PREGO_EINVAL, "stream_pool_vote: pool is NULL");
+  if (!ids) return prego_fail_(PREGO_EINVAL, "stream_pool_vote: ids is NULL");
+  if (int rc = check_slots(p, "stream_pool_vote", n, slots)) return rc;
+  if (launch_pool_vote(p->g, slots, n, ids, (hipStream_t)stream)) return prego_fail_(PREGO_EINVAL, "stream_pool_vote: bad arguments");
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+extern "C" int prego_stream_pool_flush(prego_stream_pool* p, int n, const int32_t* slots, prego_stream_t stream) {
+  if (!p) return prego_fail_(PREGO_EINVAL, "stream_pool_flush: pool is NULL");
+  if (int rc = check_slots(p, "stream_pool_flush", n, slots)) return rc;
+  if (launch_pool_flush(p->g, slots, n, (hipStream_t)stream)) return prego_fail_(PREGO_EINVAL, "stream_pool_flush: bad arguments");
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+extern "C" int prego_stream_pool_reset(prego_stream_pool* p, int n, const int32_t* slots, prego_stream_t stream) {
+  if (!p) return prego_fail_(PREGO_EINVAL, "stream_pool_reset: pool is NULL");
+  if (int rc = check_slots(p, "stream_pool_reset", n, slots)) return rc;
+  if (launch_pool_reset(p->g, slots, n, (hipStream_t)stream)) return prego_fail_(PREGO_EINVAL, "stream_pool_reset: bad arguments");
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+extern "C" int prego_stream_pool_record(const prego_stream_pool* p, int slot, const void** device_record, size_t* bytes) {
+  if (!p || !device_record || !bytes) return prego_fail_(PREGO_EINVAL, "stream_pool_record: NULL argument");
+  if (slot < 0 || slot >= p->g.capacity) return prego_fail_(PREGO_EINVAL, "stream_pool_record: slot %d is outside the pool (capacity %d)", slot, p->g.capacity);
+  *device_record = p->g.rec + (size_t)slot * p->g.rec_words;
+  *bytes = (size_t)p->g.rec_words * 4;
+  return PREGO_OK;
+}

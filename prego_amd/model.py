@@ -136,6 +136,15 @@ class MROAD(nn.Module):
         stream's results are bit for bit those of a 5..16-stream `step`.  Returns what `step` returns."""
         return self.engine().step_wide(rgb, flow, h, softmax=True)
 
+    @torch.no_grad()
+    def stream_pool(self, capacity: int = 256, window: int = 200, max_events: int = 1024):
+        """A StreamPool (prego_amd/stream_pool.py) on this model's inference engine: every live video owns a slot with its GRU state and
+        its running aggregation record; `push(slots, rgb, flow)` advances any subset by one frame with `step_wide`'s bits (MiniROADA: the
+        anticipation head included), `close(slot)` returns the stream's 'pred' / 'changes_pred' (utils/aggregate.py:46-90).  Built after
+        the weights are final: the pool keeps the engine it was built on."""
+        from .stream_pool import StreamPool
+        return StreamPool(self, capacity=capacity, window=window, max_events=max_events)
+
 
 @META_ARCHITECTURES.register("MiniROADA")
 class MROADA(MROAD):

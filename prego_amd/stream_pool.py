@@ -1,0 +1,225 @@
+"""Stream pool: the online detector as one object.  Every live video owns a SLOT of one device block - its GRU state row and its running
+aggregation record (utils/aggregate.py:46-90, one id at a time) - and `push` advances any subset of the slots by one frame with the wide
+step's bits (prego_miniroad_step_pool: gather, the unchanged prego_miniroad_step_wide, commit + vote; csrc/stream_pool.hip).  `close`
+returns what `aggregate` would return for the stream's per-frame predictions ('pred', 'changes_pred'); no argmax crosses to the host on
+the way.  `SlotTable` is the host bookkeeping (which slots are open), usable without a device."""
+from __future__ import annotations
+
+import ctypes as C
+import heapq
+
+import torch
+
+from ._lib import PregoError
+from .aggregate import OVERFLOW_BAD_ID, OVERFLOW_FULL
+
+REC_HEADER = 4               # frames, last vote + 1, n_events, overflow (csrc/stream_pool.hip)
+MAX_ACTIVE = 256             # slots per call
+
+
+class SlotTable:
+    """Which slots of a pool are open.  open() hands out the lowest free slot."""
+
+    def __init__(self, capacity: int):
+        if capacity < 1:
+            raise PregoError(f"stream pool: capacity {capacity} (>= 1)")
+        self.capacity = int(capacity)
+        self._free = list(range(self.capacity))          # a heap: range() is one already
+        self._open = set()
+
+    @property
+    def free(self) -> int:
+        return len(self._free)
+
+    def is_open(self, slot: int) -> bool:
+        return slot in self._open
+
+    def open(self) -> int:
+        if not self._free:
+            raise PregoError(f"stream pool: all {self.capacity} slots are open")
+        slot = heapq.heappop(self._free)
+        self._open.add(slot)
+        return slot
+
+    def release(self, slot: int):
+        self.check([slot], "close")
+        self._open.remove(slot)
+        heapq.heappush(self._free, slot)
+
+    def check(self, slots, who: str) -> list:
+        """the slot list of one call as ints: 1..min(256, capacity) open slots, each named once"""
+        slots = [int(s) for s in slots]
+        n_max = min(MAX_ACTIVE, self.capacity)
+        if not 1 <= len(slots) <= n_max:
+            raise PregoError(f"stream pool {who}: {len(slots)} slots (1..{n_max} per call)")
+        seen = set()
+        for s in slots:
+            if s not in self._open:
+                raise PregoError(f"stream pool {who}: slot {s} is not open" + ("" if 0 <= s < self.capacity else f" (capacity {self.capacity})"))
+            if s in seen:
+                raise PregoError(f"stream pool {who}: slot {s} is named twice")
+            seen.add(s)
+        return slots
+
+
+class StreamPool:
+    """StreamPool(model_or_engine, capacity=256, window=200, max_events=1024): `capacity` slots of GRU state + vote record in one device
+    block; a record holds up to `max_events` (step id, first frame) events of `window`-frame majority votes.
+    `push` needs an engine the streaming kernels are built for (bf16 / fp16 operands, hidden_dim 1024, one GRU layer); `vote`, `events`
+    and `close` serve every engine (ids from the Transformer path or a general forward)."""
+
+    def __init__(self, model_or_engine, capacity: int = 256, window: int = 200, max_events: int = 1024):
+        from .engine import _stream_ptr
+        eng = model_or_engine.engine() if hasattr(model_or_engine, "engine") else model_or_engine
+        self.engine, self.lib, self.device = eng, eng.lib, eng.device
+        self.window, self.max_events = int(window), int(max_events)
+        self.slots = SlotTable(capacity)
+        self._stream_ptr = _stream_ptr
+        d_rgb, d_flow, emb, hid, ncls = eng.dims
+        self._hid, self._ncls, self._ncls_pad = hid, ncls, (ncls + 3) // 4 * 4
+        self._fast = eng.compute_dtype in ("bf16", "fp16") and hid == 1024 and eng.num_layers == 1
+        need = self.lib.prego_stream_pool_bytes(eng.h, int(capacity), self.max_events)
+        if need == 0:
+            raise PregoError(f"stream pool: capacity {capacity}, max_events {max_events} (each 1..{1 << 20})")
+        self._block = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._ws = None
+        p = C.c_void_p()
+        with torch.cuda.device(self.device):
+            rc = self.lib.prego_stream_pool_create(C.byref(p), eng.h, int(capacity), self.window, self.max_events, C.c_void_p(self._block.data_ptr()),
+                                                   need, C.c_void_p(_stream_ptr(self.device)))
+        self._check(rc)
+        self.p = p
+
+    def __del__(self):
+        try:
+            if getattr(self, "p", None):
+                self.lib.prego_stream_pool_destroy(self.p)
+                self.p = None
+        except Exception:
+            pass
+
+    def _check(self, rc: int):
+        if rc != 0:
+            raise PregoError(f"prego_amd error {rc}: {self.lib.prego_last_error().decode()}")
+
+    # -- bookkeeping ---------------------------------------------------------------------------
+    @property
+    def capacity(self) -> int:
+        return self.slots.capacity
+
+    @property
+    def free(self) -> int:
+        return self.slots.free
+
+    def open(self) -> int:
+        """the lowest free slot; it is zero (after create, after close), so nothing is launched"""
+        return self.slots.open()
+
+    @staticmethod
+    def _slot_array(slots):
+        return (C.c_int32 * len(slots))(*slots)
+
+    # -- one frame for a subset of the streams ---------------------------------------------------
+    def push(self, slots, rgb, flow=None, softmax: bool = True, want_ant=None, out=None, argmax=None, ant_out=None, ant_argmax=None):
+        """One new frame for each open slot of `slots`: rgb [n, d_rgb] / flow [n, d_flow] (None = zero flow) fp32 cuda contiguous, rows in
+        `slots` order.  Returns step_wide's tuple - (out [n, C], argmax int32 [n]) and, with want_ant (default: the model has an
+        anticipation head), (ant_out [n, L, C], ant_argmax int32 [n, L]) - bit for bit what step_wide returns for a dense call of these
+        streams; each slot's state is advanced and its record takes the frame's argmax.  Pass buffers to reuse them."""
+        eng = self.engine
+        if not self._fast:
+            raise PregoError(f"stream pool push: the streaming kernels are built for bf16 / fp16 operands, hidden_dim 1024, one GRU layer "
+                             f"(this engine: {eng.compute_dtype}, hidden_dim {self._hid}, {eng.num_layers} layers); run the general forward "
+                             "and feed its ids to vote()")
+        slots = self.slots.check(slots, "push")
+        n = len(slots)
+        d_rgb, d_flow, emb, hid, ncls = eng.dims
+        if want_ant is None:
+            want_ant = bool(getattr(eng, "ant_len", 0))
+        if want_ant and not getattr(eng, "ant_len", 0):
+            raise PregoError("stream pool push(want_ant=True) before set_anticipation")
+        if (rgb if d_rgb > 0 else flow) is None:
+            raise PregoError("stream pool push: a --no_rgb model needs the flow frame" if d_rgb == 0 else "stream pool push: rgb is None")
+        L = eng.ant_len if want_ant else 0
+        if out is None:
+            out = torch.empty((n, ncls), dtype=torch.float32, device=self.device)
+        if argmax is None:
+            argmax = torch.empty((n,), dtype=torch.int32, device=self.device)
+        if want_ant and ant_out is None:
+            ant_out = torch.empty((n, L, ncls), dtype=torch.float32, device=self.device)
+        if want_ant and ant_argmax is None:
+            ant_argmax = torch.empty((n, L), dtype=torch.int32, device=self.device)
+        checks = [(rgb if d_rgb > 0 else None, (n, d_rgb), torch.float32, "rgb"), (flow, (n, d_flow), torch.float32, "flow"),
+                  (out, (n, ncls), torch.float32, "out"), (argmax, (n,), torch.int32, "argmax")]
+        if want_ant:
+            checks += [(ant_out, (n, L, ncls), torch.float32, "anticipation out"), (ant_argmax, (n, L), torch.int32, "anticipation argmax")]
+        for t, shape, dt, what in checks:
+            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
+                raise PregoError(f"stream pool push: expected {what} as contiguous {dt} cuda {list(shape)}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        need = self.lib.prego_miniroad_step_pool_workspace_bytes(eng.h, n)
+        if self._ws is None or self._ws.numel() < need:          # grown here, outside the C call
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(self.device):
+            rc = self.lib.prego_miniroad_step_pool(eng.h, self.p, n, self._slot_array(slots), p(rgb if d_rgb > 0 else None), p(flow), p(out),
+                                                   p(argmax), p(ant_out) if want_ant else None, p(ant_argmax) if want_ant else None,
+                                                   1 if softmax else 0, p(self._ws), self._ws.numel(), C.c_void_p(self._stream_ptr(self.device)))
+        self._check(rc)
+        return (out, argmax, ant_out, ant_argmax) if want_ant else (out, argmax)
+
+    def vote(self, slots, ids):
+        """Aggregation alone: ids (int32 cuda [n], or a host sequence) are the new frame's step ids of `slots`, from whatever produced them."""
+        slots = self.slots.check(slots, "vote")
+        if not isinstance(ids, torch.Tensor):
+            ids = torch.tensor([int(i) for i in ids], dtype=torch.int32).to(self.device)
+        if not ids.is_cuda or ids.dtype != torch.int32 or not ids.is_contiguous() or tuple(ids.shape) != (len(slots),):
+            raise PregoError(f"stream pool vote: expected ids as contiguous int32 cuda [{len(slots)}], got {tuple(ids.shape)} {ids.dtype} on {ids.device}")
+        with torch.cuda.device(self.device):
+            rc = self.lib.prego_stream_pool_vote(self.p, len(slots), self._slot_array(slots), C.c_void_p(ids.data_ptr()),
+                                                 C.c_void_p(self._stream_ptr(self.device)))
+        self._check(rc)
+
+    # -- reading a slot ------------------------------------------------------------------------
+    def _record(self, slot: int):
+        """one D2H copy of the slot's record (it waits for the stream): (frames, overflow, event ids, event starts)"""
+        ptr, nbytes = C.c_void_p(), C.c_size_t()
+        self._check(self.lib.prego_stream_pool_record(self.p, slot, C.byref(ptr), C.byref(nbytes)))
+        off = ptr.value - self._block.data_ptr()
+        w = self._block[off:off + nbytes.value].view(torch.int32).cpu().numpy()
+        n_ev = int(w[2])
+        e0 = REC_HEADER + self._ncls_pad
+        return int(w[0]), int(w[3]), [int(v) for v in w[e0:e0 + n_ev]], [int(v) for v in w[e0 + self.max_events:e0 + self.max_events + n_ev]]
+
+    def events(self, slot: int) -> dict:
+        """{'pred', 'changes_pred', 'frames'}: the step sequence of the slot's finished windows so far ('changes_pred' ends where the last
+        finished window ends) and the frames it has taken.  One small D2H copy; it waits."""
+        slot = self.slots.check([slot], "events")[0]
+        frames, overflow, ev_id, ev_start = self._record(slot)
+        self._raise_overflow(slot, overflow)
+        return {"pred": ev_id, "changes_pred": ev_start[1:] + [frames - frames % self.window], "frames": frames}
+
+    def _raise_overflow(self, slot: int, overflow: int):
+        if overflow & OVERFLOW_BAD_ID:
+            raise PregoError(f"stream pool: slot {slot} was fed a step id outside [0, {self._ncls}) (np.bincount of utils/aggregate.py:60 would raise)")
+        if overflow & OVERFLOW_FULL:
+            raise PregoError(f"stream pool: slot {slot} produced more than max_events = {self.max_events} events; the record dropped the rest")
+
+    def close(self, slot: int) -> dict:
+        """Ends the stream: votes its unfinished window, reads the record (one D2H copy), zeroes the slot and frees it.  Returns
+        {'pred', 'changes_pred'} as utils/aggregate.py:46-90 gives them for the stream's per-frame predictions; a stream closed before its
+        first frame returns {'pred': [], 'changes_pred': [0]}.  Raises PregoError, the slot freed all the same, if the record overflowed
+        or met an id outside the classes."""
+        slot = self.slots.check([slot], "close")[0]
+        arr, s = self._slot_array([slot]), C.c_void_p(self._stream_ptr(self.device))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.prego_stream_pool_flush(self.p, 1, arr, s))
+            frames, overflow, ev_id, ev_start = self._record(slot)
+            self._check(self.lib.prego_stream_pool_reset(self.p, 1, arr, s))
+        self.slots.release(slot)
+        self._raise_overflow(slot, overflow)
+        return {"pred": ev_id, "changes_pred": ev_start[1:] + [frames]}
+
+    def state(self, slot: int):
+        """a clone of the slot's GRU state [hid]"""
+        slot = self.slots.check([slot], "state")[0]
+        return self._block[:self.capacity * self._hid * 4].view(torch.float32).view(self.capacity, self._hid)[slot].clone()
+

@@ -25,6 +25,13 @@ same protocol: (w) step_wide (csrc/stream_wide.hip), (g) ceil(n / 16) `step` cal
 what a caller had before (w) existed - and (c) the general forward at T = 1.  --models / --streams / --paths narrow the run.
 
     python scripts/anticipation_bench.py --step --wide [--steps 200] [--warmup 20] [--rounds 4] [--streams 17,256] [--models L0,L8] [--paths w,g]
+
+--step --pool: the stream pool (prego_amd/stream_pool.py), n_active = 4 / 16 / 64 / 256 scattered slots of a 256-slot pool for MiniROAD and
+MiniROADA at L = 8 (zero flow), the same protocol: (p) StreamPool.push, (w) the dense step_wide on the same streams - the lower bound, the
+pool can only add to it - and (t) the route a caller has without the pool: index_select the active states out of a table, step_wide,
+index_copy_ them back, argmax.cpu(), the window vote on the host.  `p_minus_w_us` stands beside two kernel boundaries.
+
+    python scripts/anticipation_bench.py --step --pool [--steps 200] [--warmup 20] [--rounds 4] [--streams 4,256] [--models L0,L8]
 """
 from __future__ import annotations
 
@@ -59,16 +66,19 @@ def main():
     ap.add_argument("--step", action="store_true")
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--wide", action="store_true", help="with --step: step_wide against the loop of 16-stream steps")
-    ap.add_argument("--streams", default="17,32,64,128,256")
-    ap.add_argument("--models", default="L0,L1,L8", help="L0 = MiniROAD, Lk = MiniROADA with anticipation_length k")
+    ap.add_argument("--pool", action="store_true", help="with --step: StreamPool.push against the dense step_wide and the torch route around it")
+    ap.add_argument("--streams", default=None, help="default: 17,32,64,128,256 (--wide), 4,16,64,256 (--pool)")
+    ap.add_argument("--models", default=None, help="L0 = MiniROAD, Lk = MiniROADA with anticipation_length k; default: L0,L1,L8 (--wide), L0,L8 (--pool)")
     ap.add_argument("--paths", default="w,g,c")
     a = ap.parse_args()
     if a.warmup is None:
         a.warmup = 20 if (a.train or a.step) else 1
     if a.train:
         return train_bench(a)
+    a.streams = a.streams or ("4,16,64,256" if a.pool else "17,32,64,128,256")
+    a.models = a.models or ("L0,L8" if a.pool else "L0,L1,L8")
     if a.step:
-        return step_wide_bench(a) if a.wide else step_bench(a)
+        return step_pool_bench(a) if a.pool else step_wide_bench(a) if a.wide else step_bench(a)
     dev = "cuda:0"
     lens = workloads.assembly101_eval_lengths()
     if a.clips:
@@ -304,6 +314,84 @@ def step_wide_bench(a):
     print(json.dumps({"metric": "per-frame device time, us (median of device-event pairs around every frame; zero flow): w = step_wide, "
                                 "g = ceil(n / 16) step calls, c = general forward at T = 1", "dtype": a.dtype,
                       "frames_per_path_and_round": frames, "rounds": a.rounds, "table": table}))
+
+
+def step_pool_bench(a):
+    import random
+
+    from prego_amd.aggregate import OnlineRecord
+    dev, H, C, cap = "cuda:0", 1024, 86, 256
+    frames = max(a.steps, 200)
+    base = assembly101_cfg(compute_dtype=a.dtype, assume_zero_flow=True)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1234)
+    x = torch.randn((16, 256, 2048), device=dev, generator=gen).clamp_(min=0)
+    table = {}
+    for name in a.models.split(","):
+        L = int(name[1:])
+        cfg = anticipation_cfg(base, L) if L else base
+        sd = W.miniroad_a_state_dict(cfg, 20, head_gain=8.0, ant_gain=4.0) if L else W.miniroad_state_dict(base, 20, head_gain=8.0)
+        m = build_model(cfg, dev)
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+        m.eval()
+        eng, ant = m.engine(), L > 0
+        for n in (int(s) for s in a.streams.split(",")):
+            pool = m.stream_pool(capacity=cap)
+            for _ in range(cap):
+                pool.open()
+            slots = random.Random(n).sample(range(cap), n)            # scattered, in no order
+            xs = [x[i, :n].contiguous() for i in range(16)]
+            out, arg = torch.empty((n, C), device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
+            ao, aa = (torch.empty((n, L, C), device=dev), torch.empty((n, L), dtype=torch.int32, device=dev)) if ant else (None, None)
+            hw = torch.zeros((n, H), device=dev)
+            states, idx = torch.zeros((cap, H), device=dev), torch.tensor(slots, device=dev)
+            recs = [OnlineRecord(200, C, 1024) for _ in range(n)]
+
+            def fp(i):
+                pool.push(slots, xs[i & 15], None, out=out, argmax=arg, want_ant=ant, ant_out=ao, ant_argmax=aa)
+
+            def fw(i):
+                eng.step_wide(xs[i & 15], None, hw, out=out, argmax=arg, want_ant=ant, ant_out=ao, ant_argmax=aa)
+
+            def ft(i):
+                h = states.index_select(0, idx)
+                eng.step_wide(xs[i & 15], None, h, out=out, argmax=arg, want_ant=ant, ant_out=ao, ant_argmax=aa)
+                states.index_copy_(0, idx, h)
+                for r, v in zip(recs, arg.cpu().tolist()):
+                    r.push(v)
+            paths = {"p": fp, "w": fw, "t": ft}
+            times, rounds = {k: [] for k in paths}, {k: [] for k in paths}
+            for f in paths.values():
+                for i in range(a.warmup):
+                    f(i)
+            torch.cuda.synchronize()
+            for _ in range(a.rounds):
+                for k, f in paths.items():
+                    evs = [torch.cuda.Event(enable_timing=True) for _ in range(2 * frames)]
+                    r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    r0.record()
+                    for i in range(frames):
+                        evs[2 * i].record()
+                        f(i)
+                        evs[2 * i + 1].record()
+                    r1.record()
+                    torch.cuda.synchronize()
+                    times[k] += [evs[2 * i].elapsed_time(evs[2 * i + 1]) * 1e3 for i in range(frames)]
+                    rounds[k].append(r0.elapsed_time(r1) * 1e3 / frames)
+            eng.check()
+            t = {k: {"median_us": float(np.median(v)), "p10_us": float(np.percentile(v, 10)), "p90_us": float(np.percentile(v, 90)),
+                     "round_us": float(np.median(rounds[k]))} for k, v in times.items()}
+            t["p_minus_w_us"] = t["p"]["median_us"] - t["w"]["median_us"]
+            t["p_spread_us"] = t["p"]["p90_us"] - t["p"]["p10_us"]
+            t["p_below_t"] = t["p"]["median_us"] < t["t"]["median_us"]
+            table[f"{name}_n{n}"] = t
+            print(json.dumps({f"{name}_n{n}": t}), file=sys.stderr, flush=True)
+            del pool
+        del m, eng
+    print(json.dumps({"metric": "per-tick device time, us (median of device-event pairs around every tick; zero flow; n_active scattered slots of a "
+                                "256-slot pool): p = StreamPool.push, w = dense step_wide, t = index_select + step_wide + index_copy_ + "
+                                "argmax.cpu() + host vote", "dtype": a.dtype, "frames_per_path_and_round": frames, "rounds": a.rounds,
+                      "table": table}))
 
 
 if __name__ == "__main__":
