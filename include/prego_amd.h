@@ -224,6 +224,35 @@ int prego_miniroad_step_wide_anticipation(prego_miniroad* h, int n_streams, cons
                                           float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax, int flags, void* workspace,
                                           size_t workspace_bytes, prego_stream_t stream);
 
+/* Multi-frame streaming step (an addition to ABI 7, existing signatures unchanged): n_frames new frames for each of n_streams streams in ONE
+ * call - a feeder that works in batches, a stream that reconnects with a backlog, a video that joins late.  1 <= n_frames <= 32, the same
+ * for every stream of the call (ragged backlogs: group the streams by backlog, one call per group), n_streams >= 1 and
+ * n_streams * n_frames <= 256.  Longer backlogs, or more rows, are prego_miniroad_forward's work (h0 / h_last).
+ *   rgb / flow     device fp32 [n_streams, n_frames, d_rgb] / [n_streams, n_frames, d_flow]; flow == NULL = zero flow half
+ *   h_state        device fp32 [n_streams, hid], read and OVERWRITTEN with the state after the last frame
+ *   out            device fp32 [n_streams, n_frames, n_classes]: probabilities (PREGO_FWD_SOFTMAX) or logits; nullable
+ *   argmax         device int32 [n_streams, n_frames]; nullable
+ *   ant_out        device fp32 [n_streams, n_frames, ant_len, n_classes]; nullable      ant_argmax  device int32 [n_streams, n_frames, ant_len]; nullable
+ * Layer1, LayerNorm, the W_ih product, the classifier and the anticipation head do not depend on time: they run once over the
+ * n_streams * n_frames rows with prego_miniroad_step_wide's kernels, their weights crossing the memory system once per call.  Only W_hh is on
+ * the sequential path: one launch per frame that fuses gh = h W_hh^T with the GRU gates (csrc/stream_frames.hip), 5 + n_frames launches in
+ * all (+ 2 for the anticipation head).
+ * Bits: for every stream and every frame of the burst, out, argmax, ant_out, ant_argmax and the state after the frame are bit for bit what
+ * prego_miniroad_step_wide (_anticipation) gives that stream driven frame by frame in calls of 5..256 streams - the unfused LayerNorm
+ * route, at every n_streams: a call of <= 4 streams does NOT reproduce prego_miniroad_step's fused-LayerNorm bits.  They depend neither on
+ * n_streams, n_frames nor on the stream's place in the call; repeat calls are bit-identical.
+ *   workspace      device memory, 256-byte aligned, prego_miniroad_step_frames_workspace_bytes(h, n_streams, n_frames) bytes (0 = the
+ *                  shape is refused): 16-bit frames, a copy of h_state, y, e, gi, the fp32 state after every frame, relu(h) rows and, once
+ *                  set_anticipation has run, A [rows, ant_len * hid].  Query again after set_anticipation.
+ * No device allocation, no host wait.  PREGO_EINVAL with a message, nothing launched: n_frames outside 1..32, n_streams * n_frames > 256,
+ * a NULL, unaligned or too small workspace, everything prego_miniroad_step refuses, and _anticipation before set_anticipation. */
+size_t prego_miniroad_step_frames_workspace_bytes(const prego_miniroad* h, int n_streams, int n_frames);
+int prego_miniroad_step_frames(prego_miniroad* h, int n_streams, int n_frames, const float* rgb, const float* flow, float* h_state, float* out,
+                               int32_t* argmax, int flags, void* workspace, size_t workspace_bytes, prego_stream_t stream);
+int prego_miniroad_step_frames_anticipation(prego_miniroad* h, int n_streams, int n_frames, const float* rgb, const float* flow, float* h_state,
+                                            float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax, int flags, void* workspace,
+                                            size_t workspace_bytes, prego_stream_t stream);
+
 /* Stream pool (an addition to ABI 7, existing signatures unchanged): the online detector for a host whose streams open and close at
  * different times and of which only some have a new frame at any tick.  Every live video owns a SLOT of one device block: its GRU state
  * row (rnn.py:58-62 with h0 = the previous frame's state) and its running aggregation record - utils/aggregate.py:55-78 fed one id at a
@@ -270,6 +299,17 @@ size_t prego_miniroad_step_pool_workspace_bytes(const prego_miniroad* h, int n_a
 int prego_miniroad_step_pool(prego_miniroad* h, prego_stream_pool* p, int n_active, const int32_t* slots, const float* rgb, const float* flow,
                              float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax, int flags, void* workspace,
                              size_t workspace_bytes, prego_stream_t stream);
+/* prego_miniroad_step_pool for a burst: n_frames frames (1..32, n_active * n_frames <= 256) for each slot named - gather, then
+ * prego_miniroad_step_frames (_anticipation when ant_out or ant_argmax is non-NULL) through its own entry point, then one commit that puts
+ * every state row back once and has the slot's lane take the burst's n_frames ids in frame order, so a window may end inside the burst any
+ * number of times; the overflow rules are the single-frame ones.  rgb, flow, out, argmax, ant_out, ant_argmax: dense with
+ * prego_miniroad_step_frames's shapes, row i belongs to slots[i].  Bits: prego_miniroad_step_frames's; a slot's record afterwards is word
+ * for word the record after n_frames prego_miniroad_step_pool calls.  A call that fails leaves the pool untouched.  Refusals:
+ * prego_miniroad_step_pool's and prego_miniroad_step_frames's, nothing launched.  No device allocation, no host wait. */
+size_t prego_miniroad_step_pool_frames_workspace_bytes(const prego_miniroad* h, int n_active, int n_frames);
+int prego_miniroad_step_pool_frames(prego_miniroad* h, prego_stream_pool* p, int n_active, int n_frames, const int32_t* slots, const float* rgb,
+                                    const float* flow, float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax, int flags,
+                                    void* workspace, size_t workspace_bytes, prego_stream_t stream);
 int prego_stream_pool_vote(prego_stream_pool* p, int n, const int32_t* slots, const int32_t* ids, prego_stream_t stream);
 int prego_stream_pool_flush(prego_stream_pool* p, int n, const int32_t* slots, prego_stream_t stream);
 int prego_stream_pool_reset(prego_stream_pool* p, int n, const int32_t* slots, prego_stream_t stream);

@@ -45,6 +45,8 @@ SYMBOLS = [
     "prego_cast_features",
     "prego_stream_pool_bytes", "prego_stream_pool_create", "prego_stream_pool_destroy", "prego_miniroad_step_pool_workspace_bytes",
     "prego_miniroad_step_pool", "prego_stream_pool_vote", "prego_stream_pool_flush", "prego_stream_pool_reset", "prego_stream_pool_record",
+    "prego_miniroad_step_frames_workspace_bytes", "prego_miniroad_step_frames", "prego_miniroad_step_frames_anticipation",
+    "prego_miniroad_step_pool_frames_workspace_bytes", "prego_miniroad_step_pool_frames",
 ]
 # include/prego_amd_debug.h: only in libprego_amd_debug.so
 DEBUG_SYMBOLS = ["prego_miniroad_debug_stamps", "prego_debug_gemm_bf16", "prego_debug_attention_bwd", "prego_debug_attention_fwd",
@@ -109,6 +111,13 @@ def _open(path: str, debug: bool) -> C.CDLL:
     lib.prego_miniroad_step_pool_workspace_bytes.argtypes = [vp, i32]
     lib.prego_miniroad_step_pool_workspace_bytes.restype = sz
     lib.prego_miniroad_step_pool.argtypes = [vp, vp, i32, C.POINTER(C.c_int32), vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]
+    lib.prego_miniroad_step_frames_workspace_bytes.argtypes = [vp, i32, i32]
+    lib.prego_miniroad_step_frames_workspace_bytes.restype = sz
+    lib.prego_miniroad_step_frames.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, sz, vp]
+    lib.prego_miniroad_step_frames_anticipation.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]
+    lib.prego_miniroad_step_pool_frames_workspace_bytes.argtypes = [vp, i32, i32]
+    lib.prego_miniroad_step_pool_frames_workspace_bytes.restype = sz
+    lib.prego_miniroad_step_pool_frames.argtypes = [vp, vp, i32, i32, C.POINTER(C.c_int32), vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]
     lib.prego_stream_pool_vote.argtypes = [vp, i32, C.POINTER(C.c_int32), vp, vp]
     lib.prego_stream_pool_flush.argtypes = [vp, i32, C.POINTER(C.c_int32), vp]
     lib.prego_stream_pool_reset.argtypes = [vp, i32, C.POINTER(C.c_int32), vp]

@@ -2,7 +2,7 @@
 into step_anticipation (SURVEY.md section 8 f2).  `aggregate` is the host (numpy) form over the JSON the eval loop wrote;
 `aggregate_device` takes the int32 per-frame argmax tensors the head kernel left in HBM and runs the majority vote there
 (`prego_window_vote`, csrc/postproc.hip): one int32 per 200-frame window crosses PCIe instead of one per frame.
-`aggregate_online` / `OnlineRecord` is the same rule fed one id at a time: the host model of the record a stream pool keeps per slot
+`aggregate_online` / `OnlineRecord` is the same rule fed one id at a time, or a burst at a time (`push_frames`): the host model of the record a stream pool keeps per slot
 (prego_amd/stream_pool.py, csrc/stream_pool.hip)."""
 from __future__ import annotations
 
@@ -78,6 +78,12 @@ class OnlineRecord:
         if self.frames % self.window == 0:
             self._close_window(self.frames - self.window)
 
+    def push_frames(self, ids):
+        """a burst: the host model of the pool's K-frame commit (csrc/stream_pool.hip: pool_commit_frames) - the slot's lane takes the
+        ids in frame order, so a window may end inside the burst any number of times"""
+        for i in ids:
+            self.push(i)
+
     def flush(self):
         """the reference's shorter last window (aggregate.py:57-58: e = min(s + window, len))"""
         rest = self.frames % self.window
@@ -89,12 +95,24 @@ class OnlineRecord:
         return {"pred": list(self.event_id), "changes_pred": list(self.event_start[1:]) + [self.voted_to], "frames": self.frames}
 
 
-def aggregate_online(ids, window: int = 200, n_classes: int = 128, max_events: int = 1 << 30) -> dict:
+def aggregate_online(ids, window: int = 200, n_classes: int = 128, max_events: int = 1 << 30, bursts=None) -> dict:
     """`aggregate`'s 'pred' / 'changes_pred' of one stream from its per-frame ids, fed one id at a time through the record a stream pool
-    keeps per slot and flushed at the end."""
+    keeps per slot and flushed at the end.  bursts: an int K or a sequence of burst sizes (cycled; the last burst is whatever is left) -
+    the ids are fed as StreamPool.push_frames feeds them, K at a time; the result does not depend on it."""
     rec = OnlineRecord(window, n_classes, max_events)
-    for i in ids:
-        rec.push(i)
+    ids = list(ids)
+    if bursts is None:
+        for i in ids:
+            rec.push(i)
+    else:
+        sizes = [int(bursts)] if isinstance(bursts, int) else [int(b) for b in bursts]
+        if not sizes or min(sizes) < 1:
+            raise ValueError(f"aggregate_online: burst sizes {sizes} (each >= 1)")
+        at, k = 0, 0
+        while at < len(ids):
+            rec.push_frames(ids[at:at + sizes[k % len(sizes)]])
+            at += sizes[k % len(sizes)]
+            k += 1
     rec.flush()
     if rec.overflow:
         raise ValueError(f"aggregate_online: overflow {rec.overflow} (1: more than {max_events} events, 2: an id outside [0, {n_classes}))")

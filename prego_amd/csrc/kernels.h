@@ -301,6 +301,8 @@ struct PoolSlots { int s[kPoolMaxActive]; };      // the slot list of one call, 
 // slots: HOST, n in 1..256, every slot in [0, capacity) and named once (the caller checks duplicates); -1 = refused, nothing launched
 int launch_pool_gather(const PoolGeom& g, const int* slots, int n, float* h_ws, hipStream_t s);
 int launch_pool_commit(const PoolGeom& g, const int* slots, int n, const float* h_ws, const int* argmax, hipStream_t s);
+// the commit of a burst: the state row once, then argmax[i K + t], t = 0 .. K - 1, voted in frame order by the slot's lane
+int launch_pool_commit_frames(const PoolGeom& g, const int* slots, int n, int K, const float* h_ws, const int* argmax, hipStream_t s);
 int launch_pool_vote(const PoolGeom& g, const int* slots, int n, const int* ids, hipStream_t s);
 int launch_pool_flush(const PoolGeom& g, const int* slots, int n, hipStream_t s);
 int launch_pool_reset(const PoolGeom& g, const int* slots, int n, hipStream_t s);
@@ -387,3 +389,12 @@ int launch_wide_gemv(int nprob, const StreamGemv* pr, int n, hipStream_t s, bool
 int launch_wide_ant_hidden(const void* wa, const float* ba, const float* h_state, void* A, int n, int H, int L, hipStream_t s, bool f16 = false);
 int launch_wide_ant_head(const void* A, const void* wc, const float* bc, int n, int H, int L, int C, int softmax, float* ant_out,
                          int* ant_argmax, hipStream_t s, bool f16 = false);
+
+// multi-frame streaming step (stream_frames.hip): K <= 32 frames for each of n streams, rows = n K <= 256, row s K + t = frame t of stream s.
+// xb [rows][d_rgb + d_flow] = the fp32 frames in the operand type (pack2_sat, a NULL half: zeros); h0 [n][H] = a copy of h_state
+int launch_frames_cast(const float* rgb, const float* flow, const float* h_state, void* xb, float* h0, int rows, int n, int d_rgb, int d_flow,
+                       int H, hipStream_t s, bool f16 = false);
+// frame t: gh = op16(h_{t-1}) W_hh^T and the GRU gates in one launch; h_{t-1} = h0 (t == 0) or hist row s K + t - 1; writes hist and hr
+// (relu(h_t), 16-bit) row s K + t, and h_state [n][H] when it is non-null (the last frame).  H == 1024
+int launch_frames_recur(const void* whh, const float* gi, const float* b_hn, const float* h0, float* hist, void* hr, float* h_state, int n,
+                        int K, int t, int H, hipStream_t s, bool f16 = false);

@@ -59,6 +59,16 @@ StepPoolLayout step_pool_layout(const prego_miniroad* h, int n) {
   l.total = l.wide + l.wide_bytes;
   return l;
 }
+
+// the burst call: dense state [n][hid] fp32 | argmax [n K] int32 | the multi-frame step's workspace
+StepPoolLayout step_pool_frames_layout(const prego_miniroad* h, int n, int K) {
+  StepPoolLayout l{};
+  l.am = align_up((size_t)n * h->hid * 4, 256);
+  l.wide = l.am + align_up((size_t)n * K * 4, 256);
+  l.wide_bytes = prego_miniroad_step_frames_workspace_bytes(h, n, K);
+  l.total = l.wide + l.wide_bytes;
+  return l;
+}
 }  // namespace
 
 extern "C" size_t prego_stream_pool_bytes(const prego_miniroad* h, int capacity, int max_events) {
@@ -131,6 +141,51 @@ extern "C" int prego_miniroad_step_pool(prego_miniroad* h, prego_stream_pool* p,
                      : prego_miniroad_step_wide(h, n_active, rgb, flow, h_ws, out, am, flags, ws + l.wide, l.wide_bytes, stream);
   if (rc) return rc;                                          // the pool itself is untouched: only the commit writes it
   if (launch_pool_commit(p->g, slots, n_active, h_ws, am, s)) return prego_fail_(PREGO_EINVAL, "step_pool: commit refused its arguments");
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+extern "C" size_t prego_miniroad_step_pool_frames_workspace_bytes(const prego_miniroad* h, int n_active, int n_frames) {
+  if (!h || prego_miniroad_step_frames_workspace_bytes(h, n_active, n_frames) == 0) return 0;
+  return step_pool_frames_layout(h, n_active, n_frames).total;
+}
+
+extern "C" int prego_miniroad_step_pool_frames(prego_miniroad* h, prego_stream_pool* p, int n_active, int n_frames, const int32_t* slots,
+                                               const float* rgb, const float* flow, float* out, int32_t* argmax, float* ant_out,
+                                               int32_t* ant_argmax, int flags, void* workspace, size_t workspace_bytes,
+                                               prego_stream_t stream) {
+  const bool ant = ant_out != nullptr || ant_argmax != nullptr;
+  StepPoolLayout l{};
+  {
+    HandleScope scope_(h);
+    if (!p) return prego_fail_(PREGO_EINVAL, "step_pool_frames: pool is NULL");
+    if (n_frames < 1 || n_frames > 32) return prego_fail_(PREGO_EINVAL, "step_pool_frames: %d frames per stream (1..32 per call)", n_frames);
+    if (n_active >= 1 && (long long)n_active * n_frames > kPoolMaxActive)
+      return prego_fail_(PREGO_EINVAL, "step_pool_frames: %d streams x %d frames = %lld rows (at most %d per call: use forward() with h0 / h_last)",
+                         n_active, n_frames, (long long)n_active * n_frames, kPoolMaxActive);
+    // everything the dense call would refuse, before the gather is launched (the state it will be handed is the workspace's dense copy)
+    if (int rc = step_refusals(h, n_active, kPoolMaxActive, rgb, flow, p->g.h, ant)) return rc;
+    if (p->g.hid != h->hid || p->g.ncls != h->ncls)
+      return prego_fail_(PREGO_EINVAL, "step_pool_frames: the pool was created for hidden_dim %d / %d classes, the handle has %d / %d", p->g.hid,
+                         p->g.ncls, h->hid, h->ncls);
+    if (int rc = check_slots(p, "step_pool_frames", n_active, slots)) return rc;
+    l = step_pool_frames_layout(h, n_active, n_frames);
+    if (!workspace || workspace_bytes < l.total)
+      return prego_fail_(PREGO_EINVAL, "step_pool_frames: workspace %p with %zu bytes, %d active streams x %d frames need %zu (prego_miniroad_step_pool_frames_workspace_bytes)",
+                         workspace, workspace_bytes, n_active, n_frames, l.total);
+    if ((uintptr_t)workspace & 255) return prego_fail_(PREGO_EINVAL, "step_pool_frames: the workspace must be 256-byte aligned");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  float* h_ws = (float*)ws;
+  int32_t* am = argmax ? argmax : (int32_t*)(ws + l.am);      // the votes always have their ids
+  if (launch_pool_gather(p->g, slots, n_active, h_ws, s)) return prego_fail_(PREGO_EINVAL, "step_pool_frames: gather refused its arguments");
+  const int rc = ant ? prego_miniroad_step_frames_anticipation(h, n_active, n_frames, rgb, flow, h_ws, out, am, ant_out, ant_argmax, flags,
+                                                               ws + l.wide, l.wide_bytes, stream)
+                     : prego_miniroad_step_frames(h, n_active, n_frames, rgb, flow, h_ws, out, am, flags, ws + l.wide, l.wide_bytes, stream);
+  if (rc) return rc;                                          // the pool itself is untouched: only the commit writes it
+  if (launch_pool_commit_frames(p->g, slots, n_active, n_frames, h_ws, am, s))
+    return prego_fail_(PREGO_EINVAL, "step_pool_frames: commit refused its arguments");
   HIPCHK(hipGetLastError());
   return PREGO_OK;
 }

@@ -4,6 +4,7 @@
 // step on a dense copy of the active rows (stream_wide.hip), so the pool adds no arithmetic.
 //   pool_gather   h_ws[i] <- pool.h[slots[i]]                       one workgroup per active stream, 16-byte accesses
 //   pool_commit   pool.h[slots[i]] <- h_ws[i], then lane 0 of workgroup i votes argmax[i] into the slot's record
+//   pool_commit_frames  pool_commit after a burst of K frames per slot: the state once, K votes in frame order by the slot's lane
 //   pool_vote     the vote alone, ids from the caller's device vector  (one lane per stream)
 //   pool_flush    votes a slot's unfinished window (the reference's shorter last window, aggregate.py:57-58)
 //   pool_reset    zeroes a slot's state row and record
@@ -70,6 +71,20 @@ __global__ __launch_bounds__(256) void pool_commit_kernel(PoolGeom g, PoolSlots 
   if (threadIdx.x == 0) pool_vote_update(pool_record(g, slot), g, argmax[i]);
 }
 
+// pool_commit for a burst of K frames per slot: the ids of slot i are argmax[i K .. i K + K), voted in frame order by one lane, so a window
+// boundary may fall inside the burst any number of times
+__global__ __launch_bounds__(256) void pool_commit_frames_kernel(PoolGeom g, PoolSlots sl, int K, const float* __restrict__ h_ws,
+                                                                 const int* __restrict__ argmax) {
+  const int i = blockIdx.x, slot = sl.s[i];
+  const f32x4* src = (const f32x4*)(h_ws + (size_t)i * g.hid);
+  f32x4* dst = (f32x4*)(g.h + (size_t)slot * g.hid);
+  for (int k = threadIdx.x; k < (g.hid >> 2); k += 256) dst[k] = src[k];
+  if (threadIdx.x == 0) {
+    int* rec = pool_record(g, slot);
+    for (int t = 0; t < K; ++t) pool_vote_update(rec, g, argmax[(size_t)i * K + t]);
+  }
+}
+
 __global__ __launch_bounds__(64) void pool_vote_kernel(PoolGeom g, PoolSlots sl, int n, const int* __restrict__ ids) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i < n) pool_vote_update(pool_record(g, sl.s[i]), g, ids[i]);
@@ -117,6 +132,13 @@ int launch_pool_commit(const PoolGeom& g, const int* slots, int n, const float* 
   PoolSlots sl;
   if (!h_ws || !argmax || !pool_slots(g, slots, n, &sl)) return -1;
   pool_commit_kernel<<<n, 256, 0, s>>>(g, sl, h_ws, argmax);
+  return 0;
+}
+
+int launch_pool_commit_frames(const PoolGeom& g, const int* slots, int n, int K, const float* h_ws, const int* argmax, hipStream_t s) {
+  PoolSlots sl;
+  if (!h_ws || !argmax || K < 1 || K > 32 || n * K > kPoolMaxActive || !pool_slots(g, slots, n, &sl)) return -1;
+  pool_commit_frames_kernel<<<n, 256, 0, s>>>(g, sl, K, h_ws, argmax);
   return 0;
 }
 

@@ -423,6 +423,60 @@ class MiniRoadEngine:
             check(self.lib.prego_miniroad_step_wide(self.h, n, p(rgb if d_rgb > 0 else None), p(flow), p(h), p(out), p(argmax), *tail))
         return out, argmax
 
+    def step_frames(self, rgb: Optional[torch.Tensor], flow: Optional[torch.Tensor], h: torch.Tensor, softmax: bool = True,
+                    want_ant=None, out: Optional[torch.Tensor] = None, argmax: Optional[torch.Tensor] = None,
+                    ant_out: Optional[torch.Tensor] = None, ant_argmax: Optional[torch.Tensor] = None):
+        """K frames for each of n streams in one call (prego_miniroad_step_frames / _anticipation, csrc/stream_frames.hip): rgb [n, K, d_rgb] /
+        flow [n, K, d_flow] (None = zero flow) fp32 cuda contiguous, 1 <= K <= 32 the same for every stream, n K <= 256 (ragged backlogs:
+        one call per group of equal K; longer ones: forward() with h0 / h_last).  h [n, hid] is advanced by K frames in place.  Returns
+        step_wide's tuple with a K axis - (out [n, K, C], argmax int32 [n, K]) and, with want_ant (default: the engine has an anticipation
+        head), (ant_out [n, K, L, C], ant_argmax int32 [n, K, L]).  Every frame's bits are step_wide's for a call of 5..256 streams (the
+        unfused LayerNorm route, also for n <= 4).  The weights off the sequential path are read once per call, W_hh once per frame from
+        the L2.  Raises on engines the streaming kernels are not built for (fp32, fp16x2, hidden sizes other than 1024, two layers)."""
+        d_rgb, d_flow, emb, hid, ncls = self.dims
+        if self.compute_dtype in ("fp32", "fp16x2") or hid != 1024 or self.num_layers != 1:
+            raise PregoError(f"step_frames: the streaming kernels are built for bf16 / fp16 operands, hidden_dim 1024, one GRU layer (this engine: "
+                             f"{self.compute_dtype}, hidden_dim {hid}, {self.num_layers} layers); use forward() with h0 / h_last")
+        if want_ant is None:
+            want_ant = bool(getattr(self, "ant_len", 0))
+        if want_ant and not getattr(self, "ant_len", 0):
+            raise PregoError("step_frames(want_ant=True) before set_anticipation")
+        src = rgb if d_rgb > 0 else flow
+        if src is None:
+            raise PregoError("step_frames: a --no_rgb model needs the flow frames" if d_rgb == 0 else "step_frames: rgb is None")
+        if src.dim() != 3:
+            raise PregoError(f"step_frames: expected frames as [n, K, d], got {tuple(src.shape)}")
+        n, K = int(src.shape[0]), int(src.shape[1])
+        L = self.ant_len if want_ant else 0
+        if out is None:
+            out = torch.empty((n, K, ncls), dtype=torch.float32, device=self.device)
+        if argmax is None:
+            argmax = torch.empty((n, K), dtype=torch.int32, device=self.device)
+        if want_ant and ant_out is None:
+            ant_out = torch.empty((n, K, L, ncls), dtype=torch.float32, device=self.device)
+        if want_ant and ant_argmax is None:
+            ant_argmax = torch.empty((n, K, L), dtype=torch.int32, device=self.device)
+        checks = [(rgb if d_rgb > 0 else None, (n, K, d_rgb), torch.float32, "rgb"), (flow, (n, K, d_flow), torch.float32, "flow"),
+                  (h, (n, hid), torch.float32, "GRU state"), (out, (n, K, ncls), torch.float32, "out"), (argmax, (n, K), torch.int32, "argmax")]
+        if want_ant:
+            checks += [(ant_out, (n, K, L, ncls), torch.float32, "anticipation out"), (ant_argmax, (n, K, L), torch.int32, "anticipation argmax")]
+        for t, shape, dt, what in checks:
+            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
+                raise PregoError(f"step_frames: expected {what} as contiguous {dt} cuda {list(shape)}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        need = self.lib.prego_miniroad_step_frames_workspace_bytes(self.h, n, K)      # 0: the C call refuses the shape with its message
+        if need and (getattr(self, "_ws_frames", None) is None or self._ws_frames.numel() < need):
+            self._ws_frames = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._ws_frames if need else None
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        tail = (_lib.FWD_SOFTMAX if softmax else 0, p(ws), ws.numel() if ws is not None else 0, C.c_void_p(_stream_ptr(self.device)))
+        with torch.cuda.device(self.device):
+            if want_ant:
+                check(self.lib.prego_miniroad_step_frames_anticipation(self.h, n, K, p(rgb if d_rgb > 0 else None), p(flow), p(h), p(out),
+                                                                       p(argmax), p(ant_out), p(ant_argmax), *tail))
+                return out, argmax, ant_out, ant_argmax
+            check(self.lib.prego_miniroad_step_frames(self.h, n, K, p(rgb if d_rgb > 0 else None), p(flow), p(h), p(out), p(argmax), *tail))
+        return out, argmax
+
     # -- training ------------------------------------------------------------------------
     def set_dropout(self, p: float, seed: int):
         check(self.lib.prego_miniroad_set_dropout(self.h, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF))

@@ -137,10 +137,17 @@ class MROAD(nn.Module):
         return self.engine().step_wide(rgb, flow, h, softmax=True)
 
     @torch.no_grad()
+    def step_frames(self, rgb, flow, h):
+        """A burst: K frames per stream in one call, rgb [n, K, d_rgb] / flow [n, K, d_flow] (None = zeros), 1 <= K <= 32, n K <= 256; h
+        [n, hidden_dim] is advanced by K frames in place.  Returns (probabilities [n, K, C], argmax int32 [n, K]), every frame bit for bit
+        `step_wide`'s for a call of 5..256 streams (csrc/stream_frames.hip).  Longer backlogs: forward with h0 / h_last."""
+        return self.engine().step_frames(rgb, flow, h, softmax=True, want_ant=False)
+
+    @torch.no_grad()
     def stream_pool(self, capacity: int = 256, window: int = 200, max_events: int = 1024):
         """A StreamPool (prego_amd/stream_pool.py) on this model's inference engine: every live video owns a slot with its GRU state and
         its running aggregation record; `push(slots, rgb, flow)` advances any subset by one frame with `step_wide`'s bits (MiniROADA: the
-        anticipation head included), `close(slot)` returns the stream's 'pred' / 'changes_pred' (utils/aggregate.py:46-90).  Built after
+        anticipation head included), `push_frames` by a burst of K frames each, `close(slot)` returns the stream's 'pred' / 'changes_pred' (utils/aggregate.py:46-90).  Built after
         the weights are final: the pool keeps the engine it was built on."""
         from .stream_pool import StreamPool
         return StreamPool(self, capacity=capacity, window=window, max_events=max_events)
@@ -243,3 +250,9 @@ class MROADA(MROAD):
     def step_wide(self, rgb, flow, h):
         """`step` for up to 256 streams per call, the anticipation head included (csrc/stream_wide.hip).  Returns what `step` returns."""
         return self.engine().step_wide(rgb, flow, h, softmax=True, want_ant=True)
+
+    @torch.no_grad()
+    def step_frames(self, rgb, flow, h):
+        """`MROAD.step_frames` with the anticipation head on the state after every frame.  Returns (probabilities [n, K, C], argmax int32
+        [n, K], anticipation probabilities [n, K, L, C], anticipation argmax int32 [n, K, L])."""
+        return self.engine().step_frames(rgb, flow, h, softmax=True, want_ant=True)

@@ -166,6 +166,60 @@ class StreamPool:
         self._check(rc)
         return (out, argmax, ant_out, ant_argmax) if want_ant else (out, argmax)
 
+    # -- a burst of K frames for a subset of the streams --------------------------------------------
+    def push_frames(self, slots, rgb, flow=None, softmax: bool = True, want_ant=None, out=None, argmax=None, ant_out=None, ant_argmax=None):
+        """K new frames for each open slot of `slots` in one call (prego_miniroad_step_pool_frames): rgb [n, K, d_rgb] / flow [n, K, d_flow]
+        (None = zero flow) fp32 cuda contiguous, 1 <= K <= 32 the same for every slot, n K <= 256 - group slots by backlog, one call per
+        group; a backlog longer than 32 frames is forward()'s work (h0 / h_last).  Returns `push`'s tuple with a K axis: (out [n, K, C],
+        argmax int32 [n, K]) and, with want_ant, (ant_out [n, K, L, C], ant_argmax int32 [n, K, L]); every frame's bits are `push`'s for a
+        call of 5..256 slots.  Each slot's state is advanced by K frames and its record is word for word the record after K `push`
+        calls: the K ids are voted in frame order, window boundaries inside the burst included."""
+        eng = self.engine
+        if not self._fast:
+            raise PregoError(f"stream pool push_frames: the streaming kernels are built for bf16 / fp16 operands, hidden_dim 1024, one GRU layer "
+                             f"(this engine: {eng.compute_dtype}, hidden_dim {self._hid}, {eng.num_layers} layers); run the general forward "
+                             "and feed its ids to vote()")
+        slots = self.slots.check(slots, "push_frames")
+        n = len(slots)
+        d_rgb, d_flow, emb, hid, ncls = eng.dims
+        if want_ant is None:
+            want_ant = bool(getattr(eng, "ant_len", 0))
+        if want_ant and not getattr(eng, "ant_len", 0):
+            raise PregoError("stream pool push_frames(want_ant=True) before set_anticipation")
+        src = rgb if d_rgb > 0 else flow
+        if src is None:
+            raise PregoError("stream pool push_frames: a --no_rgb model needs the flow frames" if d_rgb == 0 else "stream pool push_frames: rgb is None")
+        if src.dim() != 3 or src.shape[0] != n:
+            raise PregoError(f"stream pool push_frames: expected frames as [{n}, K, d], got {tuple(src.shape)}")
+        K = int(src.shape[1])
+        L = eng.ant_len if want_ant else 0
+        if out is None:
+            out = torch.empty((n, K, ncls), dtype=torch.float32, device=self.device)
+        if argmax is None:
+            argmax = torch.empty((n, K), dtype=torch.int32, device=self.device)
+        if want_ant and ant_out is None:
+            ant_out = torch.empty((n, K, L, ncls), dtype=torch.float32, device=self.device)
+        if want_ant and ant_argmax is None:
+            ant_argmax = torch.empty((n, K, L), dtype=torch.int32, device=self.device)
+        checks = [(rgb if d_rgb > 0 else None, (n, K, d_rgb), torch.float32, "rgb"), (flow, (n, K, d_flow), torch.float32, "flow"),
+                  (out, (n, K, ncls), torch.float32, "out"), (argmax, (n, K), torch.int32, "argmax")]
+        if want_ant:
+            checks += [(ant_out, (n, K, L, ncls), torch.float32, "anticipation out"), (ant_argmax, (n, K, L), torch.int32, "anticipation argmax")]
+        for t, shape, dt, what in checks:
+            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
+                raise PregoError(f"stream pool push_frames: expected {what} as contiguous {dt} cuda {list(shape)}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        need = self.lib.prego_miniroad_step_pool_frames_workspace_bytes(eng.h, n, K)      # 0: the C call refuses the shape with its message
+        if self._ws is None or self._ws.numel() < need:          # grown here, outside the C call
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(self.device):
+            rc = self.lib.prego_miniroad_step_pool_frames(eng.h, self.p, n, K, self._slot_array(slots), p(rgb if d_rgb > 0 else None), p(flow),
+                                                          p(out), p(argmax), p(ant_out) if want_ant else None,
+                                                          p(ant_argmax) if want_ant else None, 1 if softmax else 0, p(self._ws),
+                                                          self._ws.numel(), C.c_void_p(self._stream_ptr(self.device)))
+        self._check(rc)
+        return (out, argmax, ant_out, ant_argmax) if want_ant else (out, argmax)
+
     def vote(self, slots, ids):
         """Aggregation alone: ids (int32 cuda [n], or a host sequence) are the new frame's step ids of `slots`, from whatever produced them."""
         slots = self.slots.check(slots, "vote")

@@ -32,6 +32,15 @@ pool can only add to it - and (t) the route a caller has without the pool: index
 index_copy_ them back, argmax.cpu(), the window vote on the host.  `p_minus_w_us` stands beside two kernel boundaries.
 
     python scripts/anticipation_bench.py --step --pool [--steps 200] [--warmup 20] [--rounds 4] [--streams 4,256] [--models L0,L8]
+
+--step --pool --frames: bursts (StreamPool.push_frames, csrc/stream_frames.hip), K = 2 / 4 / 8 / 16 frames for n_active = 1 / 4 / 16 slots
+and K = 2 / 4 for n_active = 64, MiniROAD and MiniROADA at L = 8 (zero flow), the same protocol with a device-event pair around every
+call: (f) ONE push_frames of K frames, (k) K successive push calls on the same slots - what a caller had before (f) existed.  Per cell:
+both per call and per frame (/ K), and whether (f) lies below (k) by more than the p10..p90 widths of both.  `marginal_us_per_frame` is
+the slope of (f) between the two largest K of an n_active: what one more frame per stream costs - the fused recurrent launch plus the frame's
+share of the row-wise products.
+
+    python scripts/anticipation_bench.py --step --pool --frames [--steps 200] [--warmup 20] [--rounds 4] [--models L0,L8]
 """
 from __future__ import annotations
 
@@ -67,6 +76,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--wide", action="store_true", help="with --step: step_wide against the loop of 16-stream steps")
     ap.add_argument("--pool", action="store_true", help="with --step: StreamPool.push against the dense step_wide and the torch route around it")
+    ap.add_argument("--frames", action="store_true", help="with --step --pool: one push_frames of K frames against K push calls")
     ap.add_argument("--streams", default=None, help="default: 17,32,64,128,256 (--wide), 4,16,64,256 (--pool)")
     ap.add_argument("--models", default=None, help="L0 = MiniROAD, Lk = MiniROADA with anticipation_length k; default: L0,L1,L8 (--wide), L0,L8 (--pool)")
     ap.add_argument("--paths", default="w,g,c")
@@ -78,6 +88,8 @@ def main():
     a.streams = a.streams or ("4,16,64,256" if a.pool else "17,32,64,128,256")
     a.models = a.models or ("L0,L8" if a.pool else "L0,L1,L8")
     if a.step:
+        if a.pool and a.frames:
+            return step_pool_frames_bench(a)
         return step_pool_bench(a) if a.pool else step_wide_bench(a) if a.wide else step_bench(a)
     dev = "cuda:0"
     lens = workloads.assembly101_eval_lengths()
@@ -392,6 +404,79 @@ def step_pool_bench(a):
                                 "256-slot pool): p = StreamPool.push, w = dense step_wide, t = index_select + step_wide + index_copy_ + "
                                 "argmax.cpu() + host vote", "dtype": a.dtype, "frames_per_path_and_round": frames, "rounds": a.rounds,
                       "table": table}))
+
+
+def step_pool_frames_bench(a):
+    import random
+    dev, C, cap = "cuda:0", 86, 256
+    ticks = max(a.steps, 200)
+    base = assembly101_cfg(compute_dtype=a.dtype, assume_zero_flow=True)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1234)
+    cells = [(n, K) for n in (1, 4, 16) for K in (2, 4, 8, 16)] + [(64, 2), (64, 4)]
+    table = {}
+    for name in a.models.split(","):
+        L = int(name[1:])
+        cfg = anticipation_cfg(base, L) if L else base
+        sd = W.miniroad_a_state_dict(cfg, 20, head_gain=8.0, ant_gain=4.0) if L else W.miniroad_state_dict(base, 20, head_gain=8.0)
+        m = build_model(cfg, dev)
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+        m.eval()
+        eng, ant = m.engine(), L > 0
+        for n, K in cells:
+            pools = {k: m.stream_pool(capacity=cap) for k in "fk"}       # one pool per route: both streams of states advance alike
+            for pool in pools.values():
+                for _ in range(cap):
+                    pool.open()
+            slots = random.Random(n).sample(range(cap), n)            # scattered, in no order
+            x = torch.randn((16, n, K, 2048), device=dev, generator=gen).clamp_(min=0)
+            xt = [[x[i, :, t].contiguous() for t in range(K)] for i in range(16)]
+            out, arg = torch.empty((n, K, C), device=dev), torch.empty((n, K), dtype=torch.int32, device=dev)
+            ao, aa = (torch.empty((n, K, L, C), device=dev), torch.empty((n, K, L), dtype=torch.int32, device=dev)) if ant else (None, None)
+            o1, a1 = torch.empty((n, C), device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
+            ao1, aa1 = (torch.empty((n, L, C), device=dev), torch.empty((n, L), dtype=torch.int32, device=dev)) if ant else (None, None)
+
+            def ff(i):
+                pools["f"].push_frames(slots, x[i & 15], None, out=out, argmax=arg, want_ant=ant, ant_out=ao, ant_argmax=aa)
+
+            def fk(i):
+                for t in range(K):
+                    pools["k"].push(slots, xt[i & 15][t], None, out=o1, argmax=a1, want_ant=ant, ant_out=ao1, ant_argmax=aa1)
+            paths = {"f": ff, "k": fk}
+            times, rounds = {k: [] for k in paths}, {k: [] for k in paths}
+            for f in paths.values():
+                for i in range(a.warmup):
+                    f(i)
+            torch.cuda.synchronize()
+            for _ in range(a.rounds):
+                for k, f in paths.items():
+                    evs = [torch.cuda.Event(enable_timing=True) for _ in range(2 * ticks)]
+                    r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    r0.record()
+                    for i in range(ticks):
+                        evs[2 * i].record()
+                        f(i)
+                        evs[2 * i + 1].record()
+                    r1.record()
+                    torch.cuda.synchronize()
+                    times[k] += [evs[2 * i].elapsed_time(evs[2 * i + 1]) * 1e3 for i in range(ticks)]
+                    rounds[k].append(r0.elapsed_time(r1) * 1e3 / ticks)
+            eng.check()
+            t = {k: {"median_us": float(np.median(v)), "p10_us": float(np.percentile(v, 10)), "p90_us": float(np.percentile(v, 90)),
+                     "round_us": float(np.median(rounds[k])), "median_us_per_frame": float(np.median(v)) / K} for k, v in times.items()}
+            t["k_minus_f_us"] = t["k"]["median_us"] - t["f"]["median_us"]
+            t["spreads_us"] = (t["k"]["p90_us"] - t["k"]["p10_us"]) + (t["f"]["p90_us"] - t["f"]["p10_us"])
+            t["f_below_k_by_more_than_the_spreads"] = t["k_minus_f_us"] > t["spreads_us"]
+            table[f"{name}_n{n}_K{K}"] = t
+            print(json.dumps({f"{name}_n{n}_K{K}": t}), file=sys.stderr, flush=True)
+            del pools
+        for n in (1, 4, 16):
+            hi, lo = table[f"{name}_n{n}_K16"]["f"]["median_us"], table[f"{name}_n{n}_K8"]["f"]["median_us"]
+            table[f"{name}_n{n}_marginal_us_per_frame"] = (hi - lo) / 8.0
+        del m, eng
+    print(json.dumps({"metric": "per-call device time, us (median of device-event pairs around every call; zero flow; n_active scattered slots of a "
+                                "256-slot pool): f = ONE StreamPool.push_frames of K frames, k = K successive StreamPool.push calls",
+                      "dtype": a.dtype, "calls_per_path_and_round": ticks, "rounds": a.rounds, "table": table}))
 
 
 if __name__ == "__main__":
