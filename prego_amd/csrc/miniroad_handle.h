@@ -3,13 +3,18 @@
 //   miniroad.cpp          error state (g_err, g_cur), create / destroy, weight setters, check, timing (ev_begin / ev_end), pass_info,
 //                         the debug library's allocation / wait counters (g_dbg_mallocs, g_dbg_syncs)
 //   miniroad_plan.cpp     build_plan, device_plan, stage_tables, feed events, row_bytes / fwd_layout and the workspace size
-//   miniroad_forward.cpp  validate_forward, choose_pass, run_chunked_pass, the forward entry points, prego_miniroad_step (_anticipation), prego_miniroad_step_wide (_anticipation), ant_head
+//   miniroad_forward.cpp  validate_forward, choose_pass, run_chunked_pass, the forward entry points, ant_head
+//   stream_step.cpp       step_refusals, prego_miniroad_step (_anticipation), prego_miniroad_step_wide (_anticipation)
+//   stream_frames.cpp     prego_miniroad_step_frames (_anticipation)
 //   stream_pool.cpp       the stream pool: prego_stream_pool_*, prego_miniroad_step_pool (kernels: stream_pool.hip)
 //   miniroad_split.cpp    ring / resident-buffer sizing, forward_split; the per-device order of split passes (g_split_mu, g_split_last)
 //   miniroad_train.cpp    dropout, loss, bwd_layout, backward, AdamW; the debug library's g_ant_full_span
 #pragma once
 #include "host_common.h"
 
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
 #include <string>
 #include <vector>
 #ifdef PREGO_DEBUG_ABI
@@ -223,7 +228,31 @@ int forward_split(prego_miniroad* h, const AntOut& ao, int R, int flags, bool wi
 // the anticipation head of a forward_anticipation call over packed rows [row0, row0 + nrows) of the plan, relu(h) rows at HR (chunk-relative);
 // the destinations come from the plan (the same lookup in every pass: which pass ran changes no bit)
 int ant_head(prego_miniroad* h, const AntOut& ao, const void* HR, const SlotPlan& plan, int row0, int nrows, int flags, hipStream_t s);
+
+// ---- stream_step.cpp
 // what every streaming step refuses, n_max streams per call (16: step, 256: step_wide, step_pool); 0 = the call may go ahead.  Under a HandleScope
 int step_refusals(prego_miniroad* h, int n_streams, int n_max, const float* rgb, const float* flow, const float* h_state, bool ant);
+
+// ---- the caller's workspace of a streaming entry point
+// carves it into parts that each start 256-byte aligned: take() returns the part's offset, `o` is the size so far
+struct WsCarver {
+  size_t o = 0;
+  size_t take(size_t bytes) { const size_t at = o; o += align_up(bytes, 256); return at; }
+};
+// refuses a workspace that is NULL, smaller than `need` or not 256-byte aligned; 0 = it will do.  who: the entry point's short name,
+// hint: the function that tells the size, what...: printf-style, what it is that needs `need` bytes
+__attribute__((format(printf, 6, 7))) static inline int workspace_refusal(const char* who, const char* hint, void* ws, size_t bytes, size_t need,
+                                                                          const char* what, ...) {
+  if (!ws || bytes < need) {
+    char buf[96];
+    va_list ap;
+    va_start(ap, what);
+    vsnprintf(buf, sizeof buf, what, ap);
+    va_end(ap);
+    return prego_fail_(PREGO_EINVAL, "%s: workspace %p with %zu bytes, %s need %zu (%s)", who, ws, bytes, buf, need, hint);
+  }
+  if ((uintptr_t)ws & 255) return prego_fail_(PREGO_EINVAL, "%s: the workspace must be 256-byte aligned", who);
+  return 0;
+}
 
 #pragma GCC visibility pop

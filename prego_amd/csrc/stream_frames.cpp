@@ -4,8 +4,6 @@
 // Every refusal is decided before the first launch.
 #include "miniroad_handle.h"
 
-#include <cstdint>
-
 namespace {
 constexpr int kMaxFrames = 32, kMaxRows = 256;
 
@@ -16,12 +14,11 @@ struct FramesLayout { size_t xb, h0, y, e, gi, hist, hr, a, total; };
 FramesLayout frames_layout(const prego_miniroad* h, int n, int K) {
   const size_t E = (size_t)h->emb, H = (size_t)h->hid, din = (size_t)(h->d_rgb + h->d_flow), R = (size_t)n * K;
   FramesLayout w{};
-  size_t o = 0;
-  auto take = [&o](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
-  w.xb = take(R * din * 2); w.h0 = take((size_t)n * H * 4); w.y = take(R * E * 4); w.e = take(R * E * 2);
-  w.gi = take(R * 3 * H * 4); w.hist = take(R * H * 4); w.hr = take(R * H * 2);
-  w.a = take(h->ant_len > 0 ? R * h->ant_len * H * 2 : 0);          // after set_anticipation: either entry point fits
-  w.total = o;
+  WsCarver c;
+  w.xb = c.take(R * din * 2); w.h0 = c.take((size_t)n * H * 4); w.y = c.take(R * E * 4); w.e = c.take(R * E * 2);
+  w.gi = c.take(R * 3 * H * 4); w.hist = c.take(R * H * 4); w.hr = c.take(R * H * 2);
+  w.a = c.take(h->ant_len > 0 ? R * h->ant_len * H * 2 : 0);          // after set_anticipation: either entry point fits
+  w.total = c.o;
   return w;
 }
 
@@ -38,10 +35,8 @@ int step_frames_impl(prego_miniroad* h, int n, int K, const float* rgb, const fl
                        (long long)n * K, kMaxRows);
   if (int rc = step_refusals(h, n, kMaxRows, rgb, flow, h_state, ant)) return rc;
   const FramesLayout w = frames_layout(h, n, K);
-  if (!workspace || workspace_bytes < w.total)
-    return prego_fail_(PREGO_EINVAL, "step_frames: workspace %p with %zu bytes, %d streams x %d frames need %zu (prego_miniroad_step_frames_workspace_bytes)",
-                       workspace, workspace_bytes, n, K, w.total);
-  if ((uintptr_t)workspace & 255) return prego_fail_(PREGO_EINVAL, "step_frames: the workspace must be 256-byte aligned");
+  if (int rc = workspace_refusal("step_frames", "prego_miniroad_step_frames_workspace_bytes", workspace, workspace_bytes, w.total,
+                                 "%d streams x %d frames", n, K)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int E = h->emb, H = h->hid, din = h->d_rgb + h->d_flow, sm = (flags & PREGO_FWD_SOFTMAX) ? 1 : 0, R = n * K;
   char* ws = (char*)workspace;

@@ -49,25 +49,65 @@ int check_slots(prego_stream_pool* p, const char* who, int n, const int32_t* slo
   return 0;
 }
 
-// dense state [n][hid] fp32 | argmax [n] int32 | the wide step's own workspace, each part 256-byte aligned
+// the step calls' workspace: dense state [n][hid] fp32 | argmax [n] (the burst call: [n K]) int32 | the dense call's own workspace.
+// burst = false (K = 1): the one-frame call through step_wide (its workspace is 0 bytes up to 16 streams: step's launches on the
+// handle's scratch); burst = true: K frames through step_frames
 struct StepPoolLayout { size_t am, wide, wide_bytes, total; };
-StepPoolLayout step_pool_layout(const prego_miniroad* h, int n) {
+StepPoolLayout step_pool_layout(const prego_miniroad* h, int n, bool burst, int K) {
   StepPoolLayout l{};
-  l.am = align_up((size_t)n * h->hid * 4, 256);
-  l.wide = l.am + align_up((size_t)n * 4, 256);
-  l.wide_bytes = prego_miniroad_step_wide_workspace_bytes(h, n);      // 0 up to 16 streams: step's launches on the handle's scratch
+  WsCarver c;
+  c.take((size_t)n * h->hid * 4);
+  l.am = c.take((size_t)n * K * 4);
+  l.wide = c.o;
+  l.wide_bytes = burst ? prego_miniroad_step_frames_workspace_bytes(h, n, K) : prego_miniroad_step_wide_workspace_bytes(h, n);
   l.total = l.wide + l.wide_bytes;
   return l;
 }
 
-// the burst call: dense state [n][hid] fp32 | argmax [n K] int32 | the multi-frame step's workspace
-StepPoolLayout step_pool_frames_layout(const prego_miniroad* h, int n, int K) {
+// prego_miniroad_step_pool (burst = false, K = 1) and prego_miniroad_step_pool_frames (burst = true, K = n_frames): gather the slots'
+// states into the workspace, make the dense call a caller without a pool would make, through the same entry point (the pool adds no
+// arithmetic), commit
+int step_pool_impl(const char* who, prego_miniroad* h, prego_stream_pool* p, int n_active, bool burst, int K, const int32_t* slots,
+                   const float* rgb, const float* flow, float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax, int flags, void* workspace,
+                   size_t workspace_bytes, prego_stream_t stream) {
+  const bool ant = ant_out != nullptr || ant_argmax != nullptr;
   StepPoolLayout l{};
-  l.am = align_up((size_t)n * h->hid * 4, 256);
-  l.wide = l.am + align_up((size_t)n * K * 4, 256);
-  l.wide_bytes = prego_miniroad_step_frames_workspace_bytes(h, n, K);
-  l.total = l.wide + l.wide_bytes;
-  return l;
+  {
+    HandleScope scope_(h);
+    if (!p) return prego_fail_(PREGO_EINVAL, "%s: pool is NULL", who);
+    if (burst && (K < 1 || K > 32)) return prego_fail_(PREGO_EINVAL, "%s: %d frames per stream (1..32 per call)", who, K);
+    if (burst && n_active >= 1 && (long long)n_active * K > kPoolMaxActive)
+      return prego_fail_(PREGO_EINVAL, "%s: %d streams x %d frames = %lld rows (at most %d per call: use forward() with h0 / h_last)", who,
+                         n_active, K, (long long)n_active * K, kPoolMaxActive);
+    // everything the dense call would refuse, before the gather is launched (the state it will be handed is the workspace's dense copy)
+    if (int rc = step_refusals(h, n_active, kPoolMaxActive, rgb, flow, p->g.h, ant)) return rc;
+    if (p->g.hid != h->hid || p->g.ncls != h->ncls)
+      return prego_fail_(PREGO_EINVAL, "%s: the pool was created for hidden_dim %d / %d classes, the handle has %d / %d", who, p->g.hid,
+                         p->g.ncls, h->hid, h->ncls);
+    if (int rc = check_slots(p, who, n_active, slots)) return rc;
+    l = step_pool_layout(h, n_active, burst, K);
+    if (int rc = burst ? workspace_refusal(who, "prego_miniroad_step_pool_frames_workspace_bytes", workspace, workspace_bytes, l.total,
+                                           "%d active streams x %d frames", n_active, K)
+                       : workspace_refusal(who, "prego_miniroad_step_pool_workspace_bytes", workspace, workspace_bytes, l.total,
+                                           "%d active streams", n_active)) return rc;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  float* h_ws = (float*)ws;
+  int32_t* am = argmax ? argmax : (int32_t*)(ws + l.am);      // the vote always has its ids
+  if (launch_pool_gather(p->g, slots, n_active, h_ws, s)) return prego_fail_(PREGO_EINVAL, "%s: gather refused its arguments", who);
+  void* dws = ws + l.wide;
+  const int rc = burst ? (ant ? prego_miniroad_step_frames_anticipation(h, n_active, K, rgb, flow, h_ws, out, am, ant_out, ant_argmax, flags, dws,
+                                                                        l.wide_bytes, stream)
+                              : prego_miniroad_step_frames(h, n_active, K, rgb, flow, h_ws, out, am, flags, dws, l.wide_bytes, stream))
+                       : (ant ? prego_miniroad_step_wide_anticipation(h, n_active, rgb, flow, h_ws, out, am, ant_out, ant_argmax, flags, dws,
+                                                                      l.wide_bytes, stream)
+                              : prego_miniroad_step_wide(h, n_active, rgb, flow, h_ws, out, am, flags, dws, l.wide_bytes, stream));
+  if (rc) return rc;                                          // the pool itself is untouched: only the commit writes it
+  if (burst ? launch_pool_commit_frames(p->g, slots, n_active, K, h_ws, am, s) : launch_pool_commit(p->g, slots, n_active, h_ws, am, s))
+    return prego_fail_(PREGO_EINVAL, "%s: commit refused its arguments", who);
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
 }
 }  // namespace
 
@@ -107,87 +147,27 @@ extern "C" void prego_stream_pool_destroy(prego_stream_pool* p) { delete p; }
 
 extern "C" size_t prego_miniroad_step_pool_workspace_bytes(const prego_miniroad* h, int n_active) {
   if (!h || n_active < 1 || n_active > kPoolMaxActive) return 0;
-  return step_pool_layout(h, n_active).total;
+  return step_pool_layout(h, n_active, false, 1).total;
 }
 
 extern "C" int prego_miniroad_step_pool(prego_miniroad* h, prego_stream_pool* p, int n_active, const int32_t* slots, const float* rgb,
                                         const float* flow, float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax, int flags,
                                         void* workspace, size_t workspace_bytes, prego_stream_t stream) {
-  const bool ant = ant_out != nullptr || ant_argmax != nullptr;
-  StepPoolLayout l{};
-  {
-    HandleScope scope_(h);
-    if (!p) return prego_fail_(PREGO_EINVAL, "step_pool: pool is NULL");
-    // everything the wide step would refuse, before the gather is launched (the state it will be handed is the workspace's dense copy)
-    if (int rc = step_refusals(h, n_active, kPoolMaxActive, rgb, flow, p->g.h, ant)) return rc;
-    if (p->g.hid != h->hid || p->g.ncls != h->ncls)
-      return prego_fail_(PREGO_EINVAL, "step_pool: the pool was created for hidden_dim %d / %d classes, the handle has %d / %d", p->g.hid,
-                         p->g.ncls, h->hid, h->ncls);
-    if (int rc = check_slots(p, "step_pool", n_active, slots)) return rc;
-    l = step_pool_layout(h, n_active);
-    if (!workspace || workspace_bytes < l.total)
-      return prego_fail_(PREGO_EINVAL, "step_pool: workspace %p with %zu bytes, %d active streams need %zu (prego_miniroad_step_pool_workspace_bytes)",
-                         workspace, workspace_bytes, n_active, l.total);
-    if ((uintptr_t)workspace & 255) return prego_fail_(PREGO_EINVAL, "step_pool: the workspace must be 256-byte aligned");
-  }
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  float* h_ws = (float*)ws;
-  int32_t* am = argmax ? argmax : (int32_t*)(ws + l.am);      // the vote always has its ids
-  if (launch_pool_gather(p->g, slots, n_active, h_ws, s)) return prego_fail_(PREGO_EINVAL, "step_pool: gather refused its arguments");
-  // the dense call a caller without a pool would make, through the same entry point: the pool adds no arithmetic
-  const int rc = ant ? prego_miniroad_step_wide_anticipation(h, n_active, rgb, flow, h_ws, out, am, ant_out, ant_argmax, flags, ws + l.wide,
-                                                             l.wide_bytes, stream)
-                     : prego_miniroad_step_wide(h, n_active, rgb, flow, h_ws, out, am, flags, ws + l.wide, l.wide_bytes, stream);
-  if (rc) return rc;                                          // the pool itself is untouched: only the commit writes it
-  if (launch_pool_commit(p->g, slots, n_active, h_ws, am, s)) return prego_fail_(PREGO_EINVAL, "step_pool: commit refused its arguments");
-  HIPCHK(hipGetLastError());
-  return PREGO_OK;
+  return step_pool_impl("step_pool", h, p, n_active, false, 1, slots, rgb, flow, out, argmax, ant_out, ant_argmax, flags, workspace, workspace_bytes,
+                        stream);
 }
 
 extern "C" size_t prego_miniroad_step_pool_frames_workspace_bytes(const prego_miniroad* h, int n_active, int n_frames) {
   if (!h || prego_miniroad_step_frames_workspace_bytes(h, n_active, n_frames) == 0) return 0;
-  return step_pool_frames_layout(h, n_active, n_frames).total;
+  return step_pool_layout(h, n_active, true, n_frames).total;
 }
 
 extern "C" int prego_miniroad_step_pool_frames(prego_miniroad* h, prego_stream_pool* p, int n_active, int n_frames, const int32_t* slots,
                                                const float* rgb, const float* flow, float* out, int32_t* argmax, float* ant_out,
                                                int32_t* ant_argmax, int flags, void* workspace, size_t workspace_bytes,
                                                prego_stream_t stream) {
-  const bool ant = ant_out != nullptr || ant_argmax != nullptr;
-  StepPoolLayout l{};
-  {
-    HandleScope scope_(h);
-    if (!p) return prego_fail_(PREGO_EINVAL, "step_pool_frames: pool is NULL");
-    if (n_frames < 1 || n_frames > 32) return prego_fail_(PREGO_EINVAL, "step_pool_frames: %d frames per stream (1..32 per call)", n_frames);
-    if (n_active >= 1 && (long long)n_active * n_frames > kPoolMaxActive)
-      return prego_fail_(PREGO_EINVAL, "step_pool_frames: %d streams x %d frames = %lld rows (at most %d per call: use forward() with h0 / h_last)",
-                         n_active, n_frames, (long long)n_active * n_frames, kPoolMaxActive);
-    // everything the dense call would refuse, before the gather is launched (the state it will be handed is the workspace's dense copy)
-    if (int rc = step_refusals(h, n_active, kPoolMaxActive, rgb, flow, p->g.h, ant)) return rc;
-    if (p->g.hid != h->hid || p->g.ncls != h->ncls)
-      return prego_fail_(PREGO_EINVAL, "step_pool_frames: the pool was created for hidden_dim %d / %d classes, the handle has %d / %d", p->g.hid,
-                         p->g.ncls, h->hid, h->ncls);
-    if (int rc = check_slots(p, "step_pool_frames", n_active, slots)) return rc;
-    l = step_pool_frames_layout(h, n_active, n_frames);
-    if (!workspace || workspace_bytes < l.total)
-      return prego_fail_(PREGO_EINVAL, "step_pool_frames: workspace %p with %zu bytes, %d active streams x %d frames need %zu (prego_miniroad_step_pool_frames_workspace_bytes)",
-                         workspace, workspace_bytes, n_active, n_frames, l.total);
-    if ((uintptr_t)workspace & 255) return prego_fail_(PREGO_EINVAL, "step_pool_frames: the workspace must be 256-byte aligned");
-  }
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  float* h_ws = (float*)ws;
-  int32_t* am = argmax ? argmax : (int32_t*)(ws + l.am);      // the votes always have their ids
-  if (launch_pool_gather(p->g, slots, n_active, h_ws, s)) return prego_fail_(PREGO_EINVAL, "step_pool_frames: gather refused its arguments");
-  const int rc = ant ? prego_miniroad_step_frames_anticipation(h, n_active, n_frames, rgb, flow, h_ws, out, am, ant_out, ant_argmax, flags,
-                                                               ws + l.wide, l.wide_bytes, stream)
-                     : prego_miniroad_step_frames(h, n_active, n_frames, rgb, flow, h_ws, out, am, flags, ws + l.wide, l.wide_bytes, stream);
-  if (rc) return rc;                                          // the pool itself is untouched: only the commit writes it
-  if (launch_pool_commit_frames(p->g, slots, n_active, n_frames, h_ws, am, s))
-    return prego_fail_(PREGO_EINVAL, "step_pool_frames: commit refused its arguments");
-  HIPCHK(hipGetLastError());
-  return PREGO_OK;
+  return step_pool_impl("step_pool_frames", h, p, n_active, true, n_frames, slots, rgb, flow, out, argmax, ant_out, ant_argmax, flags,
+                        workspace, workspace_bytes, stream);
 }
 
 extern "C" int prego_stream_pool_vote(prego_stream_pool* p, int n, const int32_t* slots, const int32_t* ids, prego_stream_t stream) {

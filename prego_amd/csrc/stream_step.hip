@@ -9,52 +9,33 @@
 //   ln_relu_rows       LayerNorm + ReLU (the batched path's kernel, rowwise.hip)
 //   stream_gemv x 2    gi = e W_ih^T + b_ih (+ b_hh for r, z)  and  gh = h W_hh^T   in ONE launch (two problem descriptors)
 //   stream_gates_head  GRU gates + state update, ReLU, classifier, softmax, argmax: one workgroup per stream
-// stream_gemv: a workgroup owns 16 output features (one MFMA M tile), wave q the K-quarter [q K/4, (q+1) K/4); every weight
-// fragment of the wave (up to 32 x 16 B per lane) is requested before the first MFMA, the streams ride on the MFMA N dimension
-// (lanes whose stream index is >= n load nothing), the four partial tiles meet in LDS and are added in K order.
-#include "common.h"
-#include "kernels.h"
+// The product itself - who owns which rows, the K-quarters, the permuted contraction index, the K-order join - is stream_tile.h's, the
+// classifier stream_head.h's.  This file adds: stream_gemv's input side (two fp32 or 16-bit halves converted in registers, or the
+// LayerNorm fusion), with every request of the kernel out before the first MFMA, and the GRU gates in front of the classifier.
 #include "stream_head.h"
+#include "stream_launch.h"
 
 #define SG_MAXKS 32            // k-steps of 32 per wave: K <= 4096
 
-struct GemvProb {
-  const bf16_t* W;             // [Nout][K] bf16, row-major
-  const void* X;               // input columns [0, kx1): [n][ldx], fp32 or bf16
-  const void* X2;              // input columns [kx1, K): [n][ldx2]; nullptr = zeros (all-zero flow half)
-  const float* bias;           // [Nout], nullable
-  float* Y;                    // [n][Nout] fp32
-  const float* ln_g;           // non-null: X is the fp32 PRE-LayerNorm row [n][K] (n <= 4): the workgroup normalises it itself
-  const float* ln_b;
-  float ln_eps;
-  int Nout, K, kx1, ldx, ldx2, x_bf16, block0;
-};
-struct GemvArgs { GemvProb p[2]; int nprob, n, rows; };
-
 // MAXKS: k-steps of 32 a wave may hold (32: K <= 4096, one workgroup per CU; 16: K <= 2048, 192 registers, two per CU).
-// a.rows: output features per workgroup, 8 or 16 (8 = half an MFMA M tile: the matrix pipe is idle anyway, and 2048 outputs
-// then make 256 workgroups - every CU pulls its share of the weights; the per-CU request rate, not HBM, bounds this kernel).
-// A lane requests 32 CONTIGUOUS bytes of its weight row per pair of k-steps (the four lanes of a row cover one 128-byte line);
-// the contraction index is permuted accordingly - MFMA 2p takes columns 16 g .. 16 g + 7 of the pair's 64, MFMA 2p + 1 columns
-// 16 g + 8 .. 16 g + 15 - and the input fragment is loaded with the same permutation.
+// a.rows: output features per workgroup, 8 or 16 (stream_rows_per_wg).  Lanes whose stream index is >= n load nothing.
 // LNX: problems whose ln_g is set take their input through LayerNorm + ReLU (rnn.py:41-42) inside the kernel: the workgroup loads
 // the <= 4 pre-LayerNorm rows (requests issued BEFORE the weight requests, so that waiting for them leaves the weights in
 // flight), computes the two-pass statistics with two block reductions, and reads its input fragments from the normalised bf16
 // rows in LDS.  384 workgroups repeat the same 8 KB row: cheaper than the extra launch of a LayerNorm kernel (5.9 us).
-// OT: 16-bit operand type tag (bf16_t / f16_t, common.h)
 template <int MAXKS, bool LNX, typename OT = bf16_t>
 __global__ __launch_bounds__(256, MAXKS > 16 ? 1 : 2) void stream_gemv_kernel(GemvArgs a) {
-  __shared__ f32x4 red[4][64];
+  __shared__ f32x4 red[1][4][64];
   __shared__ __attribute__((aligned(16))) bf16_t xs[LNX ? 4 : 1][LNX ? MAXKS * 128 : 8];
   __shared__ float sred[2][4][4];
   const int pi = (a.nprob > 1 && (int)blockIdx.x >= a.p[1].block0) ? 1 : 0;
   const GemvProb p = a.p[pi];
-  const int tid = threadIdx.x, lane = tid & 63, q = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l15 = lane & 15, g = lane >> 4;
+  const Lane L = lane_coords();
+  const int tid = L.tid, lane = L.lane, q = L.q, l15 = L.l15, g = L.g;
   const int j0 = ((int)blockIdx.x - p.block0) * a.rows;
   const int kq = p.K >> 2, npair = kq >> 6;                  // K % 256 == 0
   const bool live = l15 < a.n, wlive = l15 < a.rows;
-  const bf16_t* wrow = p.W + (size_t)(j0 + (wlive ? l15 : 0)) * p.K + q * kq + 16 * g;
+  const bf16_t* wrow = p.W + (size_t)(j0 + (wlive ? l15 : 0)) * p.K + quarter_col(L, kq);
   constexpr int MAXP = MAXKS / 2;
   // every global request of the kernel goes out up front: a dependent round trip to memory costs ~2 us here, the arithmetic nothing
   f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
@@ -83,14 +64,7 @@ __global__ __launch_bounds__(256, MAXKS > 16 ? 1 : 2) void stream_gemv_kernel(Ge
 
   u32x4 wa[MAXP][2];
   u32x4 xr[MAXP][4];
-#pragma unroll
-  for (int pr = 0; pr < MAXP; ++pr) {
-    wa[pr][0] = (u32x4){0u, 0u, 0u, 0u}; wa[pr][1] = (u32x4){0u, 0u, 0u, 0u};
-    if (pr < npair && wlive) {                               // read once: streams past the L2
-      wa[pr][0] = __builtin_nontemporal_load((const u32x4*)(wrow + pr * 64));
-      wa[pr][1] = __builtin_nontemporal_load((const u32x4*)(wrow + pr * 64 + 8));
-    }
-  }
+  load_w_pairs<MAXP, true>(wrow, npair, wlive, wa);
   if constexpr (LNX) {
     if (ln) {
       const float invK = 1.0f / (float)p.K;
@@ -106,7 +80,7 @@ __global__ __launch_bounds__(256, MAXKS > 16 ? 1 : 2) void stream_gemv_kernel(Ge
       __syncthreads();
 #pragma unroll
       for (int r = 0; r < 4; ++r) if (r < a.n) {
-        mu[r] = ((sred[0][0][r] + sred[0][1][r]) + (sred[0][2][r] + sred[0][3][r])) * invK;
+        mu[r] = join_quarters(sred[0][0][r], sred[0][1][r], sred[0][2][r], sred[0][3][r]) * invK;
         float qacc = 0.f;
 #pragma unroll
         for (int c = 0; c < EPL; ++c) if (c < epl) { const float d = yv[r][c] - mu[r]; qacc += d * d; }
@@ -116,7 +90,7 @@ __global__ __launch_bounds__(256, MAXKS > 16 ? 1 : 2) void stream_gemv_kernel(Ge
       __syncthreads();
 #pragma unroll
       for (int r = 0; r < 4; ++r) if (r < a.n) {
-        rstd[r] = 1.0f / sqrtf(((sred[1][0][r] + sred[1][1][r]) + (sred[1][2][r] + sred[1][3][r])) * invK + p.ln_eps);
+        rstd[r] = 1.0f / sqrtf(join_quarters(sred[1][0][r], sred[1][1][r], sred[1][2][r], sred[1][3][r]) * invK + p.ln_eps);
 #pragma unroll
         for (int c = 0; c < EPL; c += 2)
           if (c < epl) {
@@ -134,7 +108,7 @@ __global__ __launch_bounds__(256, MAXKS > 16 ? 1 : 2) void stream_gemv_kernel(Ge
     for (int v = 0; v < 4; ++v) xr[pr][v] = (u32x4){0u, 0u, 0u, 0u};
     if (LNX && ln) {
       if (pr < npair && live) {                              // n <= 4 rows: live lanes are l15 < n
-        const bf16_t* src = &xs[l15][q * kq + pr * 64 + 16 * g];
+        const bf16_t* src = &xs[l15][quarter_col(L, kq) + pr * 64];
         xr[pr][0] = *(const u32x4*)src; xr[pr][1] = *(const u32x4*)(src + 8);
       }
     } else if (pr < npair) {
@@ -154,141 +128,94 @@ __global__ __launch_bounds__(256, MAXKS > 16 ? 1 : 2) void stream_gemv_kernel(Ge
     }
   }
   __builtin_amdgcn_sched_barrier(0);                         // every request is out before the first use
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int pr = 0; pr < MAXP; ++pr)
-    if (pr < npair) {
-      u32x4 x0 = xr[pr][0], x1 = xr[pr][1];
-      if (!p.x_bf16 && !(LNX && ln)) {
-        const f32x4 f0 = __builtin_bit_cast(f32x4, xr[pr][0]), f1 = __builtin_bit_cast(f32x4, xr[pr][1]);
-        const f32x4 f2 = __builtin_bit_cast(f32x4, xr[pr][2]), f3 = __builtin_bit_cast(f32x4, xr[pr][3]);
-        x0 = (u32x4){op16<OT>::pack2_sat(f0[0], f0[1]), op16<OT>::pack2_sat(f0[2], f0[3]), op16<OT>::pack2_sat(f1[0], f1[1]), op16<OT>::pack2_sat(f1[2], f1[3])};
-        x1 = (u32x4){op16<OT>::pack2_sat(f2[0], f2[1]), op16<OT>::pack2_sat(f2[2], f2[3]), op16<OT>::pack2_sat(f3[0], f3[1]), op16<OT>::pack2_sat(f3[2], f3[3])};
-      }
-      acc = op16<OT>::mfma(__builtin_bit_cast(bf16x8, wa[pr][0]), __builtin_bit_cast(bf16x8, x0), acc);
-      acc = op16<OT>::mfma(__builtin_bit_cast(bf16x8, wa[pr][1]), __builtin_bit_cast(bf16x8, x1), acc);
-    }
-  red[q][lane] = acc;
-  __syncthreads();
+  const f32x4 acc = mfma_pairs<OT, MAXP>(wa, npair, [&](int pr, u32x4& x0, u32x4& x1) {
+    x0 = xr[pr][0]; x1 = xr[pr][1];
+    if (!p.x_bf16 && !(LNX && ln))
+      pack16_sat<OT>(__builtin_bit_cast(f32x4, xr[pr][0]), __builtin_bit_cast(f32x4, xr[pr][1]), __builtin_bit_cast(f32x4, xr[pr][2]),
+                     __builtin_bit_cast(f32x4, xr[pr][3]), x0, x1);
+  });
+  const auto& rd = meet_quarters(red, 0, L, acc);
   if (q == 0 && 4 * g < a.rows) {
     // accumulator element e of lane (column l15 = stream, g): output feature j0 + 4 g + e
-    f32x4 r = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+    f32x4 r = join_quarters(rd, lane);
     r += bias4;
     if (live) *(f32x4*)(p.Y + (size_t)l15 * p.Nout + j0 + 4 * g) = r;
   }
 }
 
-// GRU gates + state update (rnn.py:61, torch.nn.GRU's equations), ReLU + classifier (rnn.py:62-64), eval softmax (rnn.py:66-70),
-// np.argmax (eval.py:53, first max wins).  gi already holds b_ih (+ b_hh for the r, z rows), gh = h W_hh^T without bias.
-// One workgroup per stream.  The classifier is the batched head's arithmetic for one frame: logits^T = W_c relu(h)^T on the MFMA
-// with the frame in column 0, wave q the K-quarter of every class tile (all NT x 8 weight fragments requested at once), the four
-// partials added in K order.
+// GRU gates + state update (rnn.py:61, gru_unit), ReLU + classifier (rnn.py:62-64), eval softmax (rnn.py:66-70), np.argmax (eval.py:53,
+// first max wins).  gi already holds b_ih (+ b_hh for the r, z rows), gh = h W_hh^T without bias.  One workgroup per stream; the
+// classifier's operand row is relu(h_t) in LDS, on MFMA column 0.
 template <int NT, typename OT = bf16_t>
 __global__ __launch_bounds__(256, 1) void stream_gates_head_kernel(const float* __restrict__ gi, const float* __restrict__ gh,
                                                                    const float* __restrict__ b_hn, float* __restrict__ h_state,
                                                                    const bf16_t* __restrict__ wc, const float* __restrict__ bc, int C,
                                                                    int softmax, float* __restrict__ out, int* __restrict__ argmax) {
-  constexpr int H = 1024;
+  constexpr int H = kStreamH;
   __shared__ __attribute__((aligned(16))) bf16_t shb[H];      // relu(h_t) as the bf16 the head multiplies
-  __shared__ f32x4 redh[4][NT][4];
+  __shared__ f32x4 redh[1][4][NT][4];
   __shared__ float sl[128];
-  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, q = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l15 = lane & 15, g = lane >> 4;
+  const int s = blockIdx.x;
+  const Lane L = lane_coords();
   // classifier weights first: they do not depend on the gates (requests in flight under the gate math)
   bf16x8 wa[NT][8];
-#pragma unroll
-  for (int ct = 0; ct < NT; ++ct)
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) wa[ct][ks] = *(const bf16x8*)(wc + (size_t)(ct * 16 + l15) * H + q * 256 + ks * 32 + 8 * g);
-  const float bc_t = tid < C ? bc[tid] : 0.f;               // requested with everything else (a late load is one more ~2 us round trip)
+  float bc_t;
+  head_request<NT>(wc, bc, C, L, wa, bc_t);
   const float* gis = gi + (size_t)s * 3 * H;
   const float* ghs = gh + (size_t)s * 3 * H;
   {
-    const int u = tid * 4;                                    // four consecutive hidden units per thread
+    const int u = L.tid * 4;                                  // four consecutive hidden units per thread
     const f32x4 ir = *(const f32x4*)(gis + u), iz = *(const f32x4*)(gis + H + u), in_ = *(const f32x4*)(gis + 2 * H + u);
     const f32x4 hr = *(const f32x4*)(ghs + u), hz = *(const f32x4*)(ghs + H + u), hn_ = *(const f32x4*)(ghs + 2 * H + u);
     const f32x4 bn = *(const f32x4*)(b_hn + u), hp = *(const f32x4*)(h_state + (size_t)s * H + u);
     f32x4 hnew;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float r = sigmoidf_(ir[e] + hr[e]);
-      const float z = sigmoidf_(iz[e] + hz[e]);
-      const float n = tanhf_(in_[e] + r * (hn_[e] + bn[e]));
-      hnew[e] = (1.0f - z) * n + z * hp[e];
-    }
+    for (int e = 0; e < 4; ++e) hnew[e] = gru_unit(ir[e], hr[e], iz[e], hz[e], in_[e], hn_[e], bn[e], hp[e]);
     *(f32x4*)(h_state + (size_t)s * H + u) = hnew;
-    u32x2 w; w[0] = op16<OT>::pack2(fmaxf(hnew[0], 0.f), fmaxf(hnew[1], 0.f)); w[1] = op16<OT>::pack2(fmaxf(hnew[2], 0.f), fmaxf(hnew[3], 0.f));
-    *(u32x2*)(shb + u) = w;
+    store_relu4<OT>(shb + u, hnew);
   }
   __syncthreads();
-  f32x4 acc[NT];
-#pragma unroll
-  for (int ct = 0; ct < NT; ++ct) acc[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int ks = 0; ks < 8; ++ks) {
-    u32x4 hb = *(const u32x4*)(shb + q * 256 + ks * 32 + 8 * g);
-    if (l15 != 0) hb = (u32x4){0u, 0u, 0u, 0u};              // the frame is column 0 of the N dimension
-#pragma unroll
-    for (int ct = 0; ct < NT; ++ct) acc[ct] = op16<OT>::mfma(wa[ct][ks], __builtin_bit_cast(bf16x8, hb), acc[ct]);
-  }
-  if (l15 == 0) {
-#pragma unroll
-    for (int ct = 0; ct < NT; ++ct) redh[q][ct][g] = acc[ct];
-  }
+  head_products<NT, OT>(wa, L, [&](int ks) {
+    u32x4 hb = *(const u32x4*)(shb + L.q * 256 + ks * 32 + 8 * L.g);
+    if (L.l15 != 0) hb = (u32x4){0u, 0u, 0u, 0u};            // the frame is column 0 of the N dimension
+    return hb;
+  }, redh);
   __syncthreads();
-  stream_head_logits<NT>(redh, sl, tid, C, bc_t);
+  stream_head_logits<NT>(redh[0], sl, L.tid, C, bc_t);
   __syncthreads();
-  if (q == 0)
-    stream_head_finish(sl, lane, C, softmax, out != nullptr ? out + (size_t)s * C : nullptr, argmax != nullptr ? argmax + s : nullptr);
+  if (L.q == 0)
+    stream_head_finish(sl, L.lane, C, softmax, out != nullptr ? out + (size_t)s * C : nullptr, argmax != nullptr ? argmax + s : nullptr);
 }
 
 // y[n][Nout] = x[n][K] W^T + bias for one or two problems in one launch.  Returns -1 on an unsupported shape.
 int launch_stream_gemv(int nprob, const StreamGemv* pr, int n, hipStream_t s, bool f16) {
   if (nprob < 1 || nprob > 2 || n < 1 || n > 16) return -1;
-  GemvArgs a{};
-  a.nprob = nprob; a.n = n;
-  int kmax = 0, tiles16 = 0;
+  bool any_ln = false;
   for (int i = 0; i < nprob; ++i) {
     if (pr[i].Nout % 16 || pr[i].K % 256 || pr[i].K > 128 * SG_MAXKS || pr[i].kx1 % 64 || pr[i].kx1 > pr[i].K) return -1;
-    kmax = pr[i].K > kmax ? pr[i].K : kmax;
-    tiles16 += pr[i].Nout / 16;
-  }
-  a.rows = tiles16 < 200 ? 8 : 16;                           // fewer than ~one workgroup per CU at 16 rows: halve the tile
-  int blocks = 0;
-  for (int i = 0; i < nprob; ++i) {
-    a.p[i] = GemvProb{(const bf16_t*)pr[i].W, pr[i].X, pr[i].X2, pr[i].bias, pr[i].Y, pr[i].ln_g, pr[i].ln_b, pr[i].ln_eps, pr[i].Nout, pr[i].K,
-                      pr[i].kx1, pr[i].ldx, pr[i].ldx2, pr[i].x_bf16, blocks};
-    blocks += pr[i].Nout / a.rows;
-  }
-  bool any_ln = false;
-  for (int i = 0; i < nprob; ++i)
     if (pr[i].ln_g != nullptr) {
       if (n > 4 || pr[i].K % 2048 || pr[i].kx1 != pr[i].K || pr[i].x_bf16 || !pr[i].ln_b) return -1;
       any_ln = true;
     }
-  if (f16) {
-    if (kmax > 2048) { if (any_ln) stream_gemv_kernel<32, true, f16_t><<<blocks, 256, 0, s>>>(a); else stream_gemv_kernel<32, false, f16_t><<<blocks, 256, 0, s>>>(a); }
-    else { if (any_ln) stream_gemv_kernel<16, true, f16_t><<<blocks, 256, 0, s>>>(a); else stream_gemv_kernel<16, false, f16_t><<<blocks, 256, 0, s>>>(a); }
-    return 0;
   }
-  if (kmax > 2048) { if (any_ln) stream_gemv_kernel<32, true><<<blocks, 256, 0, s>>>(a); else stream_gemv_kernel<32, false><<<blocks, 256, 0, s>>>(a); }
-  else { if (any_ln) stream_gemv_kernel<16, true><<<blocks, 256, 0, s>>>(a); else stream_gemv_kernel<16, false><<<blocks, 256, 0, s>>>(a); }
+  GemvArgs a{};
+  int kmax = 0;
+  const int blocks = fill_gemv_args(nprob, pr, n, a, &kmax);
+  for_operand(f16, [&](auto ot) {
+    using OT = typename decltype(ot)::type;
+    if (kmax > 2048) { if (any_ln) stream_gemv_kernel<32, true, OT><<<blocks, 256, 0, s>>>(a); else stream_gemv_kernel<32, false, OT><<<blocks, 256, 0, s>>>(a); }
+    else { if (any_ln) stream_gemv_kernel<16, true, OT><<<blocks, 256, 0, s>>>(a); else stream_gemv_kernel<16, false, OT><<<blocks, 256, 0, s>>>(a); }
+  });
   return 0;
 }
 
 // H == 1024 (the handle's hidden size); C <= 128, wc holds ceil(C / 16) * 16 rows
 int launch_stream_gates_head(const float* gi, const float* gh, const float* b_hn, float* h_state, const void* wc, const float* bc, int n,
                              int H, int C, int softmax, float* out, int* argmax, hipStream_t s, bool f16) {
-  if (H != 1024 || C < 1 || C > 128) return -1;
-#define SGH(NT)                                                                                                                              \
-  do {                                                                                                                                       \
-    if (f16) stream_gates_head_kernel<NT, f16_t><<<n, 256, 0, s>>>(gi, gh, b_hn, h_state, (const bf16_t*)wc, bc, C, softmax, out, argmax);   \
-    else stream_gates_head_kernel<NT><<<n, 256, 0, s>>>(gi, gh, b_hn, h_state, (const bf16_t*)wc, bc, C, softmax, out, argmax);              \
-  } while (0)
-  switch ((C + 15) / 16) {
-    case 1: SGH(1); break; case 2: SGH(2); break; case 3: SGH(3); break; case 4: SGH(4); break;
-    case 5: SGH(5); break; case 6: SGH(6); break; case 7: SGH(7); break; default: SGH(8); break;
-  }
-#undef SGH
+  if (H != kStreamH || C < 1 || C > 128) return -1;
+  for_class_tiles(C, f16, [&](auto nt, auto ot) {
+    stream_gates_head_kernel<decltype(nt)::value, typename decltype(ot)::type><<<n, 256, 0, s>>>(gi, gh, b_hn, h_state, (const bf16_t*)wc, bc, C,
+                                                                                                   softmax, out, argmax);
+  });
   return 0;
 }
