@@ -226,7 +226,7 @@ int prego_miniroad_step_wide_anticipation(prego_miniroad* h, int n_streams, cons
 
 /* Multi-frame streaming step (an addition to ABI 7, existing signatures unchanged): n_frames new frames for each of n_streams streams in ONE
  * call - a feeder that works in batches, a stream that reconnects with a backlog, a video that joins late.  1 <= n_frames <= 32, the same
- * for every stream of the call (ragged backlogs: group the streams by backlog, one call per group), n_streams >= 1 and
+ * for every stream of the call (ragged backlogs: prego_miniroad_step_ragged below), n_streams >= 1 and
  * n_streams * n_frames <= 256.  Longer backlogs, or more rows, are prego_miniroad_forward's work (h0 / h_last).
  *   rgb / flow     device fp32 [n_streams, n_frames, d_rgb] / [n_streams, n_frames, d_flow]; flow == NULL = zero flow half
  *   h_state        device fp32 [n_streams, hid], read and OVERWRITTEN with the state after the last frame
@@ -252,6 +252,35 @@ int prego_miniroad_step_frames(prego_miniroad* h, int n_streams, int n_frames, c
 int prego_miniroad_step_frames_anticipation(prego_miniroad* h, int n_streams, int n_frames, const float* rgb, const float* flow, float* h_state,
                                             float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax, int flags, void* workspace,
                                             size_t workspace_bytes, prego_stream_t stream);
+
+/* Ragged streaming burst (an addition to ABI 7, existing signatures unchanged): prego_miniroad_step_frames with a frame count PER STREAM -
+ * streams that reconnect with different backlogs, late joiners, a batching extractor that returns a different number of frames per video -
+ * in ONE call instead of one call per group of equal backlog.
+ *   n_frames       HOST int32 [n_streams], 1 <= n_frames[s] <= 32, R = sum n_frames[s] <= 256.  Read before the call returns and never
+ *                  after: it may be freed or overwritten at once.  What the kernels need of it travels in their arguments.
+ *   rgb / flow     device fp32, PACKED: [R, d_rgb] / [R, d_flow]; stream s owns rows off[s] .. off[s] + n_frames[s]) in frame order, off =
+ *                  the prefix sum of n_frames in the caller's stream order; flow == NULL = zero flow half
+ *   h_state        device fp32 [n_streams, hid], read and OVERWRITTEN: stream s is advanced by n_frames[s] frames
+ *   out [R, n_classes], argmax [R], ant_out [R, ant_len, n_classes], ant_argmax [R, ant_len]: packed as the frames are; nullable as in
+ *                  prego_miniroad_step_frames.  With every count equal to K this is byte for byte its [n_streams, K, ...] layout.
+ * The launches are prego_miniroad_step_frames's over R rows, with one recurrent launch per frame index t = 0 .. max n_frames - 1 that
+ * advances only the streams with n_frames[s] > t (csrc/stream_frames.hip: the streams are walked in descending order of count, so those
+ * are a prefix): 5 + max n_frames launches (+ 2 for the anticipation head).
+ * Bits: for every stream and frame, every output, the state after the frame and the state left in h_state are bit for bit
+ * prego_miniroad_step_frames's (hence prego_miniroad_step_wide's frame by frame), whatever the other streams' counts, the order of the
+ * streams in the call or the internal order.
+ *   workspace      device memory, 256-byte aligned, prego_miniroad_step_ragged_workspace_bytes(h, n_streams, R) bytes (0 = the shape is
+ *                  refused: n_streams outside 1..256, R < n_streams, R > 256); it depends on n_streams and R only.  Query again after
+ *                  set_anticipation.
+ * No device allocation, no host wait.  PREGO_EINVAL with a message, nothing launched: n_frames NULL, a count outside 1..32 (the message
+ * names stream and count), R > 256, n_streams outside 1..256, a NULL, unaligned or too small workspace, everything prego_miniroad_step
+ * refuses, and _anticipation before set_anticipation. */
+size_t prego_miniroad_step_ragged_workspace_bytes(const prego_miniroad* h, int n_streams, int n_rows);
+int prego_miniroad_step_ragged(prego_miniroad* h, int n_streams, const int32_t* n_frames, const float* rgb, const float* flow, float* h_state,
+                               float* out, int32_t* argmax, int flags, void* workspace, size_t workspace_bytes, prego_stream_t stream);
+int prego_miniroad_step_ragged_anticipation(prego_miniroad* h, int n_streams, const int32_t* n_frames, const float* rgb, const float* flow,
+                                            float* h_state, float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax, int flags,
+                                            void* workspace, size_t workspace_bytes, prego_stream_t stream);
 
 /* Stream pool (an addition to ABI 7, existing signatures unchanged): the online detector for a host whose streams open and close at
  * different times and of which only some have a new frame at any tick.  Every live video owns a SLOT of one device block: its GRU state
@@ -310,6 +339,17 @@ size_t prego_miniroad_step_pool_frames_workspace_bytes(const prego_miniroad* h, 
 int prego_miniroad_step_pool_frames(prego_miniroad* h, prego_stream_pool* p, int n_active, int n_frames, const int32_t* slots, const float* rgb,
                                     const float* flow, float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax, int flags,
                                     void* workspace, size_t workspace_bytes, prego_stream_t stream);
+/* prego_miniroad_step_pool_frames with a frame count per slot: n_frames HOST int32 [n_active] (1..32 each, R = their sum <= 256; free to
+ * reuse once the call returns, as `slots` is), frames and outputs packed as in prego_miniroad_step_ragged with row block i belonging to
+ * slots[i] - gather, prego_miniroad_step_ragged (_anticipation when ant_out or ant_argmax is non-NULL) through its own entry point, then
+ * one commit that puts every state row back once and has slot i's lane take its n_frames[i] ids in frame order.  Bits:
+ * prego_miniroad_step_ragged's; a slot's record afterwards is word for word the record after n_frames[i] prego_miniroad_step_pool calls.
+ * A call that fails leaves the pool untouched.  Refusals: prego_miniroad_step_pool's and prego_miniroad_step_ragged's, nothing launched.
+ * Workspace: prego_miniroad_step_pool_ragged_workspace_bytes(h, n_active, R) bytes.  No device allocation, no host wait. */
+size_t prego_miniroad_step_pool_ragged_workspace_bytes(const prego_miniroad* h, int n_active, int n_rows);
+int prego_miniroad_step_pool_ragged(prego_miniroad* h, prego_stream_pool* p, int n_active, const int32_t* n_frames, const int32_t* slots,
+                                    const float* rgb, const float* flow, float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax,
+                                    int flags, void* workspace, size_t workspace_bytes, prego_stream_t stream);
 int prego_stream_pool_vote(prego_stream_pool* p, int n, const int32_t* slots, const int32_t* ids, prego_stream_t stream);
 int prego_stream_pool_flush(prego_stream_pool* p, int n, const int32_t* slots, prego_stream_t stream);
 int prego_stream_pool_reset(prego_stream_pool* p, int n, const int32_t* slots, prego_stream_t stream);

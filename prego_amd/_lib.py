@@ -47,6 +47,8 @@ SYMBOLS = [
     "prego_miniroad_step_pool", "prego_stream_pool_vote", "prego_stream_pool_flush", "prego_stream_pool_reset", "prego_stream_pool_record",
     "prego_miniroad_step_frames_workspace_bytes", "prego_miniroad_step_frames", "prego_miniroad_step_frames_anticipation",
     "prego_miniroad_step_pool_frames_workspace_bytes", "prego_miniroad_step_pool_frames",
+    "prego_miniroad_step_ragged_workspace_bytes", "prego_miniroad_step_ragged", "prego_miniroad_step_ragged_anticipation",
+    "prego_miniroad_step_pool_ragged_workspace_bytes", "prego_miniroad_step_pool_ragged",
 ]
 # include/prego_amd_debug.h: only in libprego_amd_debug.so
 DEBUG_SYMBOLS = ["prego_miniroad_debug_stamps", "prego_debug_gemm_bf16", "prego_debug_attention_bwd", "prego_debug_attention_fwd",
@@ -118,6 +120,14 @@ def _open(path: str, debug: bool) -> C.CDLL:
     lib.prego_miniroad_step_pool_frames_workspace_bytes.argtypes = [vp, i32, i32]
     lib.prego_miniroad_step_pool_frames_workspace_bytes.restype = sz
     lib.prego_miniroad_step_pool_frames.argtypes = [vp, vp, i32, i32, C.POINTER(C.c_int32), vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]
+    lib.prego_miniroad_step_ragged_workspace_bytes.argtypes = [vp, i32, i32]
+    lib.prego_miniroad_step_ragged_workspace_bytes.restype = sz
+    lib.prego_miniroad_step_ragged.argtypes = [vp, i32, C.POINTER(C.c_int32), vp, vp, vp, vp, vp, i32, vp, sz, vp]
+    lib.prego_miniroad_step_ragged_anticipation.argtypes = [vp, i32, C.POINTER(C.c_int32), vp, vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]
+    lib.prego_miniroad_step_pool_ragged_workspace_bytes.argtypes = [vp, i32, i32]
+    lib.prego_miniroad_step_pool_ragged_workspace_bytes.restype = sz
+    lib.prego_miniroad_step_pool_ragged.argtypes = [vp, vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, vp, vp, vp, vp, i32, vp, sz,
+                                                    vp]
     lib.prego_stream_pool_vote.argtypes = [vp, i32, C.POINTER(C.c_int32), vp, vp]
     lib.prego_stream_pool_flush.argtypes = [vp, i32, C.POINTER(C.c_int32), vp]
     lib.prego_stream_pool_reset.argtypes = [vp, i32, C.POINTER(C.c_int32), vp]

@@ -398,3 +398,22 @@ int launch_frames_cast(const float* rgb, const float* flow, const float* h_state
 // (relu(h_t), 16-bit) row s K + t, and h_state [n][H] when it is non-null (the last frame).  H == 1024
 int launch_frames_recur(const void* whh, const float* gi, const float* b_hn, const float* h0, float* hist, void* hr, float* h_state, int n,
                         int K, int t, int H, hipStream_t s, bool f16 = false);
+
+// ragged streaming step (stream_frames.hip, stream_pool.hip): n <= 256 streams with 1..32 frames each, packed rows, stream s owns rows
+// off[s] .. off[s] + count[s]).  One entry per stream, by value in the kernel arguments (1 KB): off | stream << 16 | count << 24
+constexpr int kRaggedMaxStreams = 256;
+struct RaggedMap { unsigned e[kRaggedMaxStreams]; };
+__host__ __device__ inline unsigned ragged_entry(unsigned off, unsigned stream, unsigned count) { return off | (stream << 16) | (count << 24); }
+__host__ __device__ inline unsigned ragged_off(unsigned e) { return e & 0xffffu; }
+__host__ __device__ inline unsigned ragged_stream(unsigned e) { return (e >> 16) & 0xffu; }
+__host__ __device__ inline unsigned ragged_count(unsigned e) { return e >> 24; }
+// frame t of a ragged call of n streams / `rows` rows: positions [0, n_t) of `walk` - the streams in descending order of count, so those
+// with more than t frames come first - advance; h_{t-1} = h0[stream] (t == 0) or hist row off + t - 1; writes hist and hr row off + t and
+// h_state[stream] in the stream's own last frame.  single_frame: the call's largest count is 1 (W_hh read once: non-temporal)
+int launch_frames_recur_ragged(const void* whh, const float* gi, const float* b_hn, const float* h0, float* hist, void* hr, float* h_state,
+                               const RaggedMap& walk, int n, int rows, int n_t, int t, bool single_frame, int H, hipStream_t s,
+                               bool f16 = false);
+// stream_pool.hip, the commit of a ragged burst: the state row once, then the ids argmax[off .. off + count) of rows.e[i] (the caller's order: entry i =
+// slots[i]) voted in frame order by the slot's lane; off + count <= n_rows <= 256 for every entry, or nothing is launched
+int launch_pool_commit_ragged(const PoolGeom& g, const int* slots, int n, const RaggedMap& rows, int n_rows, const float* h_ws,
+                              const int* argmax, hipStream_t s);

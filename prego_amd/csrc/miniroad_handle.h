@@ -5,7 +5,7 @@
 //   miniroad_plan.cpp     build_plan, device_plan, stage_tables, feed events, row_bytes / fwd_layout and the workspace size
 //   miniroad_forward.cpp  validate_forward, choose_pass, run_chunked_pass, the forward entry points, ant_head
 //   stream_step.cpp       step_refusals, prego_miniroad_step (_anticipation), prego_miniroad_step_wide (_anticipation)
-//   stream_frames.cpp     prego_miniroad_step_frames (_anticipation)
+//   stream_frames.cpp     prego_miniroad_step_frames (_anticipation), prego_miniroad_step_ragged (_anticipation), ragged_plan
 //   stream_pool.cpp       the stream pool: prego_stream_pool_*, prego_miniroad_step_pool (kernels: stream_pool.hip)
 //   miniroad_split.cpp    ring / resident-buffer sizing, forward_split; the per-device order of split passes (g_split_mu, g_split_last)
 //   miniroad_train.cpp    dropout, loss, bwd_layout, backward, AdamW; the debug library's g_ant_full_span
@@ -232,6 +232,13 @@ int ant_head(prego_miniroad* h, const AntOut& ao, const void* HR, const SlotPlan
 // ---- stream_step.cpp
 // what every streaming step refuses, n_max streams per call (16: step, 256: step_wide, step_pool); 0 = the call may go ahead.  Under a HandleScope
 int step_refusals(prego_miniroad* h, int n_streams, int n_max, const float* rgb, const float* flow, const float* h_state, bool ant);
+
+// ---- stream_frames.cpp
+// a ragged call's host array turned into kernel arguments (nothing of the array outlives the call): by_stream = entry i for stream i in
+// the caller's order, walk = the same entries in descending order of count (stable), alive[t] = streams with more than t frames,
+// kmax = the largest count, rows = their sum.  0 = fine; n outside 1..256 is NOT refused here (rows = 0: the caller's own check refuses it)
+struct RaggedPlan { RaggedMap by_stream, walk; int alive[32]; int kmax, rows; };
+int ragged_plan(const char* who, int n, const int32_t* n_frames, RaggedPlan* p);
 
 // ---- the caller's workspace of a streaming entry point
 // carves it into parts that each start 256-byte aligned: take() returns the part's offset, `o` is the size so far

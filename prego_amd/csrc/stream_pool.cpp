@@ -1,4 +1,4 @@
-// Host side of the stream pool (include/prego_amd.h: prego_stream_pool_*, prego_miniroad_step_pool; kernels: stream_pool.hip).  The pool
+// Host side of the stream pool (include/prego_amd.h: prego_stream_pool_*, prego_miniroad_step_pool (_frames, _ragged); kernels: stream_pool.hip).  The pool
 // object is host memory only: the geometry, the addresses inside the caller's device block and a stamp table for the duplicate check.
 // Every entry point validates the whole slot list before its first launch, so a refused call has launched nothing.
 #include "miniroad_handle.h"
@@ -60,6 +60,17 @@ StepPoolLayout step_pool_layout(const prego_miniroad* h, int n, bool burst, int 
   l.am = c.take((size_t)n * K * 4);
   l.wide = c.o;
   l.wide_bytes = burst ? prego_miniroad_step_frames_workspace_bytes(h, n, K) : prego_miniroad_step_wide_workspace_bytes(h, n);
+  l.total = l.wide + l.wide_bytes;
+  return l;
+}
+// the ragged burst: argmax [rows], the dense call is prego_miniroad_step_ragged
+StepPoolLayout step_pool_ragged_layout(const prego_miniroad* h, int n, int rows) {
+  StepPoolLayout l{};
+  WsCarver c;
+  c.take((size_t)n * h->hid * 4);
+  l.am = c.take((size_t)rows * 4);
+  l.wide = c.o;
+  l.wide_bytes = prego_miniroad_step_ragged_workspace_bytes(h, n, rows);
   l.total = l.wide + l.wide_bytes;
   return l;
 }
@@ -168,6 +179,50 @@ extern "C" int prego_miniroad_step_pool_frames(prego_miniroad* h, prego_stream_p
                                                prego_stream_t stream) {
   return step_pool_impl("step_pool_frames", h, p, n_active, true, n_frames, slots, rgb, flow, out, argmax, ant_out, ant_argmax, flags,
                         workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t prego_miniroad_step_pool_ragged_workspace_bytes(const prego_miniroad* h, int n_active, int n_rows) {
+  if (!h || prego_miniroad_step_ragged_workspace_bytes(h, n_active, n_rows) == 0) return 0;
+  return step_pool_ragged_layout(h, n_active, n_rows).total;
+}
+
+// prego_miniroad_step_pool_frames with a frame count per slot: gather, prego_miniroad_step_ragged (_anticipation) through its own entry
+// point, pool_commit_ragged.  The refusals of all three are decided before the gather
+extern "C" int prego_miniroad_step_pool_ragged(prego_miniroad* h, prego_stream_pool* p, int n_active, const int32_t* n_frames,
+                                               const int32_t* slots, const float* rgb, const float* flow, float* out, int32_t* argmax,
+                                               float* ant_out, int32_t* ant_argmax, int flags, void* workspace, size_t workspace_bytes,
+                                               prego_stream_t stream) {
+  const char* who = "step_pool_ragged";
+  const bool ant = ant_out != nullptr || ant_argmax != nullptr;
+  StepPoolLayout l{};
+  RaggedPlan plan;
+  {
+    HandleScope scope_(h);
+    if (!p) return prego_fail_(PREGO_EINVAL, "%s: pool is NULL", who);
+    if (int rc = ragged_plan(who, n_active, n_frames, &plan)) return rc;
+    if (int rc = step_refusals(h, n_active, kPoolMaxActive, rgb, flow, p->g.h, ant)) return rc;
+    if (p->g.hid != h->hid || p->g.ncls != h->ncls)
+      return prego_fail_(PREGO_EINVAL, "%s: the pool was created for hidden_dim %d / %d classes, the handle has %d / %d", who, p->g.hid,
+                         p->g.ncls, h->hid, h->ncls);
+    if (int rc = check_slots(p, who, n_active, slots)) return rc;
+    l = step_pool_ragged_layout(h, n_active, plan.rows);
+    if (int rc = workspace_refusal(who, "prego_miniroad_step_pool_ragged_workspace_bytes", workspace, workspace_bytes, l.total,
+                                   "%d active streams with %d frames in all", n_active, plan.rows)) return rc;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  float* h_ws = (float*)ws;
+  int32_t* am = argmax ? argmax : (int32_t*)(ws + l.am);      // the vote always has its ids
+  if (launch_pool_gather(p->g, slots, n_active, h_ws, s)) return prego_fail_(PREGO_EINVAL, "%s: gather refused its arguments", who);
+  void* dws = ws + l.wide;
+  const int rc = ant ? prego_miniroad_step_ragged_anticipation(h, n_active, n_frames, rgb, flow, h_ws, out, am, ant_out, ant_argmax, flags, dws,
+                                                               l.wide_bytes, stream)
+                     : prego_miniroad_step_ragged(h, n_active, n_frames, rgb, flow, h_ws, out, am, flags, dws, l.wide_bytes, stream);
+  if (rc) return rc;                                          // the pool itself is untouched: only the commit writes it
+  if (launch_pool_commit_ragged(p->g, slots, n_active, plan.by_stream, plan.rows, h_ws, am, s))
+    return prego_fail_(PREGO_EINVAL, "%s: commit refused its arguments", who);
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
 }
 
 extern "C" int prego_stream_pool_vote(prego_stream_pool* p, int n, const int32_t* slots, const int32_t* ids, prego_stream_t stream) {

@@ -5,6 +5,7 @@
 //   pool_gather   h_ws[i] <- pool.h[slots[i]]                       one workgroup per active stream, 16-byte accesses
 //   pool_commit   pool.h[slots[i]] <- h_ws[i], then lane 0 of workgroup i votes argmax[i] into the slot's record
 //   pool_commit_frames  pool_commit after a burst of K frames per slot: the state once, K votes in frame order by the slot's lane
+//   pool_commit_ragged  pool_commit after a ragged burst: a frame count per slot, the ids in packed rows (RaggedMap, by value as the slots)
 //   pool_vote     the vote alone, ids from the caller's device vector  (one lane per stream)
 //   pool_flush    votes a slot's unfinished window (the reference's shorter last window, aggregate.py:57-58)
 //   pool_reset    zeroes a slot's state row and record
@@ -85,6 +86,21 @@ __global__ __launch_bounds__(256) void pool_commit_frames_kernel(PoolGeom g, Poo
   }
 }
 
+// pool_commit for a ragged burst: the ids of slot i are argmax[off .. off + count) of its table entry (packed rows, the caller's order)
+__global__ __launch_bounds__(256) void pool_commit_ragged_kernel(PoolGeom g, PoolSlots sl, RaggedMap rows, const float* __restrict__ h_ws,
+                                                                 const int* __restrict__ argmax) {
+  const int i = blockIdx.x, slot = sl.s[i];
+  const f32x4* src = (const f32x4*)(h_ws + (size_t)i * g.hid);
+  f32x4* dst = (f32x4*)(g.h + (size_t)slot * g.hid);
+  for (int k = threadIdx.x; k < (g.hid >> 2); k += 256) dst[k] = src[k];
+  if (threadIdx.x == 0) {
+    int* rec = pool_record(g, slot);
+    const unsigned e = rows.e[i];
+    const int off = (int)ragged_off(e), K = (int)ragged_count(e);
+    for (int t = 0; t < K; ++t) pool_vote_update(rec, g, argmax[off + t]);
+  }
+}
+
 __global__ __launch_bounds__(64) void pool_vote_kernel(PoolGeom g, PoolSlots sl, int n, const int* __restrict__ ids) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i < n) pool_vote_update(pool_record(g, sl.s[i]), g, ids[i]);
@@ -139,6 +155,16 @@ int launch_pool_commit_frames(const PoolGeom& g, const int* slots, int n, int K,
   PoolSlots sl;
   if (!h_ws || !argmax || K < 1 || K > 32 || n * K > kPoolMaxActive || !pool_slots(g, slots, n, &sl)) return -1;
   pool_commit_frames_kernel<<<n, 256, 0, s>>>(g, sl, K, h_ws, argmax);
+  return 0;
+}
+
+int launch_pool_commit_ragged(const PoolGeom& g, const int* slots, int n, const RaggedMap& rows, int n_rows, const float* h_ws,
+                              const int* argmax, hipStream_t s) {
+  PoolSlots sl;
+  if (!h_ws || !argmax || n_rows < n || n_rows > kPoolMaxActive || !pool_slots(g, slots, n, &sl)) return -1;
+  for (int i = 0; i < n; ++i)
+    if (ragged_count(rows.e[i]) < 1u || ragged_count(rows.e[i]) > 32u || ragged_off(rows.e[i]) + ragged_count(rows.e[i]) > (unsigned)n_rows) return -1;
+  pool_commit_ragged_kernel<<<n, 256, 0, s>>>(g, sl, rows, h_ws, argmax);
   return 0;
 }
 

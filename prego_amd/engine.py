@@ -428,7 +428,7 @@ class MiniRoadEngine:
                     ant_out: Optional[torch.Tensor] = None, ant_argmax: Optional[torch.Tensor] = None):
         """K frames for each of n streams in one call (prego_miniroad_step_frames / _anticipation, csrc/stream_frames.hip): rgb [n, K, d_rgb] /
         flow [n, K, d_flow] (None = zero flow) fp32 cuda contiguous, 1 <= K <= 32 the same for every stream, n K <= 256 (ragged backlogs:
-        one call per group of equal K; longer ones: forward() with h0 / h_last).  h [n, hid] is advanced by K frames in place.  Returns
+        step_ragged; longer ones: forward() with h0 / h_last).  h [n, hid] is advanced by K frames in place.  Returns
         step_wide's tuple with a K axis - (out [n, K, C], argmax int32 [n, K]) and, with want_ant (default: the engine has an anticipation
         head), (ant_out [n, K, L, C], ant_argmax int32 [n, K, L]).  Every frame's bits are step_wide's for a call of 5..256 streams (the
         unfused LayerNorm route, also for n <= 4).  The weights off the sequential path are read once per call, W_hh once per frame from
@@ -475,6 +475,67 @@ class MiniRoadEngine:
                                                                        p(argmax), p(ant_out), p(ant_argmax), *tail))
                 return out, argmax, ant_out, ant_argmax
             check(self.lib.prego_miniroad_step_frames(self.h, n, K, p(rgb if d_rgb > 0 else None), p(flow), p(h), p(out), p(argmax), *tail))
+        return out, argmax
+
+    def step_ragged(self, rgb: Optional[torch.Tensor], flow: Optional[torch.Tensor], counts, h: torch.Tensor, softmax: bool = True,
+                    want_ant=None, out: Optional[torch.Tensor] = None, argmax: Optional[torch.Tensor] = None,
+                    ant_out: Optional[torch.Tensor] = None, ant_argmax: Optional[torch.Tensor] = None):
+        """`step_frames` with a frame count per stream (prego_miniroad_step_ragged / _anticipation, csrc/stream_frames.hip): counts = a
+        sequence of n ints or a CPU int tensor, 1 <= counts[s] <= 32, R = sum(counts) <= 256; rgb [R, d_rgb] / flow [R, d_flow] (None =
+        zero flow) fp32 cuda contiguous, PACKED: stream s owns rows off[s] .. off[s] + counts[s]) in frame order, off = the prefix sum
+        (`prego_amd.stream_pool.pack_bursts`).  h [n, hid]: stream s is advanced by counts[s] frames in place.  Returns step_frames's
+        tuple with a row axis in place of [n, K] - (out [R, C], argmax int32 [R]) and, with want_ant, (ant_out [R, L, C], ant_argmax int32
+        [R, L]) -, every row bit for bit step_frames's whatever the other streams' counts or the order of the streams.  One recurrent
+        launch per frame index up to max(counts), each over the streams that still have a frame.  `counts` is read before the call
+        returns.  Raises on engines the streaming kernels are not built for (fp32, fp16x2, hidden sizes other than 1024, two layers)."""
+        d_rgb, d_flow, emb, hid, ncls = self.dims
+        if self.compute_dtype in ("fp32", "fp16x2") or hid != 1024 or self.num_layers != 1:
+            raise PregoError(f"step_ragged: the streaming kernels are built for bf16 / fp16 operands, hidden_dim 1024, one GRU layer (this engine: "
+                             f"{self.compute_dtype}, hidden_dim {hid}, {self.num_layers} layers); use forward() with h0 / h_last")
+        if want_ant is None:
+            want_ant = bool(getattr(self, "ant_len", 0))
+        if want_ant and not getattr(self, "ant_len", 0):
+            raise PregoError("step_ragged(want_ant=True) before set_anticipation")
+        src = rgb if d_rgb > 0 else flow
+        if src is None:
+            raise PregoError("step_ragged: a --no_rgb model needs the flow frames" if d_rgb == 0 else "step_ragged: rgb is None")
+        if isinstance(counts, torch.Tensor):
+            if counts.is_cuda or counts.is_floating_point() or counts.dim() != 1:
+                raise PregoError(f"step_ragged: counts is a sequence of ints or a 1-d CPU int tensor, got {tuple(counts.shape)} {counts.dtype} on {counts.device}")
+            counts = counts.tolist()
+        counts = [int(k) for k in counts]
+        n, R = len(counts), sum(counts)
+        if src.dim() != 2 or src.shape[0] != R:
+            raise PregoError(f"step_ragged: expected packed frames as [sum(counts) = {R}, d], got {tuple(src.shape)}")
+        L = self.ant_len if want_ant else 0
+        if out is None:
+            out = torch.empty((R, ncls), dtype=torch.float32, device=self.device)
+        if argmax is None:
+            argmax = torch.empty((R,), dtype=torch.int32, device=self.device)
+        if want_ant and ant_out is None:
+            ant_out = torch.empty((R, L, ncls), dtype=torch.float32, device=self.device)
+        if want_ant and ant_argmax is None:
+            ant_argmax = torch.empty((R, L), dtype=torch.int32, device=self.device)
+        checks = [(rgb if d_rgb > 0 else None, (R, d_rgb), torch.float32, "rgb"), (flow, (R, d_flow), torch.float32, "flow"),
+                  (h, (n, hid), torch.float32, "GRU state"), (out, (R, ncls), torch.float32, "out"), (argmax, (R,), torch.int32, "argmax")]
+        if want_ant:
+            checks += [(ant_out, (R, L, ncls), torch.float32, "anticipation out"), (ant_argmax, (R, L), torch.int32, "anticipation argmax")]
+        for t, shape, dt, what in checks:
+            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
+                raise PregoError(f"step_ragged: expected {what} as contiguous {dt} cuda {list(shape)}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        need = self.lib.prego_miniroad_step_ragged_workspace_bytes(self.h, n, R)      # 0: the C call refuses the shape with its message
+        if need and (getattr(self, "_ws_frames", None) is None or self._ws_frames.numel() < need):
+            self._ws_frames = torch.empty(need, dtype=torch.uint8, device=self.device)      # grown here, outside the C call
+        ws = self._ws_frames if need else None
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        tail = (_lib.FWD_SOFTMAX if softmax else 0, p(ws), ws.numel() if ws is not None else 0, C.c_void_p(_stream_ptr(self.device)))
+        arr = (C.c_int32 * max(n, 1))(*[min(max(k, -(2 ** 31)), 2 ** 31 - 1) for k in counts])
+        with torch.cuda.device(self.device):
+            if want_ant:
+                check(self.lib.prego_miniroad_step_ragged_anticipation(self.h, n, arr, p(rgb if d_rgb > 0 else None), p(flow), p(h), p(out),
+                                                                       p(argmax), p(ant_out), p(ant_argmax), *tail))
+                return out, argmax, ant_out, ant_argmax
+            check(self.lib.prego_miniroad_step_ragged(self.h, n, arr, p(rgb if d_rgb > 0 else None), p(flow), p(h), p(out), p(argmax), *tail))
         return out, argmax
 
     # -- training ------------------------------------------------------------------------

@@ -144,10 +144,18 @@ class MROAD(nn.Module):
         return self.engine().step_frames(rgb, flow, h, softmax=True, want_ant=False)
 
     @torch.no_grad()
+    def step_ragged(self, rgb, flow, counts, h):
+        """`step_frames` with a frame count per stream: counts[s] in 1..32, R = sum(counts) <= 256, rgb [R, d_rgb] / flow [R, d_flow] (None =
+        zeros) packed - stream s owns rows off[s] .. off[s] + counts[s]), `prego_amd.stream_pool.pack_bursts` builds them; h [n, hidden_dim]:
+        stream s is advanced by counts[s] frames in place.  Returns (probabilities [R, C], argmax int32 [R]), every row bit for bit
+        `step_frames`'s (csrc/stream_frames.hip)."""
+        return self.engine().step_ragged(rgb, flow, counts, h, softmax=True, want_ant=False)
+
+    @torch.no_grad()
     def stream_pool(self, capacity: int = 256, window: int = 200, max_events: int = 1024):
         """A StreamPool (prego_amd/stream_pool.py) on this model's inference engine: every live video owns a slot with its GRU state and
         its running aggregation record; `push(slots, rgb, flow)` advances any subset by one frame with `step_wide`'s bits (MiniROADA: the
-        anticipation head included), `push_frames` by a burst of K frames each, `close(slot)` returns the stream's 'pred' / 'changes_pred' (utils/aggregate.py:46-90).  Built after
+        anticipation head included), `push_frames` by a burst of K frames each, `push_ragged` by a burst of its own length per slot, `close(slot)` returns the stream's 'pred' / 'changes_pred' (utils/aggregate.py:46-90).  Built after
         the weights are final: the pool keeps the engine it was built on."""
         from .stream_pool import StreamPool
         return StreamPool(self, capacity=capacity, window=window, max_events=max_events)
@@ -256,3 +264,9 @@ class MROADA(MROAD):
         """`MROAD.step_frames` with the anticipation head on the state after every frame.  Returns (probabilities [n, K, C], argmax int32
         [n, K], anticipation probabilities [n, K, L, C], anticipation argmax int32 [n, K, L])."""
         return self.engine().step_frames(rgb, flow, h, softmax=True, want_ant=True)
+
+    @torch.no_grad()
+    def step_ragged(self, rgb, flow, counts, h):
+        """`MROAD.step_ragged` with the anticipation head on the state after every frame.  Returns (probabilities [R, C], argmax int32 [R],
+        anticipation probabilities [R, L, C], anticipation argmax int32 [R, L])."""
+        return self.engine().step_ragged(rgb, flow, counts, h, softmax=True, want_ant=True)

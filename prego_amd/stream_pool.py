@@ -17,6 +17,37 @@ REC_HEADER = 4               # frames, last vote + 1, n_events, overflow (csrc/s
 MAX_ACTIVE = 256             # slots per call
 
 
+def pack_bursts(bursts):
+    """[K_s, d] tensors, one per stream in the caller's order -> (packed [sum K_s, d], counts): the rows `step_ragged` / `push_ragged`
+    take, stream s at rows off[s] .. off[s] + K_s) with off the prefix sum of counts.  Device-free; the inverse is
+    `torch.split(packed, counts)` (`unpack_bursts`)."""
+    bursts = list(bursts)
+    if not bursts:
+        raise PregoError("pack_bursts: no streams")
+    for s, b in enumerate(bursts):
+        if b.dim() != 2 or b.shape[0] < 1 or b.shape[1] != bursts[0].shape[1] or b.dtype != bursts[0].dtype or b.device != bursts[0].device:
+            raise PregoError(f"pack_bursts: stream {s}: expected [K >= 1, {bursts[0].shape[1]}] {bursts[0].dtype} on {bursts[0].device}, got "
+                             f"{tuple(b.shape)} {b.dtype} on {b.device}")
+    return torch.cat(bursts, dim=0).contiguous(), [int(b.shape[0]) for b in bursts]
+
+
+def unpack_bursts(packed, counts):
+    """the inverse of `pack_bursts`, for packed outputs as well: one [K_s, ...] view per stream"""
+    counts = [int(k) for k in counts]
+    if packed.shape[0] != sum(counts):
+        raise PregoError(f"unpack_bursts: {packed.shape[0]} rows, counts sum to {sum(counts)}")
+    return list(torch.split(packed, counts, dim=0))
+
+
+def burst_offsets(counts):
+    """off[s]: the first packed row of stream s"""
+    off, at = [], 0
+    for k in counts:
+        off.append(at)
+        at += int(k)
+    return off
+
+
 class SlotTable:
     """Which slots of a pool are open.  open() hands out the lowest free slot."""
 
@@ -169,8 +200,8 @@ class StreamPool:
     # -- a burst of K frames for a subset of the streams --------------------------------------------
     def push_frames(self, slots, rgb, flow=None, softmax: bool = True, want_ant=None, out=None, argmax=None, ant_out=None, ant_argmax=None):
         """K new frames for each open slot of `slots` in one call (prego_miniroad_step_pool_frames): rgb [n, K, d_rgb] / flow [n, K, d_flow]
-        (None = zero flow) fp32 cuda contiguous, 1 <= K <= 32 the same for every slot, n K <= 256 - group slots by backlog, one call per
-        group; a backlog longer than 32 frames is forward()'s work (h0 / h_last).  Returns `push`'s tuple with a K axis: (out [n, K, C],
+        (None = zero flow) fp32 cuda contiguous, 1 <= K <= 32 the same for every slot, n K <= 256 - slots with different backlogs: `push_ragged`;
+        a backlog longer than 32 frames is forward()'s work (h0 / h_last).  Returns `push`'s tuple with a K axis: (out [n, K, C],
         argmax int32 [n, K]) and, with want_ant, (ant_out [n, K, L, C], ant_argmax int32 [n, K, L]); every frame's bits are `push`'s for a
         call of 5..256 slots.  Each slot's state is advanced by K frames and its record is word for word the record after K `push`
         calls: the K ids are voted in frame order, window boundaries inside the burst included."""
@@ -217,6 +248,65 @@ class StreamPool:
                                                           p(out), p(argmax), p(ant_out) if want_ant else None,
                                                           p(ant_argmax) if want_ant else None, 1 if softmax else 0, p(self._ws),
                                                           self._ws.numel(), C.c_void_p(self._stream_ptr(self.device)))
+        self._check(rc)
+        return (out, argmax, ant_out, ant_argmax) if want_ant else (out, argmax)
+
+    # -- a burst of its own length for each of a subset of the streams -------------------------------
+    def push_ragged(self, slots, counts, rgb, flow=None, softmax: bool = True, want_ant=None, out=None, argmax=None, ant_out=None, ant_argmax=None):
+        """counts[i] new frames (1..32, R = sum(counts) <= 256) for open slot slots[i] in one call (prego_miniroad_step_pool_ragged): rgb
+        [R, d_rgb] / flow [R, d_flow] (None = zero flow) fp32 cuda contiguous, packed in `slots` order (`pack_bursts`).  Returns `push`'s
+        tuple over the packed rows: (out [R, C], argmax int32 [R]) and, with want_ant, (ant_out [R, L, C], ant_argmax int32 [R, L]); every
+        row's bits are `push_frames`'s.  Slot i's state is advanced by counts[i] frames and its record is word for word the record after
+        counts[i] `push` calls."""
+        eng = self.engine
+        if not self._fast:
+            raise PregoError(f"stream pool push_ragged: the streaming kernels are built for bf16 / fp16 operands, hidden_dim 1024, one GRU layer "
+                             f"(this engine: {eng.compute_dtype}, hidden_dim {self._hid}, {eng.num_layers} layers); run the general forward "
+                             "and feed its ids to vote()")
+        slots = self.slots.check(slots, "push_ragged")
+        n = len(slots)
+        if isinstance(counts, torch.Tensor):
+            counts = counts.tolist()
+        counts = [int(k) for k in counts]
+        if len(counts) != n:
+            raise PregoError(f"stream pool push_ragged: {n} slots, {len(counts)} counts")
+        R = sum(counts)
+        d_rgb, d_flow, emb, hid, ncls = eng.dims
+        if want_ant is None:
+            want_ant = bool(getattr(eng, "ant_len", 0))
+        if want_ant and not getattr(eng, "ant_len", 0):
+            raise PregoError("stream pool push_ragged(want_ant=True) before set_anticipation")
+        src = rgb if d_rgb > 0 else flow
+        if src is None:
+            raise PregoError("stream pool push_ragged: a --no_rgb model needs the flow frames" if d_rgb == 0 else "stream pool push_ragged: rgb is None")
+        if src.dim() != 2 or src.shape[0] != R:
+            raise PregoError(f"stream pool push_ragged: expected packed frames as [sum(counts) = {R}, d], got {tuple(src.shape)}")
+        L = eng.ant_len if want_ant else 0
+        if out is None:
+            out = torch.empty((R, ncls), dtype=torch.float32, device=self.device)
+        if argmax is None:
+            argmax = torch.empty((R,), dtype=torch.int32, device=self.device)
+        if want_ant and ant_out is None:
+            ant_out = torch.empty((R, L, ncls), dtype=torch.float32, device=self.device)
+        if want_ant and ant_argmax is None:
+            ant_argmax = torch.empty((R, L), dtype=torch.int32, device=self.device)
+        checks = [(rgb if d_rgb > 0 else None, (R, d_rgb), torch.float32, "rgb"), (flow, (R, d_flow), torch.float32, "flow"),
+                  (out, (R, ncls), torch.float32, "out"), (argmax, (R,), torch.int32, "argmax")]
+        if want_ant:
+            checks += [(ant_out, (R, L, ncls), torch.float32, "anticipation out"), (ant_argmax, (R, L), torch.int32, "anticipation argmax")]
+        for t, shape, dt, what in checks:
+            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
+                raise PregoError(f"stream pool push_ragged: expected {what} as contiguous {dt} cuda {list(shape)}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        need = self.lib.prego_miniroad_step_pool_ragged_workspace_bytes(eng.h, n, R)      # 0: the C call refuses the shape with its message
+        if self._ws is None or self._ws.numel() < need:          # grown here, outside the C call
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(self.device):
+            rc = self.lib.prego_miniroad_step_pool_ragged(eng.h, self.p, n, self._slot_array(counts), self._slot_array(slots),
+                                                          p(rgb if d_rgb > 0 else None), p(flow), p(out), p(argmax),
+                                                          p(ant_out) if want_ant else None, p(ant_argmax) if want_ant else None,
+                                                          1 if softmax else 0, p(self._ws), self._ws.numel(),
+                                                          C.c_void_p(self._stream_ptr(self.device)))
         self._check(rc)
         return (out, argmax, ant_out, ant_argmax) if want_ant else (out, argmax)
 

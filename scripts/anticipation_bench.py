@@ -41,6 +41,14 @@ the slope of (f) between the two largest K of an n_active: what one more frame p
 share of the row-wise products.
 
     python scripts/anticipation_bench.py --step --pool --frames [--steps 200] [--warmup 20] [--rounds 4] [--models L0,L8]
+
+--step --pool --ragged: ragged bursts (StreamPool.push_ragged, csrc/stream_frames.hip: frames_recur_ragged), 16 and 64 scattered slots,
+the same protocol: (r) ONE push_ragged, (g) the route a caller had before it - one push_frames per group of equal count on the same
+slots.  Workloads: counts uniform in 1..8 (seeded, about eight groups, at most 256 rows), one straggler with 32 frames beside streams with
+one, and the control - all counts 4, where (g) is a single push_frames and (r) has nothing to gain: `r_within_control` says whether
+|r - g| stays within the larger of the two p10..p90 widths.
+
+    python scripts/anticipation_bench.py --step --pool --ragged [--steps 200] [--warmup 20] [--rounds 4] [--models L0,L8]
 """
 from __future__ import annotations
 
@@ -77,6 +85,7 @@ def main():
     ap.add_argument("--wide", action="store_true", help="with --step: step_wide against the loop of 16-stream steps")
     ap.add_argument("--pool", action="store_true", help="with --step: StreamPool.push against the dense step_wide and the torch route around it")
     ap.add_argument("--frames", action="store_true", help="with --step --pool: one push_frames of K frames against K push calls")
+    ap.add_argument("--ragged", action="store_true", help="with --step --pool: one push_ragged against one push_frames per group of equal count")
     ap.add_argument("--streams", default=None, help="default: 17,32,64,128,256 (--wide), 4,16,64,256 (--pool)")
     ap.add_argument("--models", default=None, help="L0 = MiniROAD, Lk = MiniROADA with anticipation_length k; default: L0,L1,L8 (--wide), L0,L8 (--pool)")
     ap.add_argument("--paths", default="w,g,c")
@@ -90,6 +99,8 @@ def main():
     if a.step:
         if a.pool and a.frames:
             return step_pool_frames_bench(a)
+        if a.pool and a.ragged:
+            return step_pool_ragged_bench(a)
         return step_pool_bench(a) if a.pool else step_wide_bench(a) if a.wide else step_bench(a)
     dev = "cuda:0"
     lens = workloads.assembly101_eval_lengths()
@@ -476,6 +487,102 @@ def step_pool_frames_bench(a):
         del m, eng
     print(json.dumps({"metric": "per-call device time, us (median of device-event pairs around every call; zero flow; n_active scattered slots of a "
                                 "256-slot pool): f = ONE StreamPool.push_frames of K frames, k = K successive StreamPool.push calls",
+                      "dtype": a.dtype, "calls_per_path_and_round": ticks, "rounds": a.rounds, "table": table}))
+
+
+def _ragged_workloads(n):
+    """{name: counts} of the ragged leg for n streams, every sum <= 256"""
+    import random
+    seed = n
+    while True:                                               # the first seed whose draw fits a call
+        rng = random.Random(seed)
+        uni = [rng.randint(1, 8) for _ in range(n)]
+        if sum(uni) <= 256:
+            break
+        seed += 1
+    return {"uniform1-8": uni, "straggler32": [1] * (n // 2) + [32] + [1] * (n - n // 2 - 1), "equal4": [4] * n}
+
+
+def step_pool_ragged_bench(a):
+    import random
+    from prego_amd.stream_pool import burst_offsets
+    dev, C, cap = "cuda:0", 86, 256
+    ticks = max(a.steps, 200)
+    base = assembly101_cfg(compute_dtype=a.dtype, assume_zero_flow=True)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1234)
+    table = {}
+    for name in a.models.split(","):
+        L = int(name[1:])
+        cfg = anticipation_cfg(base, L) if L else base
+        sd = W.miniroad_a_state_dict(cfg, 20, head_gain=8.0, ant_gain=4.0) if L else W.miniroad_state_dict(base, 20, head_gain=8.0)
+        m = build_model(cfg, dev)
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+        m.eval()
+        eng, ant = m.engine(), L > 0
+        for n in (16, 64):
+            for wl, counts in _ragged_workloads(n).items():
+                pools = {k: m.stream_pool(capacity=cap) for k in "rg"}       # one pool per route: both streams of states advance alike
+                for pool in pools.values():
+                    for _ in range(cap):
+                        pool.open()
+                slots = random.Random(n).sample(range(cap), n)            # scattered, in no order
+                R, off = sum(counts), burst_offsets(counts)
+                x = torch.randn((8, R, 2048), device=dev, generator=gen).clamp_(min=0)
+                out, arg = torch.empty((R, C), device=dev), torch.empty((R,), dtype=torch.int32, device=dev)
+                ao, aa = (torch.empty((R, L, C), device=dev), torch.empty((R, L), dtype=torch.int32, device=dev)) if ant else (None, None)
+                # the grouped route's inputs and buffers are laid out ahead of the timed calls: [n_g, K, d] per group of equal count
+                groups = {}
+                for i, k in enumerate(counts):
+                    groups.setdefault(k, []).append(i)
+                gcalls = []
+                for K, mem in groups.items():
+                    rows = torch.tensor([off[i] + t for i in mem for t in range(K)], device=dev)
+                    ng = len(mem)
+                    gcalls.append(([slots[i] for i in mem], [x[j][rows].view(ng, K, 2048).contiguous() for j in range(8)],
+                                   torch.empty((ng, K, C), device=dev), torch.empty((ng, K), dtype=torch.int32, device=dev),
+                                   torch.empty((ng, K, L, C), device=dev) if ant else None,
+                                   torch.empty((ng, K, L), dtype=torch.int32, device=dev) if ant else None))
+
+                def fr(i):
+                    pools["r"].push_ragged(slots, counts, x[i & 7], None, out=out, argmax=arg, want_ant=ant, ant_out=ao, ant_argmax=aa)
+
+                def fg(i):
+                    for gs, gx, go, ga, gao, gaa in gcalls:
+                        pools["g"].push_frames(gs, gx[i & 7], None, out=go, argmax=ga, want_ant=ant, ant_out=gao, ant_argmax=gaa)
+                paths = {"r": fr, "g": fg}
+                times, rounds = {k: [] for k in paths}, {k: [] for k in paths}
+                for f in paths.values():
+                    for i in range(a.warmup):
+                        f(i)
+                torch.cuda.synchronize()
+                for _ in range(a.rounds):
+                    for k, f in paths.items():
+                        evs = [torch.cuda.Event(enable_timing=True) for _ in range(2 * ticks)]
+                        r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        r0.record()
+                        for i in range(ticks):
+                            evs[2 * i].record()
+                            f(i)
+                            evs[2 * i + 1].record()
+                        r1.record()
+                        torch.cuda.synchronize()
+                        times[k] += [evs[2 * i].elapsed_time(evs[2 * i + 1]) * 1e3 for i in range(ticks)]
+                        rounds[k].append(r0.elapsed_time(r1) * 1e3 / ticks)
+                eng.check()
+                t = {k: {"median_us": float(np.median(v)), "p10_us": float(np.percentile(v, 10)), "p90_us": float(np.percentile(v, 90)),
+                         "round_us": float(np.median(rounds[k]))} for k, v in times.items()}
+                t.update(rows=R, groups=len(groups), max_count=max(counts), g_minus_r_us=t["g"]["median_us"] - t["r"]["median_us"])
+                width = max(t["r"]["p90_us"] - t["r"]["p10_us"], t["g"]["p90_us"] - t["g"]["p10_us"])
+                t["larger_p10_p90_width_us"] = width
+                if wl == "equal4":
+                    t["r_within_control"] = abs(t["g_minus_r_us"]) <= width
+                table[f"{name}_n{n}_{wl}"] = t
+                print(json.dumps({f"{name}_n{n}_{wl}": t}), file=sys.stderr, flush=True)
+                del pools
+        del m, eng
+    print(json.dumps({"metric": "per-call device time, us (median of device-event pairs around every call; zero flow; n scattered slots of a "
+                                "256-slot pool): r = ONE StreamPool.push_ragged, g = one StreamPool.push_frames per group of equal count",
                       "dtype": a.dtype, "calls_per_path_and_round": ticks, "rounds": a.rounds, "table": table}))
 
 
