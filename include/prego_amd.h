@@ -560,6 +560,53 @@ size_t prego_vit_frames_workspace_bytes(const prego_vit* h, int n_frames, int wi
 int prego_vit_forward_frames(prego_vit* h, int n_frames, const float* rgb, const float* flow, float* out_logits, int32_t* out_argmax,
                              int windows_per_batch, int flags, void* workspace, size_t workspace_bytes, prego_stream_t stream);
 
+/* Transformer stream pool (an addition to ABI 7, existing signatures unchanged): live serving for the `Transformer` entry, the
+ * counterpart of prego_stream_pool_* / prego_miniroad_step_pool.  It replaces what a host does around ViTEnc.forward when frames arrive
+ * one at a time (trainer/eval.py:36-56 over dataset.py:53-55,96-103 at stride 1, then utils/aggregate.py:46-90 on the argmax): keeping
+ * the last window_size feature rows of every stream, rebuilding [n, window_size, d] windows each tick, encoding every frame window_size
+ * times (ViT.py:124 does not depend on the position in the window; ViT.py:129 adds the positional row afterwards) and voting on the host.
+ * Every live video owns a SLOT of one device block:
+ *   ring            fp32 [window_size][embedding_dim]: row f mod window_size = linear_encoding(frame f), bias included - the row
+ *                   prego_vit_forward_frames keeps per frame
+ *   ring words      int32 head (the next row to write = frames mod window_size), fill (min(frames, window_size)), two spare words
+ *   record          the stream pool's vote record, unchanged (prego_stream_pool_* above: layout, update rule, overflow bits)
+ *   block           device memory, 256-byte aligned, at least prego_vit_stream_pool_bytes(h, capacity, max_events) bytes, the caller's:
+ *                   the rings at offset 0, then the ring words, then the records.  create enqueues its zeroing on `stream`; an all-zero
+ *                   slot is an empty stream, so opening a stream needs no call.  window_size * embedding_dim * 4 bytes per slot (512 KB
+ *                   at 128 / 1024, 8 MB at 1024 / 2048): the capacity is the caller's choice; _bytes returns 0 and create refuses
+ *                   only what size_t cannot hold.  The handle must outlive the pool.
+ * prego_vit_step_pool: one new frame for the slots named (HOST int32 [n_active], 1 <= n_active <= min(256, capacity), each inside the
+ * pool and named once; free to reuse once the call returns) - the frames are converted and encoded (n_active rows), every row goes into
+ * its slot's ring, one window per slot is read out of the rings (token j: cls + pe[T] for j == T; the bias row + pe[j] where the stream
+ * has fewer than T - j frames, a zero feature row in front of the video; else ring[(head + j) mod T] + pe[j]), the encoder blocks and the
+ * head run exactly as prego_vit_forward_frames runs them for a batch of n_active windows, and every slot's record takes its argmax.
+ * rgb / flow: device fp32 [n_active][d_rgb | d_flow] (flow NULL = zeros), row i belongs to slots[i]; out_logits: device fp32
+ * [n_active][n_classes] raw logits; argmax (nullable: the ids go through the workspace): device int32 [n_active].  flags bit 0: causal
+ * attention.  Bits: the same streams pushed in the same order with the same n_active give the same bits whatever their slot numbers; the
+ * GEMM kernels are chosen by row count, so logits are NOT promised bit-identical to prego_vit_forward_frames or to a call with another
+ * n_active (they agree to the tolerance that holds prego_vit_forward_frames against prego_vit_forward).  No device allocation, no host wait.
+ *   workspace       device memory, 256-byte aligned, prego_vit_step_pool_workspace_bytes(h, n_active) bytes
+ * prego_vit_stream_pool_flush / _reset / _record: prego_stream_pool_flush / _reset / _record for this pool; reset zeroes head, fill and
+ * the record and leaves the ring rows (nothing reads a row that fill does not cover).  prego_vit_stream_pool_window: the slot's logical
+ * window, oldest frame first, into out (device fp32 [window_size][embedding_dim]; bias rows where fill does not reach) and fill into
+ * fill_out (device int32, nullable): for inspection.
+ * PREGO_EINVAL / PREGO_EWORKSPACE with a message, nothing launched: an fp32-operand handle, a call before set_weights, n_active outside
+ * 1..min(256, capacity), a slot outside the pool, a slot named twice, a NULL, unaligned or too small block or workspace, vote_window < 1,
+ * max_events outside 1..1 048 576, a pool created for another window_size, embedding_dim or class count, a missing input.  Not covered:
+ * bursts (K frames per slot per call), a dense step without a pool, the fp32 parity mode.  A pool belongs to one stream at a time. */
+typedef struct prego_vit_stream_pool prego_vit_stream_pool;
+size_t prego_vit_stream_pool_bytes(const prego_vit* h, int capacity, int max_events);
+int prego_vit_stream_pool_create(prego_vit_stream_pool** out, const prego_vit* h, int capacity, int vote_window, int max_events,
+                                 void* device_block, size_t bytes, prego_stream_t stream);
+void prego_vit_stream_pool_destroy(prego_vit_stream_pool* p);
+size_t prego_vit_step_pool_workspace_bytes(const prego_vit* h, int n_active);
+int prego_vit_step_pool(prego_vit* h, prego_vit_stream_pool* p, int n_active, const int32_t* slots, const float* rgb, const float* flow,
+                        float* out_logits, int32_t* argmax, int flags, void* workspace, size_t workspace_bytes, prego_stream_t stream);
+int prego_vit_stream_pool_flush(prego_vit_stream_pool* p, int n, const int32_t* slots, prego_stream_t stream);
+int prego_vit_stream_pool_reset(prego_vit_stream_pool* p, int n, const int32_t* slots, prego_stream_t stream);
+int prego_vit_stream_pool_record(const prego_vit_stream_pool* p, int slot, const void** device_record, size_t* bytes);
+int prego_vit_stream_pool_window(prego_vit_stream_pool* p, int slot, float* out, int32_t* fill_out, prego_stream_t stream);
+
 /* Training of the "Transformer" registry entry: trainer/train.py:20-24 (fwd, loss, backward) over ViTEnc (ViT.py:117-143,
  * Transformer.py:5-82, Attention.py:21-41).  forward_train is ViTEnc.forward in training mode with every dropout rate 0
  * (cfg['dropout'] == cfg['attn_dropout_rate'] == 0; non-zero rates are rejected by the host module) and keeps the activations

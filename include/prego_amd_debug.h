@@ -87,6 +87,11 @@ int prego_debug_attention_bwd(int batch, int len, int heads, int dh, int causal,
 int prego_debug_attention_fwd(int batch, int n_query, int len, int heads, int dh, int causal, const void* qs, const void* k,
                               const void* v, void* out, float* lse, prego_stream_t stream);
 
+/* Unit test only (tests/test_gpu_vit_stream_pool.py): the Transformer stream pool's token kernel alone, on the pool as it stands (no
+ * frame is committed): x_out device fp32 [n][window_size + 1][embedding_dim] = the residual-stream rows of the windows of `slots` (HOST
+ * int32 [n], as prego_vit_step_pool takes them); neither the fused LayerNorm output nor the token-0 copy is written. */
+int prego_debug_vit_ring_tokens(prego_vit_stream_pool* p, int n, const int32_t* slots, float* x_out, prego_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -307,6 +307,23 @@ int launch_pool_vote(const PoolGeom& g, const int* slots, int n, const int* ids,
 int launch_pool_flush(const PoolGeom& g, const int* slots, int n, hipStream_t s);
 int launch_pool_reset(const PoolGeom& g, const int* slots, int n, hipStream_t s);
 
+// Transformer stream pool (vit_stream.hip): a ring of encoded frames per slot in the caller's device block.  ring [capacity][T][E] fp32,
+// row f mod T = linear_encoding(frame f); hf [capacity][4] int32 = head (next row to write) | fill (rows that hold a frame) | 0 | 0
+struct VitRing {
+  float* ring;
+  int* hf;
+  int T, E, capacity;
+};
+constexpr int kVitRingStateWords = 4;
+// slots: as the pool launchers above (HOST, 1..256, inside the pool, named once); -1 = refused, nothing launched
+// ring[slots[i]][head] <- enc[i], then head and fill advance
+int launch_vit_ring_commit(const VitRing& r, const int* slots, int n, const float* enc, hipStream_t s);
+// launch_vit_sliding_tokens with the rings as the source: window i = the last T frames of slots[i], bias rows where fill does not reach
+int launch_vit_ring_tokens(const VitRing& r, const int* slots, int n, const float* enc_b, const float* cls, const float* pe, float* x,
+                           const float* ln_w, const float* ln_b, void* xn, float* x0, hipStream_t s, bool f16 = false);
+// out [T][E] <- the slot's logical window, oldest to newest (bias rows in front), *fill_out <- fill
+int launch_vit_ring_window(const VitRing& r, int slot, const float* enc_b, float* out, int* fill_out, hipStream_t s);
+
 // split pass (round 6): rows gate * H + u of a 16-bit [3H][E] matrix and an fp32 [3H] vector -> rows (u / 2) * 6 + 2 * gate + u % 2 (rowwise.hip)
 void launch_permute_gi_rows(const void* w, const float* bias, void* w_perm, float* bias_perm, int H, int E, hipStream_t s);
 

@@ -1,0 +1,33 @@
+// The slot list of one stream-pool call, checked on the host before anything is launched: shared by the GRU pool (stream_pool.cpp) and
+// the Transformer pool (vit_stream.cpp).  The stamp table says which call last named a slot, so the duplicate check allocates nothing.
+#pragma once
+#include "host_common.h"
+
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+struct SlotStamps {
+  std::vector<unsigned> stamp;           // [capacity]: the call that last named the slot
+  unsigned call = 0;
+};
+
+// n in 1..min(256, capacity), every slot inside the pool and named once; 0 = fine, else PREGO_EINVAL with a message
+static inline int check_slot_list(SlotStamps& st, int capacity, const char* who, int n, const int32_t* slots) {
+  const int n_max = capacity < kPoolMaxActive ? capacity : kPoolMaxActive;
+  if (n < 1 || n > n_max)
+    return prego_fail_(PREGO_EINVAL, "%s: %d slots (1..%d per call: at most %d, pool capacity %d)", who, n, n_max, kPoolMaxActive, capacity);
+  if (!slots) return prego_fail_(PREGO_EINVAL, "%s: slots is NULL", who);
+  for (int i = 0; i < n; ++i)
+    if (slots[i] < 0 || slots[i] >= capacity)
+      return prego_fail_(PREGO_EINVAL, "%s: slots[%d] = %d is outside the pool (capacity %d)", who, i, slots[i], capacity);
+  if (++st.call == 0) {                                       // the counter wrapped: old stamps could alias
+    std::fill(st.stamp.begin(), st.stamp.end(), 0u);
+    st.call = 1;
+  }
+  for (int i = 0; i < n; ++i) {
+    if (st.stamp[(size_t)slots[i]] == st.call) return prego_fail_(PREGO_EINVAL, "%s: slot %d is named twice", who, slots[i]);
+    st.stamp[(size_t)slots[i]] = st.call;
+  }
+  return 0;
+}

@@ -2,6 +2,7 @@
 // object is host memory only: the geometry, the addresses inside the caller's device block and a stamp table for the duplicate check.
 // Every entry point validates the whole slot list before its first launch, so a refused call has launched nothing.
 #include "miniroad_handle.h"
+#include "pool_slot_check.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -10,8 +11,7 @@
 struct prego_stream_pool {
   PoolGeom g;
   size_t bytes;                          // of the block, as laid out
-  std::vector<unsigned> stamp;           // [capacity]: the call that last named the slot (duplicate check without a per-call allocation)
-  unsigned call = 0;
+  SlotStamps stamps;                     // the duplicate check without a per-call allocation
 };
 
 namespace {
@@ -29,24 +29,9 @@ PoolLayout pool_layout(int hid, int ncls, int capacity, int max_events) {
 
 bool pool_shape_ok(int capacity, int max_events) { return capacity >= 1 && capacity <= (1 << 20) && max_events >= 1 && max_events <= (1 << 20); }
 
-// the slot list of one call: n in 1..min(256, capacity), every slot inside the pool and named once
+// the slot list of one call: n in 1..min(256, capacity), every slot inside the pool and named once (pool_slot_check.h)
 int check_slots(prego_stream_pool* p, const char* who, int n, const int32_t* slots) {
-  const int n_max = p->g.capacity < kPoolMaxActive ? p->g.capacity : kPoolMaxActive;
-  if (n < 1 || n > n_max)
-    return prego_fail_(PREGO_EINVAL, "%s: %d slots (1..%d per call: at most %d, pool capacity %d)", who, n, n_max, kPoolMaxActive, p->g.capacity);
-  if (!slots) return prego_fail_(PREGO_EINVAL, "%s: slots is NULL", who);
-  for (int i = 0; i < n; ++i)
-    if (slots[i] < 0 || slots[i] >= p->g.capacity)
-      return prego_fail_(PREGO_EINVAL, "%s: slots[%d] = %d is outside the pool (capacity %d)", who, i, slots[i], p->g.capacity);
-  if (++p->call == 0) {                                       // the counter wrapped: old stamps could alias
-    std::fill(p->stamp.begin(), p->stamp.end(), 0u);
-    p->call = 1;
-  }
-  for (int i = 0; i < n; ++i) {
-    if (p->stamp[(size_t)slots[i]] == p->call) return prego_fail_(PREGO_EINVAL, "%s: slot %d is named twice", who, slots[i]);
-    p->stamp[(size_t)slots[i]] = p->call;
-  }
-  return 0;
+  return check_slot_list(p->stamps, p->g.capacity, who, n, slots);
 }
 
 // the step calls' workspace: dense state [n][hid] fp32 | argmax [n] (the burst call: [n K]) int32 | the dense call's own workspace.
@@ -144,7 +129,7 @@ extern "C" int prego_stream_pool_create(prego_stream_pool** out, const prego_min
   p->g = PoolGeom{(float*)device_block, (int*)((char*)device_block + l.h_bytes), h->hid, h->ncls, (int)align_up((size_t)h->ncls, 4), window,
                   max_events, (int)l.rec_words, capacity};
   p->bytes = l.total;
-  p->stamp.assign((size_t)capacity, 0u);
+  p->stamps.stamp.assign((size_t)capacity, 0u);
   const hipError_t e = hipMemsetAsync(device_block, 0, l.total, (hipStream_t)stream);      // every slot empty: open launches nothing
   if (e != hipSuccess) {
     delete p;

@@ -4,6 +4,7 @@
 //   vit_head      pre_head_ln on token 0 (a frame token, not the cls token: ViT.py:136), mlp_head Linear   ViT.py:134-138
 #include "common.h"
 #include "kernels.h"
+#include "vit_token_row.h"
 
 template <typename OT>
 __global__ void cat_convert_kernel(const float* __restrict__ rgb, const float* __restrict__ flow, int rows, int d_rgb,
@@ -52,44 +53,14 @@ __global__ __launch_bounds__(256) void vit_sliding_tokens_kernel(const float* __
                                                                  const float* __restrict__ ln_w, const float* __restrict__ ln_b,
                                                                  bf16_t* __restrict__ xn, float* __restrict__ x0) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int N = T + 1, nv = E / 256;                      // 4-column groups per lane
+  const int N = T + 1;
   for (long long row = (long long)blockIdx.x * 4 + wave; row < (long long)B * N; row += (long long)gridDim.x * 4) {
     const int b = (int)(row / N), j = (int)(row - (long long)b * N);
     const int f = t0 + b - T + 1 + j;                     // frame of token j (j < T)
     const float* src = j == T ? cls : (f >= 0 ? enc + (size_t)f * E : enc_b);
-    const float* per = pe + (size_t)j * E;
-    float v[MAXV][4];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i)
-      if (i < nv) {
-        const int c = (i * 64 + lane) * 4;
-        const float4 a = *(const float4*)(src + c), p = *(const float4*)(per + c);
-        v[i][0] = a.x + p.x; v[i][1] = a.y + p.y; v[i][2] = a.z + p.z; v[i][3] = a.w + p.w;
-        s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-        if (x) *(float4*)(x + (size_t)row * E + c) = make_float4(v[i][0], v[i][1], v[i][2], v[i][3]);
-        if (x0 && j == 0) *(float4*)(x0 + (size_t)b * E + c) = make_float4(v[i][0], v[i][1], v[i][2], v[i][3]);
-      }
-    if (xn == nullptr) continue;
-    const float mu = wave_sum(s) / (float)E;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i)
-      if (i < nv) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { const float d = v[i][k] - mu; q += d * d; }
-      }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)E + 1e-5f);
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i)
-      if (i < nv) {
-        const int c = (i * 64 + lane) * 4;
-        const float4 g = *(const float4*)(ln_w + c), bb = *(const float4*)(ln_b + c);
-        uint2 o;
-        o.x = op16<OT>::pack2_sat((v[i][0] - mu) * rstd * g.x + bb.x, (v[i][1] - mu) * rstd * g.y + bb.y);
-        o.y = op16<OT>::pack2_sat((v[i][2] - mu) * rstd * g.z + bb.z, (v[i][3] - mu) * rstd * g.w + bb.w);
-        *(uint2*)(xn + (size_t)row * E + c) = o;
-      }
+    // the row itself (add, statistics, LayerNorm, pack): vit_token_row.h, shared with the stream pool's ring kernel
+    vit_token_row<MAXV, OT>(src, pe + (size_t)j * E, E, lane, x ? x + (size_t)row * E : nullptr,
+                            (x0 && j == 0) ? x0 + (size_t)b * E : nullptr, ln_w, ln_b, xn ? xn + (size_t)row * E : nullptr);
   }
 }
 

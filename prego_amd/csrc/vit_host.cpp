@@ -1,6 +1,6 @@
 // C ABI of the "Transformer" (ViTEnc) path and of the causal AttentionLayer op (include/prego_amd.h).
 // bf16 (or, inference only, IEEE fp16) MFMA operands, fp32 accumulation / residual stream / LayerNorm / softmax.
-#include "host_common.h"
+#include "vit_handle.h"      // struct prego_vit, VitWs, the encoder-block runners shared with vit_stream.cpp
 
 #include <algorithm>
 #include <cmath>
@@ -11,26 +11,6 @@
 
 extern "C" const char* prego_last_error(void);
 
-struct VitLayer {
-  float *ln1_w, *ln1_b, *proj_b, *ln2_w, *ln2_b, *ff1_b, *ff2_b;
-  void *qkv_w, *proj_w, *ff1_w, *ff2_w;    // bf16
-  float *qkv_w32 = nullptr, *proj_w32 = nullptr, *ff1_w32 = nullptr, *ff2_w32 = nullptr;   // PREGO_F32 handles only
-};
-struct prego_vit {
-  int d_rgb, d_flow, emb, mlp, heads, layers, window, ncls;
-  void* enc_w = nullptr; float* enc_b = nullptr; float* cls = nullptr; float* pe = nullptr;
-  std::vector<VitLayer> L;
-  float *lnf_w = nullptr, *lnf_b = nullptr, *head_w = nullptr, *head_b = nullptr;
-  std::vector<void*> allocs;
-  bool have_weights = false;
-  bool f16 = false;                // IEEE fp16 operands / 16-bit activations instead of bf16 (prego_vit_set_compute_dtype; inference only)
-  bool f32 = false;                // fp32 operands everywhere (parity mode, prego_vit_forward only): the matrices are kept in fp32
-  float* enc_w32 = nullptr;
-  // training-mode dropout (cfg['dropout']; ViT.py:130 pe_dropout, Transformer.py:31 PreNormDrop, Transformer.py:41,46 FeedForward)
-  float drop_p = 0.f;
-  float attn_drop_p = 0.f;         // cfg['attn_dropout_rate']: attention probabilities (Attention.py:17,36) and proj_drop (Attention.py:19,40)
-  unsigned long long drop_seed = 0;
-};
 // per-site mask seeds: site 0 = positional dropout, per layer: 1 = attention branch, 2 = after GELU, 3 = FFN output,
 // 4 = attention probabilities, 5 = proj_drop
 static inline unsigned long long site_seed(const prego_vit* h, int layer, int site) {
@@ -188,8 +168,7 @@ extern "C" int prego_vit_adamw_step(prego_vit* h, float* const* params, const fl
   return PREGO_OK;
 }
 
-struct VitWs { size_t xb, enc, x, xn, q, k, vn, ao, f, x0, q0, ao0, xn0, f0, total; };
-static VitWs vit_ws(const prego_vit* h, int B) {
+VitWs vit_ws(const prego_vit* h, int B) {
   const size_t E = h->emb, T = h->window, N = T + 1, din = h->d_rgb + h->d_flow;
   VitWs w{};
   size_t off = 0;
@@ -249,8 +228,7 @@ static int vit_forward_f32(prego_vit* h, int B, const float* rgb, const float* f
 }
 
 // one pre-norm encoder block on the fp32 residual stream x [M = B*N, E] (Transformer.py:60-77)
-static int encoder_block(const prego_vit* h, const VitLayer& l, float* x, char* ws, const VitWs& w, int B, int N, int causal,
-                         hipStream_t s) {
+int encoder_block(const prego_vit* h, const VitLayer& l, float* x, char* ws, const VitWs& w, int B, int N, int causal, hipStream_t s) {
   const int E = h->emb, M = B * N, dh = E / h->heads;
   launch_ln_relu(true, x, l.ln1_w, l.ln1_b, M, E, 1e-5f, ws + w.xn, nullptr, 0.f, 0, 0, s, 0, false, h->f16);
   GemmEpi e{}; e.f16 = h->f16 ? 1 : 0;
@@ -273,8 +251,8 @@ static int encoder_block(const prego_vit* h, const VitLayer& l, float* x, char* 
 // it removes 44 % of a window's FLOPs.  Leaves the block's token-0 output in x0 [B, E].
 // have_xn: the caller already wrote LayerNorm1(x) to w.xn and token 0 of every window to w.x0 (the sliding-window token kernel
 // does both): x is not read at all.
-static int encoder_block_token0(const prego_vit* h, const VitLayer& l, const float* x, char* ws, const VitWs& w, int B, int N,
-                                int causal, hipStream_t s, bool have_xn = false) {
+int encoder_block_token0(const prego_vit* h, const VitLayer& l, const float* x, char* ws, const VitWs& w, int B, int N, int causal,
+                         hipStream_t s, bool have_xn) {
   const int E = h->emb, M = B * N, dh = E / h->heads;
   if (!have_xn) launch_ln_relu(true, x, l.ln1_w, l.ln1_b, M, E, 1e-5f, ws + w.xn, nullptr, 0.f, 0, 0, s, 0, false, h->f16);
   GemmEpi e{}; e.f16 = h->f16 ? 1 : 0;

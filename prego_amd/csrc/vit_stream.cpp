@@ -1,0 +1,195 @@
+// Host side of the Transformer stream pool (include/prego_amd.h: prego_vit_stream_pool_*, prego_vit_step_pool; kernels: vit_stream.hip,
+// the vote record and its kernels: stream_pool.hip).  The pool object is host memory only: the geometry, the addresses inside the caller's
+// device block and a stamp table for the duplicate check.  Every entry point decides all its refusals before its first launch, so a
+// refused call has written nothing.
+#include "vit_handle.h"
+#include "pool_slot_check.h"
+
+#include <cstdint>
+
+struct prego_vit_stream_pool {
+  VitRing r;
+  PoolGeom g;                            // the vote records; g.h = the ring words [capacity][4], so pool_reset zeroes head, fill and the record
+  const prego_vit* owner;                // the handle the pool was created for: prego_vit_stream_pool_window reads its encoding bias
+  size_t bytes;                          // of the block, as laid out
+  SlotStamps stamps;
+};
+
+namespace {
+// block: ring [capacity][window][E] fp32 | ring words [capacity][4] int32 | records [capacity][rec_words] int32, each part 256-byte aligned
+struct VitPoolLayout { size_t ring_bytes, hf_bytes, rec_words, total; };
+
+// false: capacity or max_events below 1, max_events above 1 048 576 (the record's word count is an int), or a block that size_t cannot hold
+bool vit_pool_layout(const prego_vit* h, int capacity, int max_events, VitPoolLayout* l) {
+  if (capacity < 1 || max_events < 1 || max_events > (1 << 20)) return false;
+  using u128 = unsigned __int128;
+  const u128 rec_words = align_up((size_t)kPoolRecHeader + align_up((size_t)h->ncls, 4) + 2 * (size_t)max_events, 4);
+  const u128 ring = (u128)capacity * (u128)h->window * (u128)h->emb * 4, hf = (u128)capacity * kVitRingStateWords * 4;
+  const u128 rec = (u128)capacity * rec_words * 4;
+  if (rec_words > 0x7fffffffu || ring + hf + rec + 3 * 256 > (u128)SIZE_MAX) return false;
+  l->rec_words = (size_t)rec_words;
+  l->ring_bytes = align_up((size_t)ring, 256);
+  l->hf_bytes = align_up((size_t)hf, 256);
+  l->total = l->ring_bytes + l->hf_bytes + align_up((size_t)rec, 256);
+  return true;
+}
+
+// the step call's workspace: xb [n][din] 16-bit | enc [n][E] fp32 | argmax [n] int32 | the per-batch arena of n windows (vit_ws)
+struct VitStepWs { size_t xb, enc, am, win; VitWs w; size_t total; };
+VitStepWs vit_step_ws(const prego_vit* h, int n) {
+  VitStepWs f{};
+  const size_t E = h->emb, din = h->d_rgb + h->d_flow;
+  size_t off = 0;
+  auto put = [&](size_t bytes) { size_t o = off; off += align_up(bytes, 256); return o; };
+  f.xb = put((size_t)n * din * 2); f.enc = put((size_t)n * E * 4); f.am = put((size_t)n * 4);
+  f.w = vit_ws(h, n);
+  f.win = put(f.w.total);
+  f.total = off;
+  return f;
+}
+
+int slot_in_pool(const prego_vit_stream_pool* p, const char* who, int slot) {
+  if (slot < 0 || slot >= p->r.capacity) return prego_fail_(PREGO_EINVAL, "%s: slot %d is outside the pool (capacity %d)", who, slot, p->r.capacity);
+  return 0;
+}
+}  // namespace
+
+extern "C" size_t prego_vit_stream_pool_bytes(const prego_vit* h, int capacity, int max_events) {
+  VitPoolLayout l{};
+  return (h && vit_pool_layout(h, capacity, max_events, &l)) ? l.total : 0;
+}
+
+extern "C" int prego_vit_stream_pool_create(prego_vit_stream_pool** out, const prego_vit* h, int capacity, int vote_window, int max_events,
+                                            void* device_block, size_t bytes, prego_stream_t stream) {
+  if (!out) return prego_fail_(PREGO_EINVAL, "vit_stream_pool_create: out is NULL");
+  *out = nullptr;
+  if (!h) return prego_fail_(PREGO_EINVAL, "vit_stream_pool_create: handle is NULL");
+  if (vote_window < 1) return prego_fail_(PREGO_EINVAL, "vit_stream_pool_create: vote_window %d (>= 1)", vote_window);
+  VitPoolLayout l{};
+  if (!vit_pool_layout(h, capacity, max_events, &l))
+    return prego_fail_(PREGO_EINVAL, "vit_stream_pool_create: capacity %d (>= 1), max_events %d (1..%d), or a block of %d x %d x %d fp32 rows is "
+                       "beyond size_t", capacity, max_events, 1 << 20, capacity, h->window, h->emb);
+  if (!device_block || bytes < l.total)
+    return prego_fail_(PREGO_EINVAL, "vit_stream_pool_create: block %p with %zu bytes, %d slots of %d x %d ring rows and %d events need %zu "
+                       "(prego_vit_stream_pool_bytes)", device_block, bytes, capacity, h->window, h->emb, max_events, l.total);
+  if ((uintptr_t)device_block & 255) return prego_fail_(PREGO_EINVAL, "vit_stream_pool_create: the block must be 256-byte aligned");
+  prego_vit_stream_pool* p = new prego_vit_stream_pool();
+  char* base = (char*)device_block;
+  p->r = VitRing{(float*)base, (int*)(base + l.ring_bytes), h->window, h->emb, capacity};
+  p->g = PoolGeom{(float*)(base + l.ring_bytes), (int*)(base + l.ring_bytes + l.hf_bytes), kVitRingStateWords, h->ncls,
+                  (int)align_up((size_t)h->ncls, 4), vote_window, max_events, (int)l.rec_words, capacity};
+  p->owner = h;
+  p->bytes = l.total;
+  p->stamps.stamp.assign((size_t)capacity, 0u);
+  const hipError_t e = hipMemsetAsync(device_block, 0, l.total, (hipStream_t)stream);      // every slot empty: open launches nothing
+  if (e != hipSuccess) {
+    delete p;
+    return prego_fail_(PREGO_EHIP, "vit_stream_pool_create: hipMemsetAsync failed: %s", hipGetErrorString(e));
+  }
+  *out = p;
+  return PREGO_OK;
+}
+
+extern "C" void prego_vit_stream_pool_destroy(prego_vit_stream_pool* p) { delete p; }
+
+extern "C" size_t prego_vit_step_pool_workspace_bytes(const prego_vit* h, int n_active) {
+  if (!h || n_active < 1 || n_active > kPoolMaxActive) return 0;
+  return vit_step_ws(h, n_active).total;
+}
+
+// One new frame for the slots named: cat + convert, the encoding GEMM on n_active rows, the rows into their rings, one window per slot out
+// of the rings, then the blocks, the head and the vote exactly as prego_vit_forward_frames runs them for a batch of n_active windows
+extern "C" int prego_vit_step_pool(prego_vit* h, prego_vit_stream_pool* p, int n_active, const int32_t* slots, const float* rgb,
+                                   const float* flow, float* out_logits, int32_t* argmax, int flags, void* workspace, size_t workspace_bytes,
+                                   prego_stream_t stream) {
+  const char* who = "vit_step_pool";
+  if (!h || !p || !out_logits) return prego_fail_(PREGO_EINVAL, "%s: NULL argument", who);
+  if (h->f32) return prego_fail_(PREGO_EINVAL, "prego_vit_step_pool on an fp32-operand handle: the parity mode covers prego_vit_forward");
+  if (!h->have_weights) return prego_fail_(PREGO_EINVAL, "%s before set_weights", who);
+  if ((h->d_rgb > 0 && !rgb) || (h->d_rgb == 0 && !flow)) return prego_fail_(PREGO_EINVAL, "%s: missing input", who);
+  if (p->r.T != h->window || p->r.E != h->emb || p->g.ncls != h->ncls)
+    return prego_fail_(PREGO_EINVAL, "%s: the pool was created for window_size %d / embedding_dim %d / %d classes, the handle has %d / %d / %d",
+                       who, p->r.T, p->r.E, p->g.ncls, h->window, h->emb, h->ncls);
+  if (int rc = check_slot_list(p->stamps, p->r.capacity, who, n_active, slots)) return rc;
+  const VitStepWs f = vit_step_ws(h, n_active);
+  if (!workspace) return prego_fail_(PREGO_EINVAL, "%s: workspace is NULL", who);
+  if ((uintptr_t)workspace & 255) return prego_fail_(PREGO_EINVAL, "%s: the workspace must be 256-byte aligned", who);
+  if (workspace_bytes < f.total)
+    return prego_fail_(PREGO_EWORKSPACE, "%s: workspace %zu < %zu for %d active streams (prego_vit_step_pool_workspace_bytes)", who,
+                       workspace_bytes, f.total, n_active);
+  hipStream_t s = (hipStream_t)stream;
+  char* base = (char*)workspace;
+  char* ws = base + f.win;                      // the per-batch arena, laid out as prego_vit_forward's
+  const VitWs& w = f.w;
+  const int n = n_active, N = h->window + 1, E = h->emb, din = h->d_rgb + h->d_flow;
+  const int causal = (flags & 1) ? 1 : 0;
+  float* enc = (float*)(base + f.enc);
+  int32_t* am = argmax ? argmax : (int32_t*)(base + f.am);      // the vote always has its ids
+  launch_cat_convert(rgb, flow, n, h->d_rgb, h->d_flow, base + f.xb, s, h->f16);
+  launch_gemm_bf16_nt(base + f.xb, din, h->enc_w, din, h->enc_b, enc, E, n, E, din, s, h->f16);       // ViT.py:124, once per frame
+  if (launch_vit_ring_commit(p->r, slots, n, enc, s)) return prego_fail_(PREGO_EINVAL, "%s: ring commit refused its arguments", who);
+  const bool fused = h->layers == 1;            // one layer: the token kernel writes LayerNorm1(x) and x0; x is never materialised
+  const VitLayer& l0 = h->L[0];
+  if (launch_vit_ring_tokens(p->r, slots, n, h->enc_b, h->cls, h->pe, fused ? nullptr : (float*)(ws + w.x), l0.ln1_w, l0.ln1_b,
+                             fused ? ws + w.xn : nullptr, fused ? (float*)(ws + w.x0) : nullptr, s, h->f16))
+    return prego_fail_(PREGO_EINVAL, "%s: ring tokens refused its arguments", who);
+  for (int li = 0; li < h->layers; ++li) {
+    const bool last = li + 1 == h->layers;
+    const int rc = last ? encoder_block_token0(h, h->L[li], (const float*)(ws + w.x), ws, w, n, N, causal, s, fused)
+                        : encoder_block(h, h->L[li], (float*)(ws + w.x), ws, w, n, N, causal, s);
+    if (rc) return prego_fail_(PREGO_EINVAL, "%s: encoder block launch failed", who);
+  }
+  launch_vit_head((const float*)(ws + w.x0), n, 1, E, h->lnf_w, h->lnf_b, h->head_w, h->head_b, h->ncls, out_logits, s, (int*)am);
+  if (launch_pool_vote(p->g, slots, n, (const int*)am, s)) return prego_fail_(PREGO_EINVAL, "%s: vote refused its arguments", who);
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+extern "C" int prego_vit_stream_pool_flush(prego_vit_stream_pool* p, int n, const int32_t* slots, prego_stream_t stream) {
+  if (!p) return prego_fail_(PREGO_EINVAL, "vit_stream_pool_flush: pool is NULL");
+  if (int rc = check_slot_list(p->stamps, p->r.capacity, "vit_stream_pool_flush", n, slots)) return rc;
+  if (launch_pool_flush(p->g, slots, n, (hipStream_t)stream)) return prego_fail_(PREGO_EINVAL, "vit_stream_pool_flush: bad arguments");
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+// head, fill and the record go to zero; the ring rows stay, since nothing reads a row that fill does not cover
+extern "C" int prego_vit_stream_pool_reset(prego_vit_stream_pool* p, int n, const int32_t* slots, prego_stream_t stream) {
+  if (!p) return prego_fail_(PREGO_EINVAL, "vit_stream_pool_reset: pool is NULL");
+  if (int rc = check_slot_list(p->stamps, p->r.capacity, "vit_stream_pool_reset", n, slots)) return rc;
+  if (launch_pool_reset(p->g, slots, n, (hipStream_t)stream)) return prego_fail_(PREGO_EINVAL, "vit_stream_pool_reset: bad arguments");
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+extern "C" int prego_vit_stream_pool_record(const prego_vit_stream_pool* p, int slot, const void** device_record, size_t* bytes) {
+  if (!p || !device_record || !bytes) return prego_fail_(PREGO_EINVAL, "vit_stream_pool_record: NULL argument");
+  if (int rc = slot_in_pool(p, "vit_stream_pool_record", slot)) return rc;
+  *device_record = p->g.rec + (size_t)slot * p->g.rec_words;
+  *bytes = (size_t)p->g.rec_words * 4;
+  return PREGO_OK;
+}
+
+extern "C" int prego_vit_stream_pool_window(prego_vit_stream_pool* p, int slot, float* out, int32_t* fill_out, prego_stream_t stream) {
+  if (!p || !out) return prego_fail_(PREGO_EINVAL, "vit_stream_pool_window: NULL argument");
+  if (int rc = slot_in_pool(p, "vit_stream_pool_window", slot)) return rc;
+  if (!p->owner->have_weights) return prego_fail_(PREGO_EINVAL, "vit_stream_pool_window before set_weights");
+  if (launch_vit_ring_window(p->r, slot, p->owner->enc_b, out, (int*)fill_out, (hipStream_t)stream))
+    return prego_fail_(PREGO_EINVAL, "vit_stream_pool_window: bad arguments");
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+#ifdef PREGO_DEBUG_ABI
+// unit-test hook: vit_ring_tokens alone, only x wanted, on the pool as it stands (no commit)
+extern "C" int prego_debug_vit_ring_tokens(prego_vit_stream_pool* p, int n, const int32_t* slots, float* x_out, prego_stream_t stream) {
+  if (!p || !x_out) return prego_fail_(PREGO_EINVAL, "debug_vit_ring_tokens: NULL argument");
+  if (!p->owner->have_weights) return prego_fail_(PREGO_EINVAL, "debug_vit_ring_tokens before set_weights");
+  if (int rc = check_slot_list(p->stamps, p->r.capacity, "debug_vit_ring_tokens", n, slots)) return rc;
+  const prego_vit* h = p->owner;
+  if (launch_vit_ring_tokens(p->r, slots, n, h->enc_b, h->cls, h->pe, x_out, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, h->f16))
+    return prego_fail_(PREGO_EINVAL, "debug_vit_ring_tokens: bad arguments");
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+#endif

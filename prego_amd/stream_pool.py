@@ -93,38 +93,15 @@ class SlotTable:
         return slots
 
 
-class StreamPool:
-    """StreamPool(model_or_engine, capacity=256, window=200, max_events=1024): `capacity` slots of GRU state + vote record in one device
-    block; a record holds up to `max_events` (step id, first frame) events of `window`-frame majority votes.
-    `push` needs an engine the streaming kernels are built for (bf16 / fp16 operands, hidden_dim 1024, one GRU layer); `vote`, `events`
-    and `close` serve every engine (ids from the Transformer path or a general forward)."""
-
-    def __init__(self, model_or_engine, capacity: int = 256, window: int = 200, max_events: int = 1024):
-        from .engine import _stream_ptr
-        eng = model_or_engine.engine() if hasattr(model_or_engine, "engine") else model_or_engine
-        self.engine, self.lib, self.device = eng, eng.lib, eng.device
-        self.window, self.max_events = int(window), int(max_events)
-        self.slots = SlotTable(capacity)
-        self._stream_ptr = _stream_ptr
-        d_rgb, d_flow, emb, hid, ncls = eng.dims
-        self._hid, self._ncls, self._ncls_pad = hid, ncls, (ncls + 3) // 4 * 4
-        self._fast = eng.compute_dtype in ("bf16", "fp16") and hid == 1024 and eng.num_layers == 1
-        need = self.lib.prego_stream_pool_bytes(eng.h, int(capacity), self.max_events)
-        if need == 0:
-            raise PregoError(f"stream pool: capacity {capacity}, max_events {max_events} (each 1..{1 << 20})")
-        self._block = torch.empty(need, dtype=torch.uint8, device=self.device)
-        self._ws = None
-        p = C.c_void_p()
-        with torch.cuda.device(self.device):
-            rc = self.lib.prego_stream_pool_create(C.byref(p), eng.h, int(capacity), self.window, self.max_events, C.c_void_p(self._block.data_ptr()),
-                                                   need, C.c_void_p(_stream_ptr(self.device)))
-        self._check(rc)
-        self.p = p
+class _RecordPool:
+    """What the two pools share: the slot bookkeeping and the reading of a slot's vote record (csrc/stream_pool.hip).  A subclass sets
+    lib, device, p, slots (SlotTable), _block, _vote_window, max_events, _ncls, _ncls_pad and names its C entry points in `_C`."""
+    _C = {}                      # 'destroy', 'flush', 'reset', 'record' -> symbol
 
     def __del__(self):
         try:
             if getattr(self, "p", None):
-                self.lib.prego_stream_pool_destroy(self.p)
+                getattr(self.lib, self._C["destroy"])(self.p)
                 self.p = None
         except Exception:
             pass
@@ -149,6 +126,79 @@ class StreamPool:
     @staticmethod
     def _slot_array(slots):
         return (C.c_int32 * len(slots))(*slots)
+
+    # -- reading a slot ------------------------------------------------------------------------
+    def _record(self, slot: int):
+        """one D2H copy of the slot's record (it waits for the stream): (frames, overflow, event ids, event starts)"""
+        ptr, nbytes = C.c_void_p(), C.c_size_t()
+        self._check(getattr(self.lib, self._C["record"])(self.p, slot, C.byref(ptr), C.byref(nbytes)))
+        off = ptr.value - self._block.data_ptr()
+        w = self._block[off:off + nbytes.value].view(torch.int32).cpu().numpy()
+        n_ev = int(w[2])
+        e0 = REC_HEADER + self._ncls_pad
+        return int(w[0]), int(w[3]), [int(v) for v in w[e0:e0 + n_ev]], [int(v) for v in w[e0 + self.max_events:e0 + self.max_events + n_ev]]
+
+    def events(self, slot: int) -> dict:
+        """{'pred', 'changes_pred', 'frames'}: the step sequence of the slot's finished windows so far ('changes_pred' ends where the last
+        finished window ends) and the frames it has taken.  One small D2H copy; it waits."""
+        slot = self.slots.check([slot], "events")[0]
+        frames, overflow, ev_id, ev_start = self._record(slot)
+        self._raise_overflow(slot, overflow)
+        return {"pred": ev_id, "changes_pred": ev_start[1:] + [frames - frames % self._vote_window], "frames": frames}
+
+    def _raise_overflow(self, slot: int, overflow: int):
+        if overflow & OVERFLOW_BAD_ID:
+            raise PregoError(f"stream pool: slot {slot} was fed a step id outside [0, {self._ncls}) (np.bincount of utils/aggregate.py:60 would raise)")
+        if overflow & OVERFLOW_FULL:
+            raise PregoError(f"stream pool: slot {slot} produced more than max_events = {self.max_events} events; the record dropped the rest")
+
+    def close(self, slot: int) -> dict:
+        """Ends the stream: votes its unfinished window, reads the record (one D2H copy), zeroes the slot and frees it.  Returns
+        {'pred', 'changes_pred'} as utils/aggregate.py:46-90 gives them for the stream's per-frame predictions; a stream closed before its
+        first frame returns {'pred': [], 'changes_pred': [0]}.  Raises PregoError, the slot freed all the same, if the record overflowed
+        or met an id outside the classes."""
+        slot = self.slots.check([slot], "close")[0]
+        arr, s = self._slot_array([slot]), C.c_void_p(self._stream_ptr(self.device))
+        with torch.cuda.device(self.device):
+            self._check(getattr(self.lib, self._C["flush"])(self.p, 1, arr, s))
+            frames, overflow, ev_id, ev_start = self._record(slot)
+            self._check(getattr(self.lib, self._C["reset"])(self.p, 1, arr, s))
+        self.slots.release(slot)
+        self._raise_overflow(slot, overflow)
+        return {"pred": ev_id, "changes_pred": ev_start[1:] + [frames]}
+
+
+class StreamPool(_RecordPool):
+    """StreamPool(model_or_engine, capacity=256, window=200, max_events=1024): `capacity` slots of GRU state + vote record in one device
+    block; a record holds up to `max_events` (step id, first frame) events of `window`-frame majority votes.
+    `push` needs an engine the streaming kernels are built for (bf16 / fp16 operands, hidden_dim 1024, one GRU layer); `vote`, `events`
+    and `close` serve every engine (ids from the Transformer path or a general forward); live Transformer streams have a pool of their
+    own, `TransformerStreamPool` below (`ViTEnc.stream_pool`)."""
+    _C = {"destroy": "prego_stream_pool_destroy", "flush": "prego_stream_pool_flush", "reset": "prego_stream_pool_reset",
+          "record": "prego_stream_pool_record"}
+
+    def __init__(self, model_or_engine, capacity: int = 256, window: int = 200, max_events: int = 1024):
+        from .engine import _stream_ptr
+        eng = model_or_engine.engine() if hasattr(model_or_engine, "engine") else model_or_engine
+        self.engine, self.lib, self.device = eng, eng.lib, eng.device
+        self.window, self.max_events = int(window), int(max_events)
+        self._vote_window = self.window
+        self.slots = SlotTable(capacity)
+        self._stream_ptr = _stream_ptr
+        d_rgb, d_flow, emb, hid, ncls = eng.dims
+        self._hid, self._ncls, self._ncls_pad = hid, ncls, (ncls + 3) // 4 * 4
+        self._fast = eng.compute_dtype in ("bf16", "fp16") and hid == 1024 and eng.num_layers == 1
+        need = self.lib.prego_stream_pool_bytes(eng.h, int(capacity), self.max_events)
+        if need == 0:
+            raise PregoError(f"stream pool: capacity {capacity}, max_events {max_events} (each 1..{1 << 20})")
+        self._block = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._ws = None
+        p = C.c_void_p()
+        with torch.cuda.device(self.device):
+            rc = self.lib.prego_stream_pool_create(C.byref(p), eng.h, int(capacity), self.window, self.max_events, C.c_void_p(self._block.data_ptr()),
+                                                   need, C.c_void_p(_stream_ptr(self.device)))
+        self._check(rc)
+        self.p = p
 
     # -- one frame for a subset of the streams ---------------------------------------------------
     def push(self, slots, rgb, flow=None, softmax: bool = True, want_ant=None, out=None, argmax=None, ant_out=None, ant_argmax=None):
@@ -322,48 +372,120 @@ class StreamPool:
                                                  C.c_void_p(self._stream_ptr(self.device)))
         self._check(rc)
 
-    # -- reading a slot ------------------------------------------------------------------------
-    def _record(self, slot: int):
-        """one D2H copy of the slot's record (it waits for the stream): (frames, overflow, event ids, event starts)"""
-        ptr, nbytes = C.c_void_p(), C.c_size_t()
-        self._check(self.lib.prego_stream_pool_record(self.p, slot, C.byref(ptr), C.byref(nbytes)))
-        off = ptr.value - self._block.data_ptr()
-        w = self._block[off:off + nbytes.value].view(torch.int32).cpu().numpy()
-        n_ev = int(w[2])
-        e0 = REC_HEADER + self._ncls_pad
-        return int(w[0]), int(w[3]), [int(v) for v in w[e0:e0 + n_ev]], [int(v) for v in w[e0 + self.max_events:e0 + self.max_events + n_ev]]
-
-    def events(self, slot: int) -> dict:
-        """{'pred', 'changes_pred', 'frames'}: the step sequence of the slot's finished windows so far ('changes_pred' ends where the last
-        finished window ends) and the frames it has taken.  One small D2H copy; it waits."""
-        slot = self.slots.check([slot], "events")[0]
-        frames, overflow, ev_id, ev_start = self._record(slot)
-        self._raise_overflow(slot, overflow)
-        return {"pred": ev_id, "changes_pred": ev_start[1:] + [frames - frames % self.window], "frames": frames}
-
-    def _raise_overflow(self, slot: int, overflow: int):
-        if overflow & OVERFLOW_BAD_ID:
-            raise PregoError(f"stream pool: slot {slot} was fed a step id outside [0, {self._ncls}) (np.bincount of utils/aggregate.py:60 would raise)")
-        if overflow & OVERFLOW_FULL:
-            raise PregoError(f"stream pool: slot {slot} produced more than max_events = {self.max_events} events; the record dropped the rest")
-
-    def close(self, slot: int) -> dict:
-        """Ends the stream: votes its unfinished window, reads the record (one D2H copy), zeroes the slot and frees it.  Returns
-        {'pred', 'changes_pred'} as utils/aggregate.py:46-90 gives them for the stream's per-frame predictions; a stream closed before its
-        first frame returns {'pred': [], 'changes_pred': [0]}.  Raises PregoError, the slot freed all the same, if the record overflowed
-        or met an id outside the classes."""
-        slot = self.slots.check([slot], "close")[0]
-        arr, s = self._slot_array([slot]), C.c_void_p(self._stream_ptr(self.device))
-        with torch.cuda.device(self.device):
-            self._check(self.lib.prego_stream_pool_flush(self.p, 1, arr, s))
-            frames, overflow, ev_id, ev_start = self._record(slot)
-            self._check(self.lib.prego_stream_pool_reset(self.p, 1, arr, s))
-        self.slots.release(slot)
-        self._raise_overflow(slot, overflow)
-        return {"pred": ev_id, "changes_pred": ev_start[1:] + [frames]}
-
     def state(self, slot: int):
         """a clone of the slot's GRU state [hid]"""
         slot = self.slots.check([slot], "state")[0]
         return self._block[:self.capacity * self._hid * 4].view(torch.float32).view(self.capacity, self._hid)[slot].clone()
 
+
+RING_CLS, RING_BIAS = -2, -1
+
+
+def ring_source(head: int, fill: int, T: int, j: int) -> int:
+    """Where token j of a slot's window comes from (csrc/vit_stream.hip, vit_ring_tokens): RING_CLS for j == T (cls + pe[T]), RING_BIAS
+    for j < T - fill (a zero feature row in front of the stream encodes to the bias alone), else the ring row (head - (T - j)) mod T.
+    head = frames mod T is the next row to write, fill = min(frames, T); the newest frame is token T - 1."""
+    if not (0 <= j <= T and 0 <= head < T and 0 <= fill <= T):
+        raise ValueError(f"ring_source: head {head}, fill {fill}, T {T}, j {j}")
+    if j == T:
+        return RING_CLS
+    if j < T - fill:
+        return RING_BIAS
+    return (head - (T - j)) % T
+
+
+class TransformerStreamPool(_RecordPool):
+    """TransformerStreamPool(vit, capacity=256, vote_window=200, max_events=1024) - `ViTEnc.stream_pool(...)`: live streams through the
+    `Transformer` entry.  Every slot of one device block holds a ring of the stream's last `window_size` encoded frames
+    (linear_encoding runs once per frame, as in `forward_frames`) and the vote record `StreamPool` keeps; `push` gives any subset of the
+    slots one new frame and returns one ViTEnc window per slot - the window ending at that frame, zero feature rows in front of the
+    stream (prego_vit_step_pool; csrc/vit_stream.hip).  window_size * embedding_dim * 4 bytes per slot.  bf16 / fp16 operands; one
+    frame per slot per call (no bursts)."""
+    _C = {"destroy": "prego_vit_stream_pool_destroy", "flush": "prego_vit_stream_pool_flush", "reset": "prego_vit_stream_pool_reset",
+          "record": "prego_vit_stream_pool_record"}
+
+    def __init__(self, vit, capacity: int = 256, vote_window: int = 200, max_events: int = 1024):
+        from .engine import _stream_ptr
+        self.model = vit
+        self._refuse_fp32("stream_pool")
+        lib, dev, hnd = vit._eval_handle()
+        self.lib, self.device, self._h = lib, dev, hnd
+        self.vote_window, self.max_events = int(vote_window), int(max_events)      # `window` is a method here: the slot's ring
+        self._vote_window = self.vote_window
+        self.slots = SlotTable(capacity)
+        self._stream_ptr = _stream_ptr
+        self._T, self._E = int(vit.img_dim), int(vit.embedding_dim)
+        self._ncls, self._ncls_pad = int(vit.out_dim), (int(vit.out_dim) + 3) // 4 * 4
+        need = lib.prego_vit_stream_pool_bytes(hnd, int(capacity), self.max_events)
+        if need == 0:
+            raise PregoError(f"transformer stream pool: capacity {capacity} (>= 1), max_events {max_events} (1..{1 << 20}), or a block "
+                             "beyond size_t")
+        self._block = torch.empty(need, dtype=torch.uint8, device=dev)
+        self._ws = None
+        p = C.c_void_p()
+        with torch.cuda.device(dev):
+            rc = lib.prego_vit_stream_pool_create(C.byref(p), hnd, int(capacity), self.vote_window, self.max_events,
+                                                  C.c_void_p(self._block.data_ptr()), need, C.c_void_p(_stream_ptr(dev)))
+        self._check(rc)
+        self.p = p
+
+    def _refuse_fp32(self, who: str):
+        if self.model.compute_dtype == "fp32":
+            raise PregoError(f"ViTEnc {who}: compute_dtype 'fp32' is the parity mode of the window forward; the stream pool runs on bf16 / "
+                             "fp16 operands (prego_vit_step_pool refuses an fp32-operand handle)")
+
+    def _handle(self, who: str):
+        """the model's inference handle with its current weights (changed weights are ingested here, as for forward_frames)"""
+        self._refuse_fp32(who)
+        lib, dev, hnd = self.model._eval_handle()
+        if hnd is not self._h:
+            raise PregoError(f"ViTEnc {who}: the model's inference handle changed since the pool was created (compute_dtype switched); "
+                             "create a new pool")
+        return hnd
+
+    def push(self, slots, rgb, flow=None, out=None, argmax=None):
+        """One new frame for each open slot of `slots`: rgb [n, d_rgb] / flow [n, d_flow] (None = zero flow) fp32 cuda contiguous, rows in
+        `slots` order.  Returns (logits [n, C] fp32 - raw, ViTEnc applies no softmax -, argmax int32 [n]): row i is the model's forward on
+        the window_size frames of slot slots[i] ending at this frame.  Each slot's ring takes the frame and its record the argmax.
+        Pass buffers to reuse them."""
+        m = self.model
+        hnd = self._handle("push")
+        slots = self.slots.check(slots, "push")
+        n = len(slots)
+        d_rgb, d_flow, ncls = m.d_rgb, m.d_flow, self._ncls
+        if (rgb if d_rgb > 0 else flow) is None:
+            raise PregoError("transformer stream pool push: a --no_rgb model needs the flow frame" if d_rgb == 0 else
+                             "transformer stream pool push: rgb is None")
+        if d_flow == 0:
+            flow = None
+        if out is None:
+            out = torch.empty((n, ncls), dtype=torch.float32, device=self.device)
+        if argmax is None:
+            argmax = torch.empty((n,), dtype=torch.int32, device=self.device)
+        for t, shape, dt, what in [(rgb if d_rgb > 0 else None, (n, d_rgb), torch.float32, "rgb"), (flow, (n, d_flow), torch.float32, "flow"),
+                                   (out, (n, ncls), torch.float32, "out"), (argmax, (n,), torch.int32, "argmax")]:
+            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
+                raise PregoError(f"transformer stream pool push: expected {what} as contiguous {dt} cuda {list(shape)}, got {tuple(t.shape)} "
+                                 f"{t.dtype} on {t.device}")
+        need = self.lib.prego_vit_step_pool_workspace_bytes(hnd, n)
+        if self._ws is None or self._ws.numel() < need:          # grown here, outside the C call
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(self.device):
+            rc = self.lib.prego_vit_step_pool(hnd, self.p, n, self._slot_array(slots), p(rgb if d_rgb > 0 else None), p(flow), p(out),
+                                              p(argmax), 1 if m.causal else 0, p(self._ws), self._ws.numel(),
+                                              C.c_void_p(self._stream_ptr(self.device)))
+        self._check(rc)
+        return out, argmax
+
+    def window(self, slot: int):
+        """([window_size, E] fp32 tensor, fill): the slot's encoded frames, oldest first - linear_encoding's rows, its bias where the
+        stream has no frame yet - and how many of them are frames.  For inspection; it waits for the stream."""
+        slot = self.slots.check([slot], "window")[0]
+        self._handle("window")
+        rows = torch.empty((self._T, self._E), dtype=torch.float32, device=self.device)
+        fill = torch.empty((1,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.prego_vit_stream_pool_window(self.p, slot, C.c_void_p(rows.data_ptr()), C.c_void_p(fill.data_ptr()),
+                                                              C.c_void_p(self._stream_ptr(self.device))))
+        return rows, int(fill.item())

@@ -227,6 +227,12 @@ class ViTEnc(nn.Module):
             args.append(a)
         return (outs if want_probs else None), (args if want_argmax else None), None
 
+    def stream_pool(self, capacity: int = 256, vote_window: int = 200, max_events: int = 1024):
+        """Live serving (INTEGRATION.md "Serving live streams"): a `TransformerStreamPool` of `capacity` slots, each a ring of the
+        stream's last window_size encoded frames and a record of `vote_window`-frame majority votes (up to `max_events` events)."""
+        from .stream_pool import TransformerStreamPool
+        return TransformerStreamPool(self, capacity, vote_window, max_events)
+
     def check(self):
         """ViTEnc kernels have no bounded spins: nothing to poll (MROAD.check surfaces a recurrence timeout)"""
         torch.cuda.synchronize(self.mlp_head.weight.device)
