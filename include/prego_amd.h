@@ -593,7 +593,18 @@ int prego_vit_forward_frames(prego_vit* h, int n_frames, const float* rgb, const
  * PREGO_EINVAL / PREGO_EWORKSPACE with a message, nothing launched: an fp32-operand handle, a call before set_weights, n_active outside
  * 1..min(256, capacity), a slot outside the pool, a slot named twice, a NULL, unaligned or too small block or workspace, vote_window < 1,
  * max_events outside 1..1 048 576, a pool created for another window_size, embedding_dim or class count, a missing input.  Not covered:
- * bursts (K frames per slot per call), a dense step without a pool, the fp32 parity mode.  A pool belongs to one stream at a time. */
+ * a dense step without a pool, the fp32 parity mode.  A pool belongs to one stream at a time.
+ * prego_vit_step_pool_bursts: counts[i] new frames (HOST int32 [n_active], 1 <= counts[i] <= min(32, window_size)) for slots[i] in one
+ * call, R = sum(counts) <= 256 packed rows in `slots` order: slot i owns rows off[i] .. off[i] + counts[i]), off the prefix sums.  One
+ * window per packed row comes back - the window ending at that frame.  With head / fill the slot's ring words before the call and
+ * d = T - 1 - j, token j < T of the window of (slot i, burst frame k) is: the call's own encoded row off[i] + k - d where d <= k; the bias
+ * row where d - k > fill; else ring[(head - (d - k)) mod T] as it was before the call; each + pe[j].  Afterwards the slot's ring, head
+ * and fill are byte for byte what counts[i] calls of prego_vit_step_pool with the same rows leave, and its record has taken the
+ * counts[i] ids in frame order (a vote-window boundary may fall inside a burst).  rgb / flow: device fp32 [R][d_rgb | d_flow]; out_logits
+ * [R][n_classes]; argmax (nullable) int32 [R].  The encoding GEMM runs once at M = R and the blocks once for R windows; the GEMM kernels
+ * are chosen by row count, so a burst's logits agree with R one-frame calls to the tolerance above, not bit for bit (every count 1:
+ * the same shapes, the same bits).  Refused as prego_vit_step_pool refuses, and: counts NULL, a count outside 1..min(32, window_size),
+ * R > 256.  Workspace: prego_vit_step_pool_bursts_workspace_bytes(h, n_active, R) bytes (0 for a shape the call refuses). */
 typedef struct prego_vit_stream_pool prego_vit_stream_pool;
 size_t prego_vit_stream_pool_bytes(const prego_vit* h, int capacity, int max_events);
 int prego_vit_stream_pool_create(prego_vit_stream_pool** out, const prego_vit* h, int capacity, int vote_window, int max_events,
@@ -602,6 +613,10 @@ void prego_vit_stream_pool_destroy(prego_vit_stream_pool* p);
 size_t prego_vit_step_pool_workspace_bytes(const prego_vit* h, int n_active);
 int prego_vit_step_pool(prego_vit* h, prego_vit_stream_pool* p, int n_active, const int32_t* slots, const float* rgb, const float* flow,
                         float* out_logits, int32_t* argmax, int flags, void* workspace, size_t workspace_bytes, prego_stream_t stream);
+size_t prego_vit_step_pool_bursts_workspace_bytes(const prego_vit* h, int n_active, int n_rows);
+int prego_vit_step_pool_bursts(prego_vit* h, prego_vit_stream_pool* p, int n_active, const int32_t* counts, const int32_t* slots,
+                               const float* rgb, const float* flow, float* out_logits, int32_t* argmax, int flags, void* workspace,
+                               size_t workspace_bytes, prego_stream_t stream);
 int prego_vit_stream_pool_flush(prego_vit_stream_pool* p, int n, const int32_t* slots, prego_stream_t stream);
 int prego_vit_stream_pool_reset(prego_vit_stream_pool* p, int n, const int32_t* slots, prego_stream_t stream);
 int prego_vit_stream_pool_record(const prego_vit_stream_pool* p, int slot, const void** device_record, size_t* bytes);

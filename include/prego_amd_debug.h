@@ -92,6 +92,15 @@ int prego_debug_attention_fwd(int batch, int n_query, int len, int heads, int dh
  * int32 [n], as prego_vit_step_pool takes them); neither the fused LayerNorm output nor the token-0 copy is written. */
 int prego_debug_vit_ring_tokens(prego_vit_stream_pool* p, int n, const int32_t* slots, float* x_out, prego_stream_t stream);
 
+/* Unit test only (tests/test_gpu_vit_bursts.py): the two burst kernels of the Transformer stream pool alone.  slots / counts: HOST int32
+ * [n] as prego_vit_step_pool_bursts takes them; enc: device fp32 [sum(counts)][embedding_dim], the caller's rows in place of the
+ * encoding GEMM's.  _tokens: x_out device fp32 [sum(counts)][window_size + 1][embedding_dim], one window per packed row out of the rings
+ * as they stand and enc; nothing is committed.  _commit: the rows go into the rings and the ring words advance; nothing else runs. */
+int prego_debug_vit_burst_tokens(prego_vit_stream_pool* p, int n, const int32_t* slots, const int32_t* counts, const float* enc,
+                                 float* x_out, prego_stream_t stream);
+int prego_debug_vit_burst_commit(prego_vit_stream_pool* p, int n, const int32_t* slots, const int32_t* counts, const float* enc,
+                                 prego_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

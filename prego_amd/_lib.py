@@ -51,13 +51,14 @@ SYMBOLS = [
     "prego_miniroad_step_pool_ragged_workspace_bytes", "prego_miniroad_step_pool_ragged",
     "prego_vit_stream_pool_bytes", "prego_vit_stream_pool_create", "prego_vit_stream_pool_destroy", "prego_vit_step_pool_workspace_bytes",
     "prego_vit_step_pool", "prego_vit_stream_pool_flush", "prego_vit_stream_pool_reset", "prego_vit_stream_pool_record",
-    "prego_vit_stream_pool_window",
+    "prego_vit_stream_pool_window", "prego_vit_step_pool_bursts_workspace_bytes", "prego_vit_step_pool_bursts",
 ]
 # include/prego_amd_debug.h: only in libprego_amd_debug.so
 DEBUG_SYMBOLS = ["prego_miniroad_debug_stamps", "prego_debug_gemm_bf16", "prego_debug_attention_bwd", "prego_debug_attention_fwd",
                  "prego_debug_recurrence_only", "prego_debug_gemm_worker", "prego_debug_head_only",
                  "prego_debug_split_fault", "prego_debug_split_state", "prego_debug_set_abort", "prego_debug_alloc_count", "prego_debug_hog",
-                 "prego_debug_ant_full_span", "prego_debug_gemm_tn", "prego_debug_gemm_nt", "prego_debug_vit_ring_tokens"]
+                 "prego_debug_ant_full_span", "prego_debug_gemm_tn", "prego_debug_gemm_nt", "prego_debug_vit_ring_tokens",
+                 "prego_debug_vit_burst_tokens", "prego_debug_vit_burst_commit"]
 
 
 class PregoError(RuntimeError):
@@ -185,6 +186,9 @@ def _open(path: str, debug: bool) -> C.CDLL:
     lib.prego_vit_step_pool_workspace_bytes.argtypes = [vp, i32]
     lib.prego_vit_step_pool_workspace_bytes.restype = sz
     lib.prego_vit_step_pool.argtypes = [vp, vp, i32, C.POINTER(C.c_int32), vp, vp, vp, vp, i32, vp, sz, vp]
+    lib.prego_vit_step_pool_bursts_workspace_bytes.argtypes = [vp, i32, i32]
+    lib.prego_vit_step_pool_bursts_workspace_bytes.restype = sz
+    lib.prego_vit_step_pool_bursts.argtypes = [vp, vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, vp, vp, i32, vp, sz, vp]
     lib.prego_vit_stream_pool_flush.argtypes = [vp, i32, C.POINTER(C.c_int32), vp]
     lib.prego_vit_stream_pool_reset.argtypes = [vp, i32, C.POINTER(C.c_int32), vp]
     lib.prego_vit_stream_pool_record.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz)]
@@ -230,6 +234,8 @@ def _open(path: str, debug: bool) -> C.CDLL:
         lib.prego_debug_hog.argtypes = [i32, i32, i32, vp, vp, sz, vp, vp]
         lib.prego_debug_ant_full_span.argtypes = [i32]
         lib.prego_debug_vit_ring_tokens.argtypes = [vp, i32, C.POINTER(C.c_int32), vp, vp]
+        lib.prego_debug_vit_burst_tokens.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, vp]
+        lib.prego_debug_vit_burst_commit.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp]
     return lib
 
 

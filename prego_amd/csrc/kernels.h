@@ -434,3 +434,18 @@ int launch_frames_recur_ragged(const void* whh, const float* gi, const float* b_
 // slots[i]) voted in frame order by the slot's lane; off + count <= n_rows <= 256 for every entry, or nothing is launched
 int launch_pool_commit_ragged(const PoolGeom& g, const int* slots, int n, const RaggedMap& rows, int n_rows, const float* h_ws,
                               const int* argmax, hipStream_t s);
+// stream_pool.hip, the vote alone for packed ids: slot slots[i]'s lane votes ids[off .. off + count) of rows.e[i] in frame order; the same
+// bounds on the entries as launch_pool_commit_ragged, or nothing is launched
+int launch_pool_vote_ragged(const PoolGeom& g, const int* slots, int n, const RaggedMap& rows, int n_rows, const int* ids, hipStream_t s);
+
+// Transformer stream pool, bursts (vit_stream.hip): slot slots[i] takes count[i] frames (1..min(32, T)), its encoded rows enc[off[i] ..
+// off[i] + count[i]) of the call's packed enc [n_rows][E], n_rows <= 256.  by_slot.e[i] = off[i] | i << 16 | count[i] << 24 for i < n;
+// by_row.e[b] = the entry of the slot that owns packed row b, for b < n_rows.  The launchers check both tables against each other and
+// against n_rows and T; -1 = refused, nothing launched.
+// one window per packed row (the window ending at that frame) out of the rings AS THEY STAND - before the commit - and enc
+int launch_vit_burst_tokens(const VitRing& r, const int* slots, int n, const RaggedMap& by_slot, const RaggedMap& by_row, int n_rows,
+                            const float* enc, const float* enc_b, const float* cls, const float* pe, float* x, const float* ln_w,
+                            const float* ln_b, void* xn, float* x0, hipStream_t s, bool f16 = false);
+// ring[slots[i]][(head + k) mod T] <- enc[off[i] + k], k < count[i]; then head and fill advance by count[i]
+int launch_vit_ring_commit_burst(const VitRing& r, const int* slots, int n, const RaggedMap& by_slot, int n_rows, const float* enc,
+                                 hipStream_t s);

@@ -7,6 +7,7 @@
 //   pool_commit_frames  pool_commit after a burst of K frames per slot: the state once, K votes in frame order by the slot's lane
 //   pool_commit_ragged  pool_commit after a ragged burst: a frame count per slot, the ids in packed rows (RaggedMap, by value as the slots)
 //   pool_vote     the vote alone, ids from the caller's device vector  (one lane per stream)
+//   pool_vote_ragged  the vote alone for a ragged burst: a frame count per slot, the ids in packed rows (the Transformer pool's bursts)
 //   pool_flush    votes a slot's unfinished window (the reference's shorter last window, aggregate.py:57-58)
 //   pool_reset    zeroes a slot's state row and record
 // The slot list travels by value in the kernel arguments (PoolSlots, 1 KB): no staging buffer, no H2D copy, nothing for the caller to
@@ -106,6 +107,16 @@ __global__ __launch_bounds__(64) void pool_vote_kernel(PoolGeom g, PoolSlots sl,
   if (i < n) pool_vote_update(pool_record(g, sl.s[i]), g, ids[i]);
 }
 
+// pool_vote for a ragged burst: lane i votes ids[off .. off + count) of its table entry in frame order
+__global__ __launch_bounds__(64) void pool_vote_ragged_kernel(PoolGeom g, PoolSlots sl, RaggedMap rows, int n, const int* __restrict__ ids) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  int* rec = pool_record(g, sl.s[i]);
+  const unsigned e = rows.e[i];
+  const int off = (int)ragged_off(e), K = (int)ragged_count(e);
+  for (int t = 0; t < K; ++t) pool_vote_update(rec, g, ids[off + t]);
+}
+
 __global__ __launch_bounds__(64) void pool_flush_kernel(PoolGeom g, PoolSlots sl, int n) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= n) return;
@@ -172,6 +183,15 @@ int launch_pool_vote(const PoolGeom& g, const int* slots, int n, const int* ids,
   PoolSlots sl;
   if (!ids || !pool_slots(g, slots, n, &sl)) return -1;
   pool_vote_kernel<<<(n + 63) / 64, 64, 0, s>>>(g, sl, n, ids);
+  return 0;
+}
+
+int launch_pool_vote_ragged(const PoolGeom& g, const int* slots, int n, const RaggedMap& rows, int n_rows, const int* ids, hipStream_t s) {
+  PoolSlots sl;
+  if (!ids || n_rows < n || n_rows > kPoolMaxActive || !pool_slots(g, slots, n, &sl)) return -1;
+  for (int i = 0; i < n; ++i)
+    if (ragged_count(rows.e[i]) < 1u || ragged_count(rows.e[i]) > 32u || ragged_off(rows.e[i]) + ragged_count(rows.e[i]) > (unsigned)n_rows) return -1;
+  pool_vote_ragged_kernel<<<(n + 63) / 64, 64, 0, s>>>(g, sl, rows, n, ids);
   return 0;
 }
 

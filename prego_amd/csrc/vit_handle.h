@@ -1,7 +1,7 @@
 // Private to the ViTEnc host files (vit_host.cpp, vit_stream.cpp): the handle, the per-batch workspace layout of the inference entry
 // points and the two encoder-block runners that cross files.  Which file defines what:
 //   vit_host.cpp      create / destroy, weight setters, vit_ws, encoder_block, encoder_block_token0, forward, forward_frames, training
-//   vit_stream.cpp    the Transformer stream pool: prego_vit_stream_pool_*, prego_vit_step_pool (kernels: vit_stream.hip)
+//   vit_stream.cpp    the Transformer stream pool: prego_vit_stream_pool_*, prego_vit_step_pool(_bursts) (kernels: vit_stream.hip)
 #pragma once
 #include "host_common.h"
 
@@ -28,7 +28,7 @@ struct prego_vit {
   unsigned long long drop_seed = 0;
 };
 
-// the per-batch arena of the 16-bit inference paths (prego_vit_forward, prego_vit_forward_frames, prego_vit_step_pool): B windows
+// the per-batch arena of the 16-bit inference paths (prego_vit_forward, prego_vit_forward_frames, prego_vit_step_pool(_bursts)): B windows
 struct VitWs { size_t xb, enc, x, xn, q, k, vn, ao, f, x0, q0, ao0, xn0, f0, total; };
 VitWs vit_ws(const prego_vit* h, int B);
 

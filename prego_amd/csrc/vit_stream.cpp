@@ -1,4 +1,4 @@
-// Host side of the Transformer stream pool (include/prego_amd.h: prego_vit_stream_pool_*, prego_vit_step_pool; kernels: vit_stream.hip,
+// Host side of the Transformer stream pool (include/prego_amd.h: prego_vit_stream_pool_*, prego_vit_step_pool(_bursts); kernels: vit_stream.hip,
 // the vote record and its kernels: stream_pool.hip).  The pool object is host memory only: the geometry, the addresses inside the caller's
 // device block and a stamp table for the duplicate check.  Every entry point decides all its refusals before its first launch, so a
 // refused call has written nothing.
@@ -46,6 +46,47 @@ VitStepWs vit_step_ws(const prego_vit* h, int n) {
   f.win = put(f.w.total);
   f.total = off;
   return f;
+}
+
+// the encoder blocks on B windows whose tokens the token kernel has written (fused: LayerNorm1(x) and x0 instead of x), then the head
+// with its argmax: what prego_vit_forward_frames runs for a batch of B windows
+int blocks_and_head(const prego_vit* h, const char* who, char* ws, const VitWs& w, int B, int causal, bool fused, float* out_logits,
+                    int32_t* am, hipStream_t s) {
+  const int N = h->window + 1;
+  for (int li = 0; li < h->layers; ++li) {
+    const bool last = li + 1 == h->layers;
+    const int rc = last ? encoder_block_token0(h, h->L[li], (const float*)(ws + w.x), ws, w, B, N, causal, s, fused)
+                        : encoder_block(h, h->L[li], (float*)(ws + w.x), ws, w, B, N, causal, s);
+    if (rc) return prego_fail_(PREGO_EINVAL, "%s: encoder block launch failed", who);
+  }
+  launch_vit_head((const float*)(ws + w.x0), B, 1, h->emb, h->lnf_w, h->lnf_b, h->head_w, h->head_b, h->ncls, out_logits, s, (int*)am);
+  return 0;
+}
+
+// a burst call's host arrays turned into kernel arguments: by_slot = entry i for slots[i], by_row = the owner's entry for every packed
+// row, rows = the sum of the counts.  n is already known to be in 1..256.  0 = fine, else PREGO_EINVAL with a message
+struct BurstPlan { RaggedMap by_slot, by_row; int rows; };
+int burst_plan(const char* who, int window, int n, const int32_t* counts, BurstPlan* bp) {
+  if (!counts) return prego_fail_(PREGO_EINVAL, "%s: counts is NULL", who);
+  const int kmax = window < 32 ? window : 32;
+  int rows = 0;
+  for (int i = 0; i < n; ++i) {
+    if (counts[i] < 1 || counts[i] > kmax)
+      return prego_fail_(PREGO_EINVAL, "%s: counts[%d] = %d (1..%d frames per slot per call: at most 32, window_size %d; split a longer "
+                         "backlog)", who, i, counts[i], kmax, window);
+    rows += counts[i];
+  }
+  if (rows > kPoolMaxActive)
+    return prego_fail_(PREGO_EINVAL, "%s: the counts sum to %d rows (at most %d windows per call)", who, rows, kPoolMaxActive);
+  for (int i = 0, at = 0; i < kRaggedMaxStreams; ++i) {
+    bp->by_slot.e[i] = i < n ? ragged_entry((unsigned)at, (unsigned)i, (unsigned)counts[i]) : 0u;
+    if (i < n) at += counts[i];
+  }
+  for (int i = 0, b = 0; i < n; ++i)
+    for (int k = 0; k < counts[i]; ++k) bp->by_row.e[b++] = bp->by_slot.e[i];
+  for (int b = rows; b < kRaggedMaxStreams; ++b) bp->by_row.e[b] = 0u;
+  bp->rows = rows;
+  return 0;
 }
 
 int slot_in_pool(const prego_vit_stream_pool* p, const char* who, int slot) {
@@ -121,7 +162,7 @@ extern "C" int prego_vit_step_pool(prego_vit* h, prego_vit_stream_pool* p, int n
   char* base = (char*)workspace;
   char* ws = base + f.win;                      // the per-batch arena, laid out as prego_vit_forward's
   const VitWs& w = f.w;
-  const int n = n_active, N = h->window + 1, E = h->emb, din = h->d_rgb + h->d_flow;
+  const int n = n_active, E = h->emb, din = h->d_rgb + h->d_flow;
   const int causal = (flags & 1) ? 1 : 0;
   float* enc = (float*)(base + f.enc);
   int32_t* am = argmax ? argmax : (int32_t*)(base + f.am);      // the vote always has its ids
@@ -133,14 +174,61 @@ extern "C" int prego_vit_step_pool(prego_vit* h, prego_vit_stream_pool* p, int n
   if (launch_vit_ring_tokens(p->r, slots, n, h->enc_b, h->cls, h->pe, fused ? nullptr : (float*)(ws + w.x), l0.ln1_w, l0.ln1_b,
                              fused ? ws + w.xn : nullptr, fused ? (float*)(ws + w.x0) : nullptr, s, h->f16))
     return prego_fail_(PREGO_EINVAL, "%s: ring tokens refused its arguments", who);
-  for (int li = 0; li < h->layers; ++li) {
-    const bool last = li + 1 == h->layers;
-    const int rc = last ? encoder_block_token0(h, h->L[li], (const float*)(ws + w.x), ws, w, n, N, causal, s, fused)
-                        : encoder_block(h, h->L[li], (float*)(ws + w.x), ws, w, n, N, causal, s);
-    if (rc) return prego_fail_(PREGO_EINVAL, "%s: encoder block launch failed", who);
-  }
-  launch_vit_head((const float*)(ws + w.x0), n, 1, E, h->lnf_w, h->lnf_b, h->head_w, h->head_b, h->ncls, out_logits, s, (int*)am);
+  if (int rc = blocks_and_head(h, who, ws, w, n, causal, fused, out_logits, am, s)) return rc;
   if (launch_pool_vote(p->g, slots, n, (const int*)am, s)) return prego_fail_(PREGO_EINVAL, "%s: vote refused its arguments", who);
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+extern "C" size_t prego_vit_step_pool_bursts_workspace_bytes(const prego_vit* h, int n_active, int n_rows) {
+  if (!h || n_active < 1 || n_active > kPoolMaxActive || n_rows < n_active || n_rows > kPoolMaxActive) return 0;
+  if ((long long)n_rows > (long long)n_active * (h->window < 32 ? h->window : 32)) return 0;
+  return vit_step_ws(h, n_rows).total;
+}
+
+// counts[i] new frames for slots[i], R packed rows: cat + convert and the encoding GEMM on R rows, one window per packed row out of the
+// rings as they stand and the call's own rows, THEN the rows into their rings (the token kernel reads what the commit overwrites), the
+// blocks and the head for a batch of R windows, and every slot's record takes its ids in frame order
+extern "C" int prego_vit_step_pool_bursts(prego_vit* h, prego_vit_stream_pool* p, int n_active, const int32_t* counts, const int32_t* slots,
+                                          const float* rgb, const float* flow, float* out_logits, int32_t* argmax, int flags, void* workspace,
+                                          size_t workspace_bytes, prego_stream_t stream) {
+  const char* who = "vit_step_pool_bursts";
+  if (!h || !p || !out_logits) return prego_fail_(PREGO_EINVAL, "%s: NULL argument", who);
+  if (h->f32) return prego_fail_(PREGO_EINVAL, "prego_vit_step_pool_bursts on an fp32-operand handle: the parity mode covers prego_vit_forward");
+  if (!h->have_weights) return prego_fail_(PREGO_EINVAL, "%s before set_weights", who);
+  if ((h->d_rgb > 0 && !rgb) || (h->d_rgb == 0 && !flow)) return prego_fail_(PREGO_EINVAL, "%s: missing input", who);
+  if (p->r.T != h->window || p->r.E != h->emb || p->g.ncls != h->ncls)
+    return prego_fail_(PREGO_EINVAL, "%s: the pool was created for window_size %d / embedding_dim %d / %d classes, the handle has %d / %d / %d",
+                       who, p->r.T, p->r.E, p->g.ncls, h->window, h->emb, h->ncls);
+  if (int rc = check_slot_list(p->stamps, p->r.capacity, who, n_active, slots)) return rc;
+  BurstPlan bp;
+  if (int rc = burst_plan(who, h->window, n_active, counts, &bp)) return rc;
+  const int n = n_active, R = bp.rows, E = h->emb, din = h->d_rgb + h->d_flow;
+  const VitStepWs f = vit_step_ws(h, R);
+  if (!workspace) return prego_fail_(PREGO_EINVAL, "%s: workspace is NULL", who);
+  if ((uintptr_t)workspace & 255) return prego_fail_(PREGO_EINVAL, "%s: the workspace must be 256-byte aligned", who);
+  if (workspace_bytes < f.total)
+    return prego_fail_(PREGO_EWORKSPACE, "%s: workspace %zu < %zu for %d rows of %d active streams (prego_vit_step_pool_bursts_workspace_bytes)",
+                       who, workspace_bytes, f.total, R, n);
+  hipStream_t s = (hipStream_t)stream;
+  char* base = (char*)workspace;
+  char* ws = base + f.win;
+  const VitWs& w = f.w;
+  const int causal = (flags & 1) ? 1 : 0;
+  float* enc = (float*)(base + f.enc);
+  int32_t* am = argmax ? argmax : (int32_t*)(base + f.am);
+  launch_cat_convert(rgb, flow, R, h->d_rgb, h->d_flow, base + f.xb, s, h->f16);
+  launch_gemm_bf16_nt(base + f.xb, din, h->enc_w, din, h->enc_b, enc, E, R, E, din, s, h->f16);       // ViT.py:124, once per frame
+  const bool fused = h->layers == 1;
+  const VitLayer& l0 = h->L[0];
+  if (launch_vit_burst_tokens(p->r, slots, n, bp.by_slot, bp.by_row, R, enc, h->enc_b, h->cls, h->pe, fused ? nullptr : (float*)(ws + w.x),
+                              l0.ln1_w, l0.ln1_b, fused ? ws + w.xn : nullptr, fused ? (float*)(ws + w.x0) : nullptr, s, h->f16))
+    return prego_fail_(PREGO_EINVAL, "%s: burst tokens refused its arguments", who);
+  if (launch_vit_ring_commit_burst(p->r, slots, n, bp.by_slot, R, enc, s))
+    return prego_fail_(PREGO_EINVAL, "%s: ring commit refused its arguments", who);
+  if (int rc = blocks_and_head(h, who, ws, w, R, causal, fused, out_logits, am, s)) return rc;
+  if (launch_pool_vote_ragged(p->g, slots, n, bp.by_slot, R, (const int*)am, s))
+    return prego_fail_(PREGO_EINVAL, "%s: vote refused its arguments", who);
   HIPCHK(hipGetLastError());
   return PREGO_OK;
 }
@@ -189,6 +277,37 @@ extern "C" int prego_debug_vit_ring_tokens(prego_vit_stream_pool* p, int n, cons
   const prego_vit* h = p->owner;
   if (launch_vit_ring_tokens(p->r, slots, n, h->enc_b, h->cls, h->pe, x_out, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, h->f16))
     return prego_fail_(PREGO_EINVAL, "debug_vit_ring_tokens: bad arguments");
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+// unit-test hook: vit_burst_tokens alone, only x wanted, on the pool as it stands (no commit) and the caller's enc [sum counts][E]
+extern "C" int prego_debug_vit_burst_tokens(prego_vit_stream_pool* p, int n, const int32_t* slots, const int32_t* counts, const float* enc,
+                                            float* x_out, prego_stream_t stream) {
+  const char* who = "debug_vit_burst_tokens";
+  if (!p || !enc || !x_out) return prego_fail_(PREGO_EINVAL, "%s: NULL argument", who);
+  if (!p->owner->have_weights) return prego_fail_(PREGO_EINVAL, "%s before set_weights", who);
+  if (int rc = check_slot_list(p->stamps, p->r.capacity, who, n, slots)) return rc;
+  BurstPlan bp;
+  if (int rc = burst_plan(who, p->r.T, n, counts, &bp)) return rc;
+  const prego_vit* h = p->owner;
+  if (launch_vit_burst_tokens(p->r, slots, n, bp.by_slot, bp.by_row, bp.rows, enc, h->enc_b, h->cls, h->pe, x_out, nullptr, nullptr, nullptr,
+                              nullptr, (hipStream_t)stream, h->f16))
+    return prego_fail_(PREGO_EINVAL, "%s: bad arguments", who);
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+// unit-test hook: vit_ring_commit_burst alone on the caller's enc [sum counts][E]
+extern "C" int prego_debug_vit_burst_commit(prego_vit_stream_pool* p, int n, const int32_t* slots, const int32_t* counts, const float* enc,
+                                            prego_stream_t stream) {
+  const char* who = "debug_vit_burst_commit";
+  if (!p || !enc) return prego_fail_(PREGO_EINVAL, "%s: NULL argument", who);
+  if (int rc = check_slot_list(p->stamps, p->r.capacity, who, n, slots)) return rc;
+  BurstPlan bp;
+  if (int rc = burst_plan(who, p->r.T, n, counts, &bp)) return rc;
+  if (launch_vit_ring_commit_burst(p->r, slots, n, bp.by_slot, bp.rows, enc, (hipStream_t)stream))
+    return prego_fail_(PREGO_EINVAL, "%s: bad arguments", who);
   HIPCHK(hipGetLastError());
   return PREGO_OK;
 }

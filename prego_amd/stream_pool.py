@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import heapq
+from typing import NamedTuple
 
 import torch
 
@@ -394,13 +395,45 @@ def ring_source(head: int, fill: int, T: int, j: int) -> int:
     return (head - (T - j)) % T
 
 
+class BurstRow(NamedTuple):
+    """`burst_source`'s answer for a token that comes from the call itself: burst row k of the same slot (packed row off + k).  Not an
+    int, so that it never compares equal to a ring row."""
+    k: int
+
+
+def burst_source(head: int, fill: int, T: int, k: int, j: int):
+    """Where token j of the window of burst frame k comes from (csrc/vit_stream.hip, vit_burst_tokens), head / fill being the slot's ring
+    words BEFORE the call.  d = T - 1 - j frames back from the window's newest: RING_CLS for j == T; BurstRow(k - d) where d <= k (a
+    row of this call); RING_BIAS where d - k > fill (a zero feature row in front of the stream); else the ring row
+    (head - (d - k)) mod T as it was before the call.  0 <= k < min(32, T)."""
+    if not (0 <= j <= T and 0 <= head < T and 0 <= fill <= T and 0 <= k < min(32, T)):
+        raise ValueError(f"burst_source: head {head}, fill {fill}, T {T}, k {k}, j {j}")
+    if j == T:
+        return RING_CLS
+    d = T - 1 - j
+    if d <= k:
+        return BurstRow(k - d)
+    if d - k > fill:
+        return RING_BIAS
+    return (head - (d - k)) % T
+
+
+def ring_after_burst(head: int, fill: int, T: int, count: int):
+    """(head, fill, rows) after a burst of `count` frames: the ring words vit_ring_commit_burst leaves and the ring rows it wrote, burst
+    frame k into rows[k] - what `count` one-frame commits leave"""
+    if not (0 <= head < T and 0 <= fill <= T and 1 <= count <= min(32, T)):
+        raise ValueError(f"ring_after_burst: head {head}, fill {fill}, T {T}, count {count}")
+    return (head + count) % T, min(fill + count, T), [(head + k) % T for k in range(count)]
+
+
 class TransformerStreamPool(_RecordPool):
     """TransformerStreamPool(vit, capacity=256, vote_window=200, max_events=1024) - `ViTEnc.stream_pool(...)`: live streams through the
     `Transformer` entry.  Every slot of one device block holds a ring of the stream's last `window_size` encoded frames
     (linear_encoding runs once per frame, as in `forward_frames`) and the vote record `StreamPool` keeps; `push` gives any subset of the
     slots one new frame and returns one ViTEnc window per slot - the window ending at that frame, zero feature rows in front of the
-    stream (prego_vit_step_pool; csrc/vit_stream.hip).  window_size * embedding_dim * 4 bytes per slot.  bf16 / fp16 operands; one
-    frame per slot per call (no bursts)."""
+    stream (prego_vit_step_pool; csrc/vit_stream.hip).  window_size * embedding_dim * 4 bytes per slot.  bf16 / fp16 operands.
+    `push_bursts` gives every slot named a frame count of its own (1..min(32, window_size), at most 256 frames per call) and returns one
+    window per frame: a backlog costs one encoding GEMM and one encoder batch, not one call per frame (prego_vit_step_pool_bursts)."""
     _C = {"destroy": "prego_vit_stream_pool_destroy", "flush": "prego_vit_stream_pool_flush", "reset": "prego_vit_stream_pool_reset",
           "record": "prego_vit_stream_pool_record"}
 
@@ -475,6 +508,59 @@ class TransformerStreamPool(_RecordPool):
             rc = self.lib.prego_vit_step_pool(hnd, self.p, n, self._slot_array(slots), p(rgb if d_rgb > 0 else None), p(flow), p(out),
                                               p(argmax), 1 if m.causal else 0, p(self._ws), self._ws.numel(),
                                               C.c_void_p(self._stream_ptr(self.device)))
+        self._check(rc)
+        return out, argmax
+
+    def push_bursts(self, slots, counts, rgb, flow=None, out=None, argmax=None):
+        """counts[i] new frames (1..min(32, window_size); one int = the same for every slot; R = sum(counts) <= 256) for open slot
+        slots[i] in one call: rgb [R, d_rgb] / flow [R, d_flow] (None = zero flow) fp32 cuda contiguous, packed in `slots` order
+        (`pack_bursts`).  Returns (logits [R, C] fp32, argmax int32 [R]): packed row off[i] + k is the model's forward on the
+        window_size frames of slot slots[i] ending at its burst frame k.  Afterwards each slot's ring and record are what counts[i]
+        `push` calls leave; the logits agree with those calls at the tolerance that holds `push` against `forward_frames` (the GEMM
+        kernels are chosen by row count), bit for bit when every count is 1.  A longer backlog is the caller's to split."""
+        m = self.model
+        hnd = self._handle("push_bursts")
+        slots = self.slots.check(slots, "push_bursts")
+        n = len(slots)
+        if isinstance(counts, torch.Tensor):
+            counts = counts.tolist()
+        try:
+            counts = [int(k) for k in counts]
+        except TypeError:                                        # one number: the same count for every slot
+            counts = [int(counts)] * n
+        if len(counts) != n:
+            raise PregoError(f"transformer stream pool push_bursts: {n} slots, {len(counts)} counts")
+        k_max = min(32, self._T)
+        for i, k in enumerate(counts):
+            if not 1 <= k <= k_max:
+                raise PregoError(f"transformer stream pool push_bursts: counts[{i}] = {k} (1..{k_max} frames per slot per call: at most 32, "
+                                 f"window_size {self._T}; split a longer backlog)")
+        R = sum(counts)
+        if R > MAX_ACTIVE:
+            raise PregoError(f"transformer stream pool push_bursts: the counts sum to {R} rows (at most {MAX_ACTIVE} windows per call)")
+        d_rgb, d_flow, ncls = m.d_rgb, m.d_flow, self._ncls
+        if (rgb if d_rgb > 0 else flow) is None:
+            raise PregoError("transformer stream pool push_bursts: a --no_rgb model needs the flow frames" if d_rgb == 0 else
+                             "transformer stream pool push_bursts: rgb is None")
+        if d_flow == 0:
+            flow = None
+        if out is None:
+            out = torch.empty((R, ncls), dtype=torch.float32, device=self.device)
+        if argmax is None:
+            argmax = torch.empty((R,), dtype=torch.int32, device=self.device)
+        for t, shape, dt, what in [(rgb if d_rgb > 0 else None, (R, d_rgb), torch.float32, "rgb"), (flow, (R, d_flow), torch.float32, "flow"),
+                                   (out, (R, ncls), torch.float32, "out"), (argmax, (R,), torch.int32, "argmax")]:
+            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
+                raise PregoError(f"transformer stream pool push_bursts: expected {what} as contiguous {dt} cuda {list(shape)} "
+                                 f"(sum(counts) = {R} packed rows), got {tuple(t.shape)} {t.dtype} on {t.device}")
+        need = self.lib.prego_vit_step_pool_bursts_workspace_bytes(hnd, n, R)
+        if self._ws is None or self._ws.numel() < need:          # grown here, outside the C call
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(self.device):
+            rc = self.lib.prego_vit_step_pool_bursts(hnd, self.p, n, self._slot_array(counts), self._slot_array(slots),
+                                                     p(rgb if d_rgb > 0 else None), p(flow), p(out), p(argmax), 1 if m.causal else 0,
+                                                     p(self._ws), self._ws.numel(), C.c_void_p(self._stream_ptr(self.device)))
         self._check(rc)
         return out, argmax
 
