@@ -622,6 +622,43 @@ int prego_vit_stream_pool_reset(prego_vit_stream_pool* p, int n, const int32_t* 
 int prego_vit_stream_pool_record(const prego_vit_stream_pool* p, int slot, const void** device_record, size_t* bytes);
 int prego_vit_stream_pool_window(prego_vit_stream_pool* p, int slot, float* out, int32_t* fill_out, prego_stream_t stream);
 
+/* Event feed of a stream pool (an addition to ABI 7, existing signatures unchanged): what changed in ANY slot since the previous drain, in
+ * one small report - for a live consumer that acts when a new step appears (step_anticipation), without one record copy per slot per
+ * tick.  One feed serves either pool type; it reads the pool's records and never writes the pool's block.
+ *   feed block      device memory, 256-byte aligned, at least prego_stream_pool_feed_bytes(capacity, max_out) bytes, the caller's; create
+ *                   enqueues its zeroing on `stream`.  One cursor word per slot - bits 0..29 the slot's events already delivered, bits
+ *                   30..31 the overflow bits (record full, id out of range) already reported -, the drain counter and one word of
+ *                   scratch per 256 slots.
+ *   report          device memory, 256-byte aligned, at least prego_stream_pool_feed_report_bytes(max_out) bytes, the caller's and
+ *                   separate from the feed block, so several may be in flight.  int32 words: count | pending | seq | 0, then max_out
+ *                   entries slot | index | step id | first frame (16 bytes each); `index` is the event's position in the slot's record.
+ *                   An entry with index -1 reports a slot's newly set overflow bits, once: the bits in the id field, the slot's
+ *                   `frames` in the last.
+ * prego_stream_pool_feed_drain: for every slot of the pool, n_events (clamped to 0..max_events) and the overflow word are read; when
+ * n_events is below the cursor's count, or a bit the cursor holds as reported is no longer set, the record was reset behind the feed's
+ * back and the cursor restarts at 0; the entries due are the slot's newly set overflow bits (if any), then its events
+ * [delivered, n_events).  Entries are written in ascending slot order, then ascending index (-1 first) - a function of the slot numbers
+ * alone, whatever the capacity.  When more than max_out entries are due the first max_out in that order are written, the cursors move
+ * only past what was written (a slot may be delivered in part), `pending` holds the count left behind (saturating at 2^31 - 1) and the
+ * next drain goes on from there: nothing is lost, nothing is delivered twice.  The header is always written (count 0 when nothing is
+ * new); nothing is written behind entry `count`; seq counts the drains of this feed from 1.  Two launches (one for a pool of up to 256
+ * slots); no atomics, no workgroup waits for another, no device allocation, no host wait.
+ * prego_stream_pool_feed_forget: zeroes the cursors of the slots named (HOST int32 [n], the pool calls' rules), for a slot that was
+ * reset and handed to a new stream.
+ * PREGO_EINVAL / PREGO_EWORKSPACE (a block or report too small) with a message, nothing launched: a NULL feed, pool, block, report or
+ * slot list, an unaligned block or report, max_out outside 1..16 777 216, n outside 1..min(256, capacity), a slot outside the pool or
+ * named twice.  The pool's block must outlive the feed; a feed belongs to the stream its pool belongs to. */
+typedef struct prego_stream_pool_feed prego_stream_pool_feed;
+size_t prego_stream_pool_feed_bytes(int capacity, int max_out);
+size_t prego_stream_pool_feed_report_bytes(int max_out);
+int prego_stream_pool_feed_create(prego_stream_pool_feed** out, const prego_stream_pool* p, int max_out, void* device_block, size_t bytes,
+                                  prego_stream_t stream);
+int prego_vit_stream_pool_feed_create(prego_stream_pool_feed** out, const prego_vit_stream_pool* p, int max_out, void* device_block,
+                                      size_t bytes, prego_stream_t stream);
+void prego_stream_pool_feed_destroy(prego_stream_pool_feed* f);
+int prego_stream_pool_feed_drain(prego_stream_pool_feed* f, void* report, size_t report_bytes, prego_stream_t stream);
+int prego_stream_pool_feed_forget(prego_stream_pool_feed* f, int n, const int32_t* slots, prego_stream_t stream);
+
 /* Training of the "Transformer" registry entry: trainer/train.py:20-24 (fwd, loss, backward) over ViTEnc (ViT.py:117-143,
  * Transformer.py:5-82, Attention.py:21-41).  forward_train is ViTEnc.forward in training mode with every dropout rate 0
  * (cfg['dropout'] == cfg['attn_dropout_rate'] == 0; non-zero rates are rejected by the host module) and keeps the activations

@@ -52,6 +52,8 @@ SYMBOLS = [
     "prego_vit_stream_pool_bytes", "prego_vit_stream_pool_create", "prego_vit_stream_pool_destroy", "prego_vit_step_pool_workspace_bytes",
     "prego_vit_step_pool", "prego_vit_stream_pool_flush", "prego_vit_stream_pool_reset", "prego_vit_stream_pool_record",
     "prego_vit_stream_pool_window", "prego_vit_step_pool_bursts_workspace_bytes", "prego_vit_step_pool_bursts",
+    "prego_stream_pool_feed_bytes", "prego_stream_pool_feed_report_bytes", "prego_stream_pool_feed_create",
+    "prego_vit_stream_pool_feed_create", "prego_stream_pool_feed_destroy", "prego_stream_pool_feed_drain", "prego_stream_pool_feed_forget",
 ]
 # include/prego_amd_debug.h: only in libprego_amd_debug.so
 DEBUG_SYMBOLS = ["prego_miniroad_debug_stamps", "prego_debug_gemm_bf16", "prego_debug_attention_bwd", "prego_debug_attention_fwd",
@@ -193,6 +195,16 @@ def _open(path: str, debug: bool) -> C.CDLL:
     lib.prego_vit_stream_pool_reset.argtypes = [vp, i32, C.POINTER(C.c_int32), vp]
     lib.prego_vit_stream_pool_record.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz)]
     lib.prego_vit_stream_pool_window.argtypes = [vp, i32, vp, vp, vp]
+    lib.prego_stream_pool_feed_bytes.argtypes = [i32, i32]
+    lib.prego_stream_pool_feed_bytes.restype = sz
+    lib.prego_stream_pool_feed_report_bytes.argtypes = [i32]
+    lib.prego_stream_pool_feed_report_bytes.restype = sz
+    lib.prego_stream_pool_feed_create.argtypes = [C.POINTER(vp), vp, i32, vp, sz, vp]
+    lib.prego_vit_stream_pool_feed_create.argtypes = [C.POINTER(vp), vp, i32, vp, sz, vp]
+    lib.prego_stream_pool_feed_destroy.argtypes = [vp]
+    lib.prego_stream_pool_feed_destroy.restype = None
+    lib.prego_stream_pool_feed_drain.argtypes = [vp, vp, sz, vp]
+    lib.prego_stream_pool_feed_forget.argtypes = [vp, i32, C.POINTER(C.c_int32), vp]
     lib.prego_vit_set_compute_dtype.argtypes = [vp, i32]
     lib.prego_attention_layer_set_compute_dtype.argtypes = [vp, i32]
     lib.prego_vit_set_dropout.argtypes = [vp, C.c_float, C.c_float, C.c_uint64]

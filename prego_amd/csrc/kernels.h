@@ -307,6 +307,19 @@ int launch_pool_vote(const PoolGeom& g, const int* slots, int n, const int* ids,
 int launch_pool_flush(const PoolGeom& g, const int* slots, int n, hipStream_t s);
 int launch_pool_reset(const PoolGeom& g, const int* slots, int n, hipStream_t s);
 
+// event feed of a stream pool (stream_feed.hip): the events appended to the slots' records since the previous drain, in one report
+constexpr int kFeedWg = 256;             // slots one workgroup of the drain handles (one trip, one lane per slot)
+struct FeedGeom {
+  int* cursor;                           // [capacity]: events delivered (bits 0..29) | overflow bits reported (bits 30..31)
+  int* seq;                              // drains so far
+  int* wg_due;                           // [ceil(capacity / kFeedWg)]: entries due per workgroup of the drain in flight
+  int max_out;                           // entries a report holds
+};
+// report: device, 16-byte aligned, (1 + f.max_out) x 16 bytes.  Reads g's records, writes f's words and the report; -1 = nothing launched
+int launch_feed_drain(const PoolGeom& g, const FeedGeom& f, int* report, hipStream_t s);
+// cursor[slots[i]] <- 0; slots: HOST, n in 1..256, each in [0, capacity); -1 = nothing launched
+int launch_feed_forget(const FeedGeom& f, int capacity, const int* slots, int n, hipStream_t s);
+
 // Transformer stream pool (vit_stream.hip): a ring of encoded frames per slot in the caller's device block.  ring [capacity][T][E] fp32,
 // row f mod T = linear_encoding(frame f); hf [capacity][4] int32 = head (next row to write) | fill (rows that hold a frame) | 0 | 0
 struct VitRing {

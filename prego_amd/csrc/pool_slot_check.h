@@ -7,6 +7,10 @@
 #include <cstdint>
 #include <vector>
 
+// the vote records of a pool, for what serves both pool types (stream_feed.cpp); each is defined beside its pool's struct
+const PoolGeom* stream_pool_geom(const prego_stream_pool* p);
+const PoolGeom* vit_stream_pool_geom(const prego_vit_stream_pool* p);
+
 struct SlotStamps {
   std::vector<unsigned> stamp;           // [capacity]: the call that last named the slot
   unsigned call = 0;

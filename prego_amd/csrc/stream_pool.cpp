@@ -13,6 +13,7 @@ struct prego_stream_pool {
   size_t bytes;                          // of the block, as laid out
   SlotStamps stamps;                     // the duplicate check without a per-call allocation
 };
+const PoolGeom* stream_pool_geom(const prego_stream_pool* p) { return &p->g; }      // pool_slot_check.h
 
 namespace {
 struct PoolLayout { size_t h_bytes, rec_words, total; };

@@ -14,6 +14,7 @@ struct prego_vit_stream_pool {
   size_t bytes;                          // of the block, as laid out
   SlotStamps stamps;
 };
+const PoolGeom* vit_stream_pool_geom(const prego_vit_stream_pool* p) { return &p->g; }      // pool_slot_check.h
 
 namespace {
 // block: ring [capacity][window][E] fp32 | ring words [capacity][4] int32 | records [capacity][rec_words] int32, each part 256-byte aligned

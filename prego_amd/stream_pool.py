@@ -2,11 +2,14 @@
 aggregation record (utils/aggregate.py:46-90, one id at a time) - and `push` advances any subset of the slots by one frame with the wide
 step's bits (prego_miniroad_step_pool: gather, the unchanged prego_miniroad_step_wide, commit + vote; csrc/stream_pool.hip).  `close`
 returns what `aggregate` would return for the stream's per-frame predictions ('pred', 'changes_pred'); no argmax crosses to the host on
-the way.  `SlotTable` is the host bookkeeping (which slots are open), usable without a device."""
+the way.  `SlotTable` is the host bookkeeping (which slots are open), usable without a device.  `EventFeed` (`pool.event_feed()`,
+csrc/stream_feed.hip) tells a live consumer which slots gained an event since it last asked, in one asynchronous report per tick;
+`FeedModel` is its host model."""
 from __future__ import annotations
 
 import ctypes as C
 import heapq
+import weakref
 from typing import NamedTuple
 
 import torch
@@ -97,7 +100,8 @@ class SlotTable:
 class _RecordPool:
     """What the two pools share: the slot bookkeeping and the reading of a slot's vote record (csrc/stream_pool.hip).  A subclass sets
     lib, device, p, slots (SlotTable), _block, _vote_window, max_events, _ncls, _ncls_pad and names its C entry points in `_C`."""
-    _C = {}                      # 'destroy', 'flush', 'reset', 'record' -> symbol
+    _C = {}                      # 'destroy', 'flush', 'reset', 'record', 'feed_create' -> symbol
+    _feeds = ()                  # the event feeds attached (a WeakSet once there is one): close() has them forget the slot
 
     def __del__(self):
         try:
@@ -164,9 +168,177 @@ class _RecordPool:
             self._check(getattr(self.lib, self._C["flush"])(self.p, 1, arr, s))
             frames, overflow, ev_id, ev_start = self._record(slot)
             self._check(getattr(self.lib, self._C["reset"])(self.p, 1, arr, s))
+            for feed in self._feeds:                         # a reopened slot starts at index 0
+                feed.forget([slot])
         self.slots.release(slot)
         self._raise_overflow(slot, overflow)
         return {"pred": ev_id, "changes_pred": ev_start[1:] + [frames]}
+
+    def event_feed(self, max_out: int = 1024, depth: int = 2) -> "EventFeed":
+        """An `EventFeed` over this pool: `feed.drain()` reports every event that any slot's record gained since the previous drain,
+        whatever push variant produced it, in one asynchronous copy of at most `max_out` entries; `depth` reports may be in flight."""
+        return EventFeed(self, max_out, depth)
+
+
+FEED_COUNT_MASK, FEED_REP_SHIFT = (1 << 30) - 1, 30          # a feed's cursor word (csrc/stream_feed.hip)
+
+
+class FeedModel:
+    """Host model of an event feed (csrc/stream_feed.hip) over `OnlineRecord`s, usable without a device: `records[slot]` is the slot's
+    record (the list is the caller's: putting a fresh OnlineRecord in place is a reset behind the feed's back).  `drain()` returns
+    {'count', 'pending', 'seq', 'entries'} with entries (slot, index, step id, first frame) in ascending slot order, then ascending
+    index; a slot's newly set overflow bits are the entry (slot, -1, bits, frames) in front of its events.  At most `max_out` entries
+    per drain: the cursors move only past what was written and the next drain goes on from there."""
+
+    def __init__(self, records, max_out: int = 1024):
+        if max_out < 1:
+            raise ValueError(f"FeedModel: max_out {max_out} (>= 1)")
+        self.records, self.max_out = records, int(max_out)
+        self.delivered, self.reported, self.seq = [0] * len(records), [0] * len(records), 0
+
+    def drain(self) -> dict:
+        entries, due = [], 0
+        for slot, rec in enumerate(self.records):
+            n = min(len(rec.event_id), rec.max_events)
+            if n < self.delivered[slot] or self.reported[slot] & ~rec.overflow:      # the record was reset behind the feed's back
+                self.delivered[slot], self.reported[slot] = 0, 0
+            fresh = rec.overflow & ~self.reported[slot]
+            if fresh:
+                due += 1
+                if len(entries) < self.max_out:
+                    entries.append((slot, -1, fresh, rec.frames))
+                    self.reported[slot] |= fresh
+            for i in range(self.delivered[slot], n):
+                due += 1
+                if len(entries) < self.max_out:
+                    entries.append((slot, i, rec.event_id[i], rec.event_start[i]))
+                    self.delivered[slot] = i + 1
+        self.seq += 1
+        return {"count": len(entries), "pending": due - len(entries), "seq": self.seq, "entries": entries}
+
+    def forget(self, slots):
+        for s in slots:
+            self.delivered[s], self.reported[s] = 0, 0
+
+    def cursor(self, slot: int) -> int:
+        """the slot's cursor word as the device keeps it"""
+        return self.delivered[slot] | self.reported[slot] << FEED_REP_SHIFT
+
+
+class FeedTicket:
+    """One drain in flight: `ready()` - has the report landed in host memory; `events()` - waits if it must, returns the entries as
+    (slot, index, step, start) and hands the buffer back to the feed; `pending` - entries the report had no room for (the next drain
+    brings them); `count`, `seq` - the header; `entries` - the report as it is, overflow entries (index -1) included, and like
+    `events()` it hands the buffer back."""
+
+    def __init__(self, feed, k: int):
+        self._feed, self._k, self._report, self._read = feed, k, None, False
+
+    def ready(self) -> bool:
+        return self._report is not None or self._feed._done[self._k].query()
+
+    def _wait(self):
+        if self._report is None:
+            self._feed._done[self._k].synchronize()
+            w = self._feed._host[self._k]
+            count = int(w[0])
+            if not 0 <= count <= self._feed.max_out:
+                raise PregoError(f"event feed: a report with count {count} (max_out {self._feed.max_out})")
+            self._report = (count, int(w[1]), int(w[2]), [tuple(r) for r in w[4:4 + 4 * count].view(count, 4).tolist()])
+        return self._report
+
+    @property
+    def count(self) -> int:
+        return self._wait()[0]
+
+    @property
+    def pending(self) -> int:
+        return self._wait()[1]
+
+    @property
+    def seq(self) -> int:
+        return self._wait()[2]
+
+    @property
+    def entries(self) -> list:
+        ent = self._wait()[3]
+        self._read = True                                        # as events(): the report has reached the caller
+        return list(ent)
+
+    def events(self) -> list:
+        """[(slot, index, step, start)]; raises PregoError, in `events(slot)`'s words, if a slot's record overflowed or met an id
+        outside the classes (the ticket counts as read all the same; `entries` still holds the whole report)"""
+        ent = self._wait()[3]
+        self._read = True                                        # the host buffer is the feed's again
+        for slot, index, bits, _ in ent:
+            if index < 0:
+                self._feed.pool._raise_overflow(slot, bits)
+        return list(ent)
+
+
+class EventFeed:
+    """EventFeed(pool, max_out=1024, depth=2) - `pool.event_feed(...)`: a live consumer's view of either pool (csrc/stream_feed.hip).
+    `drain()` enqueues, on the current stream, one scan of every slot's record and one non-blocking copy of the report (at most
+    `max_out` entries, 16 bytes each) into one of `depth` pinned host buffers, and returns a `FeedTicket` without waiting.  The
+    cursors advance on the device when the drain runs, so an unread ticket holds events nobody else will be handed: `drain()` raises,
+    before it launches anything, when all `depth` buffers hold unread tickets.  The pool's `close` has the feed forget the slot."""
+
+    def __init__(self, pool, max_out: int = 1024, depth: int = 2):
+        self.pool, self.lib, self.device = pool, pool.lib, pool.device
+        self.max_out, self.depth = int(max_out), int(depth)
+        if self.depth < 1:
+            raise PregoError(f"event feed: depth {depth} (>= 1)")
+        need = self.lib.prego_stream_pool_feed_bytes(pool.capacity, self.max_out)
+        self._report_bytes = self.lib.prego_stream_pool_feed_report_bytes(self.max_out)
+        if need == 0 or self._report_bytes == 0:
+            raise PregoError(f"event feed: max_out {max_out} (1..{1 << 24} entries per report)")
+        self._block = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._dev = [torch.empty(self._report_bytes, dtype=torch.uint8, device=self.device) for _ in range(self.depth)]
+        self._host = [torch.empty(self._report_bytes // 4, dtype=torch.int32).pin_memory() for _ in range(self.depth)]
+        self._done = [torch.cuda.Event() for _ in range(self.depth)]
+        self._tickets = [None] * self.depth
+        self._next = 0
+        self.f = None
+        f = C.c_void_p()
+        with torch.cuda.device(self.device):
+            rc = getattr(self.lib, pool._C["feed_create"])(C.byref(f), pool.p, self.max_out, C.c_void_p(self._block.data_ptr()), need,
+                                                           C.c_void_p(pool._stream_ptr(self.device)))
+        pool._check(rc)
+        self.f = f
+        if not isinstance(pool._feeds, weakref.WeakSet):
+            pool._feeds = weakref.WeakSet()
+        pool._feeds.add(self)
+
+    def __del__(self):
+        try:
+            if getattr(self, "f", None):
+                self.lib.prego_stream_pool_feed_destroy(self.f)
+                self.f = None
+        except Exception:
+            pass
+
+    def drain(self) -> FeedTicket:
+        k = self._next
+        held = self._tickets[k]
+        if held is not None and not held._read:                  # the oldest buffer: if it is unread, all of them are
+            raise PregoError(f"event feed drain: all {self.depth} report buffers hold unread tickets (read one with events(); the "
+                             "cursors advance when a drain runs, so its events would reach nobody)")
+        with torch.cuda.device(self.device):
+            self.pool._check(self.lib.prego_stream_pool_feed_drain(self.f, C.c_void_p(self._dev[k].data_ptr()), self._report_bytes,
+                                                                   C.c_void_p(self.pool._stream_ptr(self.device))))
+            self._host[k].copy_(self._dev[k].view(torch.int32), non_blocking=True)
+            self._done[k].record()
+        ticket = FeedTicket(self, k)
+        self._tickets[k] = ticket
+        self._next = (k + 1) % self.depth
+        return ticket
+
+    def forget(self, slots):
+        """zeroes the cursors of `slots` (any slots of the pool, each named once): what `close` does for the slot it frees"""
+        slots = [int(s) for s in slots]
+        with torch.cuda.device(self.device):
+            self.pool._check(self.lib.prego_stream_pool_feed_forget(self.f, len(slots), self.pool._slot_array(slots),
+                                                                    C.c_void_p(self.pool._stream_ptr(self.device))))
 
 
 class StreamPool(_RecordPool):
@@ -176,7 +348,7 @@ class StreamPool(_RecordPool):
     and `close` serve every engine (ids from the Transformer path or a general forward); live Transformer streams have a pool of their
     own, `TransformerStreamPool` below (`ViTEnc.stream_pool`)."""
     _C = {"destroy": "prego_stream_pool_destroy", "flush": "prego_stream_pool_flush", "reset": "prego_stream_pool_reset",
-          "record": "prego_stream_pool_record"}
+          "record": "prego_stream_pool_record", "feed_create": "prego_stream_pool_feed_create"}
 
     def __init__(self, model_or_engine, capacity: int = 256, window: int = 200, max_events: int = 1024):
         from .engine import _stream_ptr
@@ -435,7 +607,7 @@ class TransformerStreamPool(_RecordPool):
     `push_bursts` gives every slot named a frame count of its own (1..min(32, window_size), at most 256 frames per call) and returns one
     window per frame: a backlog costs one encoding GEMM and one encoder batch, not one call per frame (prego_vit_step_pool_bursts)."""
     _C = {"destroy": "prego_vit_stream_pool_destroy", "flush": "prego_vit_stream_pool_flush", "reset": "prego_vit_stream_pool_reset",
-          "record": "prego_vit_stream_pool_record"}
+          "record": "prego_vit_stream_pool_record", "feed_create": "prego_vit_stream_pool_feed_create"}
 
     def __init__(self, vit, capacity: int = 256, vote_window: int = 200, max_events: int = 1024):
         from .engine import _stream_ptr

@@ -49,6 +49,14 @@ one, and the control - all counts 4, where (g) is a single push_frames and (r) h
 |r - g| stays within the larger of the two p10..p90 widths.
 
     python scripts/anticipation_bench.py --step --pool --ragged [--steps 200] [--warmup 20] [--rounds 4] [--models L0,L8]
+
+--step --pool --feed: the event feed (EventFeed, csrc/stream_feed.hip), n_active = 4 / 16 / 64 / 256 scattered slots of a 256-slot pool with
+1 024 events per record and a vote window of --vote-window frames (1: every frame votes, so events occur on most ticks), the same protocol: (a) push + drain + reading
+the ticket of the tick before, (b) the route a caller had before the feed - push, then events(slot) for every active slot, one blocking
+record copy each - and (c) push alone.  `a_minus_c_us` / `b_minus_c_us`: what learning of the new events adds to a tick.  Every record is
+emptied (outside the timed part) before a leg's round, so no record fills.
+
+    python scripts/anticipation_bench.py --step --pool --feed [--steps 200] [--warmup 20] [--rounds 4] [--streams 4,256] [--models L0,L8]
 """
 from __future__ import annotations
 
@@ -86,6 +94,8 @@ def main():
     ap.add_argument("--pool", action="store_true", help="with --step: StreamPool.push against the dense step_wide and the torch route around it")
     ap.add_argument("--frames", action="store_true", help="with --step --pool: one push_frames of K frames against K push calls")
     ap.add_argument("--ragged", action="store_true", help="with --step --pool: one push_ragged against one push_frames per group of equal count")
+    ap.add_argument("--feed", action="store_true", help="with --step --pool: push + EventFeed.drain against push + events(slot) per active slot")
+    ap.add_argument("--vote-window", type=int, default=1, help="with --feed: the pool's vote window, small so that events occur on most ticks")
     ap.add_argument("--streams", default=None, help="default: 17,32,64,128,256 (--wide), 4,16,64,256 (--pool)")
     ap.add_argument("--models", default=None, help="L0 = MiniROAD, Lk = MiniROADA with anticipation_length k; default: L0,L1,L8 (--wide), L0,L8 (--pool)")
     ap.add_argument("--paths", default="w,g,c")
@@ -101,6 +111,8 @@ def main():
             return step_pool_frames_bench(a)
         if a.pool and a.ragged:
             return step_pool_ragged_bench(a)
+        if a.pool and a.feed:
+            return step_pool_feed_bench(a)
         return step_pool_bench(a) if a.pool else step_wide_bench(a) if a.wide else step_bench(a)
     dev = "cuda:0"
     lens = workloads.assembly101_eval_lengths()
@@ -415,6 +427,109 @@ def step_pool_bench(a):
                                 "256-slot pool): p = StreamPool.push, w = dense step_wide, t = index_select + step_wide + index_copy_ + "
                                 "argmax.cpu() + host vote", "dtype": a.dtype, "frames_per_path_and_round": frames, "rounds": a.rounds,
                       "table": table}))
+
+
+def step_pool_feed_bench(a):
+    import ctypes as Ct
+    import random
+
+    dev, C, cap = "cuda:0", 86, 256
+    frames = max(a.steps, 200)
+    base = assembly101_cfg(compute_dtype=a.dtype, assume_zero_flow=True)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1234)
+    x = torch.randn((16, 256, 2048), device=dev, generator=gen).clamp_(min=0)
+    table = {}
+    for name in a.models.split(","):
+        L = int(name[1:])
+        cfg = anticipation_cfg(base, L) if L else base
+        sd = W.miniroad_a_state_dict(cfg, 20, head_gain=8.0, ant_gain=4.0) if L else W.miniroad_state_dict(base, 20, head_gain=8.0)
+        m = build_model(cfg, dev)
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+        m.eval()
+        eng, ant = m.engine(), L > 0
+        for n in (int(s) for s in a.streams.split(",")):
+            pool = m.stream_pool(capacity=cap, window=a.vote_window)      # max_events 1024: the record events(slot) copies is 8.5 KB
+            feed = pool.event_feed(max_out=1024, depth=2)
+            for _ in range(cap):
+                pool.open()
+            slots = random.Random(n).sample(range(cap), n)            # scattered, in no order
+            every = (Ct.c_int32 * cap)(*range(cap))
+            xs = [x[i, :n].contiguous() for i in range(16)]
+            out, arg = torch.empty((n, C), device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
+            ao, aa = (torch.empty((n, L, C), device=dev), torch.empty((n, L), dtype=torch.int32, device=dev)) if ant else (None, None)
+            seen = {"a": 0, "b": 0, "ticks": 0, "hit": 0, "prev": None, "last": {}}
+
+            def fresh():
+                """every record empty again, outside the timed part: a leg's frames never fill a record"""
+                if seen["prev"] is not None:
+                    seen["prev"].events()
+                    seen["prev"] = None
+                pool._check(pool.lib.prego_stream_pool_reset(pool.p, cap, every, None))
+                feed.forget(range(cap))
+                seen["last"] = {}
+                torch.cuda.synchronize()
+
+            def fc(i):
+                pool.push(slots, xs[i & 15], None, out=out, argmax=arg, want_ant=ant, ant_out=ao, ant_argmax=aa)
+
+            def fa(i):
+                fc(i)
+                t = feed.drain()
+                if seen["prev"] is not None:                          # the ticket of the tick before: its copy has had a tick to land
+                    got = len(seen["prev"].events())
+                    seen["a"] += got
+                    seen["hit"] += got > 0
+                seen["prev"] = t
+                seen["ticks"] += 1
+
+            def fb(i):
+                fc(i)
+                for s in slots:                                       # one blocking record copy per slot, then the diff against the last poll
+                    n_ev = len(pool.events(s)["pred"])
+                    seen["b"] += n_ev - seen["last"].get(s, 0)
+                    seen["last"][s] = n_ev
+            paths = {"a": fa, "b": fb, "c": fc}
+            times, rounds = {k: [] for k in paths}, {k: [] for k in paths}
+            for f in paths.values():
+                fresh()
+                for i in range(a.warmup):
+                    f(i)
+            seen.update(a=0, b=0, ticks=0, hit=0)
+            for _ in range(a.rounds):
+                for k, f in paths.items():
+                    fresh()
+                    evs = [torch.cuda.Event(enable_timing=True) for _ in range(2 * frames)]
+                    r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    r0.record()
+                    for i in range(frames):
+                        evs[2 * i].record()
+                        f(i)
+                        evs[2 * i + 1].record()
+                    r1.record()
+                    torch.cuda.synchronize()
+                    times[k] += [evs[2 * i].elapsed_time(evs[2 * i + 1]) * 1e3 for i in range(frames)]
+                    rounds[k].append(r0.elapsed_time(r1) * 1e3 / frames)
+            fresh()
+            eng.check()
+            t = {k: {"median_us": float(np.median(v)), "p10_us": float(np.percentile(v, 10)), "p90_us": float(np.percentile(v, 90)),
+                     "round_us": float(np.median(rounds[k]))} for k, v in times.items()}
+            t["a_minus_c_us"] = t["a"]["median_us"] - t["c"]["median_us"]
+            t["b_minus_c_us"] = t["b"]["median_us"] - t["c"]["median_us"]
+            t["a_minus_c_round_us"] = t["a"]["round_us"] - t["c"]["round_us"]
+            t["b_minus_c_round_us"] = t["b"]["round_us"] - t["c"]["round_us"]
+            t["c_spread_us"] = t["c"]["p90_us"] - t["c"]["p10_us"]
+            t["events_per_tick"] = seen["a"] / max(seen["ticks"], 1)
+            t["ticks_with_events"] = seen["hit"] / max(seen["ticks"], 1)
+            t["events_a"], t["events_b"] = seen["a"], seen["b"]         # (a) reads one tick late: it may lack each round's last tick
+            table[f"{name}_n{n}"] = t
+            print(json.dumps({f"{name}_n{n}": t}), file=sys.stderr, flush=True)
+            del feed, pool
+        del m, eng
+    print(json.dumps({"metric": "per-tick device time, us (median of device-event pairs around every tick; zero flow; n_active scattered slots of a "
+                                "256-slot pool, 1024 events per record): a = push + EventFeed.drain + reading the previous tick's ticket, b = push + "
+                                "events(slot) for every active slot, c = push alone; round_us = a whole round between two events / its ticks",
+                      "dtype": a.dtype, "vote_window": a.vote_window, "frames_per_path_and_round": frames, "rounds": a.rounds, "table": table}))
 
 
 def step_pool_frames_bench(a):
