@@ -659,6 +659,47 @@ void prego_stream_pool_feed_destroy(prego_stream_pool_feed* f);
 int prego_stream_pool_feed_drain(prego_stream_pool_feed* f, void* report, size_t report_bytes, prego_stream_t stream);
 int prego_stream_pool_feed_forget(prego_stream_pool_feed* f, int n, const int32_t* slots, prego_stream_t stream);
 
+/* Slot images of a stream pool (an addition to ABI 7, existing signatures unchanged): a live slot taken out of a pool as data and put
+ * into a pool again - another pool, other slot numbers, another device or another process by way of the host -, bit for bit the stream
+ * it was, with its feed position.  Both pool types.  An image is only meaningful for the weights that made it: the geometry is checked,
+ * the weights are the caller's business.
+ * Image of a slot: prego_stream_pool_image_bytes(p) bytes (a multiple of 256), the same for every slot of a pool, 32-bit words:
+ *   tag    [16]  magic 0x474d4950 | image version 1 | kind (1 GRU pool, 2 Transformer pool) | hid or embedding_dim | window_size (0 for
+ *                the GRU pool) | n_classes | vote window | max_events | frames | ring head | ring fill | feed cursor word (0 when no feed
+ *                was named) | 0 | 0 | 0 | 0
+ *   state        GRU pool: the fp32 state row [hid].  Transformer pool: the ring [window_size][embedding_dim] fp32 at its physical row
+ *                positions, the rows that fill does not cover (fill .. window_size - 1) as zeros
+ *   record       the slot's vote record, all of its words: frames | last vote + 1 | n_events | overflow | counts[n_classes rounded up
+ *                to 4] | event_id[max_events] | event_start[max_events]
+ *   zeros        up to the next multiple of 256 bytes
+ * An image is canonical: the same stream gives the same bytes whatever slot it lived in and whatever lived there before.
+ * prego_stream_pool_snapshot: images[i] <- slot slots[i]; the pool's block is only read.  With a feed, the slot's cursor word travels
+ * in the tag.  One launch.
+ * prego_stream_pool_restore: slot slots[i] <- images[i]: state or ring, ring words, record and, with a feed, its cursor word for the
+ * slot.  Every image is validated on the device before anything of its slot is written; an image that fails leaves its slot and the
+ * feed's cursor byte for byte as they were.  status (device int32 [n], nullable): 0 = restored, else a bit per failed clause -
+ *   1   tag words 0..7 differ from the pool's geometry       2   frames < 0, or the record's frames is not the tag's
+ *   4   n_events outside 0..max_events                        8   last vote + 1 outside 0..n_classes
+ *   16  overflow word outside 0..3                            32  a counter outside 0..vote window
+ *   64  Transformer pool: head != frames mod window_size or fill != min(frames, window_size)
+ *   128 the cursor's delivered count (bits 0..29) is above n_events
+ * One launch; no atomics, no workgroup waits for another.  The caller reads status when it wants to know; restoring into a slot that
+ * holds a stream overwrites it.
+ * slots: HOST int32 [n], n in 1..min(256, capacity), inside the pool, each named once.  images: device memory, 256-byte aligned, at
+ * least n * image_bytes, outside the pool's and the feed's blocks.  PREGO_EINVAL / PREGO_EWORKSPACE (images too small) with a message,
+ * nothing launched: a NULL pool, slot list or images, a feed that belongs to another pool, unaligned or overlapping memory.  No device
+ * allocation, no host wait. */
+size_t prego_stream_pool_image_bytes(const prego_stream_pool* p);
+int prego_stream_pool_snapshot(prego_stream_pool* p, const prego_stream_pool_feed* feed /* nullable */, int n, const int32_t* slots,
+                               void* images, size_t bytes, prego_stream_t stream);
+int prego_stream_pool_restore(prego_stream_pool* p, prego_stream_pool_feed* feed /* nullable */, int n, const int32_t* slots,
+                              const void* images, size_t bytes, int32_t* status /* nullable */, prego_stream_t stream);
+size_t prego_vit_stream_pool_image_bytes(const prego_vit_stream_pool* p);
+int prego_vit_stream_pool_snapshot(prego_vit_stream_pool* p, const prego_stream_pool_feed* feed /* nullable */, int n, const int32_t* slots,
+                                   void* images, size_t bytes, prego_stream_t stream);
+int prego_vit_stream_pool_restore(prego_vit_stream_pool* p, prego_stream_pool_feed* feed /* nullable */, int n, const int32_t* slots,
+                                  const void* images, size_t bytes, int32_t* status /* nullable */, prego_stream_t stream);
+
 /* Training of the "Transformer" registry entry: trainer/train.py:20-24 (fwd, loss, backward) over ViTEnc (ViT.py:117-143,
  * Transformer.py:5-82, Attention.py:21-41).  forward_train is ViTEnc.forward in training mode with every dropout rate 0
  * (cfg['dropout'] == cfg['attn_dropout_rate'] == 0; non-zero rates are rejected by the host module) and keeps the activations

@@ -101,6 +101,12 @@ int prego_debug_vit_burst_tokens(prego_vit_stream_pool* p, int n, const int32_t*
 int prego_debug_vit_burst_commit(prego_vit_stream_pool* p, int n, const int32_t* slots, const int32_t* counts, const float* enc,
                                  prego_stream_t stream);
 
+/* Unit test only (tests/test_stream_image_cpu.py), no device: the slot images' validity rule (csrc/pool_image.h: pool_image_fault) on HOST
+ * words, so that the Python model `image_fault` is held against the function the restore kernel evaluates.  geometry6: kind | dim |
+ * window_size | n_classes | vote window | max_events; tag: the image's 16 tag words; rec: the first 4 + n_classes (rounded up to 4) words
+ * of its record.  Returns the clause bits, -1 for a NULL argument. */
+int prego_debug_pool_image_fault(const int32_t* geometry6, const int32_t* tag, const int32_t* rec);
+
 #ifdef __cplusplus
 }
 #endif

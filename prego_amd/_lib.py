@@ -54,13 +54,15 @@ SYMBOLS = [
     "prego_vit_stream_pool_window", "prego_vit_step_pool_bursts_workspace_bytes", "prego_vit_step_pool_bursts",
     "prego_stream_pool_feed_bytes", "prego_stream_pool_feed_report_bytes", "prego_stream_pool_feed_create",
     "prego_vit_stream_pool_feed_create", "prego_stream_pool_feed_destroy", "prego_stream_pool_feed_drain", "prego_stream_pool_feed_forget",
+    "prego_stream_pool_image_bytes", "prego_stream_pool_snapshot", "prego_stream_pool_restore",
+    "prego_vit_stream_pool_image_bytes", "prego_vit_stream_pool_snapshot", "prego_vit_stream_pool_restore",
 ]
 # include/prego_amd_debug.h: only in libprego_amd_debug.so
 DEBUG_SYMBOLS = ["prego_miniroad_debug_stamps", "prego_debug_gemm_bf16", "prego_debug_attention_bwd", "prego_debug_attention_fwd",
                  "prego_debug_recurrence_only", "prego_debug_gemm_worker", "prego_debug_head_only",
                  "prego_debug_split_fault", "prego_debug_split_state", "prego_debug_set_abort", "prego_debug_alloc_count", "prego_debug_hog",
                  "prego_debug_ant_full_span", "prego_debug_gemm_tn", "prego_debug_gemm_nt", "prego_debug_vit_ring_tokens",
-                 "prego_debug_vit_burst_tokens", "prego_debug_vit_burst_commit"]
+                 "prego_debug_vit_burst_tokens", "prego_debug_vit_burst_commit", "prego_debug_pool_image_fault"]
 
 
 class PregoError(RuntimeError):
@@ -205,6 +207,11 @@ def _open(path: str, debug: bool) -> C.CDLL:
     lib.prego_stream_pool_feed_destroy.restype = None
     lib.prego_stream_pool_feed_drain.argtypes = [vp, vp, sz, vp]
     lib.prego_stream_pool_feed_forget.argtypes = [vp, i32, C.POINTER(C.c_int32), vp]
+    for pre in ("prego_stream_pool", "prego_vit_stream_pool"):
+        getattr(lib, pre + "_image_bytes").argtypes = [vp]
+        getattr(lib, pre + "_image_bytes").restype = sz
+        getattr(lib, pre + "_snapshot").argtypes = [vp, vp, i32, C.POINTER(C.c_int32), vp, sz, vp]
+        getattr(lib, pre + "_restore").argtypes = [vp, vp, i32, C.POINTER(C.c_int32), vp, sz, vp, vp]
     lib.prego_vit_set_compute_dtype.argtypes = [vp, i32]
     lib.prego_attention_layer_set_compute_dtype.argtypes = [vp, i32]
     lib.prego_vit_set_dropout.argtypes = [vp, C.c_float, C.c_float, C.c_uint64]
@@ -248,6 +255,7 @@ def _open(path: str, debug: bool) -> C.CDLL:
         lib.prego_debug_vit_ring_tokens.argtypes = [vp, i32, C.POINTER(C.c_int32), vp, vp]
         lib.prego_debug_vit_burst_tokens.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, vp]
         lib.prego_debug_vit_burst_commit.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp]
+        lib.prego_debug_pool_image_fault.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     return lib
 
 

@@ -90,6 +90,40 @@ class OnlineRecord:
         if rest and any(self.counts):
             self._close_window(self.frames - rest)
 
+    def to_words(self, n_classes=None, max_events=None) -> list:
+        """the record as the device lays it out (csrc/stream_pool.hip), rec_words ints: frames | last vote + 1 | n_events | overflow |
+        counts[n_classes rounded up to 4] | event_id[max_events] | event_start[max_events], rounded up to 4 words - a slot image's record
+        part (csrc/pool_image.h).  n_classes / max_events: the pool's, when they are not the record's own"""
+        ncls = self.n_classes if n_classes is None else int(n_classes)
+        mev = self.max_events if max_events is None else int(max_events)
+        if ncls < self.n_classes or mev < len(self.event_id):
+            raise ValueError(f"OnlineRecord.to_words: n_classes {ncls} / max_events {mev} below the record's {self.n_classes} / {len(self.event_id)} events")
+        pad = (ncls + 3) // 4 * 4
+        n = len(self.event_id)
+        w = [self.frames, 0 if self.last_vote is None else self.last_vote + 1, n, self.overflow]
+        w += self.counts + [0] * (pad - self.n_classes)
+        w += self.event_id + [0] * (mev - n) + self.event_start + [0] * (mev - n)
+        return w + [0] * (-len(w) % 4)
+
+    @classmethod
+    def from_words(cls, words, window: int, n_classes: int, max_events: int) -> "OnlineRecord":
+        """the record the words of `to_words` describe.  `voted_to` is not a word of the device record: it is rebuilt as the end of the
+        last window the words show voted - `frames` when no count is pending (a window boundary, or a flush), else the last boundary"""
+        w = [int(v) for v in words]
+        pad = (int(n_classes) + 3) // 4 * 4
+        need = (4 + pad + 2 * int(max_events) + 3) // 4 * 4
+        if len(w) < need:
+            raise ValueError(f"OnlineRecord.from_words: {len(w)} words, a record of {n_classes} classes and {max_events} events has {need}")
+        rec = cls(window, n_classes, max_events)
+        n = w[2]
+        if not 0 <= n <= rec.max_events:
+            raise ValueError(f"OnlineRecord.from_words: n_events {n} (0..{rec.max_events})")
+        rec.frames, rec.last_vote, rec.overflow = w[0], (w[1] - 1 if w[1] else None), w[3]
+        rec.counts = w[4:4 + rec.n_classes]
+        rec.event_id, rec.event_start = w[4 + pad:4 + pad + n], w[4 + pad + rec.max_events:4 + pad + rec.max_events + n]
+        rec.voted_to = 0 if rec.last_vote is None else rec.frames if not any(rec.counts) else rec.frames - rec.frames % rec.window
+        return rec
+
     def result(self) -> dict:
         """{'pred', 'changes_pred'} of the windows voted so far (an unfinished window counts once flushed) and the frames fed"""
         return {"pred": list(self.event_id), "changes_pred": list(self.event_start[1:]) + [self.voted_to], "frames": self.frames}

@@ -337,6 +337,23 @@ int launch_vit_ring_tokens(const VitRing& r, const int* slots, int n, const floa
 // out [T][E] <- the slot's logical window, oldest to newest (bias rows in front), *fill_out <- fill
 int launch_vit_ring_window(const VitRing& r, int slot, const float* enc_b, float* out, int* fill_out, hipStream_t s);
 
+// slot images of either pool type (stream_image.hip; layout and validity rule: pool_image.h).  ImageRing::ring == nullptr: the GRU pool,
+// a slot's state is its row of g.h; else the Transformer pool, g.h holds the ring words [capacity][4] and the state is the slot's ring
+struct PoolImageDims;                    // pool_image.h
+struct ImageRing {
+  float* ring;                           // [capacity][T][E] fp32 or nullptr
+  int T, E;
+};
+constexpr int kImageChunkVecs = 4096;    // 16-byte vectors of an image one workgroup moves (64 KB): grid = chunks x n
+// slots: as the pool launchers (HOST, 1..256, inside the pool, named once); images: device, 16-byte aligned, n x d.image_words words;
+// cursor: the feed's cursor words [capacity] or nullptr; -1 = refused, nothing launched
+// images[i] <- slot slots[i] (the pool and the cursors are only read)
+int launch_pool_snapshot(const PoolGeom& g, const ImageRing& r, const PoolImageDims& d, const int* cursor, const int* slots, int n,
+                         int* images, hipStream_t s);
+// slot slots[i] <- images[i] where pool_image_fault says 0, else nothing of that slot; status (nullable) [n] <- the fault words
+int launch_pool_restore(const PoolGeom& g, const ImageRing& r, const PoolImageDims& d, int* cursor, const int* slots, int n,
+                        const int* images, int* status, hipStream_t s);
+
 // split pass (round 6): rows gate * H + u of a 16-bit [3H][E] matrix and an fp32 [3H] vector -> rows (u / 2) * 6 + 2 * gate + u % 2 (rowwise.hip)
 void launch_permute_gi_rows(const void* w, const float* bias, void* w_perm, float* bias_perm, int H, int E, hipStream_t s);
 

@@ -10,6 +10,17 @@
 // the vote records of a pool, for what serves both pool types (stream_feed.cpp); each is defined beside its pool's struct
 const PoolGeom* stream_pool_geom(const prego_stream_pool* p);
 const PoolGeom* vit_stream_pool_geom(const prego_vit_stream_pool* p);
+// what the slot images need on top (stream_image.cpp): a pool's stamp table, its block, the Transformer pool's ring, and of a feed the pool
+// it was created over and its cursor words
+struct SlotStamps;
+struct PoolBlock { const char* base; size_t bytes; };
+SlotStamps* stream_pool_stamps(prego_stream_pool* p);
+SlotStamps* vit_stream_pool_stamps(prego_vit_stream_pool* p);
+PoolBlock stream_pool_block(const prego_stream_pool* p);
+PoolBlock vit_stream_pool_block(const prego_vit_stream_pool* p);
+const VitRing* vit_stream_pool_ring(const prego_vit_stream_pool* p);
+const PoolGeom* stream_pool_feed_pool(const prego_stream_pool_feed* f);
+const FeedGeom* stream_pool_feed_geom(const prego_stream_pool_feed* f);
 
 struct SlotStamps {
   std::vector<unsigned> stamp;           // [capacity]: the call that last named the slot

@@ -13,6 +13,9 @@ struct prego_stream_pool_feed {
   SlotStamps stamps;
 };
 
+const PoolGeom* stream_pool_feed_pool(const prego_stream_pool_feed* f) { return &f->g; }      // pool_slot_check.h
+const FeedGeom* stream_pool_feed_geom(const prego_stream_pool_feed* f) { return &f->f; }
+
 namespace {
 constexpr int kFeedMaxOut = 1 << 24;
 

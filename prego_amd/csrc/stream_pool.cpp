@@ -14,6 +14,8 @@ struct prego_stream_pool {
   SlotStamps stamps;                     // the duplicate check without a per-call allocation
 };
 const PoolGeom* stream_pool_geom(const prego_stream_pool* p) { return &p->g; }      // pool_slot_check.h
+SlotStamps* stream_pool_stamps(prego_stream_pool* p) { return &p->stamps; }
+PoolBlock stream_pool_block(const prego_stream_pool* p) { return PoolBlock{(const char*)p->g.h, p->bytes}; }
 
 namespace {
 struct PoolLayout { size_t h_bytes, rec_words, total; };

@@ -15,6 +15,9 @@ struct prego_vit_stream_pool {
   SlotStamps stamps;
 };
 const PoolGeom* vit_stream_pool_geom(const prego_vit_stream_pool* p) { return &p->g; }      // pool_slot_check.h
+SlotStamps* vit_stream_pool_stamps(prego_vit_stream_pool* p) { return &p->stamps; }
+PoolBlock vit_stream_pool_block(const prego_vit_stream_pool* p) { return PoolBlock{(const char*)p->r.ring, p->bytes}; }
+const VitRing* vit_stream_pool_ring(const prego_vit_stream_pool* p) { return &p->r; }
 
 namespace {
 // block: ring [capacity][window][E] fp32 | ring words [capacity][4] int32 | records [capacity][rec_words] int32, each part 256-byte aligned

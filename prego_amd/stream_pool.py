@@ -4,7 +4,9 @@ step's bits (prego_miniroad_step_pool: gather, the unchanged prego_miniroad_step
 returns what `aggregate` would return for the stream's per-frame predictions ('pred', 'changes_pred'); no argmax crosses to the host on
 the way.  `SlotTable` is the host bookkeeping (which slots are open), usable without a device.  `EventFeed` (`pool.event_feed()`,
 csrc/stream_feed.hip) tells a live consumer which slots gained an event since it last asked, in one asynchronous report per tick;
-`FeedModel` is its host model."""
+`FeedModel` is its host model.  `pool.snapshot` / `restore` / `detach` (csrc/stream_image.hip) take live slots out of a pool as a
+`PoolSnapshot` of canonical images and put them into a pool again - another pool, other slot numbers, another device or process -,
+validated on the device before a slot is written; `image_fault`, `image_layout` and `model_image` are their host model."""
 from __future__ import annotations
 
 import ctypes as C
@@ -100,7 +102,7 @@ class SlotTable:
 class _RecordPool:
     """What the two pools share: the slot bookkeeping and the reading of a slot's vote record (csrc/stream_pool.hip).  A subclass sets
     lib, device, p, slots (SlotTable), _block, _vote_window, max_events, _ncls, _ncls_pad and names its C entry points in `_C`."""
-    _C = {}                      # 'destroy', 'flush', 'reset', 'record', 'feed_create' -> symbol
+    _C = {}                      # 'destroy', 'flush', 'reset', 'record', 'feed_create', 'image_bytes', 'snapshot', 'restore' -> symbol
     _feeds = ()                  # the event feeds attached (a WeakSet once there is one): close() has them forget the slot
 
     def __del__(self):
@@ -179,6 +181,129 @@ class _RecordPool:
         whatever push variant produced it, in one asynchronous copy of at most `max_out` entries; `depth` reports may be in flight."""
         return EventFeed(self, max_out, depth)
 
+    # -- slot images: a live slot as data (csrc/stream_image.hip) ----------------------------------
+    def image_geometry(self) -> dict:
+        """what an image of this pool's slots must match to be restored here (csrc/pool_image.h: tag words 2..7), as plain ints"""
+        kind, dim, window_size, _ = self._image_desc()
+        return {"kind": kind, "dim": dim, "window_size": window_size, "n_classes": self._ncls, "vote_window": self._vote_window,
+                "max_events": self.max_events}
+
+    def _image_bytes(self) -> int:
+        nb = getattr(self.lib, self._C["image_bytes"])(self.p)
+        if nb == 0:
+            raise PregoError("stream pool: a slot of this pool is too large for an image")
+        return nb
+
+    def _open_slots(self, slots, who: str) -> list:
+        """any number of open slots, each named once (a C call takes at most 256 of them: the callers go in groups)"""
+        slots = [int(s) for s in slots]
+        for a in range(0, len(slots), MAX_ACTIVE):
+            self.slots.check(slots[a:a + MAX_ACTIVE], who)
+        if len(set(slots)) != len(slots):
+            raise PregoError(f"stream pool {who}: a slot is named twice")
+        return slots
+
+    def _own_feed(self, feed, who: str):
+        if feed is not None and getattr(feed, "pool", None) is not self:
+            raise PregoError(f"stream pool {who}: the feed belongs to another pool")
+        return feed.f if feed is not None else None
+
+    def snapshot(self, slots=None, feed=None) -> "PoolSnapshot":
+        """The open slots named (default: all of them, ascending) as a `PoolSnapshot`: one canonical image per slot - state or ring,
+        vote record with the unfinished window's counters, and with `feed=` the slot's position in that feed - in one device tensor.
+        The pool is only read; nothing waits.  An image is only meaningful for the weights that made it."""
+        slots = sorted(self.slots._open) if slots is None else self._open_slots(slots, "snapshot")
+        f = self._own_feed(feed, "snapshot")
+        _, _, _, dtype = self._image_desc()
+        nb = self._image_bytes()
+        images = torch.empty((len(slots), nb), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            for a in range(0, len(slots), MAX_ACTIVE):
+                grp = slots[a:a + MAX_ACTIVE]
+                self._check(getattr(self.lib, self._C["snapshot"])(self.p, f, len(grp), self._slot_array(grp), C.c_void_p(images[a].data_ptr()),
+                                                                   len(grp) * nb, C.c_void_p(self._stream_ptr(self.device))))
+        return PoolSnapshot(images, self.image_geometry(), dtype)
+
+    def restore(self, snap, feed=None, slots=None) -> list:
+        """Puts the streams of `snap` into this pool and returns their slots, image i in slots[i]: `snap.n` slots opened here, lowest
+        free first, or `slots` the caller opened and has not pushed to.  With `feed=` every stream goes on in that feed where the
+        snapshot's feed stood; every other feed attached to the pool forgets the slots, as `close` has it.  Refused before anything is
+        launched: a snapshot of the other pool kind, of another geometry or compute_dtype, too few free slots.  Every image is checked
+        on the device before its slot is written (csrc/pool_image.h); if one is refused, the slots opened here are emptied and freed and
+        PregoError names image and clause.  One small D2H copy; it waits."""
+        if not isinstance(snap, PoolSnapshot):
+            raise PregoError(f"stream pool restore: expected a PoolSnapshot, got {type(snap).__name__}")
+        f = self._own_feed(feed, "restore")
+        geom, (_, _, _, dtype) = self.image_geometry(), self._image_desc()
+        if snap.geometry.get("kind") != geom["kind"]:
+            raise PregoError(f"stream pool restore: the snapshot is of pool kind {snap.geometry.get('kind')} (1 GRU, 2 Transformer), this pool "
+                             f"is kind {geom['kind']}")
+        if snap.geometry != geom:
+            raise PregoError(f"stream pool restore: the snapshot's geometry {snap.geometry} is not this pool's {geom}")
+        if snap.compute_dtype != dtype:
+            raise PregoError(f"stream pool restore: the snapshot was taken under compute_dtype {snap.compute_dtype!r}, this pool runs {dtype!r}")
+        nb, n = self._image_bytes(), snap.n
+        if snap.images.dtype != torch.uint8 or snap.images.dim() != 2 or snap.images.shape[1] != nb:
+            raise PregoError(f"stream pool restore: expected images as uint8 [n, {nb}], got {tuple(snap.images.shape)} {snap.images.dtype}")
+        opened = slots is None
+        if opened:
+            if self.free < n:
+                raise PregoError(f"stream pool restore: {n} streams, {self.free} free slots")
+        else:
+            slots = self._open_slots(slots, "restore")
+            if len(slots) != n:
+                raise PregoError(f"stream pool restore: {n} images, {len(slots)} slots")
+        if n == 0:
+            return []
+        images = snap.images.to(self.device).contiguous()
+        if images.data_ptr() % 256:
+            images = images.clone()
+        if opened:
+            slots = [self.slots.open() for _ in range(n)]
+        status = torch.empty((n,), dtype=torch.int32, device=self.device)
+        s = C.c_void_p(self._stream_ptr(self.device))
+        try:
+            with torch.cuda.device(self.device):
+                for a in range(0, n, MAX_ACTIVE):
+                    grp = slots[a:a + MAX_ACTIVE]
+                    self._check(getattr(self.lib, self._C["restore"])(self.p, f, len(grp), self._slot_array(grp), C.c_void_p(images[a].data_ptr()),
+                                                                      len(grp) * nb, C.c_void_p(status[a:].data_ptr()), s))
+                for other in self._feeds:                        # as close(): a feed that was not named starts the slots at index 0
+                    if other is not feed:
+                        for a in range(0, n, MAX_ACTIVE):
+                            other.forget(slots[a:a + MAX_ACTIVE])
+                faults = status.cpu().tolist()
+        except Exception:
+            if opened:
+                self._drop(slots)
+            raise
+        bad = [(i, v) for i, v in enumerate(faults) if v]
+        if bad:
+            if opened:
+                self._drop(slots)
+            raise PregoError("stream pool restore: " + "; ".join(f"image {i} refused ({', '.join(image_fault_names(v))})" for i, v in bad[:8]) +
+                             (f" and {len(bad) - 8} more" if len(bad) > 8 else ""))
+        return slots
+
+    def _drop(self, slots):
+        """empties the slots, has every feed forget them and frees them: no flush, nothing read"""
+        with torch.cuda.device(self.device):
+            for a in range(0, len(slots), MAX_ACTIVE):
+                grp = slots[a:a + MAX_ACTIVE]
+                self._check(getattr(self.lib, self._C["reset"])(self.p, len(grp), self._slot_array(grp), C.c_void_p(self._stream_ptr(self.device))))
+                for feed in self._feeds:
+                    feed.forget(grp)
+        for slot in slots:
+            self.slots.release(slot)
+
+    def detach(self, slots, feed=None) -> "PoolSnapshot":
+        """`snapshot(slots, feed)`, then the slots are emptied and freed and every feed forgets them.  Nothing is flushed: the unfinished
+        window travels in the image.  Nothing waits."""
+        slots = self._open_slots(slots, "detach")
+        snap = self.snapshot(slots, feed)
+        self._drop(slots)
+        return snap
+
 
 FEED_COUNT_MASK, FEED_REP_SHIFT = (1 << 30) - 1, 30          # a feed's cursor word (csrc/stream_feed.hip)
 
@@ -223,6 +348,143 @@ class FeedModel:
     def cursor(self, slot: int) -> int:
         """the slot's cursor word as the device keeps it"""
         return self.delivered[slot] | self.reported[slot] << FEED_REP_SHIFT
+
+    cursor_word = cursor                                         # the word a slot image carries in its tag
+
+    def seek(self, slot: int, cursor_word: int):
+        """the slot's cursor set from a cursor word: what `restore(snap, feed=...)` does with the word in an image's tag"""
+        word = int(cursor_word) & 0xFFFFFFFF
+        self.delivered[slot], self.reported[slot] = word & FEED_COUNT_MASK, word >> FEED_REP_SHIFT
+
+
+# ---- slot images: the host model (csrc/pool_image.h) ---------------------------------------------------------------------------
+IMAGE_MAGIC, IMAGE_VERSION, IMAGE_TAG_WORDS = 0x474D4950, 1, 16
+IMAGE_GRU, IMAGE_VIT = 1, 2
+TAG_FRAMES, TAG_HEAD, TAG_FILL, TAG_CURSOR = 8, 9, 10, 11
+IMAGE_FAULTS = {1: "geometry", 2: "frames", 4: "n_events", 8: "last vote", 16: "overflow word", 32: "counter", 64: "ring head / fill",
+                128: "feed cursor"}
+FAULT_GEOMETRY, FAULT_FRAMES, FAULT_EVENTS, FAULT_VOTE, FAULT_OVERFLOW, FAULT_COUNTER, FAULT_RING, FAULT_CURSOR = IMAGE_FAULTS
+
+
+def image_fault_names(fault: int) -> list:
+    """the clauses a status word of `restore` names"""
+    return [name for bit, name in IMAGE_FAULTS.items() if fault & bit]
+
+
+def image_layout(geometry: dict) -> dict:
+    """word counts of a slot image of this geometry: {'state_words', 'rec_words', 'image_words', 'ncls_pad'}; the tag is words
+    [0, 16), the state [16, 16 + state_words), the record the rec_words behind it, zeros up to image_words (a multiple of 64)"""
+    g = geometry
+    pad = (g["n_classes"] + 3) // 4 * 4
+    rec = (REC_HEADER + pad + 2 * g["max_events"] + 3) // 4 * 4
+    state = g["window_size"] * g["dim"] if g["kind"] == IMAGE_VIT else g["dim"]
+    return {"state_words": state, "rec_words": rec, "image_words": (IMAGE_TAG_WORDS + state + rec + 63) // 64 * 64, "ncls_pad": pad}
+
+
+def image_geometry_words(geometry: dict) -> list:
+    """tag words 0..7 of every image a pool of this geometry writes and accepts"""
+    g = geometry
+    return [IMAGE_MAGIC, IMAGE_VERSION, g["kind"], g["dim"], g["window_size"] if g["kind"] == IMAGE_VIT else 0, g["n_classes"],
+            g["vote_window"], g["max_events"]]
+
+
+def image_fault(words, geometry: dict) -> int:
+    """The validity rule of `restore` (csrc/pool_image.h: pool_image_fault) on an image's int32 words: 0 = a pool of `geometry` restores
+    it, else the clause bits the device writes into `status` (IMAGE_FAULTS)."""
+    lay, g = image_layout(geometry), geometry
+    r0 = IMAGE_TAG_WORDS + lay["state_words"]
+    tag = [int(v) for v in words[:IMAGE_TAG_WORDS]]
+    rec = [int(v) for v in words[r0:r0 + REC_HEADER + lay["ncls_pad"]]]
+    f = 0
+    if tag[:8] != image_geometry_words(g):
+        f |= FAULT_GEOMETRY
+    frames, n_events = tag[TAG_FRAMES], rec[2]
+    if frames < 0 or rec[0] != frames:
+        f |= FAULT_FRAMES
+    if not 0 <= n_events <= g["max_events"]:
+        f |= FAULT_EVENTS
+    if not 0 <= rec[1] <= g["n_classes"]:
+        f |= FAULT_VOTE
+    if not 0 <= rec[3] <= 3:
+        f |= FAULT_OVERFLOW
+    if any(not 0 <= c <= g["vote_window"] for c in rec[REC_HEADER:]):
+        f |= FAULT_COUNTER
+    if g["kind"] == IMAGE_VIT and frames >= 0:
+        T = g["window_size"]
+        if tag[TAG_HEAD] != frames % T or tag[TAG_FILL] != min(frames, T):
+            f |= FAULT_RING
+    if (tag[TAG_CURSOR] & 0xFFFFFFFF) & FEED_COUNT_MASK > max(n_events, 0):
+        f |= FAULT_CURSOR
+    return f
+
+
+def model_image(geometry: dict, record, state=None, cursor_word: int = 0) -> list:
+    """The int32 words of the image `snapshot` writes for a slot whose record is `record` (an OnlineRecord): the tag, `state` (the
+    state_words 32-bit patterns as ints; default zeros - for the Transformer pool the rows [0, fill) are the caller's to fill, the rest
+    must stay zero), `record.to_words`, zeros.  head and fill follow from the record's frames."""
+    lay, g = image_layout(geometry), geometry
+    frames = record.frames
+    T = g["window_size"] if g["kind"] == IMAGE_VIT else 0
+    cur = int(cursor_word) & 0xFFFFFFFF
+    tag = image_geometry_words(g) + [frames, frames % T if T else 0, min(frames, T) if T else 0, cur - (1 << 32) if cur >> 31 else cur, 0, 0, 0, 0]
+    state = [0] * lay["state_words"] if state is None else [int(v) for v in state]
+    if len(state) != lay["state_words"]:
+        raise ValueError(f"model_image: {len(state)} state words, the geometry has {lay['state_words']}")
+    w = tag + state + record.to_words(g["n_classes"], g["max_events"])
+    return w + [0] * (lay["image_words"] - len(w))
+
+
+class PoolSnapshot:
+    """Slots of a stream pool as data (`pool.snapshot` / `pool.detach`): `images` uint8 [n, image_bytes], one canonical image per slot
+    (csrc/pool_image.h), `geometry` - the plain dict `pool.image_geometry()` gave -, `compute_dtype` and `n`.  It lives where `images`
+    lives: `.cpu()` / `.to(device)` move it, `.save(path)` / `PoolSnapshot.load(path)` put it through a file (`torch.save` of a plain
+    dict, loadable with weights_only=True).  An image is only meaningful for the weights that made it: `restore` checks geometry and
+    compute_dtype, the weights are the caller's business."""
+    FORMAT = "prego_amd.PoolSnapshot/1"
+
+    def __init__(self, images, geometry: dict, compute_dtype: str):
+        if images.dtype != torch.uint8 or images.dim() != 2:
+            raise PregoError(f"PoolSnapshot: expected images as uint8 [n, image_bytes], got {tuple(images.shape)} {images.dtype}")
+        self.images, self.geometry, self.compute_dtype = images, {k: int(v) for k, v in geometry.items()}, str(compute_dtype)
+        if images.shape[1] != 4 * image_layout(self.geometry)["image_words"]:
+            raise PregoError(f"PoolSnapshot: images of {images.shape[1]} bytes, the geometry {self.geometry} has "
+                             f"{4 * image_layout(self.geometry)['image_words']}")
+
+    @property
+    def n(self) -> int:
+        return int(self.images.shape[0])
+
+    @property
+    def device(self):
+        return self.images.device
+
+    def to(self, device) -> "PoolSnapshot":
+        return PoolSnapshot(self.images.to(device), self.geometry, self.compute_dtype)
+
+    def cpu(self) -> "PoolSnapshot":
+        return self.to("cpu")
+
+    def words(self):
+        """the images as int32 [n, image_words] (a view)"""
+        return self.images.view(torch.int32)
+
+    def frames(self) -> list:
+        """frames each stream has taken, from the tags; it waits for the device"""
+        return self.words()[:, TAG_FRAMES].tolist()
+
+    def save(self, path):
+        torch.save({"format": self.FORMAT, "images": self.images.cpu().contiguous(), "geometry": dict(self.geometry),
+                    "compute_dtype": self.compute_dtype, "n": self.n}, path)
+
+    @classmethod
+    def load(cls, path) -> "PoolSnapshot":
+        d = torch.load(path, map_location="cpu", weights_only=True)
+        if not isinstance(d, dict) or d.get("format") != cls.FORMAT:
+            raise PregoError(f"PoolSnapshot.load: {path} is not a saved PoolSnapshot ({cls.FORMAT})")
+        snap = cls(d["images"], d["geometry"], d["compute_dtype"])
+        if snap.n != d["n"]:
+            raise PregoError(f"PoolSnapshot.load: {path} says n = {d['n']}, its images hold {snap.n}")
+        return snap
 
 
 class FeedTicket:
@@ -348,7 +610,11 @@ class StreamPool(_RecordPool):
     and `close` serve every engine (ids from the Transformer path or a general forward); live Transformer streams have a pool of their
     own, `TransformerStreamPool` below (`ViTEnc.stream_pool`)."""
     _C = {"destroy": "prego_stream_pool_destroy", "flush": "prego_stream_pool_flush", "reset": "prego_stream_pool_reset",
-          "record": "prego_stream_pool_record", "feed_create": "prego_stream_pool_feed_create"}
+          "record": "prego_stream_pool_record", "feed_create": "prego_stream_pool_feed_create",
+          "image_bytes": "prego_stream_pool_image_bytes", "snapshot": "prego_stream_pool_snapshot", "restore": "prego_stream_pool_restore"}
+
+    def _image_desc(self):
+        return IMAGE_GRU, self._hid, 0, self.engine.compute_dtype
 
     def __init__(self, model_or_engine, capacity: int = 256, window: int = 200, max_events: int = 1024):
         from .engine import _stream_ptr
@@ -607,7 +873,12 @@ class TransformerStreamPool(_RecordPool):
     `push_bursts` gives every slot named a frame count of its own (1..min(32, window_size), at most 256 frames per call) and returns one
     window per frame: a backlog costs one encoding GEMM and one encoder batch, not one call per frame (prego_vit_step_pool_bursts)."""
     _C = {"destroy": "prego_vit_stream_pool_destroy", "flush": "prego_vit_stream_pool_flush", "reset": "prego_vit_stream_pool_reset",
-          "record": "prego_vit_stream_pool_record", "feed_create": "prego_vit_stream_pool_feed_create"}
+          "record": "prego_vit_stream_pool_record", "feed_create": "prego_vit_stream_pool_feed_create",
+          "image_bytes": "prego_vit_stream_pool_image_bytes", "snapshot": "prego_vit_stream_pool_snapshot",
+          "restore": "prego_vit_stream_pool_restore"}
+
+    def _image_desc(self):
+        return IMAGE_VIT, self._E, self._T, self.model.compute_dtype
 
     def __init__(self, vit, capacity: int = 256, vote_window: int = 200, max_events: int = 1024):
         from .engine import _stream_ptr

@@ -57,6 +57,14 @@ record copy each - and (c) push alone.  `a_minus_c_us` / `b_minus_c_us`: what le
 emptied (outside the timed part) before a leg's round, so no record fills.
 
     python scripts/anticipation_bench.py --step --pool --feed [--steps 200] [--warmup 20] [--rounds 4] [--streams 4,256] [--models L0,L8]
+
+--step --pool --snapshot: slot images (StreamPool.snapshot / restore, csrc/stream_image.hip), n = 4 / 16 / 64 / 256 scattered slots of a
+256-slot pool that hold streams of 50 frames, the same protocol with a device-event pair per CALL: (s) snapshot of the n slots, (r) restore
+of them into a second pool (the method, status copy included), (rc) the C restore alone, (t) the read route there was before - state(slot)
+plus the record copy, per slot.  `floor_us`: the image bytes read and written once at the achievable HBM rate (scripts/pool_snapshot_legs.py).
+
+    python scripts/anticipation_bench.py --step --pool --snapshot [--steps 100] [--warmup 20] [--rounds 4] [--streams 4,16,64,256]
+                                         [--out profiles/stream_pool/snapshot_bench.json]
 """
 from __future__ import annotations
 
@@ -95,6 +103,8 @@ def main():
     ap.add_argument("--frames", action="store_true", help="with --step --pool: one push_frames of K frames against K push calls")
     ap.add_argument("--ragged", action="store_true", help="with --step --pool: one push_ragged against one push_frames per group of equal count")
     ap.add_argument("--feed", action="store_true", help="with --step --pool: push + EventFeed.drain against push + events(slot) per active slot")
+    ap.add_argument("--snapshot", action="store_true", help="with --step --pool: snapshot / restore of n slots against state(slot) + record copy per slot")
+    ap.add_argument("--out", default=None, help="with --snapshot: where the JSON line goes as well (default profiles/stream_pool/snapshot_bench.json)")
     ap.add_argument("--vote-window", type=int, default=1, help="with --feed: the pool's vote window, small so that events occur on most ticks")
     ap.add_argument("--streams", default=None, help="default: 17,32,64,128,256 (--wide), 4,16,64,256 (--pool)")
     ap.add_argument("--models", default=None, help="L0 = MiniROAD, Lk = MiniROADA with anticipation_length k; default: L0,L1,L8 (--wide), L0,L8 (--pool)")
@@ -113,6 +123,8 @@ def main():
             return step_pool_ragged_bench(a)
         if a.pool and a.feed:
             return step_pool_feed_bench(a)
+        if a.pool and a.snapshot:
+            return step_pool_snapshot_bench(a)
         return step_pool_bench(a) if a.pool else step_wide_bench(a) if a.wide else step_bench(a)
     dev = "cuda:0"
     lens = workloads.assembly101_eval_lengths()
@@ -530,6 +542,46 @@ def step_pool_feed_bench(a):
                                 "256-slot pool, 1024 events per record): a = push + EventFeed.drain + reading the previous tick's ticket, b = push + "
                                 "events(slot) for every active slot, c = push alone; round_us = a whole round between two events / its ticks",
                       "dtype": a.dtype, "vote_window": a.vote_window, "frames_per_path_and_round": frames, "rounds": a.rounds, "table": table}))
+
+
+def step_pool_snapshot_bench(a):
+    import random
+
+    from pool_snapshot_legs import snapshot_legs
+    dev, cap = "cuda:0", 256
+    calls = max(a.steps, 100)
+    base = assembly101_cfg(compute_dtype=a.dtype, assume_zero_flow=True)
+    m = build_model(base, dev)
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in W.miniroad_state_dict(base, 20, head_gain=8.0).items()})
+    m.eval()
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1234)
+    x = torch.randn((16, 256, 2048), device=dev, generator=gen).clamp_(min=0)
+    table = {}
+    for n in (int(s) for s in a.streams.split(",")):
+        pool_a, pool_b = m.stream_pool(capacity=cap, window=7), m.stream_pool(capacity=cap, window=7)
+        for _ in range(cap):
+            pool_a.open()
+            pool_b.open()
+        slots_a, slots_b = random.Random(n).sample(range(cap), n), random.Random(n + 1).sample(range(cap), n)
+        for i in range(50):                                           # streams of 50 frames: a state row and a few events per slot
+            pool_a.push(slots_a, x[i & 15, :n].contiguous(), None, want_ant=False)
+        t = snapshot_legs(pool_a, pool_b, slots_a, slots_b, lambda p, s: p.state(s), calls, a.warmup, a.rounds)
+        m.engine().check()
+        table[f"n{n}"] = t
+        print(json.dumps({f"n{n}": t}), file=sys.stderr, flush=True)
+        del pool_a, pool_b
+    line = json.dumps({"metric": "device time per call, us (median of device-event pairs around every call; n scattered slots of a 256-slot "
+                                 "MiniROAD pool, 1024 events per record): s = StreamPool.snapshot, r = StreamPool.restore into a second pool "
+                                 "(status copy included), rc = prego_stream_pool_restore alone, t = state(slot) + record copy per slot; "
+                                 "floor_us = n images read and written once at 6.3 TB/s",
+                       "device": torch.cuda.get_device_name(0), "dtype": a.dtype, "calls_per_path_and_round": calls, "rounds": a.rounds,
+                       "warmup_calls": a.warmup, "table": table})
+    print(line)
+    out_path = a.out or os.path.join("profiles", "stream_pool", "snapshot_bench.json")
+    os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write(line + "\n")
 
 
 def step_pool_frames_bench(a):

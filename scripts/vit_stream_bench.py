@@ -16,7 +16,14 @@ object in --out.
 --bursts KxR: a backlog of K frames on each of R / K scattered slots, R windows in all.
 (b) `push_bursts`: one call - one encoding GEMM at M = R, one encoder batch of R windows.
 (k) K `push` calls that deliver the same frames to the same slots - K encoding GEMMs at M = R / K, K launch chains, K encoder batches.
-The same protocol; a tick is the whole backlog (one call of (b), K calls of (k))."""
+The same protocol; a tick is the whole backlog (one call of (b), K calls of (k)).
+
+--snapshot: slot images of n = 4 / 16 / 64 scattered slots whose rings are full, a device-event pair per CALL:
+(s) `snapshot` of the n slots, (r) `restore` of them into a second pool (status copy included), (rc) the C restore alone, (t) the read
+route there was before - `window(slot)` plus the record copy, per slot.  `floor_us`: the image bytes read and written once at the
+achievable HBM rate (scripts/pool_snapshot_legs.py).
+
+    python scripts/vit_stream_bench.py --snapshot [--streams 4,16,64] [--dtypes fp16] [--out profiles/vit_stream_pool/snapshot_bench.json]"""
 import argparse
 import json
 import os
@@ -110,9 +117,51 @@ def bursts_main(a):
         f.write(line + "\n")
 
 
+def snapshot_main(a):
+    from pool_snapshot_legs import snapshot_legs
+    dev, cap, T = "cuda:0", 256, a.window
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1234)
+    x = torch.randn((16, 64, 2, 2048), device=dev, generator=gen).clamp_(min=0)
+    table = {}
+    for dtype in a.dtypes.split(","):
+        cfg = assembly101_cfg(model="Transformer", window_size=T, patch_dim=1, num_heads=8, attn_dropout_rate=0.0, dropout=0.0,
+                              num_layers=a.layers, compute_dtype=dtype)
+        m = build_model(cfg, dev)
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in W.vit_state_dict(cfg, 20).items()})
+        m.eval()
+        for n in (int(s) for s in a.streams.split(",")):
+            assert n <= 64
+            pool_a, pool_b = m.stream_pool(capacity=cap), m.stream_pool(capacity=cap)
+            for _ in range(cap):
+                pool_a.open()
+                pool_b.open()
+            slots_a, slots_b = random.Random(n).sample(range(cap), n), random.Random(n + 1).sample(range(cap), n)
+            for i in range(T + 5):                                    # every ring full and wrapped
+                pool_a.push(slots_a, x[i & 15, :n, 0].contiguous(), x[i & 15, :n, 1].contiguous())
+            t = snapshot_legs(pool_a, pool_b, slots_a, slots_b, lambda p, s: p.window(s), a.ticks, a.warmup, a.rounds)
+            table[f"{dtype}_n{n}"] = t
+            print(json.dumps({f"{dtype}_n{n}": t}), file=sys.stderr, flush=True)
+            del pool_a, pool_b
+        del m
+    res = {"metric": "device time per call, us (median of device-event pairs around every call; n scattered slots of a 256-slot pool, rings "
+                     "full): s = TransformerStreamPool.snapshot, r = restore into a second pool (status copy included), rc = "
+                     "prego_vit_stream_pool_restore alone, t = window(slot) + record copy per slot; floor_us = n images read and written "
+                     "once at 6.3 TB/s",
+           "device": torch.cuda.get_device_name(0), "window": T, "layers": a.layers, "calls_per_path_and_round": a.ticks, "rounds": a.rounds,
+           "warmup_calls": a.warmup, "table": table}
+    line = json.dumps(res)
+    print(line)
+    out_path = a.out or os.path.join("profiles", "vit_stream_pool", "snapshot_bench.json")
+    os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--streams", default="4,16,64,256")
+    ap.add_argument("--snapshot", action="store_true", help="snapshot / restore of n slots against window(slot) + record copy per slot")
+    ap.add_argument("--streams", default=None, help="default: 4,16,64,256; with --snapshot 4,16,64")
     ap.add_argument("--dtypes", default="bf16,fp16")
     ap.add_argument("--window", type=int, default=128)
     ap.add_argument("--layers", type=int, default=1)
@@ -122,6 +171,9 @@ def main():
     ap.add_argument("--bursts", default="", help="KxR cells, e.g. 4x64,8x64,4x256,8x256: push_bursts against K push calls instead of the push cells")
     ap.add_argument("--out", default=None, help="default: profiles/vit_stream_pool/push_bench.json, with --bursts bursts_bench.json")
     a = ap.parse_args()
+    a.streams = a.streams or ("4,16,64" if a.snapshot else "4,16,64,256")
+    if a.snapshot:
+        return snapshot_main(a)
     if a.bursts:
         return bursts_main(a)
     a.out = a.out or os.path.join("profiles", "vit_stream_pool", "push_bench.json")
