@@ -475,6 +475,25 @@ int prego_perframe_ap(const float* scores, const float* target, int64_t n_frames
  * frame without a positive): what a one-hot target matrix says, in 4 bytes per frame instead of 4 x n_classes.  Same results, bit for bit. */
 int prego_perframe_ap_labels(const float* scores, const int32_t* labels, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
                              double* score_sum, void* workspace, size_t workspace_bytes, prego_stream_t stream);
+/* utils/metrics.py:64-130 on the device with metrics='AP': average precision by tenth of each action (how early inside a step it is
+ * recognised).  scores: device fp32 [n_frames][n_classes]; labels: device int32 [n_frames], one class id per frame in evaluation
+ * order (an id outside [0, n_classes) = a frame that is a negative of every class).  Per class c the instances are the maximal runs
+ * of labels == c over the whole axis (videos concatenated: a run is not cut at a video boundary); a run with first frame a and last
+ * frame b has len = b - a and its stage s = 0..9 holds the frames [lo, hi), lo = a + trunc(len * (s / 10.0)),
+ * hi = max(lo + 1, a + trunc(len * ((s + 1) / 10.0))) - IEEE double products, as the reference's int(len * perc) (len 90, s 7: offset
+ * 62); a one-frame run is in all ten stages, the last frame of a longer run in none.  ap[s][c] is sklearn's average_precision_score
+ * over the frames with labels != c (negatives) plus the stage-s frames of every run of c (positives): thresholds at the distinct
+ * score values, ties share one, -0.0 == +0.0.  ap: device double [10][n_classes], 0.0 for a class without a run (what the reference
+ * reports and averages); n_pos (nullable): device int64 [10][n_classes], the positives of each set.  Every class is computed; the
+ * caller applies the "ignore class 0" rule.  Exact integer ranks, one fp64 sum per (stage, class) in a fixed order: the same bits on
+ * every run; nothing returns to the host between the launches and nothing is allocated.  Workspace:
+ * prego_perstage_ap_workspace_bytes (that of prego_perframe_ap + 40 B per frame, whatever the run lengths).  n_frames == 0: returns
+ * 0 and writes 0.0 / 0.  PREGO_EINVAL, checked before any launch (outputs and workspace untouched): a NULL scores, labels or ap, a
+ * NULL workspace with n_frames > 0, n_frames < 0 or >= 2^31, n_classes < 1 or > 65535; PREGO_EWORKSPACE: workspace_bytes below the
+ * query.  An addition to ABI 7 (existing signatures unchanged).  Dense multi-label targets: the host path (prego_amd/metrics.py). */
+size_t prego_perstage_ap_workspace_bytes(int64_t n_frames, int n_classes);
+int prego_perstage_ap_labels(const float* scores, const int32_t* labels, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
+                             void* workspace, size_t workspace_bytes, prego_stream_t stream);
 /* HOST function (no device work): the reference's loader yields fp32 target rows [n_frames][n_classes] per video (one-hot for both
  * shipped configs).  targets: n_videos host pointers, n_frames: their row counts; labels: host int32 [sum of n_frames], the videos one
  * after the other, labels[i] = np.argmax(row i) (eval.py:55, the first maximum); onehot[v] = 1 iff every row of video v holds exactly one

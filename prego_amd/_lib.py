@@ -56,6 +56,7 @@ SYMBOLS = [
     "prego_vit_stream_pool_feed_create", "prego_stream_pool_feed_destroy", "prego_stream_pool_feed_drain", "prego_stream_pool_feed_forget",
     "prego_stream_pool_image_bytes", "prego_stream_pool_snapshot", "prego_stream_pool_restore",
     "prego_vit_stream_pool_image_bytes", "prego_vit_stream_pool_snapshot", "prego_vit_stream_pool_restore",
+    "prego_perstage_ap_workspace_bytes", "prego_perstage_ap_labels",
 ]
 # include/prego_amd_debug.h: only in libprego_amd_debug.so
 DEBUG_SYMBOLS = ["prego_miniroad_debug_stamps", "prego_debug_gemm_bf16", "prego_debug_attention_bwd", "prego_debug_attention_fwd",
@@ -165,6 +166,9 @@ def _open(path: str, debug: bool) -> C.CDLL:
     lib.prego_perframe_ap_workspace_bytes.restype = sz
     lib.prego_perframe_ap.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, sz, vp]
     lib.prego_perframe_ap_labels.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, sz, vp]
+    lib.prego_perstage_ap_workspace_bytes.argtypes = [i64, i32]
+    lib.prego_perstage_ap_workspace_bytes.restype = sz
+    lib.prego_perstage_ap_labels.argtypes = [vp, vp, i64, i32, vp, vp, vp, sz, vp]
     lib.prego_onehot_labels.argtypes = [i32, C.POINTER(vp), C.POINTER(i64), i32, vp, C.POINTER(C.c_int32)]
     f32 = C.c_float
     lib.prego_adamw_step.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), i64, f32, f32, f32, f32, f32, vp]

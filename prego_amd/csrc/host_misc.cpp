@@ -71,7 +71,26 @@ extern "C" int prego_perframe_ap_labels(const float* scores, const int32_t* labe
   return perframe_ap_common(scores, nullptr, labels, n_frames, n_classes, ap, n_pos, score_sum, workspace, workspace_bytes, stream);
 }
 
-// The feeder's side of that: one-hot target rows (what the reference's dataset yields, dataset.py / eval.py:55 np.argmax(target)) reduced
+// utils/metrics.py:64-130 (the same metric by tenth of each action instance) on the device; ap / n_pos [10][n_classes]
+extern "C" size_t prego_perstage_ap_workspace_bytes(int64_t n_frames, int n_classes) {
+  if (n_frames <= 0 || n_classes <= 0) return 0;
+  return perstage_ap_workspace_bytes(n_frames, n_classes);
+}
+extern "C" int prego_perstage_ap_labels(const float* scores, const int32_t* labels, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
+                                        void* workspace, size_t workspace_bytes, prego_stream_t stream) {
+  if (!scores || !labels || !ap || (!workspace && n_frames > 0)) return prego_fail_(PREGO_EINVAL, "perstage_ap: NULL argument");
+  if (n_frames < 0 || n_frames >= (1ll << 31) || n_classes < 1 || n_classes > 65535)
+    return prego_fail_(PREGO_EINVAL, "perstage_ap: n_frames %lld (0 .. 2^31 - 1), n_classes %d (1 .. 65535)", (long long)n_frames, n_classes);
+  if (n_frames > 0 && workspace_bytes < perstage_ap_workspace_bytes(n_frames, n_classes))
+    return prego_fail_(PREGO_EWORKSPACE, "perstage_ap: workspace %zu < %zu (prego_perstage_ap_workspace_bytes)", workspace_bytes,
+                       perstage_ap_workspace_bytes(n_frames, n_classes));
+  if (launch_perstage_ap(scores, (const int*)labels, n_frames, n_classes, ap, (long long*)n_pos, workspace, (hipStream_t)stream))
+    return prego_fail_(PREGO_EINVAL, "perstage_ap: bad arguments");
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+// The feeder's side of the class-id entries: one-hot target rows (what the reference's dataset yields, dataset.py / eval.py:55 np.argmax(target)) reduced
 // to their class id on the host, in the loader's own memory, by a few threads - while the GPU is busy with the features.  HOST function.
 extern "C" int prego_onehot_labels(int n_videos, const float* const* targets, const int64_t* n_frames, int n_classes, int32_t* labels,
                                    int32_t* onehot) {

@@ -284,6 +284,10 @@ int launch_format_ids(const int* ids, long long n, unsigned* text, int* bad, hip
 size_t perframe_ap_workspace_bytes(long long n_frames, int n_classes);
 int launch_perframe_ap(const float* scores, const float* target, const int* labels, long long n_frames, int n_classes, double* ap, long long* n_pos,
                        double* score_sum, void* workspace, hipStream_t s);
+// per-stage average precision (metrics.hip): the per-frame ranks + one counter per (stage, positive); ap / n_pos [10][n_classes]
+size_t perstage_ap_workspace_bytes(long long n_frames, int n_classes);
+int launch_perstage_ap(const float* scores, const int* labels, long long n_frames, int n_classes, double* ap, long long* n_pos, void* workspace,
+                       hipStream_t s);
 
 // Evaluate's feature cache (feature_cache.hip): n fp32 values -> bf16 / fp16 (f16) with the pack kernels' conversion; n % 8 == 0, n > 0
 void launch_cast_features(bool f16, const float* src, void* dst, long long n, int n_cu, hipStream_t s);

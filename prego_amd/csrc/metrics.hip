@@ -427,11 +427,17 @@ size_t perframe_ap_workspace_bytes(long long n, int C) {
   return 4 * (size_t)C * (size_t)n * 4 + (size_t)C * AP_RADIX * ntiles * 4 + (size_t)C * 4 + 8 + (size_t)AP_SPLITS_MAX * C * 8 + 1024;
 }
 
-// Returns 0, or -1 on a bad argument.  ws must hold perframe_ap_workspace_bytes(n, C) bytes.  Positives: target != 0, or (labels != NULL)
-// the frame's class id.
-int launch_perframe_ap(const float* scores, const float* target, const int* labels, long long n, int C, double* ap, long long* n_pos,
-                       double* score_sum, void* ws, hipStream_t s) {
-  if (n <= 0 || C <= 0 || C > 65535 || n >= (1ll << 31)) return -1;    // per-class cursors are 32-bit
+// what the per-frame and the per-stage metric share: keys, every class's positives sorted, every score counted against them
+struct ApRanked {
+  unsigned* keys;      // [C][n] order-reversing keys, class-major
+  unsigned* q;         // [C][n] class c: its len[c] positives ascending (descending score)
+  unsigned* cnt;       // [C][n] class c: cnt[b] = scores whose lower_bound in q is b (nonzero at the first member of a tie run only)
+  unsigned* len;       // [C] positives per class
+  double* partial;     // [splits][C] score mass
+  int splits;
+};
+
+static ApRanked ap_rank_positives(const float* scores, const float* target, const int* labels, long long n, int C, void* ws, hipStream_t s) {
   static DeviceOnce once;
   once.run([] { (void)hipFuncSetAttribute((const void*)ap_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, AP_TAB * 4 + 128); });
   const int ntiles = (int)((n + AP_TILE - 1) / AP_TILE);
@@ -456,6 +462,296 @@ int launch_perframe_ap(const float* scores, const float* target, const int* labe
   }
   const int splits = ap_splits(C);
   ap_count_kernel<<<dim3(splits, C), 1024, AP_TAB * 4 + 128, s>>>(keys, p0, cursor, n, C, cnt, partial);
-  ap_reduce_kernel<<<C, 256, 0, s>>>(p0, cnt, cursor, n, C, partial, splits, ap, n_pos, score_sum);
+  return ApRanked{keys, p0, cnt, cursor, partial, splits};
+}
+
+// Returns 0, or -1 on a bad argument.  ws must hold perframe_ap_workspace_bytes(n, C) bytes.  Positives: target != 0, or (labels != NULL)
+// the frame's class id.
+int launch_perframe_ap(const float* scores, const float* target, const int* labels, long long n, int C, double* ap, long long* n_pos,
+                       double* score_sum, void* ws, hipStream_t s) {
+  if (n <= 0 || C <= 0 || C > 65535 || n >= (1ll << 31)) return -1;    // per-class cursors are 32-bit
+  const ApRanked r = ap_rank_positives(scores, target, labels, n, C, ws, s);
+  ap_reduce_kernel<<<C, 256, 0, s>>>(r.q, r.cnt, r.len, n, C, r.partial, r.splits, ap, n_pos, score_sum);
+  return 0;
+}
+
+// ================================================================================================================================
+// Per-stage average precision (step_recognition/utils/metrics.py:64-130 with metrics='AP'): the same metric by tenth of each action.
+// Per class c the instances are the maximal runs of labels == c; a run [a, b] has len = b - a and its stage s = 0..9 holds the frames
+// [a + trunc(len * (s / 10.0)), max(that + 1, a + trunc(len * ((s + 1) / 10.0)))) - IEEE double products, as the reference's
+// int(len * perc).  The sample set of (c, s) = the frames with labels != c (negatives) + the stage-s frames of every run of c.
+//
+// Every stage positive is one of the class's positives, so no list is sorted again: with q_c / cnt_c from the per-frame pipeline
+// (ap_extract, the radix passes, ap_count) and a threshold t = the score of a tie run of q_c that ends at rank r,
+//   samples of (c, s) at or above t = (column c at or above t) - (positives of c at or above t) + (stage-s positives of c at or above t)
+//                                   = (cnt_c[0] + ... + cnt_c[r])  -  (r + 1)                   +  (st_cs[0] + ... + st_cs[r])
+// where st_cs[b] = the stage-s positives of c whose lower_bound in q_c is b (b = the first member of their tie run).
+//   ps_edges     per 1024-frame block: its last run head (labels[i] != labels[i-1]) and its first run tail
+//   ps_carry     one workgroup: running max of the heads in front of each block, running min of the tails behind it, and the offset
+//                of each class's counters (exclusive sum of the positives per class: the labels are single, so they sum to <= n)
+//   ps_stage     per frame: run start (forward max-scan of the heads) and run end (backward min-scan of the tails); a positive derives
+//                its 10-bit stage mask from (i - a, len), finds its key's lower_bound in q_c and adds 1 to st_cs[b] of its stages
+//   ps_reduce    one workgroup per (class, stage) walks q_c, cnt_c and st_cs once: two running prefixes, the tie-run ends of q, fp64
+//                accumulation of (stage positives in the run) * (stage positives so far) / (samples so far) in ap_reduce's order.
+// Integer atomics only (any order gives the same counters); the one floating-point sum has a fixed order: the same bits on every run.
+// ================================================================================================================================
+#define PS_STAGES 10
+#define PS_BLK 1024           // frames per block of the run scans (256 threads x 4)
+
+__global__ __launch_bounds__(256) void ps_edges_kernel(const int* __restrict__ labels, long long n, int* __restrict__ bl_head,
+                                                       int* __restrict__ bl_tail) {
+  __shared__ int wh[4], wt[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long i0 = (long long)blockIdx.x * PS_BLK + (long long)tid * 4;
+  int lab[6];
+#pragma unroll
+  for (int e = 0; e < 6; ++e) { const long long i = i0 - 1 + e; lab[e] = (i >= 0 && i < n) ? labels[i] : 0; }
+  int h = -1, t = 0x7FFFFFFF;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const long long i = i0 + e;
+    if (i < n) {
+      if (i == 0 || lab[e + 1] != lab[e]) h = (int)i;
+      if ((i == n - 1 || lab[e + 1] != lab[e + 2]) && t == 0x7FFFFFFF) t = (int)i;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { h = max(h, __shfl_xor(h, o, 64)); t = min(t, __shfl_xor(t, o, 64)); }
+  if (lane == 0) { wh[wave] = h; wt[wave] = t; }
+  __syncthreads();
+  if (tid == 0) {
+    bl_head[blockIdx.x] = max(max(wh[0], wh[1]), max(wh[2], wh[3]));
+    bl_tail[blockIdx.x] = min(min(wt[0], wt[1]), min(wt[2], wt[3]));
+  }
+}
+
+template <int OP> __device__ __forceinline__ int ps_comb(int a, int b) { return OP == 0 ? max(a, b) : OP == 1 ? min(a, b) : a + b; }
+
+// exclusive scan of v[0 .. m) in place by one 256-thread workgroup; REV: from the back
+template <int OP, bool REV>
+__device__ void ps_block_scan(int* v, int m, int identity, int* wsum, int* carry) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) *carry = identity;
+  __syncthreads();
+  for (int base = 0; base < m; base += 256) {
+    const int idx = base + tid;
+    const int pos = REV ? m - 1 - idx : idx;
+    const int x = idx < m ? v[pos] : identity;
+    int incl = x;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o, 64); if (lane >= o) incl = ps_comb<OP>(incl, u); }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int off = *carry;
+    for (int w = 0; w < wave; ++w) off = ps_comb<OP>(off, wsum[w]);
+    int before = __shfl_up(incl, 1, 64);
+    if (lane == 0) before = identity;
+    if (idx < m) v[pos] = ps_comb<OP>(off, before);
+    __syncthreads();
+    if (tid == 255) *carry = ps_comb<OP>(off, incl);
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void ps_carry_kernel(int* __restrict__ bl_head, int* __restrict__ bl_tail, int nblk,
+                                                       const unsigned* __restrict__ len, int C, int* __restrict__ off) {
+  __shared__ int wsum[4];
+  __shared__ int carry;
+  ps_block_scan<0, false>(bl_head, nblk, -1, wsum, &carry);             // -> the last head in front of the block
+  ps_block_scan<1, true>(bl_tail, nblk, 0x7FFFFFFF, wsum, &carry);      // -> the first tail behind the block
+  for (int c = threadIdx.x; c < C; c += 256) off[c] = (int)len[c];
+  __syncthreads();
+  ps_block_scan<2, false>(off, C, 0, wsum, &carry);                     // positives of the classes in front (their sum is <= n < 2^31)
+}
+
+__global__ __launch_bounds__(256) void ps_stage_kernel(const float* __restrict__ scores, const int* __restrict__ labels, long long n, int C,
+                                                       const int* __restrict__ carry_head, const int* __restrict__ carry_tail,
+                                                       const unsigned* __restrict__ q_all, const unsigned* __restrict__ len,
+                                                       const int* __restrict__ off, unsigned* __restrict__ st) {
+  __shared__ int wh[4], wt[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long i0 = (long long)blockIdx.x * PS_BLK + (long long)tid * 4;
+  int lab[6];
+#pragma unroll
+  for (int e = 0; e < 6; ++e) { const long long i = i0 - 1 + e; lab[e] = (i >= 0 && i < n) ? labels[i] : 0; }
+  bool head[4], tail[4];
+  int h = -1, t = 0x7FFFFFFF;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const long long i = i0 + e;
+    head[e] = i < n && (i == 0 || lab[e + 1] != lab[e]);
+    tail[e] = i < n && (i == n - 1 || lab[e + 1] != lab[e + 2]);
+    if (head[e]) h = (int)i;
+    if (tail[e] && t == 0x7FFFFFFF) t = (int)i;
+  }
+  int hs = h, ts = t;                                       // inclusive scans over the wave: heads from the front, tails from the back
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int u = __shfl_up(hs, o, 64), d = __shfl_down(ts, o, 64);
+    if (lane >= o) hs = max(hs, u);
+    if (lane + o < 64) ts = min(ts, d);
+  }
+  if (lane == 63) wh[wave] = hs;
+  if (lane == 0) wt[wave] = ts;
+  __syncthreads();
+  int a_run = __shfl_up(hs, 1, 64), b_run = __shfl_down(ts, 1, 64);
+  if (lane == 0) a_run = -1;
+  if (lane == 63) b_run = 0x7FFFFFFF;
+  a_run = max(a_run, carry_head[blockIdx.x]);
+  b_run = min(b_run, carry_tail[blockIdx.x]);
+  for (int w = 0; w < 4; ++w) {
+    if (w < wave) a_run = max(a_run, wh[w]);
+    if (w > wave) b_run = min(b_run, wt[w]);
+  }
+  int a[4], b[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { if (head[e]) a_run = (int)(i0 + e); a[e] = a_run; }
+#pragma unroll
+  for (int e = 3; e >= 0; --e) { if (tail[e]) b_run = (int)(i0 + e); b[e] = b_run; }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const long long i = i0 + e;
+    const int c = lab[e + 1];
+    if (i >= n || c < 0 || c >= C) continue;
+    const double rl = (double)(b[e] - a[e]);
+    const long long at = i - a[e];
+    unsigned mask = 0u;
+#pragma unroll
+    for (int sg = 0; sg < PS_STAGES; ++sg) {
+      const long long lo = (long long)(rl * ((double)sg / 10.0));
+      const long long hi = max(lo + 1, (long long)(rl * ((double)(sg + 1) / 10.0)));
+      if (at >= lo && at < hi) mask |= 1u << sg;
+    }
+    if (!mask) continue;                                    // the last frame of a run of two or more
+    const unsigned P = len[c];
+    if (P == 0u) continue;
+    const unsigned k = ap_desc_key(scores[(size_t)i * C + c]);
+    const unsigned lb = ap_lower_bound(q_all + (size_t)c * n, P, k);
+    if (lb >= P) continue;                                  // cannot happen: k is in the list
+    unsigned* dst = st + (size_t)off[c] + lb;
+#pragma unroll
+    for (int sg = 0; sg < PS_STAGES; ++sg)
+      if (mask >> sg & 1u) atomicAdd(dst + (size_t)sg * n, 1u);
+  }
+}
+
+// one workgroup per (class, stage): ap_reduce_kernel with a second running prefix, the stage positives
+__global__ __launch_bounds__(256) void ps_reduce_kernel(const unsigned* __restrict__ q_all, const unsigned* __restrict__ cnt_all,
+                                                        const unsigned* __restrict__ len, long long n, int C, const unsigned* __restrict__ st_all,
+                                                        const int* __restrict__ off, double* __restrict__ ap, long long* __restrict__ n_pos) {
+  __shared__ long long w_sum[4], w_st[4], w_max[4];
+  __shared__ double w_acc[4];
+  __shared__ long long carry_cnt, carry_st, carry_end;
+  const int c = blockIdx.x, sg = blockIdx.y;
+  const long long P = (long long)len[c];
+  const unsigned* q = q_all + (size_t)c * n;
+  const unsigned* cnt = cnt_all + (size_t)c * n;
+  const unsigned* st = st_all + (size_t)sg * n + (size_t)off[c];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) { carry_cnt = 0; carry_st = 0; carry_end = 0; }
+  __syncthreads();
+  double acc = 0.0;
+  for (long long base = 0; base < P; base += 1024) {
+    const long long j = base + (long long)tid * 4;
+    unsigned k[5];
+    long long v[4], u[4], mine = 0, mine_st = 0;
+#pragma unroll
+    for (int e = 0; e < 5; ++e) k[e] = j + e < P ? q[j + e] : 0u;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[e] = j + e < P ? (long long)cnt[j + e] : 0;
+      u[e] = j + e < P ? (long long)st[j + e] : 0;
+      mine += v[e];
+      mine_st += u[e];
+    }
+    long long incl = mine, incl_st = mine_st;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const long long x = __shfl_up(incl, o, 64), y = __shfl_up(incl_st, o, 64);
+      if (lane >= o) { incl += x; incl_st += y; }
+    }
+    if (lane == 63) { w_sum[wave] = incl; w_st[wave] = incl_st; }
+    __syncthreads();
+    long long seen = carry_cnt + incl - mine;               // column scores at or above the score in front of my first element
+    long long tps = carry_st + incl_st - mine_st;           // stage positives at or above it
+    for (int w = 0; w < wave; ++w) { seen += w_sum[w]; tps += w_st[w]; }
+    long long s_after[4], t_after[4], end_local = 0;        // stage positives at my last run end (0 = none: the prefix is monotone)
+    bool is_end[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      seen += v[e];
+      tps += u[e];
+      s_after[e] = seen;
+      t_after[e] = tps;
+      is_end[e] = (j + e < P) && ((j + e + 1 >= P) || (k[e] != k[e + 1]));
+      if (is_end[e]) end_local = tps;
+    }
+    long long mx = end_local;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const long long x = __shfl_up(mx, o, 64); if (lane >= o && x > mx) mx = x; }
+    if (lane == 63) w_max[wave] = mx;
+    __syncthreads();
+    long long prev = __shfl_up(mx, 1, 64);                  // stage positives at the most recent run end before my first element
+    if (lane == 0) prev = 0;
+    if (carry_end > prev) prev = carry_end;
+    for (int w = 0; w < wave; ++w) if (w_max[w] > prev) prev = w_max[w];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (is_end[e]) {
+        const long long d = t_after[e] - prev;              // stage positives of this tie run (counted at its first member)
+        if (d > 0) {
+          const long long samples = s_after[e] - (j + e + 1) + t_after[e];
+          acc += (double)d * ((double)t_after[e] / (double)samples);
+          prev = t_after[e];
+        }
+      }
+    __syncthreads();
+    if (tid == 255) {
+      carry_cnt = seen;
+      carry_st = tps;
+      long long mm = carry_end;
+      for (int w = 0; w < 4; ++w) if (w_max[w] > mm) mm = w_max[w];
+      carry_end = mm;
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if (lane == 0) w_acc[wave] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    const long long Ps = carry_st;
+    const double a = (w_acc[0] + w_acc[1]) + (w_acc[2] + w_acc[3]);
+    ap[(size_t)sg * C + c] = Ps > 0 ? a / (double)Ps : 0.0;               // a class without a run: 0.0, as the reference reports it
+    if (n_pos) n_pos[(size_t)sg * C + c] = Ps;
+  }
+}
+
+static size_t ps_base_bytes(long long n, int C) { return (perframe_ap_workspace_bytes(n, C) + 15) & ~(size_t)15; }
+
+size_t perstage_ap_workspace_bytes(long long n, int C) {
+  const size_t nblk = (size_t)((n + PS_BLK - 1) / PS_BLK);
+  return ps_base_bytes(n, C) + (size_t)PS_STAGES * (size_t)n * 4 + (size_t)C * 4 + 2 * nblk * 4 + 64;
+}
+
+// Returns 0, or -1 on a bad argument.  ws must hold perstage_ap_workspace_bytes(n, C) bytes (n > 0).  ap / n_pos: [10][C].
+int launch_perstage_ap(const float* scores, const int* labels, long long n, int C, double* ap, long long* n_pos, void* ws, hipStream_t s) {
+  if (n < 0 || C <= 0 || C > 65535 || n >= (1ll << 31)) return -1;
+  if (n == 0) {
+    (void)hipMemsetAsync(ap, 0, (size_t)PS_STAGES * C * 8, s);
+    if (n_pos) (void)hipMemsetAsync(n_pos, 0, (size_t)PS_STAGES * C * 8, s);
+    return 0;
+  }
+  const int nblk = (int)((n + PS_BLK - 1) / PS_BLK);
+  unsigned* st = (unsigned*)((char*)ws + ps_base_bytes(n, C));
+  int* off = (int*)(st + (size_t)PS_STAGES * (size_t)n);
+  int* bl_head = off + C;
+  int* bl_tail = bl_head + nblk;
+  const ApRanked r = ap_rank_positives(scores, nullptr, labels, n, C, ws, s);
+  (void)hipMemsetAsync(st, 0, (size_t)PS_STAGES * (size_t)n * 4, s);
+  ps_edges_kernel<<<nblk, 256, 0, s>>>(labels, n, bl_head, bl_tail);
+  ps_carry_kernel<<<1, 256, 0, s>>>(bl_head, bl_tail, nblk, r.len, C, off);
+  ps_stage_kernel<<<nblk, 256, 0, s>>>(scores, labels, n, C, bl_head, bl_tail, r.q, r.len, off, st);
+  ps_reduce_kernel<<<dim3(C, PS_STAGES), 256, 0, s>>>(r.q, r.cnt, r.len, n, C, st, off, ap, n_pos);
   return 0;
 }

@@ -20,8 +20,9 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from .eval_cache import EvalFeatureCache
-from .metrics import (perframe_ap_raw, perframe_ap_raw_device, perframe_average_precision, perframe_average_precision_device,
-                      report_from_raw)
+from ._lib import PregoError
+from .metrics import (N_STAGES, perframe_ap_raw, perframe_ap_raw_device, perframe_average_precision, perframe_average_precision_device,
+                      perstage_average_precision_device, perstage_report, report_from_raw)
 from .registry import EVAL
 
 
@@ -51,6 +52,10 @@ class Evaluate(nn.Module):
         # cfg['eval_cache_device'] (not a reference key): the eval set's features stay in device memory between calls (eval_cache.py)
         self._cache = EvalFeatureCache(cfg.get("eval_cache_max_bytes")) if cfg.get("eval_cache_device", False) else None
         self.last_source = None              # "loader" | "cache": where the last call took its features from
+        # cfg['eval_perstage'] (not a reference key, off by default): the per-stage AP report of the pass (utils/metrics.py:64-130 with
+        # metrics='AP', `prego_perstage_ap_labels`) is kept here and each stage's mean is logged; what eval returns and writes is unchanged
+        self.perstage = bool(cfg.get("eval_perstage", False))
+        self.last_perstage = None
 
     @staticmethod
     def _new_copy_stream(dev):
@@ -431,6 +436,12 @@ class Evaluate(nn.Module):
         # the loader's order (no data-path collective); rank 0 gathers the per-video results once at the end
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         rank = dist.get_rank() if world > 1 else 0
+        if self.perstage and world > 1:
+            raise PregoError("cfg['eval_perstage']: per-stage AP depends on the order of the frames (action instances are runs over the "
+                             f"concatenated videos) and is computed by a single process only; this eval runs on {world} ranks")
+        if self.perstage and torch.device(device).type != "cuda":
+            raise PregoError("cfg['eval_perstage']: the per-stage AP of an eval pass runs on the device (prego_perstage_ap_labels); host "
+                             "arrays: prego_amd.metrics.perstage_average_precision")
         skip_flow = self._zero_flow(model, dataloader)
         cache = self._cache
         self.last_source = "loader"
@@ -516,6 +527,29 @@ class Evaluate(nn.Module):
                 def finish_ap(_fn=ap_fn, _s=self._ap_stream):
                     with torch.cuda.stream(_s):           # the result's device -> host copy follows the kernels on THEIR stream
                         return _fn()
+            finish_ps = None
+            self.last_perstage = None
+            if self.perstage and pred_scores:
+                # the per-stage report on the same device-resident scores and class ids, enqueued behind the per-frame metric and
+                # collected behind everything eval writes and logs today
+                if not all(t.dim() == 1 for t in gt_targets):
+                    raise PregoError("cfg['eval_perstage']: per-stage AP needs targets that are one class id per frame (one-hot rows, "
+                                     "cfg['eval_label_targets'] on); this eval set has rows that are not (dense multi-label targets: "
+                                     "prego_amd.metrics.perstage_average_precision on the host)")
+                if self._ap_stream is None:
+                    self._ap_stream = torch.cuda.Stream(torch.device(device))
+                fwd_done = torch.cuda.Event()
+                fwd_done.record(torch.cuda.current_stream(torch.device(device)))
+                with torch.cuda.stream(self._ap_stream):
+                    self._ap_stream.wait_event(fwd_done)
+                    if finish_ap is None:                 # metric 'cAP': the per-frame metric runs on the host, nothing is concatenated yet
+                        pred_all = torch.cat(pred_scores, 0)
+                        gt_all = self._cat_targets(gt_targets).to(pred_all.device)
+                    ps_fn = perstage_average_precision_device(pred_all.to(device), gt_all.to(device), self.all_class_names, defer=True)
+
+                def finish_ps(_fn=ps_fn, _s=self._ap_stream):
+                    with torch.cuda.stream(_s):
+                        return _fn()
             mark("launch")
             self._collect(pending, pred_scores, gt_targets, output, json_parts)
             mark("collect")
@@ -575,6 +609,12 @@ class Evaluate(nn.Module):
             time_taken = max(t_end - t_begin, 1e-9)
             self.last_fps = num_frames / time_taken
             logger.info(f"Processed {num_frames} frames in {time_taken:.1f} seconds ({self.last_fps:.1f} FPS)")
+            if self.perstage:
+                self.last_perstage = finish_ps() if finish_ps is not None else \
+                    perstage_report(np.zeros((N_STAGES, len(self.all_class_names))), self.all_class_names)
+                mark("perstage_done")
+                for stage, rep_ in self.last_perstage.items():
+                    logger.info(f"per-stage mAP {stage}: {rep_['mean_AP'] * 100:.2f}")
         return result["mean_AP"]
 
     def _sharded_ap(self, pred, gt, world, rank):

@@ -13,7 +13,22 @@ reference always treats as background (metrics.py:44-48).  Two routes to the sam
                                            No CPU fallback.
 
 `metric: 'cAP'` (the reference's calibrated variant for TVSeries, metrics.py:10-22; unreachable from the shipped configs) runs on the
-host path only; `Evaluate` moves the matrices to the host for it."""
+host path only; `Evaluate` moves the matrices to the host for it.
+
+Per-stage average precision (the reference's `perstage_average_precision`, metrics.py:64-130, from LSTR):
+how early inside an action it is recognised.  Per class the action instances are the maximal runs of positive frames over the whole
+concatenated axis; a run with first frame a and last frame b has len = b - a and its stage s = 0..9 holds the frames
+[a + int(len * (s / 10)), max(that + 1, a + int(len * ((s + 1) / 10)))) - float products, so len 90, s 7 starts at offset 62; a
+one-frame run is in all ten stages and the last frame of a longer run in none.  The sample set of (class, stage) is every negative
+frame of the class plus the stage's frames of every run; its AP is the one above.  A class without a run scores 0.0 (what sklearn
+1.7 answers for a set without positives) and counts in the stage's mean over the classes 1.. .  Two routes again:
+
+  * `perstage_average_precision`         - numpy on the host; metrics 'AP' or 'cAP' (cAP: ties in input order, NaN without
+                                           positives, as `calibrated_average_precision_columns` documents); dense targets or ids.
+  * `perstage_average_precision_device`  - the HIP path, `prego_perstage_ap_labels` (csrc/metrics.hip): runs and stage masks from
+                                           one class id per frame, the per-frame pipeline's ranks, one counter per (stage, positive).
+                                           'AP' only (cAP depends on the order of ties), no CPU fallback; used by `Evaluate` under
+                                           cfg `eval_perstage`."""
 from __future__ import annotations
 
 from collections import OrderedDict
@@ -154,4 +169,134 @@ def perframe_average_precision_device(prediction, ground_truth, class_names, pos
         if raw:
             return host[0].copy(), host[1].view(np.int64).copy(), host[2].copy()
         return _report(host[0], host[1].view(np.int64), host[2], class_names)
+    return finish if defer else finish()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# per-stage average precision (metrics.py:64-130 of the reference)
+# ------------------------------------------------------------------------------------------------------------------------------
+N_STAGES = 10
+STAGE_NAMES = tuple("{:2}%_{:3}%".format(s * 10, (s + 1) * 10) for s in range(N_STAGES))
+
+
+def stage_members(positive: np.ndarray) -> np.ndarray:
+    """positive [frames] bool -> [10, frames] bool: the frames of each stage of every maximal run of positives"""
+    g = np.asarray(positive, dtype=bool)
+    n = g.shape[0]
+    out = np.zeros((N_STAGES, n), dtype=bool)
+    if n == 0 or not g.any():
+        return out
+    prev = np.concatenate(([False], g[:-1]))
+    nxt = np.concatenate((g[1:], [False]))
+    starts = np.flatnonzero(g & ~prev)
+    lens = np.flatnonzero(g & ~nxt) - starts                   # last - first: one less than the frame count
+    for s in range(N_STAGES):
+        lo = starts + (lens * (s / 10)).astype(np.int64)       # the reference's int(len * perc): a float64 product, truncated
+        hi = np.maximum(lo + 1, starts + (lens * ((s + 1) / 10)).astype(np.int64))
+        edge = np.zeros(n + 1, dtype=np.int64)                 # runs do not overlap, nor do their stages
+        edge[lo] += 1
+        edge[hi] -= 1
+        out[s] = np.cumsum(edge[:n]) > 0
+    return out
+
+
+def _class_positive(truth: np.ndarray, c: int) -> np.ndarray:
+    """frames of class c: the column == 1 of a dense target matrix (metrics.py:120) or the ids == c of one id per frame"""
+    return truth == c if truth.ndim == 1 else truth[:, c] == 1
+
+
+def perstage_ap_raw(pred: np.ndarray, truth: np.ndarray, metrics="AP"):
+    """(AP or cAP [10, classes], positives [10, classes]) of host scores [frames, classes] and targets [frames, classes] or ids
+    [frames]; every class, class 0 included.  'AP': 0.0 for a set without positives; 'cAP': NaN."""
+    if metrics not in ("AP", "cAP"):
+        raise RuntimeError(f"Unknown metrics: {metrics}")
+    pred = np.asarray(pred)
+    truth = np.asarray(truth)
+    n, ncls = pred.shape
+    ap = np.zeros((N_STAGES, ncls))
+    n_pos = np.zeros((N_STAGES, ncls), dtype=np.int64)
+    cols = average_precision_columns if metrics == "AP" else calibrated_average_precision_columns
+    for c in range(ncls):
+        g = _class_positive(truth, c)
+        member = stage_members(g)
+        order = np.argsort(-pred[:, c], kind="stable")         # once per class: every stage's set is a subset in this order
+        for s in range(N_STAGES):
+            keep = order[(~g | member[s])[order]]
+            n_pos[s, c] = int(member[s].sum())
+            if n_pos[s, c] == 0:
+                ap[s, c] = 0.0 if metrics == "AP" else np.nan
+            else:
+                ap[s, c] = cols(pred[keep, c][:, None], member[s][keep][:, None])[0]
+    return ap, n_pos
+
+
+def perstage_report(ap, class_names):
+    """the reference's result dict from AP [10, classes]: per stage the AP of every class 1.. and their mean"""
+    ap = np.asarray(ap)
+    res = OrderedDict()
+    for s, name in enumerate(STAGE_NAMES):
+        per = OrderedDict((class_names[c], float(ap[s, c])) for c in range(1, len(class_names)))     # class 0 = background
+        with np.errstate(invalid="ignore"):
+            import warnings
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", RuntimeWarning)
+                mean = np.mean(list(per.values())) if per else float("nan")
+        res[name] = OrderedDict(per_class_AP=per, mean_AP=mean)
+    return res
+
+
+def perstage_average_precision(prediction, ground_truth, class_names, postprocessing=None, metrics="AP"):
+    """Host path: prediction [frames, classes]; ground_truth [frames, classes] (positive: == 1, as the reference) or one class id per
+    frame [frames].  The frames are in evaluation order: a run is not cut where two videos meet."""
+    if metrics not in ("AP", "cAP"):
+        raise RuntimeError(f"Unknown metrics: {metrics}")
+    truth = np.asarray(ground_truth)
+    pred = np.asarray(prediction)
+    if postprocessing is not None:
+        truth, pred = postprocessing(truth, pred)
+    if pred.ndim != 2 or pred.shape[0] == 0:
+        return perstage_report(np.zeros((N_STAGES, len(class_names))), class_names)
+    return perstage_report(perstage_ap_raw(pred, truth, metrics)[0], class_names)
+
+
+def perstage_average_precision_device(prediction, labels, class_names, defer=False, raw=False):
+    """Device path (metric 'AP'): prediction fp32 CUDA tensor [frames, classes], labels an integer CUDA tensor [frames] with one class
+    id per frame in evaluation order (an id outside the classes = a negative of every class); `prego_perstage_ap_labels` in
+    libprego_amd.so, one small device -> host transfer brings back AP and positives [10, classes].  No CPU fallback.
+    raw=True: (AP [10, classes], positives [10, classes]) of every class instead of the report.
+    defer=True: the kernels are only ENQUEUED and a function is returned that waits for them and builds the result."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    from ._lib import PregoError, check
+    if not (prediction.is_cuda and labels.is_cuda):
+        raise PregoError("perstage_average_precision_device needs CUDA tensors; there is no CPU fallback "
+                         "(host arrays: perstage_average_precision)")
+    if labels.dim() != 1 or labels.dtype.is_floating_point or labels.dtype == torch.bool:
+        raise PregoError("perstage_average_precision_device: labels must be one integer class id per frame [frames] "
+                         "(dense target matrices: perstage_average_precision on the host)")
+    pred = prediction.detach().to(torch.float32).contiguous()
+    ids = labels.detach().to(torch.int32).contiguous()
+    if pred.dim() != 2 or pred.shape[1] != len(class_names) or ids.shape != pred.shape[:1]:
+        raise PregoError(f"perstage_average_precision_device: shapes {tuple(pred.shape)} / {tuple(ids.shape)} for {len(class_names)} classes")
+    n, ncls = pred.shape
+    if n == 0:
+        z = (np.zeros((N_STAGES, ncls)), np.zeros((N_STAGES, ncls), np.int64))
+        rep = z if raw else perstage_report(z[0], class_names)
+        return (lambda: rep) if defer else rep
+    lib = _lib.load()
+    dev = pred.device
+    ws = torch.empty(lib.prego_perstage_ap_workspace_bytes(n, ncls), dtype=torch.uint8, device=dev)
+    out = torch.empty((2, N_STAGES, ncls), dtype=torch.float64, device=dev)          # AP | positives (int64 bits)
+    with torch.cuda.device(dev):
+        check(lib.prego_perstage_ap_labels(C.c_void_p(pred.data_ptr()), C.c_void_p(ids.data_ptr()), n, ncls, C.c_void_p(out[0].data_ptr()),
+                                           C.c_void_p(out[1].data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    def finish(_keep=(pred, ids, ws)):
+        host = out.cpu().numpy()
+        if raw:
+            return host[0].copy(), host[1].view(np.int64).copy()
+        return perstage_report(host[0], class_names)
     return finish if defer else finish()
