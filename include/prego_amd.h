@@ -494,6 +494,34 @@ int prego_perframe_ap_labels(const float* scores, const int32_t* labels, int64_t
 size_t prego_perstage_ap_workspace_bytes(int64_t n_frames, int n_classes);
 int prego_perstage_ap_labels(const float* scores, const int32_t* labels, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
                              void* workspace, size_t workspace_bytes, prego_stream_t stream);
+/* utils/metrics.py:10-22 on the device: the calibrated average precision (metric 'cAP', the TVSeries metric) of every class column,
+ * beside prego_perframe_ap with the same arguments.  The order is descending score, frames of equal score by ascending frame index
+ * (-0.0 == +0.0): the reference's unstable argsort leaves ties to chance, this is the order of the host form
+ * (prego_amd.metrics.calibrated_average_precision_columns).  With q_0 .. q_{P-1} the class's positives in that order and rank_i the
+ * 1-based position of q_i among all n frames:  tps_i = i + 1, fps_i = rank_i - tps_i, w = (n - P) / P, eps = 2^-52,
+ *   cAP = (1 / P) * sum_i tps_i / (tps_i + fps_i / (w + eps) + eps)      in IEEE double, in this operand order.
+ * ap: device double [n_classes] (NaN for a class without positives); n_pos / score_sum (nullable) as prego_perframe_ap.  Exact integer
+ * ranks (the positives sorted by (score key, frame), every (score, frame) counted against them), one fp64 sum per class in a fixed
+ * order: the same bits on every run.  Workspace: prego_perframe_cap_workspace_bytes (24 B per score + histograms).  n_frames == 0:
+ * returns 0, writes NaN / 0 / 0.0 and needs no workspace.  PREGO_EINVAL, checked before any launch (outputs and workspace untouched):
+ * a NULL scores, target / labels or ap, a NULL workspace with n_frames > 0, n_frames < 0 or >= 2^31, n_classes < 1 or > 65535;
+ * PREGO_EWORKSPACE: workspace_bytes below the query.  An addition to ABI 7 (existing signatures unchanged). */
+size_t prego_perframe_cap_workspace_bytes(int64_t n_frames, int n_classes);
+int prego_perframe_cap(const float* scores, const float* target, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
+                       double* score_sum, void* workspace, size_t workspace_bytes, prego_stream_t stream);
+/* The same with one class id per frame, as prego_perframe_ap_labels: bit for bit the results of one-hot target rows. */
+int prego_perframe_cap_labels(const float* scores, const int32_t* labels, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
+                              double* score_sum, void* workspace, size_t workspace_bytes, prego_stream_t stream);
+/* utils/metrics.py:64-130 with metrics='cAP' (the reference's default there): prego_perstage_ap_labels' sample sets - the negatives of
+ * class c plus the stage-s frames of its runs - under the calibrated metric and the order above.  For a stage member q_i of class c:
+ * tps = the stage members among q_0 .. q_i, fps = rank_i - (i + 1) (the negatives in front of q_i, the same in every stage),
+ * w = (n - P_c) / P_cs, the sum divided by P_cs = the stage's members.  ap: device double [10][n_classes], NaN where a (stage, class)
+ * has no member (what the host's perstage_ap_raw(.., 'cAP') answers); n_pos (nullable): device int64 [10][n_classes].  Workspace:
+ * prego_perstage_cap_workspace_bytes (that of prego_perframe_cap + 40 B per frame).  n_frames == 0: returns 0 and writes 0.0 / 0, as
+ * prego_perstage_ap_labels.  Refusals as prego_perstage_ap_labels.  An addition to ABI 7. */
+size_t prego_perstage_cap_workspace_bytes(int64_t n_frames, int n_classes);
+int prego_perstage_cap_labels(const float* scores, const int32_t* labels, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
+                              void* workspace, size_t workspace_bytes, prego_stream_t stream);
 /* HOST function (no device work): the reference's loader yields fp32 target rows [n_frames][n_classes] per video (one-hot for both
  * shipped configs).  targets: n_videos host pointers, n_frames: their row counts; labels: host int32 [sum of n_frames], the videos one
  * after the other, labels[i] = np.argmax(row i) (eval.py:55, the first maximum); onehot[v] = 1 iff every row of video v holds exactly one

@@ -57,6 +57,8 @@ SYMBOLS = [
     "prego_stream_pool_image_bytes", "prego_stream_pool_snapshot", "prego_stream_pool_restore",
     "prego_vit_stream_pool_image_bytes", "prego_vit_stream_pool_snapshot", "prego_vit_stream_pool_restore",
     "prego_perstage_ap_workspace_bytes", "prego_perstage_ap_labels",
+    "prego_perframe_cap_workspace_bytes", "prego_perframe_cap", "prego_perframe_cap_labels",
+    "prego_perstage_cap_workspace_bytes", "prego_perstage_cap_labels",
 ]
 # include/prego_amd_debug.h: only in libprego_amd_debug.so
 DEBUG_SYMBOLS = ["prego_miniroad_debug_stamps", "prego_debug_gemm_bf16", "prego_debug_attention_bwd", "prego_debug_attention_fwd",
@@ -169,6 +171,13 @@ def _open(path: str, debug: bool) -> C.CDLL:
     lib.prego_perstage_ap_workspace_bytes.argtypes = [i64, i32]
     lib.prego_perstage_ap_workspace_bytes.restype = sz
     lib.prego_perstage_ap_labels.argtypes = [vp, vp, i64, i32, vp, vp, vp, sz, vp]
+    lib.prego_perframe_cap_workspace_bytes.argtypes = [i64, i32]
+    lib.prego_perframe_cap_workspace_bytes.restype = sz
+    lib.prego_perframe_cap.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, sz, vp]
+    lib.prego_perframe_cap_labels.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, sz, vp]
+    lib.prego_perstage_cap_workspace_bytes.argtypes = [i64, i32]
+    lib.prego_perstage_cap_workspace_bytes.restype = sz
+    lib.prego_perstage_cap_labels.argtypes = [vp, vp, i64, i32, vp, vp, vp, sz, vp]
     lib.prego_onehot_labels.argtypes = [i32, C.POINTER(vp), C.POINTER(i64), i32, vp, C.POINTER(C.c_int32)]
     f32 = C.c_float
     lib.prego_adamw_step.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), i64, f32, f32, f32, f32, f32, vp]

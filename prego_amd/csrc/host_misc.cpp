@@ -90,6 +90,50 @@ extern "C" int prego_perstage_ap_labels(const float* scores, const int32_t* labe
   return PREGO_OK;
 }
 
+// utils/metrics.py:10-22 (calibrated average precision, ties in frame order) on the device, beside the AP entries
+extern "C" size_t prego_perframe_cap_workspace_bytes(int64_t n_frames, int n_classes) {
+  if (n_frames <= 0 || n_classes <= 0) return 0;
+  return perframe_cap_workspace_bytes(n_frames, n_classes);
+}
+static int perframe_cap_common(const float* scores, const float* target, const int32_t* labels, int64_t n_frames, int n_classes, double* ap,
+                               int64_t* n_pos, double* score_sum, void* workspace, size_t workspace_bytes, prego_stream_t stream) {
+  if (!scores || (!target && !labels) || !ap || (!workspace && n_frames > 0)) return prego_fail_(PREGO_EINVAL, "perframe_cap: NULL argument");
+  if (n_frames < 0 || n_frames >= (1ll << 31) || n_classes < 1 || n_classes > 65535)
+    return prego_fail_(PREGO_EINVAL, "perframe_cap: n_frames %lld (0 .. 2^31 - 1), n_classes %d (1 .. 65535)", (long long)n_frames, n_classes);
+  if (n_frames > 0 && workspace_bytes < perframe_cap_workspace_bytes(n_frames, n_classes))
+    return prego_fail_(PREGO_EWORKSPACE, "perframe_cap: workspace %zu < %zu (prego_perframe_cap_workspace_bytes)", workspace_bytes,
+                       perframe_cap_workspace_bytes(n_frames, n_classes));
+  if (launch_perframe_cap(scores, target, (const int*)labels, n_frames, n_classes, ap, (long long*)n_pos, score_sum, workspace, (hipStream_t)stream))
+    return prego_fail_(PREGO_EINVAL, "perframe_cap: bad arguments");
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+extern "C" int prego_perframe_cap(const float* scores, const float* target, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
+                                  double* score_sum, void* workspace, size_t workspace_bytes, prego_stream_t stream) {
+  return perframe_cap_common(scores, target, nullptr, n_frames, n_classes, ap, n_pos, score_sum, workspace, workspace_bytes, stream);
+}
+extern "C" int prego_perframe_cap_labels(const float* scores, const int32_t* labels, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
+                                         double* score_sum, void* workspace, size_t workspace_bytes, prego_stream_t stream) {
+  return perframe_cap_common(scores, nullptr, labels, n_frames, n_classes, ap, n_pos, score_sum, workspace, workspace_bytes, stream);
+}
+extern "C" size_t prego_perstage_cap_workspace_bytes(int64_t n_frames, int n_classes) {
+  if (n_frames <= 0 || n_classes <= 0) return 0;
+  return perstage_cap_workspace_bytes(n_frames, n_classes);
+}
+extern "C" int prego_perstage_cap_labels(const float* scores, const int32_t* labels, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
+                                         void* workspace, size_t workspace_bytes, prego_stream_t stream) {
+  if (!scores || !labels || !ap || (!workspace && n_frames > 0)) return prego_fail_(PREGO_EINVAL, "perstage_cap: NULL argument");
+  if (n_frames < 0 || n_frames >= (1ll << 31) || n_classes < 1 || n_classes > 65535)
+    return prego_fail_(PREGO_EINVAL, "perstage_cap: n_frames %lld (0 .. 2^31 - 1), n_classes %d (1 .. 65535)", (long long)n_frames, n_classes);
+  if (n_frames > 0 && workspace_bytes < perstage_cap_workspace_bytes(n_frames, n_classes))
+    return prego_fail_(PREGO_EWORKSPACE, "perstage_cap: workspace %zu < %zu (prego_perstage_cap_workspace_bytes)", workspace_bytes,
+                       perstage_cap_workspace_bytes(n_frames, n_classes));
+  if (launch_perstage_cap(scores, (const int*)labels, n_frames, n_classes, ap, (long long*)n_pos, workspace, (hipStream_t)stream))
+    return prego_fail_(PREGO_EINVAL, "perstage_cap: bad arguments");
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
 // The feeder's side of the class-id entries: one-hot target rows (what the reference's dataset yields, dataset.py / eval.py:55 np.argmax(target)) reduced
 // to their class id on the host, in the loader's own memory, by a few threads - while the GPU is busy with the features.  HOST function.
 extern "C" int prego_onehot_labels(int n_videos, const float* const* targets, const int64_t* n_frames, int n_classes, int32_t* labels,

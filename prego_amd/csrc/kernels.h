@@ -288,6 +288,13 @@ int launch_perframe_ap(const float* scores, const float* target, const int* labe
 size_t perstage_ap_workspace_bytes(long long n_frames, int n_classes);
 int launch_perstage_ap(const float* scores, const int* labels, long long n_frames, int n_classes, double* ap, long long* n_pos, void* workspace,
                        hipStream_t s);
+// calibrated average precision (metrics.hip): the same pipeline over (score key, frame) composites: ties in frame order
+size_t perframe_cap_workspace_bytes(long long n_frames, int n_classes);
+int launch_perframe_cap(const float* scores, const float* target, const int* labels, long long n_frames, int n_classes, double* ap, long long* n_pos,
+                        double* score_sum, void* workspace, hipStream_t s);
+size_t perstage_cap_workspace_bytes(long long n_frames, int n_classes);
+int launch_perstage_cap(const float* scores, const int* labels, long long n_frames, int n_classes, double* ap, long long* n_pos, void* workspace,
+                        hipStream_t s);
 
 // Evaluate's feature cache (feature_cache.hip): n fp32 values -> bf16 / fp16 (f16) with the pack kernels' conversion; n % 8 == 0, n > 0
 void launch_cast_features(bool f16, const float* src, void* dst, long long n, int n_cu, hipStream_t s);

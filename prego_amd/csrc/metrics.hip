@@ -21,6 +21,8 @@
 //                (positives in the run) * (positives so far) / (samples so far).
 // Exact integer ranks; the only floating-point work is the final fp64 sum (differs from sklearn's by summation order, ~1e-16) and
 // the per-class score mass (fixed summation order: the same bits on every run).
+// The kernels up to ap_count are templates over what a list holds per positive: the key (AP), or the key above the frame index (the
+// calibrated metric further down, which ranks frames of equal score in frame order).
 #include "common.h"
 #include "kernels.h"
 
@@ -47,14 +49,20 @@ __device__ __forceinline__ float ap_key_score(unsigned k) {
   return __uint_as_float(b);
 }
 
+// the order of a class's list: by key alone (unsigned), or by key and then by frame (64 bits: the key above the frame index, n < 2^31)
+typedef unsigned long long ap_u64;
+template <typename T> __device__ __forceinline__ T ap_entry(unsigned key, long long frame);
+template <> __device__ __forceinline__ unsigned ap_entry<unsigned>(unsigned key, long long) { return key; }
+template <> __device__ __forceinline__ ap_u64 ap_entry<ap_u64>(unsigned key, long long frame) { return ((ap_u64)key << 32) | (ap_u64)(unsigned)frame; }
 
 // [AP_XF frames] x [<= AP_XC classes] tile: keys written class-major through an LDS transpose, positives appended per class
 // LABELS: the positives are given as one class id per frame (one-hot targets the feeder reduced on the host: 4 bytes per frame over
 // the link instead of 4 x classes); a frame whose id is outside [0, C) has no positive
-template <bool LABELS>
+// T: what a class's list holds per positive - the key (AP: ties share a threshold) or the (key, frame) composite (cAP: ties in frame order)
+template <bool LABELS, typename T>
 __global__ __launch_bounds__(256) void ap_extract_kernel(const float* __restrict__ scores, const float* __restrict__ target,
                                                          const int* __restrict__ labels, long long n, int C, unsigned* __restrict__ keys,
-                                                         unsigned* __restrict__ pos, unsigned* __restrict__ cursor) {
+                                                         T* __restrict__ pos, unsigned* __restrict__ cursor) {
   __shared__ unsigned tile[AP_XC][AP_XF + 1];
   __shared__ unsigned lcnt[AP_XC], lbase[AP_XC];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -83,7 +91,7 @@ __global__ __launch_bounds__(256) void ap_extract_kernel(const float* __restrict
     const int f = idx / cb, c = idx - f * cb;
     const bool positive = LABELS ? labels[f0 + f] == c0 + c : target[(size_t)(f0 + f) * C + c0 + c] != 0.f;
     if (positive)
-      pos[(size_t)(c0 + c) * n + lbase[c] + atomicAdd(&lcnt[c], 1u)] = tile[c][f];
+      pos[(size_t)(c0 + c) * n + lbase[c] + atomicAdd(&lcnt[c], 1u)] = ap_entry<T>(tile[c][f], f0 + f);
   }
   for (int c = wave; c < cb; c += 4) {
     unsigned* col = keys + (size_t)(c0 + c) * n + f0;
@@ -93,13 +101,14 @@ __global__ __launch_bounds__(256) void ap_extract_kernel(const float* __restrict
 
 // digit histogram of a class's tiles: hist[c][digit][tile] with the class's own tile count as the stride; the first pass also
 // clears the class's counters for ap_count
-__global__ __launch_bounds__(64) void ap32_hist_kernel(const unsigned* __restrict__ keys, const unsigned* __restrict__ len, long long n,
+template <typename T>
+__global__ __launch_bounds__(64) void ap32_hist_kernel(const T* __restrict__ keys, const unsigned* __restrict__ len, long long n,
                                                        int ntiles_max, int shift, unsigned* __restrict__ hist, unsigned* __restrict__ zero) {
   __shared__ unsigned h[AP_RADIX];
   const int c = blockIdx.y, lane = threadIdx.x;
   const unsigned P = len[c];
   const int ntc = (int)((P + AP_TILE - 1) / AP_TILE);
-  const unsigned* col = keys + (size_t)c * n;
+  const T* col = keys + (size_t)c * n;
   unsigned* hc = hist + (size_t)c * AP_RADIX * ntiles_max;
   for (int tile = blockIdx.x; tile < ntc; tile += gridDim.x) {
     for (int d = lane; d < AP_RADIX; d += 64) h[d] = 0u;
@@ -108,7 +117,7 @@ __global__ __launch_bounds__(64) void ap32_hist_kernel(const unsigned* __restric
     for (int j = lane; j < AP_TILE; j += 64) {
       const unsigned i = i0 + j;
       if (i < P) {
-        atomicAdd(&h[(col[i] >> shift) & (AP_RADIX - 1)], 1u);
+        atomicAdd(&h[(unsigned)(col[i] >> shift) & (AP_RADIX - 1)], 1u);
         if (zero) zero[(size_t)c * n + i] = 0u;
       }
     }
@@ -150,15 +159,16 @@ __global__ __launch_bounds__(256) void ap32_scan_kernel(unsigned* __restrict__ h
 }
 
 // stable scatter of a class's tiles by the current digit
-__global__ __launch_bounds__(64) void ap32_scatter_kernel(const unsigned* __restrict__ src, unsigned* __restrict__ dst,
+template <typename T>
+__global__ __launch_bounds__(64) void ap32_scatter_kernel(const T* __restrict__ src, T* __restrict__ dst,
                                                           const unsigned* __restrict__ len, long long n, int ntiles_max, int shift,
                                                           const unsigned* __restrict__ hist) {
   __shared__ unsigned cur[AP_RADIX];
   const int c = blockIdx.y, lane = threadIdx.x;
   const unsigned P = len[c];
   const int ntc = (int)((P + AP_TILE - 1) / AP_TILE);
-  const unsigned* col = src + (size_t)c * n;
-  unsigned* out = dst + (size_t)c * n;
+  const T* col = src + (size_t)c * n;
+  T* out = dst + (size_t)c * n;
   const unsigned* hc = hist + (size_t)c * AP_RADIX * ntiles_max;
   const unsigned long long below = (1ull << lane) - 1ull;
   for (int tile = blockIdx.x; tile < ntc; tile += gridDim.x) {
@@ -169,8 +179,8 @@ __global__ __launch_bounds__(64) void ap32_scatter_kernel(const unsigned* __rest
     for (int j = 0; j < AP_TILE; j += 64) {
       const unsigned i = i0 + j + lane;
       const bool live = i < P;
-      const unsigned k = live ? col[i] : 0u;
-      const unsigned d = (k >> shift) & (AP_RADIX - 1);
+      const T k = live ? col[i] : (T)0;
+      const unsigned d = (unsigned)(k >> shift) & (AP_RADIX - 1);
       // lanes of this step that hold my digit: AND over the digit's bits of (ballot if my bit is set, else its complement)
       unsigned long long same = __ballot(live);
 #pragma unroll
@@ -191,7 +201,8 @@ __global__ __launch_bounds__(64) void ap32_scatter_kernel(const unsigned* __rest
 }
 
 // branch-free lower_bound over t[0 .. m), m >= 1: the first index whose key is >= k (m if none)
-__device__ __forceinline__ unsigned ap_lower_bound(const unsigned* t, unsigned m, unsigned k) {
+template <typename T>
+__device__ __forceinline__ unsigned ap_lower_bound(const T* t, unsigned m, T k) {
   unsigned base = 0u, nn = m;
   while (nn > 1u) {
     const unsigned half = nn >> 1;
@@ -210,20 +221,29 @@ __device__ __forceinline__ unsigned ap_lower_bound(const unsigned* t, unsigned m
 //   distinct scores, 14.5 of 17.9 with heavy ties).
 // * FALLBACK (more positives than that: multi-label targets): every AP_SPLITS-th slice of the column against a table of every sub-th
 //   positive + a second search level in the list itself, one device atomic per counted key (equal counters of a wave merged first).
-__global__ __launch_bounds__(1024) void ap_count_kernel(const unsigned* __restrict__ keys, const unsigned* __restrict__ q_all,
+// * T = the (key, frame) composite (cAP): the column's entry i is (keys[i], i) and the list holds composites; every positive is its own
+//   lower_bound, so the inclusive prefix of cnt at positive i is its 1-based rank in the stable order.  The same LDS bytes hold
+//   fewer 8-byte entries: OWN 5456 instead of 8192, a fallback table of 8192 instead of 16384.
+template <typename T> struct ApLds {
+  static constexpr unsigned OWN = sizeof(T) == 4 ? AP_OWN : (AP_TAB * 4 / (sizeof(T) + 4)) / 16 * 16;    // entries + their counters
+  static constexpr unsigned TAB = AP_TAB * 4 / sizeof(T);                                                // entries alone (fallback)
+};
+template <typename T>
+__global__ __launch_bounds__(1024) void ap_count_kernel(const unsigned* __restrict__ keys, const T* __restrict__ q_all,
                                                         const unsigned* __restrict__ len, long long n, int C, unsigned* __restrict__ cnt_all,
                                                         double* __restrict__ partial) {
-  extern __shared__ unsigned ap_lds[];
-  unsigned* tab = ap_lds;                                  // AP_OWN keys + AP_OWN counters, or AP_TAB keys (fallback)
-  unsigned* lc = ap_lds + AP_OWN;
+  extern __shared__ __align__(16) unsigned ap_lds[];
+  constexpr unsigned OWN = ApLds<T>::OWN, TABN = ApLds<T>::TAB;
+  T* tab = (T*)ap_lds;                                     // OWN entries + OWN counters, or TABN entries (fallback)
+  unsigned* lc = (unsigned*)(tab + OWN);
   double* red = (double*)(ap_lds + AP_TAB);                // 16 wave sums
   const int c = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int S = gridDim.x;
   const unsigned P = len[c];
-  const unsigned* q = q_all + (size_t)c * n;
+  const T* q = q_all + (size_t)c * n;
   unsigned* cnt = cnt_all + (size_t)c * n;
   const unsigned* col = keys + (size_t)c * n;
-  const unsigned Sb = (P + AP_OWN - 1) / AP_OWN;
+  const unsigned Sb = (P + OWN - 1) / OWN;
   double ss = 0.0;
   if (Sb <= (unsigned)S) {
     // ---- owned ranges (P = 0: one range of nothing, the score mass only) ----
@@ -235,21 +255,22 @@ __global__ __launch_bounds__(1024) void ap_count_kernel(const unsigned* __restri
       const unsigned b0 = min(P, sb * per), b1 = min(P, b0 + per), m = b1 - b0;
       for (unsigned j = tid; j < m; j += 1024) { tab[j] = q[b0 + j]; lc[j] = 0u; }
       const bool open_lo = b0 == 0u;
-      const unsigned klo = open_lo ? 0u : q[b0 - 1];         // a key belongs here iff klo < k <= khi
-      const unsigned khi = m ? q[b1 - 1] : 0u;
+      const T klo = open_lo ? (T)0 : q[b0 - 1];              // a key belongs here iff klo < k <= khi
+      const T khi = m ? q[b1 - 1] : (T)0;
       __syncthreads();
       const long long chunk = (n + Sf - 1) / Sf;
       const long long lo = (long long)sf * chunk, hi = min(n, lo + chunk);
       const bool mass = sb == 0u;                            // one range per slice adds up the scores
       for (long long base = lo; base < hi; base += 4096) {
-        unsigned k[4];
+        T k[4];
         bool mine[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const long long i = base + e * 1024 + tid;
           const bool live = i < hi;
-          k[e] = live ? col[i] : 0xFFFFFFFFu;
-          if (live && mass) ss += (double)ap_key_score(k[e]);
+          const unsigned raw = live ? col[i] : 0xFFFFFFFFu;
+          k[e] = ap_entry<T>(raw, i);
+          if (live && mass) ss += (double)ap_key_score(raw);
           mine[e] = live && m && (open_lo || k[e] > klo) && k[e] <= khi;
         }
         if (!(mine[0] || mine[1] || mine[2] || mine[3])) continue;
@@ -271,21 +292,23 @@ __global__ __launch_bounds__(1024) void ap_count_kernel(const unsigned* __restri
     }
   } else {
     // ---- fallback: one device atomic per counted key ----
-    const unsigned sub = (P + AP_TAB - 1) / AP_TAB;          // >= 2 here
+    const unsigned sub = (P + TABN - 1) / TABN;              // >= 2 here
     const unsigned m = (P + sub - 1) / sub;                  // table entry j = the LAST key of block j (blocks of `sub` keys)
     for (unsigned j = tid; j < m; j += 1024) { const unsigned long long e = (unsigned long long)(j + 1) * sub - 1; tab[j] = q[e < P ? e : P - 1]; }
     __syncthreads();
     const long long chunk = (n + S - 1) / S;
     const long long lo = (long long)blockIdx.x * chunk, hi = min(n, lo + chunk);
     for (long long base = lo; base < hi; base += 4096) {
-      unsigned k[4], b[4];
+      T k[4];
+      unsigned b[4];
       bool live[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const long long i = base + e * 1024 + tid;
         live[e] = i < hi;
-        k[e] = live[e] ? col[i] : 0xFFFFFFFFu;
-        if (live[e]) ss += (double)ap_key_score(k[e]);
+        const unsigned raw = live[e] ? col[i] : 0xFFFFFFFFu;
+        k[e] = ap_entry<T>(raw, i);
+        if (live[e]) ss += (double)ap_key_score(raw);
       }
       {                                                       // four searches in step (same trip count for every lane)
         unsigned bs[4] = {0u, 0u, 0u, 0u}, nn = m;
@@ -417,6 +440,84 @@ __global__ __launch_bounds__(256) void ap_reduce_kernel(const unsigned* __restri
   }
 }
 
+// ================================================================================================================================
+// Calibrated average precision (step_recognition/utils/metrics.py:10-22, metric 'cAP'): the order is descending score and, inside a
+// run of equal scores, ascending frame index (the host form's stable sort; the reference's unstable argsort leaves ties to chance).
+// The same pipeline over (key, frame) composites: ap_extract<.., ap_u64> appends (key << 32 | frame) per positive, the radix passes
+// run over the frame's digits (as many as n - 1 has) and then the key's four, ap_count<ap_u64> counts every (key, frame) of the column
+// against the list.  Composites are distinct, so a positive is its own lower_bound and the inclusive prefix of cnt at positive i is
+// rank_i, its 1-based position among all n frames.  With tps = i + 1, fps = rank_i - tps, w = (n - P) / P, eps = 2^-52:
+//   cAP = (1 / P) * sum_i tps / (tps + fps / (w + eps) + eps)
+//   cap_reduce   one workgroup per class: running prefix of cnt, the terms accumulated per thread in index order, then the wave
+//                and workgroup trees of ap_reduce: a fixed order, the same bits on every run.
+// ================================================================================================================================
+#define CAP_EPS 2.220446049250313e-16     // 2^-52, numpy's finfo(float).eps
+
+__device__ __forceinline__ double cap_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
+
+__global__ __launch_bounds__(256) void cap_reduce_kernel(const unsigned* __restrict__ cnt_all, const unsigned* __restrict__ len, long long n,
+                                                         int C, const double* __restrict__ partial, int splits, double* __restrict__ ap,
+                                                         long long* __restrict__ n_pos, double* __restrict__ score_sum) {
+  __shared__ long long w_sum[4];
+  __shared__ double w_acc[4];
+  __shared__ long long carry_cnt;
+  const int c = blockIdx.x;
+  const long long P = (long long)len[c];
+  const unsigned* cnt = cnt_all + (size_t)c * n;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) carry_cnt = 0;
+  __syncthreads();
+  const double wd = (double)(n - P) / (double)P + CAP_EPS;                    // P = 0: no term is formed
+  double acc = 0.0;
+  for (long long base = 0; base < P; base += 1024) {
+    const long long j = base + (long long)tid * 4;
+    long long v[4], mine = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { v[e] = j + e < P ? (long long)cnt[j + e] : 0; mine += v[e]; }
+    long long incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const long long u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
+    if (lane == 63) w_sum[wave] = incl;
+    __syncthreads();
+    long long seen = carry_cnt + incl - mine;                                 // frames in front of my first element
+    for (int w = 0; w < wave; ++w) seen += w_sum[w];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      seen += v[e];                                                           // rank of positive j + e
+      if (j + e < P) {
+        const double tps = (double)(j + e + 1), fps = (double)(seen - (j + e + 1));
+        acc += tps / (tps + fps / wd + CAP_EPS);
+      }
+    }
+    __syncthreads();
+    if (tid == 255) carry_cnt = seen;
+    __syncthreads();
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if (lane == 0) w_acc[wave] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    const double a = (w_acc[0] + w_acc[1]) + (w_acc[2] + w_acc[3]);
+    ap[c] = P > 0 ? a / (double)P : cap_nan();
+    if (n_pos) n_pos[c] = P;
+    if (score_sum) {
+      double t = 0.0;
+      for (int sp = 0; sp < splits; ++sp) t += partial[(size_t)sp * C + c];
+      score_sum[c] = t;
+    }
+  }
+}
+
+// n_frames == 0: NaN, no positives, no score mass
+__global__ void cap_empty_kernel(int C, double* __restrict__ ap, long long* __restrict__ n_pos, double* __restrict__ score_sum) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  ap[c] = cap_nan();
+  if (n_pos) n_pos[c] = 0;
+  if (score_sum) score_sum[c] = 0.0;
+}
+
 static int ap_splits(int C) {
   int s = 1024 / C;                      // workgroups per class: 16 (owned ranges up to 131 072 positives per class) or, for few classes, enough to fill the chip
   return s < 16 ? 16 : (s > AP_SPLITS_MAX ? AP_SPLITS_MAX : s);
@@ -427,42 +528,56 @@ size_t perframe_ap_workspace_bytes(long long n, int C) {
   return 4 * (size_t)C * (size_t)n * 4 + (size_t)C * AP_RADIX * ntiles * 4 + (size_t)C * 4 + 8 + (size_t)AP_SPLITS_MAX * C * 8 + 1024;
 }
 
+// the calibrated metric's lists hold 8 bytes per entry (+ 8 to align them behind the keys)
+size_t perframe_cap_workspace_bytes(long long n, int C) { return perframe_ap_workspace_bytes(n, C) + 2 * (size_t)C * (size_t)n * 4 + 8; }
+
 // what the per-frame and the per-stage metric share: keys, every class's positives sorted, every score counted against them
+// (T = unsigned: by key, AP; T = ap_u64: by (key, frame), cAP)
+template <typename T>
 struct ApRanked {
   unsigned* keys;      // [C][n] order-reversing keys, class-major
-  unsigned* q;         // [C][n] class c: its len[c] positives ascending (descending score)
-  unsigned* cnt;       // [C][n] class c: cnt[b] = scores whose lower_bound in q is b (nonzero at the first member of a tie run only)
+  T* q;                // [C][n] class c: its len[c] positives ascending (descending score)
+  unsigned* cnt;       // [C][n] class c: cnt[b] = entries whose lower_bound in q is b (AP: nonzero at the first member of a tie run only)
   unsigned* len;       // [C] positives per class
   double* partial;     // [splits][C] score mass
   int splits;
 };
 
-static ApRanked ap_rank_positives(const float* scores, const float* target, const int* labels, long long n, int C, void* ws, hipStream_t s) {
+template <typename T>
+static ApRanked<T> ap_rank_positives(const float* scores, const float* target, const int* labels, long long n, int C, void* ws, hipStream_t s) {
   static DeviceOnce once;
-  once.run([] { (void)hipFuncSetAttribute((const void*)ap_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, AP_TAB * 4 + 128); });
+  once.run([] { (void)hipFuncSetAttribute((const void*)ap_count_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, AP_TAB * 4 + 128); });
   const int ntiles = (int)((n + AP_TILE - 1) / AP_TILE);
   const size_t cn = (size_t)C * (size_t)n;
   unsigned* keys = (unsigned*)ws;
-  unsigned* p0 = keys + cn;
-  unsigned* p1 = p0 + cn;
-  unsigned* cnt = p1 + cn;
+  T* p0 = (T*)(((uintptr_t)(keys + cn) + sizeof(T) - 1) & ~(uintptr_t)(sizeof(T) - 1));
+  T* p1 = p0 + cn;
+  unsigned* cnt = (unsigned*)(p1 + cn);
   unsigned* hist = cnt + cn;
   unsigned* cursor = hist + (size_t)C * AP_RADIX * ntiles;
   double* partial = (double*)(((uintptr_t)(cursor + C) + 7) & ~(uintptr_t)7);
   (void)hipMemsetAsync(cursor, 0, (size_t)C * 4, s);
   const dim3 xg((unsigned)((n + AP_XF - 1) / AP_XF), (unsigned)((C + AP_XC - 1) / AP_XC));
-  if (labels) ap_extract_kernel<true><<<xg, 256, 0, s>>>(scores, nullptr, labels, n, C, keys, p0, cursor);
-  else ap_extract_kernel<false><<<xg, 256, 0, s>>>(scores, target, nullptr, n, C, keys, p0, cursor);
+  if (labels) ap_extract_kernel<true, T><<<xg, 256, 0, s>>>(scores, nullptr, labels, n, C, keys, p0, cursor);
+  else ap_extract_kernel<false, T><<<xg, 256, 0, s>>>(scores, target, nullptr, n, C, keys, p0, cursor);
   const int tg = ntiles < AP_TGRID ? ntiles : AP_TGRID;
-  for (int p = 0; p < AP_PASSES; ++p) {
-    ap32_hist_kernel<<<dim3(tg, C), 64, 0, s>>>(p0, cursor, n, ntiles, 8 * p, hist, p == 0 ? cnt : nullptr);
+  // digit shifts, least significant first: the key's four, below them (composites) the digits that frame indices up to n - 1 have
+  int shifts[8], np = 0;
+  if (sizeof(T) == 8) {
+    for (int p = 0; p < 4 && ((n - 1) >> (8 * p)) != 0; ++p) shifts[np++] = 8 * p;
+    for (int p = 0; p < AP_PASSES; ++p) shifts[np++] = 32 + 8 * p;
+  } else {
+    for (int p = 0; p < AP_PASSES; ++p) shifts[np++] = 8 * p;
+  }
+  for (int p = 0; p < np; ++p) {
+    ap32_hist_kernel<T><<<dim3(tg, C), 64, 0, s>>>(p0, cursor, n, ntiles, shifts[p], hist, p == 0 ? cnt : nullptr);
     ap32_scan_kernel<<<C, 256, 0, s>>>(hist, cursor, ntiles);
-    ap32_scatter_kernel<<<dim3(tg, C), 64, 0, s>>>(p0, p1, cursor, n, ntiles, 8 * p, hist);
-    unsigned* t = p0; p0 = p1; p1 = t;
+    ap32_scatter_kernel<T><<<dim3(tg, C), 64, 0, s>>>(p0, p1, cursor, n, ntiles, shifts[p], hist);
+    T* t = p0; p0 = p1; p1 = t;
   }
   const int splits = ap_splits(C);
-  ap_count_kernel<<<dim3(splits, C), 1024, AP_TAB * 4 + 128, s>>>(keys, p0, cursor, n, C, cnt, partial);
-  return ApRanked{keys, p0, cnt, cursor, partial, splits};
+  ap_count_kernel<T><<<dim3(splits, C), 1024, AP_TAB * 4 + 128, s>>>(keys, p0, cursor, n, C, cnt, partial);
+  return ApRanked<T>{keys, p0, cnt, cursor, partial, splits};
 }
 
 // Returns 0, or -1 on a bad argument.  ws must hold perframe_ap_workspace_bytes(n, C) bytes.  Positives: target != 0, or (labels != NULL)
@@ -470,8 +585,21 @@ static ApRanked ap_rank_positives(const float* scores, const float* target, cons
 int launch_perframe_ap(const float* scores, const float* target, const int* labels, long long n, int C, double* ap, long long* n_pos,
                        double* score_sum, void* ws, hipStream_t s) {
   if (n <= 0 || C <= 0 || C > 65535 || n >= (1ll << 31)) return -1;    // per-class cursors are 32-bit
-  const ApRanked r = ap_rank_positives(scores, target, labels, n, C, ws, s);
+  const ApRanked<unsigned> r = ap_rank_positives<unsigned>(scores, target, labels, n, C, ws, s);
   ap_reduce_kernel<<<C, 256, 0, s>>>(r.q, r.cnt, r.len, n, C, r.partial, r.splits, ap, n_pos, score_sum);
+  return 0;
+}
+
+// The calibrated metric, same arguments.  ws must hold perframe_cap_workspace_bytes(n, C) bytes (n > 0); n == 0 writes NaN / 0 / 0.0.
+int launch_perframe_cap(const float* scores, const float* target, const int* labels, long long n, int C, double* ap, long long* n_pos,
+                        double* score_sum, void* ws, hipStream_t s) {
+  if (n < 0 || C <= 0 || C > 65535 || n >= (1ll << 31)) return -1;     // frame indices and per-class cursors are 32-bit
+  if (n == 0) {
+    cap_empty_kernel<<<(C + 255) / 256, 256, 0, s>>>(C, ap, n_pos, score_sum);
+    return 0;
+  }
+  const ApRanked<ap_u64> r = ap_rank_positives<ap_u64>(scores, target, labels, n, C, ws, s);
+  cap_reduce_kernel<<<C, 256, 0, s>>>(r.cnt, r.len, n, C, r.partial, r.splits, ap, n_pos, score_sum);
   return 0;
 }
 
@@ -564,9 +692,11 @@ __global__ __launch_bounds__(256) void ps_carry_kernel(int* __restrict__ bl_head
   ps_block_scan<2, false>(off, C, 0, wsum, &carry);                     // positives of the classes in front (their sum is <= n < 2^31)
 }
 
+// T = the (key, frame) composite (cAP): the lower_bound of a positive is its own index, st_cs marks the stage's members
+template <typename T>
 __global__ __launch_bounds__(256) void ps_stage_kernel(const float* __restrict__ scores, const int* __restrict__ labels, long long n, int C,
                                                        const int* __restrict__ carry_head, const int* __restrict__ carry_tail,
-                                                       const unsigned* __restrict__ q_all, const unsigned* __restrict__ len,
+                                                       const T* __restrict__ q_all, const unsigned* __restrict__ len,
                                                        const int* __restrict__ off, unsigned* __restrict__ st) {
   __shared__ int wh[4], wt[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -625,7 +755,7 @@ __global__ __launch_bounds__(256) void ps_stage_kernel(const float* __restrict__
     if (!mask) continue;                                    // the last frame of a run of two or more
     const unsigned P = len[c];
     if (P == 0u) continue;
-    const unsigned k = ap_desc_key(scores[(size_t)i * C + c]);
+    const T k = ap_entry<T>(ap_desc_key(scores[(size_t)i * C + c]), i);
     const unsigned lb = ap_lower_bound(q_all + (size_t)c * n, P, k);
     if (lb >= P) continue;                                  // cannot happen: k is in the list
     unsigned* dst = st + (size_t)off[c] + lb;
@@ -727,15 +857,91 @@ __global__ __launch_bounds__(256) void ps_reduce_kernel(const unsigned* __restri
   }
 }
 
-static size_t ps_base_bytes(long long n, int C) { return (perframe_ap_workspace_bytes(n, C) + 15) & ~(size_t)15; }
-
-size_t perstage_ap_workspace_bytes(long long n, int C) {
-  const size_t nblk = (size_t)((n + PS_BLK - 1) / PS_BLK);
-  return ps_base_bytes(n, C) + (size_t)PS_STAGES * (size_t)n * 4 + (size_t)C * 4 + 2 * nblk * 4 + 64;
+// Per-stage calibrated average precision (metrics='cAP'): one workgroup per (class, stage) over cnt_c (ranks in the stable order) and
+// the stage's member flags st_cs.  A first walk counts the members P_cs (w = (n - P_c) / P_cs needs it before the first term); the
+// second keeps two running prefixes and accumulates, for a member at index i with rank r, tps / (tps + fps / (w + eps) + eps) with
+// tps = the members up to i and fps = r - (i + 1), the negatives in front of it - per thread in index order, then fixed trees.
+__global__ __launch_bounds__(256) void cps_reduce_kernel(const unsigned* __restrict__ cnt_all, const unsigned* __restrict__ len, long long n,
+                                                         int C, const unsigned* __restrict__ st_all, const int* __restrict__ off,
+                                                         double* __restrict__ ap, long long* __restrict__ n_pos) {
+  __shared__ long long w_sum[4], w_st[4];
+  __shared__ double w_acc[4];
+  __shared__ long long carry_cnt, carry_st, members;
+  const int c = blockIdx.x, sg = blockIdx.y;
+  const long long P = (long long)len[c];
+  const unsigned* cnt = cnt_all + (size_t)c * n;
+  const unsigned* st = st_all + (size_t)sg * n + (size_t)off[c];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  long long ms = 0;
+  for (long long j = tid; j < P; j += 256) ms += (long long)st[j];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ms += __shfl_xor(ms, o, 64);
+  if (lane == 0) w_sum[wave] = ms;
+  if (tid == 0) { carry_cnt = 0; carry_st = 0; }
+  __syncthreads();
+  if (tid == 0) members = (w_sum[0] + w_sum[1]) + (w_sum[2] + w_sum[3]);
+  __syncthreads();
+  const long long Ps = members;
+  const double wd = (double)(n - P) / (double)Ps + CAP_EPS;                   // Ps = 0: no term is formed
+  double acc = 0.0;
+  for (long long base = 0; base < P; base += 1024) {
+    const long long j = base + (long long)tid * 4;
+    long long v[4], u[4], mine = 0, mine_st = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[e] = j + e < P ? (long long)cnt[j + e] : 0;
+      u[e] = j + e < P ? (long long)st[j + e] : 0;
+      mine += v[e];
+      mine_st += u[e];
+    }
+    long long incl = mine, incl_st = mine_st;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const long long x = __shfl_up(incl, o, 64), y = __shfl_up(incl_st, o, 64);
+      if (lane >= o) { incl += x; incl_st += y; }
+    }
+    if (lane == 63) { w_sum[wave] = incl; w_st[wave] = incl_st; }
+    __syncthreads();
+    long long seen = carry_cnt + incl - mine;               // frames of the column in front of my first element
+    long long tps = carry_st + incl_st - mine_st;           // stage members in front of it
+    for (int w = 0; w < wave; ++w) { seen += w_sum[w]; tps += w_st[w]; }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      seen += v[e];
+      tps += u[e];
+      if (u[e]) {
+        const double t = (double)tps, fps = (double)(seen - (j + e + 1));
+        acc += t / (t + fps / wd + CAP_EPS);
+      }
+    }
+    __syncthreads();
+    if (tid == 255) { carry_cnt = seen; carry_st = tps; }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if (lane == 0) w_acc[wave] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    const double a = (w_acc[0] + w_acc[1]) + (w_acc[2] + w_acc[3]);
+    ap[(size_t)sg * C + c] = Ps > 0 ? a / (double)Ps : cap_nan();           // no member: NaN, as the host form
+    if (n_pos) n_pos[(size_t)sg * C + c] = Ps;
+  }
 }
 
-// Returns 0, or -1 on a bad argument.  ws must hold perstage_ap_workspace_bytes(n, C) bytes (n > 0).  ap / n_pos: [10][C].
-int launch_perstage_ap(const float* scores, const int* labels, long long n, int C, double* ap, long long* n_pos, void* ws, hipStream_t s) {
+template <typename T> static size_t ps_base_bytes(long long n, int C) {
+  return ((sizeof(T) == 4 ? perframe_ap_workspace_bytes(n, C) : perframe_cap_workspace_bytes(n, C)) + 15) & ~(size_t)15;
+}
+template <typename T> static size_t ps_workspace_bytes(long long n, int C) {
+  const size_t nblk = (size_t)((n + PS_BLK - 1) / PS_BLK);
+  return ps_base_bytes<T>(n, C) + (size_t)PS_STAGES * (size_t)n * 4 + (size_t)C * 4 + 2 * nblk * 4 + 64;
+}
+
+size_t perstage_ap_workspace_bytes(long long n, int C) { return ps_workspace_bytes<unsigned>(n, C); }
+size_t perstage_cap_workspace_bytes(long long n, int C) { return ps_workspace_bytes<ap_u64>(n, C); }
+
+template <typename T>
+static int perstage_launch(const float* scores, const int* labels, long long n, int C, double* ap, long long* n_pos, void* ws, hipStream_t s) {
   if (n < 0 || C <= 0 || C > 65535 || n >= (1ll << 31)) return -1;
   if (n == 0) {
     (void)hipMemsetAsync(ap, 0, (size_t)PS_STAGES * C * 8, s);
@@ -743,15 +949,25 @@ int launch_perstage_ap(const float* scores, const int* labels, long long n, int 
     return 0;
   }
   const int nblk = (int)((n + PS_BLK - 1) / PS_BLK);
-  unsigned* st = (unsigned*)((char*)ws + ps_base_bytes(n, C));
+  unsigned* st = (unsigned*)((char*)ws + ps_base_bytes<T>(n, C));
   int* off = (int*)(st + (size_t)PS_STAGES * (size_t)n);
   int* bl_head = off + C;
   int* bl_tail = bl_head + nblk;
-  const ApRanked r = ap_rank_positives(scores, nullptr, labels, n, C, ws, s);
+  const ApRanked<T> r = ap_rank_positives<T>(scores, nullptr, labels, n, C, ws, s);
   (void)hipMemsetAsync(st, 0, (size_t)PS_STAGES * (size_t)n * 4, s);
   ps_edges_kernel<<<nblk, 256, 0, s>>>(labels, n, bl_head, bl_tail);
   ps_carry_kernel<<<1, 256, 0, s>>>(bl_head, bl_tail, nblk, r.len, C, off);
-  ps_stage_kernel<<<nblk, 256, 0, s>>>(scores, labels, n, C, bl_head, bl_tail, r.q, r.len, off, st);
-  ps_reduce_kernel<<<dim3(C, PS_STAGES), 256, 0, s>>>(r.q, r.cnt, r.len, n, C, st, off, ap, n_pos);
+  ps_stage_kernel<T><<<nblk, 256, 0, s>>>(scores, labels, n, C, bl_head, bl_tail, r.q, r.len, off, st);
+  if constexpr (sizeof(T) == 4) ps_reduce_kernel<<<dim3(C, PS_STAGES), 256, 0, s>>>(r.q, r.cnt, r.len, n, C, st, off, ap, n_pos);
+  else cps_reduce_kernel<<<dim3(C, PS_STAGES), 256, 0, s>>>(r.cnt, r.len, n, C, st, off, ap, n_pos);
   return 0;
+}
+
+// Returns 0, or -1 on a bad argument.  ws must hold perstage_ap_workspace_bytes(n, C) bytes (n > 0).  ap / n_pos: [10][C].
+int launch_perstage_ap(const float* scores, const int* labels, long long n, int C, double* ap, long long* n_pos, void* ws, hipStream_t s) {
+  return perstage_launch<unsigned>(scores, labels, n, C, ap, n_pos, ws, s);
+}
+// The calibrated metric by stage: ws must hold perstage_cap_workspace_bytes(n, C) bytes (n > 0); NaN where a (stage, class) has no member.
+int launch_perstage_cap(const float* scores, const int* labels, long long n, int C, double* ap, long long* n_pos, void* ws, hipStream_t s) {
+  return perstage_launch<ap_u64>(scores, labels, n, C, ap, n_pos, ws, s);
 }

@@ -53,9 +53,14 @@ class Evaluate(nn.Module):
         self._cache = EvalFeatureCache(cfg.get("eval_cache_max_bytes")) if cfg.get("eval_cache_device", False) else None
         self.last_source = None              # "loader" | "cache": where the last call took its features from
         # cfg['eval_perstage'] (not a reference key, off by default): the per-stage AP report of the pass (utils/metrics.py:64-130 with
-        # metrics='AP', `prego_perstage_ap_labels`) is kept here and each stage's mean is logged; what eval returns and writes is unchanged
+        # metrics='AP', `prego_perstage_ap_labels`) is kept here and each stage's mean is logged; what eval returns and writes is unchanged.
+        # cfg['eval_perstage_metric']: 'AP' (the default, whatever cfg['metric'] is) or 'cAP' (`prego_perstage_cap_labels`)
         self.perstage = bool(cfg.get("eval_perstage", False))
+        self.perstage_metric = cfg.get("eval_perstage_metric", "AP")
+        if self.perstage_metric not in ("AP", "cAP"):
+            raise RuntimeError(f"Unknown eval_perstage_metric: {self.perstage_metric}")
         self.last_perstage = None
+        self.last_metric_path = None         # "device" | "host": where the last call computed cfg['metric']
 
     @staticmethod
     def _new_copy_stream(dev):
@@ -508,8 +513,8 @@ class Evaluate(nn.Module):
             rec = self._flush(model, batch, device, resident)
             self._scores(rec, pred_scores, gt_targets)
             finish_ap = None
-            if world == 1 and torch.device(device).type == "cuda" and self.metric == "AP" and pred_scores:
-                # the metric in libprego_amd.so (prego_perframe_ap), ENQUEUED here behind the last forward and collected behind the
+            if world == 1 and torch.device(device).type == "cuda" and pred_scores:
+                # the metric in libprego_amd.so (prego_perframe_ap, or prego_perframe_cap for metric 'cAP'), ENQUEUED here behind the last forward and collected behind the
                 # output file: the GPU ranks the positives while the host waits for the ids and writes the JSON
                 # ... on a stream of its own behind an event, so that model.check() below (which drains the forward's stream to read its
                 # timeout word) does not wait for the metric as well
@@ -542,10 +547,11 @@ class Evaluate(nn.Module):
                 fwd_done.record(torch.cuda.current_stream(torch.device(device)))
                 with torch.cuda.stream(self._ap_stream):
                     self._ap_stream.wait_event(fwd_done)
-                    if finish_ap is None:                 # metric 'cAP': the per-frame metric runs on the host, nothing is concatenated yet
+                    if finish_ap is None:                 # nothing is concatenated yet
                         pred_all = torch.cat(pred_scores, 0)
                         gt_all = self._cat_targets(gt_targets).to(pred_all.device)
-                    ps_fn = perstage_average_precision_device(pred_all.to(device), gt_all.to(device), self.all_class_names, defer=True)
+                    ps_fn = perstage_average_precision_device(pred_all.to(device), gt_all.to(device), self.all_class_names, defer=True,
+                                                              metrics=self.perstage_metric)
 
                 def finish_ps(_fn=ps_fn, _s=self._ap_stream):
                     with torch.cuda.stream(_s):
@@ -586,7 +592,7 @@ class Evaluate(nn.Module):
             if finish_ap is None:
                 pred_all = torch.cat(pred_scores, 0) if pred_scores else torch.zeros((0, len(self.all_class_names)))
                 gt_all = self._cat_targets(gt_targets, matrix=True).to(pred_all.device) if gt_targets else torch.zeros_like(pred_all)
-                if torch.device(device).type == "cuda" and self.metric == "AP":        # an empty eval set: the empty report
+                if torch.device(device).type == "cuda":        # an empty eval set: the empty report
                     finish_ap = perframe_average_precision_device(pred_all.to(device), gt_all.to(device), self.all_class_names,
                                                                   self.data_processing, self.metric, defer=True)
             num_frames = int(gt_all.shape[0])
@@ -600,10 +606,11 @@ class Evaluate(nn.Module):
                     else:
                         file.write(self._json_int_lists(output))
             mark("json_written")
+            self.last_metric_path = "device" if finish_ap is not None else "host"
             if finish_ap is not None:
                 result = finish_ap()
                 mark("ap_done")
-            else:       # a stand-in model on a CPU box (the gloo tests of the sharding logic), or metric 'cAP' (TVSeries' calibrated variant: host path only)
+            else:       # a stand-in model on a CPU box (the gloo tests of the sharding logic)
                 result = perframe_average_precision(pred_all.cpu().numpy(), gt_all.cpu().numpy(), self.all_class_names, self.data_processing, self.metric)
             t_end = time.time()
             time_taken = max(t_end - t_begin, 1e-9)
@@ -660,8 +667,10 @@ class Evaluate(nn.Module):
         if mine == 0:
             raw = (np.zeros(0), np.zeros(0, np.int64), np.zeros(0))
         elif p_cols.is_cuda and self.metric == "AP":
+            self.last_metric_path = "device"
             raw = perframe_ap_raw_device(p_cols, g_cols)
-        else:
+        else:                                # a CPU box, or metric 'cAP' (its class-sharded form keeps the host path)
+            self.last_metric_path = "host"
             raw = perframe_ap_raw(p_cols.cpu().numpy(), g_cols.cpu().numpy(), self.metric)
         width = max(cb[q + 1] - cb[q] for q in range(world))
         pack = torch.zeros((3, width), dtype=torch.float64, device=pred.device)
@@ -694,8 +703,9 @@ class AntEvaluate(nn.Module):
     the per-step mAP.  `self.result` holds what the reference's `result` holds: the OAD report (`mean_AP`, per class) and
     `anticipation_{l+1}` = the report of step l.
     A model with `forward_clips` on a GPU (MiniROADA) is fed whole videos in batches (one ragged forward per batch, anticipation head
-    included) and metric 'AP' is computed on the device (`prego_perframe_ap`); metric 'cAP' uses the host path, and so does a stand-in
-    model without `forward_clips` (called per loader batch, as the reference does)."""
+    included); on a CUDA device metric 'AP' (`prego_perframe_ap`) and metric 'cAP' (`prego_perframe_cap`) are computed there, for the
+    OAD scores and every anticipation step.  A stand-in model on the CPU (called per loader batch, as the reference does) uses the
+    host path.  `last_metric_path` ('device' or 'host') says what ran."""
 
     def __init__(self, cfg):
         super().__init__()
@@ -709,10 +719,13 @@ class AntEvaluate(nn.Module):
         self.max_frames_per_batch = int(cfg.get("eval_frames_per_batch", 4_000_000))
         self.result = None
         self.last_fps = None
+        self.last_metric_path = None
 
     def _metric(self, pred, gt):
-        if self.metric == "AP" and pred.is_cuda:
-            return perframe_average_precision_device(pred, gt.to(pred.device, torch.float32), self.all_class_names)
+        if pred.is_cuda:
+            self.last_metric_path = "device"
+            return perframe_average_precision_device(pred, gt.to(pred.device, torch.float32), self.all_class_names, None, self.metric)
+        self.last_metric_path = "host"
         return perframe_average_precision(pred.cpu().numpy(), gt.cpu().numpy(), self.all_class_names, None, self.metric)
 
     def eval(self, model, dataloader, logger, device=None):

@@ -12,8 +12,10 @@ reference always treats as background (metrics.py:44-48).  Two routes to the sam
                                            so that the [frames x classes] score matrix of an eval pass never leaves the device.
                                            No CPU fallback.
 
-`metric: 'cAP'` (the reference's calibrated variant for TVSeries, metrics.py:10-22; unreachable from the shipped configs) runs on the
-host path only; `Evaluate` moves the matrices to the host for it.
+`metric: 'cAP'` (the reference's calibrated variant for TVSeries, metrics.py:10-22) has the same two routes:
+`calibrated_average_precision_columns` on the host and `perframe_average_precision_device(..., metrics='cAP')`
+(`prego_perframe_cap` / `prego_perframe_cap_labels`) on the device.  Both rank frames of equal score in frame order (the reference's
+unstable argsort leaves ties to chance), so they agree up to the order of one fp64 sum.
 
 Per-stage average precision (the reference's `perstage_average_precision`, metrics.py:64-130, from LSTR):
 how early inside an action it is recognised.  Per class the action instances are the maximal runs of positive frames over the whole
@@ -27,8 +29,9 @@ frame of the class plus the stage's frames of every run; its AP is the one above
                                            positives, as `calibrated_average_precision_columns` documents); dense targets or ids.
   * `perstage_average_precision_device`  - the HIP path, `prego_perstage_ap_labels` (csrc/metrics.hip): runs and stage masks from
                                            one class id per frame, the per-frame pipeline's ranks, one counter per (stage, positive).
-                                           'AP' only (cAP depends on the order of ties), no CPU fallback; used by `Evaluate` under
-                                           cfg `eval_perstage`."""
+                                           'AP' or 'cAP' (`prego_perstage_cap_labels`: ties in frame order, NaN without a
+                                           member, as the host form), no CPU fallback; used by `Evaluate` under cfg
+                                           `eval_perstage` (`eval_perstage_metric`)."""
 from __future__ import annotations
 
 from collections import OrderedDict
@@ -121,10 +124,10 @@ def perframe_average_precision(prediction, ground_truth, class_names, postproces
     return _report(cols(pred, truth != 0), (truth != 0).sum(0), pred.sum(0, dtype=np.float64), class_names)
 
 
-def perframe_ap_raw_device(pred, truth):
-    """device counterpart of perframe_ap_raw (metric 'AP'): fp32 CUDA matrices [frames, classes] (truth: or class ids [frames]) -> three host vectors"""
+def perframe_ap_raw_device(pred, truth, metrics="AP"):
+    """device counterpart of perframe_ap_raw (metric 'AP' or 'cAP'): fp32 CUDA matrices [frames, classes] (truth: or class ids [frames]) -> three host vectors"""
     ncls = int(pred.shape[1])
-    fin = perframe_average_precision_device(pred, truth, [str(i) for i in range(ncls)], None, "AP", defer=True, raw=True)
+    fin = perframe_average_precision_device(pred, truth, [str(i) for i in range(ncls)], None, metrics, defer=True, raw=True)
     return fin()
 
 
@@ -132,6 +135,8 @@ def perframe_average_precision_device(prediction, ground_truth, class_names, pos
     """Device path: prediction / ground_truth fp32 CUDA tensors [frames, classes] - or ground_truth = an integer CUDA tensor [frames],
     one class id per frame (what one-hot targets say; an id outside the classes = no positive) -; the sort and the scan run in
     libprego_amd.so (`prego_perframe_ap`), one small device -> host transfer brings back AP, positives and score mass.
+    metrics='cAP': the calibrated metric (`prego_perframe_cap` / `prego_perframe_cap_labels`), frames of equal score in frame order as
+    `calibrated_average_precision_columns` ranks them.
     defer=True: the kernels are only ENQUEUED and a function is returned that waits for them and builds the report (Evaluate writes
     its output file while the GPU sorts)."""
     import ctypes as C
@@ -140,8 +145,9 @@ def perframe_average_precision_device(prediction, ground_truth, class_names, pos
 
     from . import _lib
     from ._lib import PregoError, check
-    if postprocessing is not None or metrics != "AP":
-        raise PregoError("perframe_average_precision_device: metric 'AP' without postprocessing only (what both shipped configs use)")
+    if postprocessing is not None or metrics not in ("AP", "cAP"):
+        raise PregoError("perframe_average_precision_device: metric 'AP' or 'cAP' without postprocessing only")
+    cal = metrics == "cAP"
     if not (prediction.is_cuda and ground_truth.is_cuda):
         raise PregoError("perframe_average_precision_device needs CUDA tensors; there is no CPU fallback "
                          "(host arrays: perframe_average_precision)")
@@ -157,10 +163,14 @@ def perframe_average_precision_device(prediction, ground_truth, class_names, pos
         return (lambda: rep) if defer else rep
     lib = _lib.load()
     dev = pred.device
-    ws = torch.empty(lib.prego_perframe_ap_workspace_bytes(n, ncls), dtype=torch.uint8, device=dev)
+    need = lib.prego_perframe_cap_workspace_bytes if cal else lib.prego_perframe_ap_workspace_bytes
+    ws = torch.empty(need(n, ncls), dtype=torch.uint8, device=dev)
     out = torch.empty((3, ncls), dtype=torch.float64, device=dev)          # AP | positives (int64 bits) | score sums
     with torch.cuda.device(dev):
-        fn = lib.prego_perframe_ap_labels if by_label else lib.prego_perframe_ap
+        if cal:
+            fn = lib.prego_perframe_cap_labels if by_label else lib.prego_perframe_cap
+        else:
+            fn = lib.prego_perframe_ap_labels if by_label else lib.prego_perframe_ap
         check(fn(C.c_void_p(pred.data_ptr()), C.c_void_p(truth.data_ptr()), n, ncls, C.c_void_p(out[0].data_ptr()),
                  C.c_void_p(out[1].data_ptr()), C.c_void_p(out[2].data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
@@ -259,10 +269,12 @@ def perstage_average_precision(prediction, ground_truth, class_names, postproces
     return perstage_report(perstage_ap_raw(pred, truth, metrics)[0], class_names)
 
 
-def perstage_average_precision_device(prediction, labels, class_names, defer=False, raw=False):
-    """Device path (metric 'AP'): prediction fp32 CUDA tensor [frames, classes], labels an integer CUDA tensor [frames] with one class
+def perstage_average_precision_device(prediction, labels, class_names, defer=False, raw=False, metrics="AP"):
+    """Device path: prediction fp32 CUDA tensor [frames, classes], labels an integer CUDA tensor [frames] with one class
     id per frame in evaluation order (an id outside the classes = a negative of every class); `prego_perstage_ap_labels` in
     libprego_amd.so, one small device -> host transfer brings back AP and positives [10, classes].  No CPU fallback.
+    metrics='cAP': the calibrated metric (`prego_perstage_cap_labels`), frames of equal score in frame order; a (class, stage)
+    without a member is NaN, as on the host.
     raw=True: (AP [10, classes], positives [10, classes]) of every class instead of the report.
     defer=True: the kernels are only ENQUEUED and a function is returned that waits for them and builds the result."""
     import ctypes as C
@@ -271,6 +283,9 @@ def perstage_average_precision_device(prediction, labels, class_names, defer=Fal
 
     from . import _lib
     from ._lib import PregoError, check
+    if metrics not in ("AP", "cAP"):
+        raise PregoError(f"perstage_average_precision_device: metrics {metrics!r} ('AP' or 'cAP')")
+    cal = metrics == "cAP"
     if not (prediction.is_cuda and labels.is_cuda):
         raise PregoError("perstage_average_precision_device needs CUDA tensors; there is no CPU fallback "
                          "(host arrays: perstage_average_precision)")
@@ -288,12 +303,14 @@ def perstage_average_precision_device(prediction, labels, class_names, defer=Fal
         return (lambda: rep) if defer else rep
     lib = _lib.load()
     dev = pred.device
-    ws = torch.empty(lib.prego_perstage_ap_workspace_bytes(n, ncls), dtype=torch.uint8, device=dev)
+    need = lib.prego_perstage_cap_workspace_bytes if cal else lib.prego_perstage_ap_workspace_bytes
+    ws = torch.empty(need(n, ncls), dtype=torch.uint8, device=dev)
     out = torch.empty((2, N_STAGES, ncls), dtype=torch.float64, device=dev)          # AP | positives (int64 bits)
     with torch.cuda.device(dev):
-        check(lib.prego_perstage_ap_labels(C.c_void_p(pred.data_ptr()), C.c_void_p(ids.data_ptr()), n, ncls, C.c_void_p(out[0].data_ptr()),
-                                           C.c_void_p(out[1].data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
-                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        fn = lib.prego_perstage_cap_labels if cal else lib.prego_perstage_ap_labels
+        check(fn(C.c_void_p(pred.data_ptr()), C.c_void_p(ids.data_ptr()), n, ncls, C.c_void_p(out[0].data_ptr()),
+                 C.c_void_p(out[1].data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
+                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     def finish(_keep=(pred, ids, ws)):
         host = out.cpu().numpy()
         if raw:
