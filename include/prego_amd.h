@@ -8,7 +8,8 @@
  * Conventions
  *  - extern "C", plain pointers and sizes only; no torch / HIP types in signatures
  *    (`prego_stream_t` is a `hipStream_t` passed as void*; NULL = the default stream).
- *  - every pointer called "device" is HBM memory of the current HIP device, fp32, row-major contiguous.
+ *  - every pointer called "device" is HBM memory of the current HIP device, fp32, row-major contiguous (the one exception: the
+ *    inputs of prego_thumos_postprocess carry a row stride, ld_scores / ld_target, in elements).
  *  - functions return 0 on success, a negative PREGO_E* code otherwise; prego_last_error() gives the text.
  *  - calls only enqueue work on the caller's stream; nothing waits for the END of device work except prego_miniroad_check().  One
  *    documented wait for a START: a prego_miniroad_forward() that runs the split pass returns once the stream has reached its two
@@ -522,6 +523,37 @@ int prego_perframe_cap_labels(const float* scores, const int32_t* labels, int64_
 size_t prego_perstage_cap_workspace_bytes(int64_t n_frames, int n_classes);
 int prego_perstage_cap_labels(const float* scores, const int32_t* labels, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
                               void* workspace, size_t workspace_bytes, prego_stream_t stream);
+/* utils/postprocessing.py:4-29 on the device: what the reference applies in front of every metric when the data set is THUMOS.
+ * scores: device fp32, n_frames rows of n_classes values, row stride ld_scores ELEMENTS (>= n_classes; step l of an [n][L][C] tensor is
+ * scores + l C with ld_scores = L C, no copy); target: the same with ld_target, or labels: device int32 [n_frames], one class id per frame.
+ * In the reference's order:
+ *   1. PREGO_THUMOS_SMOOTH: s'[i][c] = max over d in (0, -1, +1, -2, +2) of s[j][c], j = i + d if 0 <= i + d < n_frames, else j = i -
+ *      bit for bit the reference's five shifted copies for n_frames >= 2; for n_frames == 1 (where the reference's np.squeeze drops
+ *      the frame axis and its result is ill-defined) it is DEFINED by this formula: the row itself.  It runs over the whole matrix
+ *      before any row is removed, across video boundaries, as the reference does.  max is np.maximum: a NaN propagates.
+ *   2. PREGO_THUMOS_SWITCH: s'[i][switch_to] = s'[i][switch_from] where that is greater (5 and 8 in the reference), after smoothing.
+ *   3. row i is kept iff target[i][ambiguous] != 1.0f exactly (a 0.5 keeps the row) / labels[i] != ambiguous (21 in the reference;
+ *      -1: every row is kept).  The kept rows of s' and of target / labels are written to scores_out / target_out (dense, row stride
+ *      n_classes) / labels_out in frame order; *n_valid (device int64) = their number.  The outputs must hold n_frames rows; rows from
+ *      *n_valid on are not written, kept rows are written once, the inputs are never written.
+ * Only comparisons and copies, a block-wise count, a scan of the counts and a scatter (no atomics): the same bits as the reference, on
+ * every run.  The scores are read from HBM once: a smoothing tile of PREGO_THUMOS_TILE_ROWS rows is staged in LDS with two rows above
+ * and below it.  Everything is enqueued on `stream`; nothing is allocated, nothing waits.  Workspace:
+ * prego_thumos_postprocess_workspace_bytes (4 B per tile).  n_frames == 0: returns 0, writes *n_valid = 0, needs no workspace.
+ * PREGO_EINVAL, checked before any launch (outputs, *n_valid and workspace untouched): a NULL input or output (a NULL workspace with
+ * n_frames > 0), a pointer not aligned to its element, n_frames < 0 or >= 2^31, n_classes outside 1 .. 65535, unknown flag bits,
+ * ld_scores / ld_target < n_classes, ambiguous < -1 or >= n_classes, with PREGO_THUMOS_SWITCH a switch column outside [0, n_classes)
+ * or switch_from == switch_to, an output (or the workspace) that overlaps an input; PREGO_EWORKSPACE: workspace_bytes below the query.
+ * An addition to ABI 7 (existing signatures unchanged). */
+enum { PREGO_THUMOS_SMOOTH = 1, PREGO_THUMOS_SWITCH = 2 };
+#define PREGO_THUMOS_TILE_ROWS 128
+size_t prego_thumos_postprocess_workspace_bytes(int64_t n_frames, int n_classes);
+int prego_thumos_postprocess(const float* scores, int64_t ld_scores, const float* target, int64_t ld_target, int64_t n_frames, int n_classes,
+                             int flags, int switch_from, int switch_to, int ambiguous, float* scores_out, float* target_out,
+                             int64_t* n_valid, void* workspace, size_t workspace_bytes, prego_stream_t stream);
+int prego_thumos_postprocess_labels(const float* scores, int64_t ld_scores, const int32_t* labels, int64_t n_frames, int n_classes, int flags,
+                                    int switch_from, int switch_to, int ambiguous, float* scores_out, int32_t* labels_out, int64_t* n_valid,
+                                    void* workspace, size_t workspace_bytes, prego_stream_t stream);
 /* HOST function (no device work): the reference's loader yields fp32 target rows [n_frames][n_classes] per video (one-hot for both
  * shipped configs).  targets: n_videos host pointers, n_frames: their row counts; labels: host int32 [sum of n_frames], the videos one
  * after the other, labels[i] = np.argmax(row i) (eval.py:55, the first maximum); onehot[v] = 1 iff every row of video v holds exactly one

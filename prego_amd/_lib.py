@@ -59,7 +59,10 @@ SYMBOLS = [
     "prego_perstage_ap_workspace_bytes", "prego_perstage_ap_labels",
     "prego_perframe_cap_workspace_bytes", "prego_perframe_cap", "prego_perframe_cap_labels",
     "prego_perstage_cap_workspace_bytes", "prego_perstage_cap_labels",
+    "prego_thumos_postprocess_workspace_bytes", "prego_thumos_postprocess", "prego_thumos_postprocess_labels",
 ]
+THUMOS_SMOOTH, THUMOS_SWITCH = 1, 2          # PREGO_THUMOS_SMOOTH / _SWITCH
+THUMOS_TILE_ROWS = 128                       # PREGO_THUMOS_TILE_ROWS: rows per scatter tile of prego_thumos_postprocess
 # include/prego_amd_debug.h: only in libprego_amd_debug.so
 DEBUG_SYMBOLS = ["prego_miniroad_debug_stamps", "prego_debug_gemm_bf16", "prego_debug_attention_bwd", "prego_debug_attention_fwd",
                  "prego_debug_recurrence_only", "prego_debug_gemm_worker", "prego_debug_head_only",
@@ -178,7 +181,11 @@ def _open(path: str, debug: bool) -> C.CDLL:
     lib.prego_perstage_cap_workspace_bytes.argtypes = [i64, i32]
     lib.prego_perstage_cap_workspace_bytes.restype = sz
     lib.prego_perstage_cap_labels.argtypes = [vp, vp, i64, i32, vp, vp, vp, sz, vp]
-    lib.prego_onehot_labels.argtypes = [i32, C.POINTER(vp), C.POINTER(i64), i32, vp, C.POINTER(C.c_int32)]
+    lib.prego_thumos_postprocess_workspace_bytes.argtypes = [i64, i32]
+    lib.prego_thumos_postprocess_workspace_bytes.restype = sz
+    lib.prego_thumos_postprocess.argtypes = [vp, i64, vp, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
+    lib.prego_thumos_postprocess_labels.argtypes = [vp, i64, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
+    lib.prego_onehot_labels.argtypes =[i32, C.POINTER(vp), C.POINTER(i64), i32, vp, C.POINTER(C.c_int32)]
     f32 = C.c_float
     lib.prego_adamw_step.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), i64, f32, f32, f32, f32, f32, vp]
     lib.prego_miniroad_adamw_step.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i64, f32, f32, f32, f32, f32, vp]

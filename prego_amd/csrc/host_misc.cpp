@@ -134,6 +134,77 @@ extern "C" int prego_perstage_cap_labels(const float* scores, const int32_t* lab
   return PREGO_OK;
 }
 
+// ================================================================================================
+// utils/postprocessing.py:4-29 (THUMOS: 5-frame max, CliffDiving -> Diving, ambiguous frames removed) on the device (thumos_post.hip)
+// ================================================================================================
+extern "C" size_t prego_thumos_postprocess_workspace_bytes(int64_t n_frames, int n_classes) {
+  if (n_frames <= 0 || n_frames >= (1ll << 31) || n_classes <= 0) return 0;
+  return thumos_postprocess_workspace_bytes(n_frames, n_classes);
+}
+static_assert(kThumosTileRows == PREGO_THUMOS_TILE_ROWS, "the header documents the scatter tile");
+static bool thumos_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+static int thumos_common(const float* scores, int64_t ld_scores, const float* target, int64_t ld_target, const int32_t* labels, int64_t n_frames,
+                         int n_classes, int flags, int switch_from, int switch_to, int ambiguous, float* scores_out, float* target_out,
+                         int32_t* labels_out, int64_t* n_valid, void* workspace, size_t workspace_bytes, prego_stream_t stream) {
+  const bool ids = target == nullptr && target_out == nullptr && (labels || labels_out);
+  if (!scores || !scores_out || !n_valid || (ids ? (!labels || !labels_out) : (!target || !target_out)) || (!workspace && n_frames > 0))
+    return prego_fail_(PREGO_EINVAL, "thumos_postprocess: NULL argument");
+  if (n_frames < 0 || n_frames >= (1ll << 31) || n_classes < 1 || n_classes > 65535)
+    return prego_fail_(PREGO_EINVAL, "thumos_postprocess: n_frames %lld (0 .. 2^31 - 1), n_classes %d (1 .. 65535)", (long long)n_frames, n_classes);
+  if (flags & ~(PREGO_THUMOS_SMOOTH | PREGO_THUMOS_SWITCH)) return prego_fail_(PREGO_EINVAL, "thumos_postprocess: flags 0x%x", flags);
+  if (ld_scores < n_classes || (!ids && ld_target < n_classes))
+    return prego_fail_(PREGO_EINVAL, "thumos_postprocess: ld_scores %lld, ld_target %lld below n_classes %d", (long long)ld_scores,
+                       (long long)ld_target, n_classes);
+  if (ambiguous < -1 || ambiguous >= n_classes)
+    return prego_fail_(PREGO_EINVAL, "thumos_postprocess: ambiguous %d (-1 .. %d)", ambiguous, n_classes - 1);
+  const bool sw = flags & PREGO_THUMOS_SWITCH;
+  if (sw && (switch_from < 0 || switch_from >= n_classes || switch_to < 0 || switch_to >= n_classes || switch_from == switch_to))
+    return prego_fail_(PREGO_EINVAL, "thumos_postprocess: switch columns %d -> %d (two different columns of [0, %d))", switch_from, switch_to,
+                       n_classes);
+  if (((uintptr_t)scores | (uintptr_t)scores_out | (uintptr_t)target | (uintptr_t)target_out | (uintptr_t)labels | (uintptr_t)labels_out) % 4 ||
+      (uintptr_t)n_valid % 8)
+    return prego_fail_(PREGO_EINVAL, "thumos_postprocess: a pointer is not aligned to its element");
+  const size_t n = (size_t)n_frames, C = (size_t)n_classes;
+  const size_t in_s = n ? ((n - 1) * (size_t)ld_scores + C) * 4 : 0;
+  const size_t in_t = n ? (ids ? n * 4 : ((n - 1) * (size_t)ld_target + C) * 4) : 0;
+  const void* in_tp = ids ? (const void*)labels : (const void*)target;
+  const size_t need = n ? thumos_postprocess_workspace_bytes(n_frames, n_classes) : 0;
+  const void* outs[4] = {scores_out, ids ? (void*)labels_out : (void*)target_out, n_valid, workspace};
+  const size_t out_b[4] = {n * C * 4, ids ? n * 4 : n * C * 4, 8, need};
+  for (int k = 0; k < 4; ++k)
+    if (thumos_overlap(outs[k], out_b[k], scores, in_s) || thumos_overlap(outs[k], out_b[k], in_tp, in_t))
+      return prego_fail_(PREGO_EINVAL, "thumos_postprocess: an output or the workspace overlaps an input");
+  if (workspace_bytes < need)
+    return prego_fail_(PREGO_EWORKSPACE, "thumos_postprocess: workspace %zu < %zu (prego_thumos_postprocess_workspace_bytes)", workspace_bytes, need);
+  if (n_frames == 0) {
+    HIPCHK(hipMemsetAsync(n_valid, 0, 8, (hipStream_t)stream));
+    return PREGO_OK;
+  }
+  if (launch_thumos_postprocess(scores, ld_scores, target, ld_target, (const int*)labels, n_frames, n_classes, flags & PREGO_THUMOS_SMOOTH,
+                                sw ? switch_from : -1, sw ? switch_to : -1, ambiguous, scores_out, target_out, (int*)labels_out,
+                                (long long*)n_valid, workspace, (hipStream_t)stream))
+    return prego_fail_(PREGO_EINVAL, "thumos_postprocess: bad arguments");
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+extern "C" int prego_thumos_postprocess(const float* scores, int64_t ld_scores, const float* target, int64_t ld_target, int64_t n_frames,
+                                        int n_classes, int flags, int switch_from, int switch_to, int ambiguous, float* scores_out,
+                                        float* target_out, int64_t* n_valid, void* workspace, size_t workspace_bytes, prego_stream_t stream) {
+  if (!target || !target_out) return prego_fail_(PREGO_EINVAL, "thumos_postprocess: NULL argument");
+  return thumos_common(scores, ld_scores, target, ld_target, nullptr, n_frames, n_classes, flags, switch_from, switch_to, ambiguous, scores_out,
+                       target_out, nullptr, n_valid, workspace, workspace_bytes, stream);
+}
+extern "C" int prego_thumos_postprocess_labels(const float* scores, int64_t ld_scores, const int32_t* labels, int64_t n_frames, int n_classes,
+                                               int flags, int switch_from, int switch_to, int ambiguous, float* scores_out, int32_t* labels_out,
+                                               int64_t* n_valid, void* workspace, size_t workspace_bytes, prego_stream_t stream) {
+  if (!labels || !labels_out) return prego_fail_(PREGO_EINVAL, "thumos_postprocess_labels: NULL argument");
+  return thumos_common(scores, ld_scores, nullptr, 0, labels, n_frames, n_classes, flags, switch_from, switch_to, ambiguous, scores_out, nullptr,
+                       labels_out, n_valid, workspace, workspace_bytes, stream);
+}
+
 // The feeder's side of the class-id entries: one-hot target rows (what the reference's dataset yields, dataset.py / eval.py:55 np.argmax(target)) reduced
 // to their class id on the host, in the loader's own memory, by a few threads - while the GPU is busy with the features.  HOST function.
 extern "C" int prego_onehot_labels(int n_videos, const float* const* targets, const int64_t* n_frames, int n_classes, int32_t* labels,

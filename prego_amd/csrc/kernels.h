@@ -296,6 +296,15 @@ size_t perstage_cap_workspace_bytes(long long n_frames, int n_classes);
 int launch_perstage_cap(const float* scores, const int* labels, long long n_frames, int n_classes, double* ap, long long* n_pos, void* workspace,
                         hipStream_t s);
 
+// THUMOS post-processing (thumos_post.hip): 5-frame max, column merge, stable removal of the ambiguous rows; count, scan, scatter
+constexpr int kThumosTileRows = 128;     // rows per scatter tile (PREGO_THUMOS_TILE_ROWS of the public header)
+constexpr int kThumosChunkCols = 96;     // columns of a tile staged in LDS at a time
+size_t thumos_postprocess_workspace_bytes(long long n_frames, int n_classes);
+// target XOR labels; sw_to < 0: no switch; amb < 0: every row kept; -1 = refused, nothing launched.  ws: the query's bytes, n > 0
+int launch_thumos_postprocess(const float* scores, long long ld_scores, const float* target, long long ld_target, const int* labels,
+                              long long n_frames, int n_classes, bool smooth, int sw_from, int sw_to, int amb, float* scores_out,
+                              float* target_out, int* labels_out, long long* n_valid, void* workspace, hipStream_t s);
+
 // Evaluate's feature cache (feature_cache.hip): n fp32 values -> bf16 / fp16 (f16) with the pack kernels' conversion; n % 8 == 0, n > 0
 void launch_cast_features(bool f16, const float* src, void* dst, long long n, int n_cu, hipStream_t s);
 

@@ -23,16 +23,30 @@ from .eval_cache import EvalFeatureCache
 from ._lib import PregoError
 from .metrics import (N_STAGES, perframe_ap_raw, perframe_ap_raw_device, perframe_average_precision, perframe_average_precision_device,
                       perstage_average_precision_device, perstage_report, report_from_raw)
+from .postprocessing import ThumosPostprocessing, thumos_postprocessing_device
 from .registry import EVAL
+
+
+def _thumos_postprocessing(cfg, is_thumos: bool):
+    """cfg['eval_thumos_postprocessing'] (not a reference key, off by default): the reference applies thumos_postprocessing in front of
+    every metric of a THUMOS data set (trainer/eval.py:19-21, 92-93); here a THUMOS data set is refused without the key and evaluated
+    with it.  cfg['eval_thumos_smooth'] / ['eval_thumos_switch'] default to False: the reference calls the function with its defaults."""
+    on = bool(cfg.get("eval_thumos_postprocessing", False))
+    if is_thumos and not on:
+        raise NotImplementedError("THUMOS post-processing is outside the PREGO datasets; cfg['eval_thumos_postprocessing'] = True "
+                                  "evaluates a THUMOS data set with it (prego_amd/postprocessing.py)")
+    if on and not is_thumos:
+        raise PregoError(f"cfg['eval_thumos_postprocessing'] is for THUMOS data sets; data_name is {cfg['data_name']!r}")
+    return ThumosPostprocessing(bool(cfg.get("eval_thumos_smooth", False)), bool(cfg.get("eval_thumos_switch", False))) if on else None
 
 
 @EVAL.register("OAD")
 class Evaluate(nn.Module):
     def __init__(self, cfg):
         super().__init__()
-        self.data_processing = None          # thumos_postprocessing applies to THUMOS only (eval.py:19-21)
-        if "THUMOS" in cfg["data_name"]:
-            raise NotImplementedError("THUMOS post-processing is outside the PREGO datasets")
+        # thumos_postprocessing applies to THUMOS only (eval.py:19-21): None, or a ThumosPostprocessing under cfg['eval_thumos_postprocessing']
+        self.data_processing = _thumos_postprocessing(cfg, "THUMOS" in cfg["data_name"])
+        self._n_valid = None                 # the frames the post-processing keeps, counted from the loader's host targets (_targets_to_device)
         self.metric = cfg["metric"]
         if self.metric not in ("AP", "cAP"):          # known before the eval pass runs, not after it (utils/metrics.py:38-44)
             raise RuntimeError(f"Unknown metrics: {self.metric}")
@@ -120,6 +134,13 @@ class Evaluate(nn.Module):
         the rows do - 4 bytes per frame over the link instead of 4 x classes (0.79 GB for the 182-video eval set: 14 ms of a 200 ms
         pass).  Such a video's entry is an int32 vector [T]; any other video's rows are copied as they are ([T, C])."""
         out = [None] * len(targets)
+        if self.data_processing is not None and self._n_valid is not None:
+            # the frames the THUMOS post-processing keeps, counted while the rows are in host memory: with this hint the device
+            # post-processing and the metric behind it are enqueued without a wait for the count (a device target: no hint)
+            if all(t.device.type == "cpu" and t.dim() == 2 for t in targets):
+                self._n_valid += sum(self.data_processing.count_valid(t.numpy()) for t in targets)
+            else:
+                self._n_valid = None
         host = [i for i, t in enumerate(targets) if t.device.type == "cpu" and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()
                 and t.shape[1] == len(self.all_class_names)]
         if host and self.cfg.get("eval_label_targets", True):
@@ -402,6 +423,16 @@ class Evaluate(nn.Module):
             return torch.cat(gt_targets, 0)
         return torch.cat([self._gt_matrix(t) for t in gt_targets], 0)
 
+    def _postprocessed(self, pred, gt):
+        """the eval set's device scores and targets as the metrics see them: unchanged, or - cfg['eval_thumos_postprocessing'] -
+        post-processed ONCE on the device (prego_thumos_postprocess, enqueued on the current stream) for the per-frame and the per-stage
+        metric; the third value compares the device's row count with the host's when the metric is collected (None: nothing to
+        compare).  The output file, the logged frame count and the FPS keep every frame: the reference post-processes inside the metric."""
+        if self.data_processing is None:
+            return pred, gt, None
+        res = thumos_postprocessing_device(pred, gt, self.data_processing, self._n_valid)
+        return res[1], res[0], (res.check if self._n_valid is not None else None)
+
     @staticmethod
     def _scores(rec, pred_scores, gt_targets):
         """the [T, C] score and target matrices of a batch's videos, taken at launch time: they stay torch tensors on the model's device
@@ -444,6 +475,10 @@ class Evaluate(nn.Module):
         if self.perstage and world > 1:
             raise PregoError("cfg['eval_perstage']: per-stage AP depends on the order of the frames (action instances are runs over the "
                              f"concatenated videos) and is computed by a single process only; this eval runs on {world} ranks")
+        if self.data_processing is not None and world > 1:
+            raise PregoError("cfg['eval_thumos_postprocessing']: the temporal smoothing runs over the concatenated frames of the whole eval "
+                             f"set, across the boundaries of the ranks' frame ranges, and is computed by a single process only; this eval "
+                             f"runs on {world} ranks")
         if self.perstage and torch.device(device).type != "cuda":
             raise PregoError("cfg['eval_perstage']: the per-stage AP of an eval pass runs on the device (prego_perstage_ap_labels); host "
                              "arrays: prego_amd.metrics.perstage_average_precision")
@@ -485,6 +520,9 @@ class Evaluate(nn.Module):
         self.last_device_argmax = {}
         max_clips = model.max_clips          # MROAD: the engine's clip capacity; ViTEnc (`model: 'Transformer'`): its own bound
         resident = self.last_source == "cache"
+        # the THUMOS post-processing's row count: summed over the batches' host targets; a cached set's targets are on the device, so
+        # its count is read back from there (8 bytes, behind the last forward)
+        self._n_valid = 0 if (self.data_processing is not None and not resident) else None
         with torch.no_grad():
             pred_scores, gt_targets = [], []
             per_video = []                       # (loader position, n_frames) to restore the loader's order on rank 0
@@ -526,12 +564,15 @@ class Evaluate(nn.Module):
                     self._ap_stream.wait_event(fwd_done)
                     pred_all = torch.cat(pred_scores, 0)
                     gt_all = self._cat_targets(gt_targets).to(pred_all.device)
-                    ap_fn = perframe_average_precision_device(pred_all.to(device), gt_all.to(device), self.all_class_names,
-                                                              self.data_processing, self.metric, defer=True)
+                    pred_m, gt_m, post_check = self._postprocessed(pred_all.to(device), gt_all.to(device))
+                    ap_fn = perframe_average_precision_device(pred_m, gt_m, self.all_class_names, None, self.metric, defer=True)
 
-                def finish_ap(_fn=ap_fn, _s=self._ap_stream):
+                def finish_ap(_fn=ap_fn, _s=self._ap_stream, _check=post_check):
                     with torch.cuda.stream(_s):           # the result's device -> host copy follows the kernels on THEIR stream
-                        return _fn()
+                        rep = _fn()
+                        if _check is not None:
+                            _check()
+                        return rep
             finish_ps = None
             self.last_perstage = None
             if self.perstage and pred_scores:
@@ -550,8 +591,8 @@ class Evaluate(nn.Module):
                     if finish_ap is None:                 # nothing is concatenated yet
                         pred_all = torch.cat(pred_scores, 0)
                         gt_all = self._cat_targets(gt_targets).to(pred_all.device)
-                    ps_fn = perstage_average_precision_device(pred_all.to(device), gt_all.to(device), self.all_class_names, defer=True,
-                                                              metrics=self.perstage_metric)
+                        pred_m, gt_m, _ = self._postprocessed(pred_all.to(device), gt_all.to(device))
+                    ps_fn = perstage_average_precision_device(pred_m, gt_m, self.all_class_names, defer=True, metrics=self.perstage_metric)
 
                 def finish_ps(_fn=ps_fn, _s=self._ap_stream):
                     with torch.cuda.stream(_s):
@@ -705,13 +746,16 @@ class AntEvaluate(nn.Module):
     A model with `forward_clips` on a GPU (MiniROADA) is fed whole videos in batches (one ragged forward per batch, anticipation head
     included); on a CUDA device metric 'AP' (`prego_perframe_ap`) and metric 'cAP' (`prego_perframe_cap`) are computed there, for the
     OAD scores and every anticipation step.  A stand-in model on the CPU (called per loader batch, as the reference does) uses the
-    host path.  `last_metric_path` ('device' or 'host') says what ran."""
+    host path.  `last_metric_path` ('device' or 'host') says what ran.
+    A THUMOS data set (the name in front of the first '_') is refused unless cfg['eval_thumos_postprocessing'] is set; with it every
+    report is computed on post-processed arrays (`ThumosPostprocessing`; on the device `prego_thumos_postprocess`, step l read in
+    place through its row stride)."""
 
     def __init__(self, cfg):
         super().__init__()
-        data_name = cfg["data_name"].split("_")[0]
-        if data_name == "THUMOS":
-            raise NotImplementedError("THUMOS post-processing is outside the PREGO datasets")
+        data_name =cfg["data_name"].split("_")[0]
+        # eval.py:92-93: the OAD report is post-processed with target[:, 21], step l with ant_target[:, l, 21]
+        self.data_processing = _thumos_postprocessing(cfg, data_name == "THUMOS")
         self.metric = cfg["metric"]
         if self.metric not in ("AP", "cAP"):
             raise RuntimeError(f"Unknown metrics: {self.metric}")
@@ -721,12 +765,19 @@ class AntEvaluate(nn.Module):
         self.last_fps = None
         self.last_metric_path = None
 
-    def _metric(self, pred, gt):
+    def _metric(self, pred, gt, n_valid=None):
+        """pred / gt [frames, C], possibly [:, l, :] views of the [frames, L, C] tensors: with the THUMOS post-processing they go to the C
+        entry as they are (ld_scores / ld_target), n_valid = the rows it keeps when they were counted on the host"""
+        post = self.data_processing
         if pred.is_cuda:
             self.last_metric_path = "device"
-            return perframe_average_precision_device(pred, gt.to(pred.device, torch.float32), self.all_class_names, None, self.metric)
+            if post is None:
+                pred, gt = pred.contiguous(), gt.contiguous()
+                return perframe_average_precision_device(pred, gt.to(pred.device, torch.float32), self.all_class_names, None, self.metric)
+            return perframe_average_precision_device(pred, gt.to(pred.device, torch.float32), self.all_class_names, post, self.metric,
+                                                     n_valid=n_valid)
         self.last_metric_path = "host"
-        return perframe_average_precision(pred.cpu().numpy(), gt.cpu().numpy(), self.all_class_names, None, self.metric)
+        return perframe_average_precision(pred.contiguous().cpu().numpy(), gt.contiguous().cpu().numpy(), self.all_class_names, post, self.metric)
 
     def eval(self, model, dataloader, logger, device=None):
         dev = torch.device(device) if device is not None else (torch.device("cuda:0") if torch.cuda.is_available() else torch.device("cpu"))
@@ -746,6 +797,8 @@ class AntEvaluate(nn.Module):
                 preds.append(o); gts.append(t); apreds.append(x); agts.append(a)
             pend, pend_frames = [], 0
 
+        post = self.data_processing
+        counts = {0: 0} if (post is not None and batched) else None      # [0]: the OAD targets, [l + 1]: step l
         t0 = time.perf_counter()
         with torch.no_grad():
             for rgb_input, flow_input, target, ant_target in dataloader:
@@ -755,6 +808,13 @@ class AntEvaluate(nn.Module):
                         T = int(target.shape[1])
                         if T == 0:
                             continue
+                        if post is not None and counts is not None:      # the rows the post-processing keeps, while the targets are host rows
+                            if target.device.type == "cpu" and ant_target.device.type == "cpu":
+                                counts[0] += post.count_valid(target[b].numpy())
+                                for l in range(ant_target.shape[2]):
+                                    counts[l + 1] = counts.get(l + 1, 0) + post.count_valid(ant_target[b][:, l].numpy())
+                            else:
+                                counts = None
                         pend.append((rgb_input[b].to(dev, torch.float32).contiguous(), flow_input[b].to(dev, torch.float32).contiguous(),
                                      target[b].to(dev), ant_target[b].to(dev)))
                         pend_frames += T
@@ -770,11 +830,12 @@ class AntEvaluate(nn.Module):
         n_frames = sum(int(p.shape[0]) for p in preds)
         pred, gt = torch.cat(preds).to(torch.float32), torch.cat(gts).to(torch.float32)
         apred, agt = torch.cat(apreds).to(torch.float32), torch.cat(agts).to(torch.float32)
-        result = self._metric(pred, gt)
+        hint = (lambda k: counts.get(k)) if counts is not None else (lambda k: None)
+        result = self._metric(pred, gt, hint(0))
         logger.info(f'OAD mAP: {result["mean_AP"] * 100:.2f}')
         maps = []
         for step in range(agt.shape[1]):
-            result[f"anticipation_{step + 1}"] = self._metric(apred[:, step, :].contiguous(), agt[:, step, :].contiguous())
+            result[f"anticipation_{step + 1}"] = self._metric(apred[:, step, :], agt[:, step, :], hint(step + 1))
             maps.append(result[f"anticipation_{step + 1}"]["mean_AP"])
             logger.info(f"Anticipation at step {step + 1}: {maps[-1] * 100:.2f}")
         logger.info(f"Mean Anticipation mAP: {np.mean(maps) * 100:.2f}")

@@ -31,7 +31,11 @@ frame of the class plus the stage's frames of every run; its AP is the one above
                                            one class id per frame, the per-frame pipeline's ranks, one counter per (stage, positive).
                                            'AP' or 'cAP' (`prego_perstage_cap_labels`: ties in frame order, NaN without a
                                            member, as the host form), no CPU fallback; used by `Evaluate` under cfg
-                                           `eval_perstage` (`eval_perstage_metric`)."""
+                                           `eval_perstage` (`eval_perstage_metric`).
+
+`postprocessing`: the host functions take any callable (ground_truth, prediction) -> (ground_truth, prediction), as the reference; the
+device functions take None or a `ThumosPostprocessing` (prego_amd/postprocessing.py), which they run on the device
+(`prego_thumos_postprocess`) in front of the same metric entries."""
 from __future__ import annotations
 
 from collections import OrderedDict
@@ -131,12 +135,36 @@ def perframe_ap_raw_device(pred, truth, metrics="AP"):
     return fin()
 
 
-def perframe_average_precision_device(prediction, ground_truth, class_names, postprocessing=None, metrics="AP", defer=False, raw=False):
+def _postprocess_device(what, prediction, ground_truth, postprocessing, n_valid):
+    """the device metrics' `postprocessing` argument: None, or a ThumosPostprocessing (prego_thumos_postprocess in front of the
+    unchanged metric entries).  Returns (prediction, ground_truth, check): `check` compares the device's count of kept rows with the
+    `n_valid` hint once the metric's kernels are done (None: nothing to compare)."""
+    from ._lib import PregoError
+    from .postprocessing import ThumosPostprocessing, thumos_postprocessing_device
+    if postprocessing is None:
+        if n_valid is not None:
+            raise PregoError(f"{what}: n_valid is the hint of a ThumosPostprocessing")
+        return prediction, ground_truth, None
+    if not isinstance(postprocessing, ThumosPostprocessing):
+        raise PregoError(f"{what}: the only postprocessing on the device is a ThumosPostprocessing (any other callable: the host "
+                         "functions)")
+    if not (prediction.is_cuda and ground_truth.is_cuda):
+        raise PregoError(f"{what} needs CUDA tensors; there is no CPU fallback")
+    res = thumos_postprocessing_device(prediction, ground_truth, postprocessing, n_valid)
+    return res[1], res[0], (res.check if n_valid is not None else None)
+
+
+def perframe_average_precision_device(prediction, ground_truth, class_names, postprocessing=None, metrics="AP", defer=False, raw=False,
+                                      n_valid=None):
     """Device path: prediction / ground_truth fp32 CUDA tensors [frames, classes] - or ground_truth = an integer CUDA tensor [frames],
     one class id per frame (what one-hot targets say; an id outside the classes = no positive) -; the sort and the scan run in
     libprego_amd.so (`prego_perframe_ap`), one small device -> host transfer brings back AP, positives and score mass.
     metrics='cAP': the calibrated metric (`prego_perframe_cap` / `prego_perframe_cap_labels`), frames of equal score in frame order as
     `calibrated_average_precision_columns` ranks them.
+    postprocessing: None or a `ThumosPostprocessing` (prego_amd/postprocessing.py): the scores and targets are post-processed on the
+    device (`prego_thumos_postprocess`) and the same metric entries run on the compacted matrices.  n_valid: the rows it keeps, when the
+    caller knows them (ThumosPostprocessing.count_valid on host targets) - then nothing here waits for the device, and the count is
+    compared when the result is collected (PregoError on a mismatch); without it the count is read back before the metric is enqueued.
     defer=True: the kernels are only ENQUEUED and a function is returned that waits for them and builds the report (Evaluate writes
     its output file while the GPU sorts)."""
     import ctypes as C
@@ -145,8 +173,10 @@ def perframe_average_precision_device(prediction, ground_truth, class_names, pos
 
     from . import _lib
     from ._lib import PregoError, check
-    if postprocessing is not None or metrics not in ("AP", "cAP"):
-        raise PregoError("perframe_average_precision_device: metric 'AP' or 'cAP' without postprocessing only")
+    if metrics not in ("AP", "cAP"):
+        raise PregoError("perframe_average_precision_device: metric 'AP' or 'cAP' only")
+    prediction, ground_truth, count_check = _postprocess_device("perframe_average_precision_device", prediction, ground_truth,
+                                                                postprocessing, n_valid)
     cal = metrics == "cAP"
     if not (prediction.is_cuda and ground_truth.is_cuda):
         raise PregoError("perframe_average_precision_device needs CUDA tensors; there is no CPU fallback "
@@ -160,7 +190,12 @@ def perframe_average_precision_device(prediction, ground_truth, class_names, pos
     if n == 0:                                          # an empty eval set: same empty report as the host path
         z = (np.zeros(ncls), np.zeros(ncls, np.int64), np.zeros(ncls))
         rep = z if raw else _report(*z, class_names)
-        return (lambda: rep) if defer else rep
+
+        def empty():
+            if count_check is not None:
+                count_check()
+            return rep
+        return empty if defer else empty()
     lib = _lib.load()
     dev = pred.device
     need = lib.prego_perframe_cap_workspace_bytes if cal else lib.prego_perframe_ap_workspace_bytes
@@ -176,6 +211,8 @@ def perframe_average_precision_device(prediction, ground_truth, class_names, pos
                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     def finish(_keep=(pred, truth, ws)):
         host = out.cpu().numpy()
+        if count_check is not None:
+            count_check()
         if raw:
             return host[0].copy(), host[1].view(np.int64).copy(), host[2].copy()
         return _report(host[0], host[1].view(np.int64), host[2], class_names)
@@ -269,14 +306,17 @@ def perstage_average_precision(prediction, ground_truth, class_names, postproces
     return perstage_report(perstage_ap_raw(pred, truth, metrics)[0], class_names)
 
 
-def perstage_average_precision_device(prediction, labels, class_names, defer=False, raw=False, metrics="AP"):
+def perstage_average_precision_device(prediction, labels, class_names, defer=False, raw=False, metrics="AP", postprocessing=None,
+                                      n_valid=None):
     """Device path: prediction fp32 CUDA tensor [frames, classes], labels an integer CUDA tensor [frames] with one class
     id per frame in evaluation order (an id outside the classes = a negative of every class); `prego_perstage_ap_labels` in
     libprego_amd.so, one small device -> host transfer brings back AP and positives [10, classes].  No CPU fallback.
     metrics='cAP': the calibrated metric (`prego_perstage_cap_labels`), frames of equal score in frame order; a (class, stage)
     without a member is NaN, as on the host.
     raw=True: (AP [10, classes], positives [10, classes]) of every class instead of the report.
-    defer=True: the kernels are only ENQUEUED and a function is returned that waits for them and builds the result."""
+    defer=True: the kernels are only ENQUEUED and a function is returned that waits for them and builds the result.
+    postprocessing / n_valid: None or a `ThumosPostprocessing` and its hint, as perframe_average_precision_device (the runs are those
+    of the frames that are left: removing a frame makes its neighbours adjacent)."""
     import ctypes as C
 
     import torch
@@ -292,6 +332,7 @@ def perstage_average_precision_device(prediction, labels, class_names, defer=Fal
     if labels.dim() != 1 or labels.dtype.is_floating_point or labels.dtype == torch.bool:
         raise PregoError("perstage_average_precision_device: labels must be one integer class id per frame [frames] "
                          "(dense target matrices: perstage_average_precision on the host)")
+    prediction, labels, count_check = _postprocess_device("perstage_average_precision_device", prediction, labels, postprocessing, n_valid)
     pred = prediction.detach().to(torch.float32).contiguous()
     ids = labels.detach().to(torch.int32).contiguous()
     if pred.dim() != 2 or pred.shape[1] != len(class_names) or ids.shape != pred.shape[:1]:
@@ -300,7 +341,12 @@ def perstage_average_precision_device(prediction, labels, class_names, defer=Fal
     if n == 0:
         z = (np.zeros((N_STAGES, ncls)), np.zeros((N_STAGES, ncls), np.int64))
         rep = z if raw else perstage_report(z[0], class_names)
-        return (lambda: rep) if defer else rep
+
+        def empty():
+            if count_check is not None:
+                count_check()
+            return rep
+        return empty if defer else empty()
     lib = _lib.load()
     dev = pred.device
     need = lib.prego_perstage_cap_workspace_bytes if cal else lib.prego_perstage_ap_workspace_bytes
@@ -313,6 +359,8 @@ def perstage_average_precision_device(prediction, labels, class_names, defer=Fal
                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     def finish(_keep=(pred, ids, ws)):
         host = out.cpu().numpy()
+        if count_check is not None:
+            count_check()
         if raw:
             return host[0].copy(), host[1].view(np.int64).copy()
         return perstage_report(host[0], class_names)
