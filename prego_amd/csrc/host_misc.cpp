@@ -44,94 +44,76 @@ extern "C" int prego_cast_features(const float* src, void* dst, int64_t n, int d
 }
 
 // ================================================================================================
-// metric: utils/metrics.py:25-62 (per-class average precision of the per-frame scores) on the device
+// metrics on the device (metrics.hip): utils/metrics.py:25-62 (per-class average precision of the per-frame scores), :64-130 (the same
+// metric by tenth of each action instance; ap / n_pos [10][n_classes]) and :10-22 (calibrated average precision, ties in frame order)
 // ================================================================================================
-extern "C" size_t prego_perframe_ap_workspace_bytes(int64_t n_frames, int n_classes) {
-  if (n_frames <= 0 || n_classes <= 0) return 0;
-  return perframe_ap_workspace_bytes(n_frames, n_classes);
+static size_t metric_workspace(size_t (*need)(long long, int), int64_t n_frames, int n_classes) {
+  return n_frames <= 0 || n_classes <= 0 ? 0 : need(n_frames, n_classes);
 }
-static int perframe_ap_common(const float* scores, const float* target, const int32_t* labels, int64_t n_frames, int n_classes, double* ap,
-                              int64_t* n_pos, double* score_sum, void* workspace, size_t workspace_bytes, prego_stream_t stream) {
-  if (!scores || (!target && !labels) || !ap || !workspace) return prego_fail_(PREGO_EINVAL, "perframe_ap: NULL argument");
-  if (n_frames <= 0 || n_frames >= (1ll << 31) || n_classes <= 0 || n_classes > 65535)
-    return prego_fail_(PREGO_EINVAL, "perframe_ap: n_frames %lld, n_classes %d", (long long)n_frames, n_classes);
-  if (workspace_bytes < perframe_ap_workspace_bytes(n_frames, n_classes))
-    return prego_fail_(PREGO_EWORKSPACE, "perframe_ap: workspace %zu < %zu", workspace_bytes, perframe_ap_workspace_bytes(n_frames, n_classes));
-  if (launch_perframe_ap(scores, target, (const int*)labels, n_frames, n_classes, ap, (long long*)n_pos, score_sum, workspace, (hipStream_t)stream))
-    return prego_fail_(PREGO_EINVAL, "perframe_ap: bad arguments");
+extern "C" size_t prego_perframe_ap_workspace_bytes(int64_t n, int c) { return metric_workspace(perframe_ap_workspace_bytes, n, c); }
+extern "C" size_t prego_perstage_ap_workspace_bytes(int64_t n, int c) { return metric_workspace(perstage_ap_workspace_bytes, n, c); }
+extern "C" size_t prego_perframe_cap_workspace_bytes(int64_t n, int c) { return metric_workspace(perframe_cap_workspace_bytes, n, c); }
+extern "C" size_t prego_perstage_cap_workspace_bytes(int64_t n, int c) { return metric_workspace(perstage_cap_workspace_bytes, n, c); }
+
+// What the six metric entries do around their launch.  name: in every message; have_args: the entry's own pointers are there;
+// zero_ok: n_frames == 0 is accepted and needs no workspace - every entry but prego_perframe_ap(_labels), which refuses it, wants its
+// workspace whatever n_frames is, and words the range and the workspace message shorter.
+template <typename LAUNCH>
+static int metric_entry(const char* name, bool zero_ok, bool have_args, int64_t n_frames, int n_classes, const void* workspace,
+                        size_t workspace_bytes, size_t (*need)(long long, int), LAUNCH launch) {
+  if (!have_args || (!workspace && (!zero_ok || n_frames > 0))) return prego_fail_(PREGO_EINVAL, "%s: NULL argument", name);
+  if (n_frames < (zero_ok ? 0 : 1) || n_frames >= (1ll << 31) || n_classes < 1 || n_classes > 65535)
+    return zero_ok ? prego_fail_(PREGO_EINVAL, "%s: n_frames %lld (0 .. 2^31 - 1), n_classes %d (1 .. 65535)", name, (long long)n_frames, n_classes)
+                   : prego_fail_(PREGO_EINVAL, "%s: n_frames %lld, n_classes %d", name, (long long)n_frames, n_classes);
+  if (n_frames > 0 && workspace_bytes < need(n_frames, n_classes))
+    return zero_ok ? prego_fail_(PREGO_EWORKSPACE, "%s: workspace %zu < %zu (prego_%s_workspace_bytes)", name, workspace_bytes,
+                                 need(n_frames, n_classes), name)
+                   : prego_fail_(PREGO_EWORKSPACE, "%s: workspace %zu < %zu", name, workspace_bytes, need(n_frames, n_classes));
+  if (launch()) return prego_fail_(PREGO_EINVAL, "%s: bad arguments", name);
   HIPCHK(hipGetLastError());
   return PREGO_OK;
+}
+
+static int perframe_common(bool cal, const float* scores, const float* target, const int32_t* labels, int64_t n_frames, int n_classes,
+                           double* ap, int64_t* n_pos, double* score_sum, void* workspace, size_t workspace_bytes, prego_stream_t stream) {
+  return metric_entry(cal ? "perframe_cap" : "perframe_ap", cal, scores && (target || labels) && ap, n_frames, n_classes, workspace,
+                      workspace_bytes, cal ? perframe_cap_workspace_bytes : perframe_ap_workspace_bytes, [&] {
+                        return (cal ? launch_perframe_cap : launch_perframe_ap)(scores, target, (const int*)labels, n_frames, n_classes, ap,
+                                                                                 (long long*)n_pos, score_sum, workspace, (hipStream_t)stream);
+                      });
 }
 extern "C" int prego_perframe_ap(const float* scores, const float* target, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
                                  double* score_sum, void* workspace, size_t workspace_bytes, prego_stream_t stream) {
-  return perframe_ap_common(scores, target, nullptr, n_frames, n_classes, ap, n_pos, score_sum, workspace, workspace_bytes, stream);
+  return perframe_common(false, scores, target, nullptr, n_frames, n_classes, ap, n_pos, score_sum, workspace, workspace_bytes, stream);
 }
 extern "C" int prego_perframe_ap_labels(const float* scores, const int32_t* labels, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
                                         double* score_sum, void* workspace, size_t workspace_bytes, prego_stream_t stream) {
-  return perframe_ap_common(scores, nullptr, labels, n_frames, n_classes, ap, n_pos, score_sum, workspace, workspace_bytes, stream);
-}
-
-// utils/metrics.py:64-130 (the same metric by tenth of each action instance) on the device; ap / n_pos [10][n_classes]
-extern "C" size_t prego_perstage_ap_workspace_bytes(int64_t n_frames, int n_classes) {
-  if (n_frames <= 0 || n_classes <= 0) return 0;
-  return perstage_ap_workspace_bytes(n_frames, n_classes);
-}
-extern "C" int prego_perstage_ap_labels(const float* scores, const int32_t* labels, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
-                                        void* workspace, size_t workspace_bytes, prego_stream_t stream) {
-  if (!scores || !labels || !ap || (!workspace && n_frames > 0)) return prego_fail_(PREGO_EINVAL, "perstage_ap: NULL argument");
-  if (n_frames < 0 || n_frames >= (1ll << 31) || n_classes < 1 || n_classes > 65535)
-    return prego_fail_(PREGO_EINVAL, "perstage_ap: n_frames %lld (0 .. 2^31 - 1), n_classes %d (1 .. 65535)", (long long)n_frames, n_classes);
-  if (n_frames > 0 && workspace_bytes < perstage_ap_workspace_bytes(n_frames, n_classes))
-    return prego_fail_(PREGO_EWORKSPACE, "perstage_ap: workspace %zu < %zu (prego_perstage_ap_workspace_bytes)", workspace_bytes,
-                       perstage_ap_workspace_bytes(n_frames, n_classes));
-  if (launch_perstage_ap(scores, (const int*)labels, n_frames, n_classes, ap, (long long*)n_pos, workspace, (hipStream_t)stream))
-    return prego_fail_(PREGO_EINVAL, "perstage_ap: bad arguments");
-  HIPCHK(hipGetLastError());
-  return PREGO_OK;
-}
-
-// utils/metrics.py:10-22 (calibrated average precision, ties in frame order) on the device, beside the AP entries
-extern "C" size_t prego_perframe_cap_workspace_bytes(int64_t n_frames, int n_classes) {
-  if (n_frames <= 0 || n_classes <= 0) return 0;
-  return perframe_cap_workspace_bytes(n_frames, n_classes);
-}
-static int perframe_cap_common(const float* scores, const float* target, const int32_t* labels, int64_t n_frames, int n_classes, double* ap,
-                               int64_t* n_pos, double* score_sum, void* workspace, size_t workspace_bytes, prego_stream_t stream) {
-  if (!scores || (!target && !labels) || !ap || (!workspace && n_frames > 0)) return prego_fail_(PREGO_EINVAL, "perframe_cap: NULL argument");
-  if (n_frames < 0 || n_frames >= (1ll << 31) || n_classes < 1 || n_classes > 65535)
-    return prego_fail_(PREGO_EINVAL, "perframe_cap: n_frames %lld (0 .. 2^31 - 1), n_classes %d (1 .. 65535)", (long long)n_frames, n_classes);
-  if (n_frames > 0 && workspace_bytes < perframe_cap_workspace_bytes(n_frames, n_classes))
-    return prego_fail_(PREGO_EWORKSPACE, "perframe_cap: workspace %zu < %zu (prego_perframe_cap_workspace_bytes)", workspace_bytes,
-                       perframe_cap_workspace_bytes(n_frames, n_classes));
-  if (launch_perframe_cap(scores, target, (const int*)labels, n_frames, n_classes, ap, (long long*)n_pos, score_sum, workspace, (hipStream_t)stream))
-    return prego_fail_(PREGO_EINVAL, "perframe_cap: bad arguments");
-  HIPCHK(hipGetLastError());
-  return PREGO_OK;
+  return perframe_common(false, scores, nullptr, labels, n_frames, n_classes, ap, n_pos, score_sum, workspace, workspace_bytes, stream);
 }
 extern "C" int prego_perframe_cap(const float* scores, const float* target, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
                                   double* score_sum, void* workspace, size_t workspace_bytes, prego_stream_t stream) {
-  return perframe_cap_common(scores, target, nullptr, n_frames, n_classes, ap, n_pos, score_sum, workspace, workspace_bytes, stream);
+  return perframe_common(true, scores, target, nullptr, n_frames, n_classes, ap, n_pos, score_sum, workspace, workspace_bytes, stream);
 }
 extern "C" int prego_perframe_cap_labels(const float* scores, const int32_t* labels, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
                                          double* score_sum, void* workspace, size_t workspace_bytes, prego_stream_t stream) {
-  return perframe_cap_common(scores, nullptr, labels, n_frames, n_classes, ap, n_pos, score_sum, workspace, workspace_bytes, stream);
+  return perframe_common(true, scores, nullptr, labels, n_frames, n_classes, ap, n_pos, score_sum, workspace, workspace_bytes, stream);
 }
-extern "C" size_t prego_perstage_cap_workspace_bytes(int64_t n_frames, int n_classes) {
-  if (n_frames <= 0 || n_classes <= 0) return 0;
-  return perstage_cap_workspace_bytes(n_frames, n_classes);
+
+static int perstage_common(bool cal, const float* scores, const int32_t* labels, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
+                           void* workspace, size_t workspace_bytes, prego_stream_t stream) {
+  return metric_entry(cal ? "perstage_cap" : "perstage_ap", true, scores && labels && ap, n_frames, n_classes, workspace, workspace_bytes,
+                      cal ? perstage_cap_workspace_bytes : perstage_ap_workspace_bytes, [&] {
+                        return (cal ? launch_perstage_cap : launch_perstage_ap)(scores, (const int*)labels, n_frames, n_classes, ap,
+                                                                                 (long long*)n_pos, workspace, (hipStream_t)stream);
+                      });
+}
+extern "C" int prego_perstage_ap_labels(const float* scores, const int32_t* labels, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
+                                        void* workspace, size_t workspace_bytes, prego_stream_t stream) {
+  return perstage_common(false, scores, labels, n_frames, n_classes, ap, n_pos, workspace, workspace_bytes, stream);
 }
 extern "C" int prego_perstage_cap_labels(const float* scores, const int32_t* labels, int64_t n_frames, int n_classes, double* ap, int64_t* n_pos,
                                          void* workspace, size_t workspace_bytes, prego_stream_t stream) {
-  if (!scores || !labels || !ap || (!workspace && n_frames > 0)) return prego_fail_(PREGO_EINVAL, "perstage_cap: NULL argument");
-  if (n_frames < 0 || n_frames >= (1ll << 31) || n_classes < 1 || n_classes > 65535)
-    return prego_fail_(PREGO_EINVAL, "perstage_cap: n_frames %lld (0 .. 2^31 - 1), n_classes %d (1 .. 65535)", (long long)n_frames, n_classes);
-  if (n_frames > 0 && workspace_bytes < perstage_cap_workspace_bytes(n_frames, n_classes))
-    return prego_fail_(PREGO_EWORKSPACE, "perstage_cap: workspace %zu < %zu (prego_perstage_cap_workspace_bytes)", workspace_bytes,
-                       perstage_cap_workspace_bytes(n_frames, n_classes));
-  if (launch_perstage_cap(scores, (const int*)labels, n_frames, n_classes, ap, (long long*)n_pos, workspace, (hipStream_t)stream))
-    return prego_fail_(PREGO_EINVAL, "perstage_cap: bad arguments");
-  HIPCHK(hipGetLastError());
-  return PREGO_OK;
+  return perstage_common(true, scores, labels, n_frames, n_classes, ap, n_pos, workspace, workspace_bytes, stream);
 }
 
 // ================================================================================================

@@ -17,12 +17,14 @@
 //                positives than 16 workgroups hold fall back to a sampled table + one device atomic per key).
 //                samples at or above positive i's score = cnt_c[0] + ... + cnt_c[i]   (lower_bound never returns the inside of a
 //                tie run, so the inclusive prefix is the same for every member of the run)
-//   ap_reduce    one workgroup per class walks q_c and cnt_c once: running prefix of cnt, run ends of q, fp64 accumulation of
+//   ap_walk<ApWalk>   one workgroup per class walks q_c and cnt_c once: running prefix of cnt, run ends of q, fp64 accumulation of
 //                (positives in the run) * (positives so far) / (samples so far).
 // Exact integer ranks; the only floating-point work is the final fp64 sum (differs from sklearn's by summation order, ~1e-16) and
 // the per-class score mass (fixed summation order: the same bits on every run).
 // The kernels up to ap_count are templates over what a list holds per positive: the key (AP), or the key above the frame index (the
 // calibrated metric further down, which ranks frames of equal score in frame order).
+// One of each: wg_scan_step / wg_scan_array (every workgroup scan), ap_walk_kernel (the walk over a class's list: per-frame and
+// per-stage, AP and cAP are four policies of it), ps_run_edges (label runs), ApLayout (the workspace).
 #include "common.h"
 #include "kernels.h"
 
@@ -35,6 +37,8 @@
 #define AP_TAB 16384          // ap_count: LDS words (64 KB: two 1024-thread workgroups per CU)
 #define AP_OWN (AP_TAB / 2)   // ap_count: positives a workgroup owns (their keys + their counters in LDS)
 #define AP_SPLITS_MAX 64      // ap_count: workgroups per class
+#define PS_STAGES 10          // per-stage metric: tenths of an action
+#define PS_BLK 1024           // per-stage metric: frames per block of the run scans (256 threads x 4)
 
 // order-reversing key of a float score: larger score -> smaller key; -0.0 == +0.0 (sklearn compares values, not bits)
 __device__ __forceinline__ unsigned ap_desc_key(float s) {
@@ -127,35 +131,66 @@ __global__ __launch_bounds__(64) void ap32_hist_kernel(const T* __restrict__ key
   }
 }
 
+// The workgroup scan of this file (256 threads, integer values: exact in any order).  OP: the combine operation.
+struct ScanSum { template <typename T> static __device__ __forceinline__ T op(T a, T b) { return a + b; } };
+struct ScanMax { template <typename T> static __device__ __forceinline__ T op(T a, T b) { return a > b ? a : b; } };
+struct ScanMin { template <typename T> static __device__ __forceinline__ T op(T a, T b) { return a < b ? a : b; } };
+
+template <typename T> __device__ __forceinline__ T wave_uniform(T v) {      // v is the same in every lane: it can live in scalar registers
+  if constexpr (sizeof(T) == 8) {
+    const unsigned long long x = (unsigned long long)v;
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(x >> 32)), lo = (unsigned)__builtin_amdgcn_readfirstlane((int)x);
+    return (T)(((unsigned long long)hi << 32) | lo);
+  } else {
+    return (T)__builtin_amdgcn_readfirstlane((int)v);
+  }
+}
+
+// One chunk of a scan.  mine: the combination of this thread's own elements of the chunk (one, or several consecutive ones).
+// Returns the combination of everything in front of this thread - the earlier chunks (carry), the earlier waves, the earlier lanes -
+// and takes the chunk into carry, which every thread holds (the same value in all of them; initialise it to the identity).  wsum:
+// shared, used alternately by `parity` (the chunk's number & 1), so that the one barrier of a step also separates it from the step
+// after the next.  Every thread of the workgroup calls it, the same number of times.
+template <typename OP, typename T>
+__device__ __forceinline__ T wg_scan_step(T mine, T& carry, T (*wsum)[4], int parity) {
+  const int lane = threadIdx.x & 63, wave = wave_uniform((int)(threadIdx.x >> 6));
+  T incl = mine;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const T u = __shfl_up(incl, o, 64); if (lane >= o) incl = OP::op(incl, u); }
+  if (lane == 63) wsum[parity][wave] = incl;
+  __syncthreads();
+  const T before = __shfl_up(incl, 1, 64);
+  T front = carry;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const T total = wave_uniform(wsum[parity][w]);
+    if (w < wave) front = OP::op(front, total);
+    carry = OP::op(carry, total);
+  }
+  return lane == 0 ? front : OP::op(front, before);
+}
+
+// exclusive scan of v[0 .. m) in place by one workgroup, E consecutive elements per thread; REV: from the back
+template <typename OP, bool REV, int E, typename T>
+__device__ void wg_scan_array(T* v, int m, T identity, T (*wsum)[4]) {
+  T carry = identity;
+  for (int base = 0, parity = 0; base < m; base += 256 * E, parity ^= 1) {
+    const int j = base + (int)threadIdx.x * E;
+    T x[E], mine = identity;
+#pragma unroll
+    for (int e = 0; e < E; ++e) { x[e] = j + e < m ? v[REV ? m - 1 - (j + e) : j + e] : identity; mine = OP::op(mine, x[e]); }
+    T run = wg_scan_step<OP>(mine, carry, wsum, parity);
+#pragma unroll
+    for (int e = 0; e < E; ++e) { if (j + e < m) v[REV ? m - 1 - (j + e) : j + e] = run; run = OP::op(run, x[e]); }
+  }
+  __syncthreads();                                              // the result is the workgroup's; wsum is free again
+}
+
 // per class: exclusive scan over its (digit, tile) counts in place (digit-major = the order a stable scatter fills the output)
 __global__ __launch_bounds__(256) void ap32_scan_kernel(unsigned* __restrict__ hist, const unsigned* __restrict__ len, int ntiles_max) {
-  __shared__ unsigned wsum[4];
-  __shared__ unsigned carry_s;
+  __shared__ unsigned wsum[2][4];
   const int ntc = (int)((len[blockIdx.x] + AP_TILE - 1) / AP_TILE);
-  unsigned* h = hist + (size_t)blockIdx.x * AP_RADIX * ntiles_max;
-  const int total = AP_RADIX * ntc, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) carry_s = 0u;
-  __syncthreads();
-  for (int base = 0; base < total; base += 1024) {
-    const int j = base + tid * 4;
-    unsigned v[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = j + e < total ? h[j + e] : 0u;
-    const unsigned mine = v[0] + v[1] + v[2] + v[3];
-    unsigned incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const unsigned u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    unsigned off = carry_s;
-    for (int w = 0; w < wave; ++w) off += wsum[w];
-    unsigned run = off + incl - mine;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { if (j + e < total) h[j + e] = run; run += v[e]; }
-    __syncthreads();
-    if (tid == 255) carry_s = off + incl;
-    __syncthreads();
-  }
+  wg_scan_array<ScanSum, false, 4>(hist + (size_t)blockIdx.x * AP_RADIX * ntiles_max, AP_RADIX * ntc, 0u, wsum);
 }
 
 // stable scatter of a class's tiles by the current digit
@@ -357,85 +392,133 @@ __global__ __launch_bounds__(1024) void ap_count_kernel(const unsigned* __restri
   }
 }
 
-// one workgroup per class over its sorted positives and their counters
-__global__ __launch_bounds__(256) void ap_reduce_kernel(const unsigned* __restrict__ q_all, const unsigned* __restrict__ cnt_all,
-                                                        const unsigned* __restrict__ len, long long n, int C, const double* __restrict__ partial,
-                                                        int splits, double* __restrict__ ap, long long* __restrict__ n_pos,
-                                                        double* __restrict__ score_sum) {
-  __shared__ long long w_sum[4], w_max[4];
+#define CAP_EPS 2.220446049250313e-16     // 2^-52, numpy's finfo(float).eps
+
+__device__ __forceinline__ double cap_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
+
+// ap_walk: one workgroup over one sorted list and its counters - a class (per frame), or a class and a stage (per stage): AP and the
+// calibrated metric, each per frame and per stage (the two sections further down say what they compute), are four policies of it.
+// The workgroup walks [0, P) in chunks of 1024, four consecutive elements per thread, and keeps for element i
+//   seen   the inclusive prefix of cnt_c: the column's entries at or above q_i (AP), the rank of positive i among all frames (cAP)
+//   hits   the set's positives among q_0 .. q_i: i + 1, or (STAGE) the inclusive prefix of st_cs
+//   fps    = seen - (i + 1): the class's negatives at or above q_i, which are every stage's negatives too
+// A policy says: STAGE; TIES - one term per tie run of q_c that holds d > 0 positives of the set, formed at the run's end against the
+// exclusive max-scan of `hits` at the earlier run ends (AP) - or one term per member (cAP: its lists are tie-free); term(); empty(),
+// what a list or a set without a positive scores.  A thread adds its terms in index order, then the 64-lane tree, then
+// (w0 + w1) + (w2 + w3): a fixed order, the same bits on every run.
+struct ApTerm {      // (positives in the run) * (positives so far) / (samples so far)
+  static constexpr bool TIES = true;
+  static __device__ __forceinline__ double term(long long d, long long hits, long long fps, double) {
+    return (double)d * ((double)hits / (double)(fps + hits));
+  }
+};
+struct CapTerm {     // tps / (tps + fps / (w + eps) + eps), wd = w + eps
+  static constexpr bool TIES = false;
+  static __device__ __forceinline__ double term(long long, long long hits, long long fps, double wd) {
+    const double tps = (double)hits;
+    return tps / (tps + (double)fps / wd + CAP_EPS);
+  }
+};
+template <typename TERM, bool STAGE_, bool EMPTY_NAN>
+struct WalkPolicy : TERM {
+  static constexpr bool STAGE = STAGE_;
+  static __device__ __forceinline__ double empty() { return EMPTY_NAN ? cap_nan() : 0.0; }
+};
+typedef WalkPolicy<ApTerm, false, true> ApWalk;       // per-frame AP: NaN for a class without positives
+typedef WalkPolicy<CapTerm, false, true> CapWalk;     // per-frame cAP: the same
+typedef WalkPolicy<ApTerm, true, false> PsWalk;       // per-stage AP: a class without a run scores 0.0, as the reference reports it
+typedef WalkPolicy<CapTerm, true, true> CpsWalk;      // per-stage cAP: no member: NaN, as the host form
+
+// grid (C) or, STAGE, (C, PS_STAGES); q_all: TIES only; st_all / off: STAGE only; partial / splits / score_sum: the per-frame entries
+template <typename POL>
+__global__ __launch_bounds__(256) void ap_walk_kernel(const unsigned* __restrict__ q_all, const unsigned* __restrict__ cnt_all,
+                                                      const unsigned* __restrict__ len, long long n, int C, const unsigned* __restrict__ st_all,
+                                                      const int* __restrict__ off, const double* __restrict__ partial, int splits,
+                                                      double* __restrict__ ap, long long* __restrict__ n_pos, double* __restrict__ score_sum) {
+  constexpr bool STAGE = POL::STAGE, TIES = POL::TIES;
+  __shared__ long long ws_cnt[2][4], ws_st[2][4], ws_end[2][4];
   __shared__ double w_acc[4];
-  __shared__ long long carry_cnt, carry_end;
-  const int c = blockIdx.x;
+  const int c = blockIdx.x, sg = blockIdx.y;
   const long long P = (long long)len[c];
-  const unsigned* q = q_all + (size_t)c * n;
+  const unsigned* q = TIES ? q_all + (size_t)c * n : nullptr;
   const unsigned* cnt = cnt_all + (size_t)c * n;
+  const unsigned* st = STAGE ? st_all + (size_t)sg * n + (size_t)off[c] : nullptr;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) { carry_cnt = 0; carry_end = 0; }
-  __syncthreads();
-  double acc = 0.0;
-  for (long long base = 0; base < P; base += 1024) {
-    const long long j = base + (long long)tid * 4;
-    unsigned k[5];
-    long long v[4], mine = 0;
+  long long members = P;                                    // cAP: w = (n - P) / members is needed before the first term
+  if constexpr (STAGE && !TIES) {                           // so the stage's members are counted in a pre-step
+    long long ms = 0;
+    for (long long j = tid; j < P; j += 256) ms += (long long)st[j];
 #pragma unroll
-    for (int e = 0; e < 5; ++e) k[e] = j + e < P ? q[j + e] : 0u;             // k[4]: the neighbour behind my last element
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { v[e] = j + e < P ? (long long)cnt[j + e] : 0; mine += v[e]; }
-    long long incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const long long u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
-    if (lane == 63) w_sum[wave] = incl;
+    for (int o = 32; o > 0; o >>= 1) ms += __shfl_xor(ms, o, 64);
+    if (lane == 0) ws_st[0][wave] = ms;
     __syncthreads();
-    long long seen = carry_cnt + incl - mine;                                 // samples at or above the score in front of my first element
-    for (int w = 0; w < wave; ++w) seen += w_sum[w];
-    // my elements: samples at or above each, and whether it ends a run of equal scores (the last positive ends one)
-    long long s_after[4], end_local = 0;                                      // largest run-end rank among my elements (0 = none)
-    bool is_end[4];
+    members = (ws_st[0][0] + ws_st[0][1]) + (ws_st[0][2] + ws_st[0][3]);
+    __syncthreads();
+  }
+  const double wd = (double)(n - P) / (double)members + CAP_EPS;       // no member: no term is formed
+  long long c_cnt = 0, c_st = 0, c_end = 0;                 // the scans' carries
+  double acc = 0.0;
+  int parity = 0;
+  for (long long base = 0; base < P; base += 1024, parity ^= 1) {
+    const long long j = base + (long long)tid * 4;
+    unsigned k[5] = {0u, 0u, 0u, 0u, 0u};                   // k[4]: the neighbour behind my last element
+    long long v[4], u[4], mine = 0, mine_st = 0;
+    if constexpr (TIES) {
+#pragma unroll
+      for (int e = 0; e < 5; ++e) k[e] = j + e < P ? q[j + e] : 0u;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[e] = j + e < P ? (long long)cnt[j + e] : 0;
+      u[e] = STAGE && j + e < P ? (long long)st[j + e] : 0;
+      mine += v[e];
+      mine_st += u[e];
+    }
+    long long seen = wg_scan_step<ScanSum>(mine, c_cnt, ws_cnt, parity), hits = j;       // in front of my first element
+    if constexpr (STAGE) hits = wg_scan_step<ScanSum>(mine_st, c_st, ws_st, parity);
+    long long fps[4], h[4], end_local = 0;                  // end_local: hits at my last run end (0 = none: hits is monotone)
+    bool act[4];                                            // forms a term: a run end (TIES) or a member
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       seen += v[e];
-      s_after[e] = seen;
-      is_end[e] = (j + e < P) && ((j + e + 1 >= P) || (k[e] != k[e + 1]));
-      if (is_end[e]) end_local = j + e + 1;
+      hits += STAGE ? u[e] : 1;
+      fps[e] = seen - (j + e + 1);
+      h[e] = hits;
+      if (TIES) {
+        act[e] = (j + e < P) && ((j + e + 1 >= P) || (k[e] != k[e + 1]));       // the last positive ends a run
+        if (act[e]) end_local = hits;
+      } else {
+        act[e] = STAGE ? u[e] != 0 : j + e < P;
+      }
     }
-    // positives at the most recent run end BEFORE my first element: exclusive max-scan (ranks are monotone)
-    long long mx = end_local;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const long long u = __shfl_up(mx, o, 64); if (lane >= o && u > mx) mx = u; }
-    if (lane == 63) w_max[wave] = mx;
-    __syncthreads();
-    long long prev = __shfl_up(mx, 1, 64);
-    if (lane == 0) prev = 0;
-    if (carry_end > prev) prev = carry_end;
-    for (int w = 0; w < wave; ++w) if (w_max[w] > prev) prev = w_max[w];
+    long long prev = 0;                                     // hits at the most recent run end before my first element
+    if constexpr (TIES) prev = wg_scan_step<ScanMax>(end_local, c_end, ws_end, parity);
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-      if (is_end[e]) {
-        const long long tps = j + e + 1;
-        acc += (double)(tps - prev) * ((double)tps / (double)s_after[e]);
-        prev = tps;
+      if (act[e]) {
+        const long long d = h[e] - prev;                    // the set's positives in this tie run
+        if (!TIES || d > 0) {
+          acc += POL::term(d, h[e], fps[e], wd);
+          prev = h[e];
+        }
       }
-    __syncthreads();
-    if (tid == 255) {
-      carry_cnt = seen;
-      long long mm = carry_end;
-      for (int w = 0; w < 4; ++w) if (w_max[w] > mm) mm = w_max[w];
-      carry_end = mm;
-    }
-    __syncthreads();
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
   if (lane == 0) w_acc[wave] = acc;
   __syncthreads();
   if (tid == 0) {
+    const long long m = STAGE ? c_st : P;                   // the set's positives
+    const size_t at = (size_t)sg * C + c;
     const double a = (w_acc[0] + w_acc[1]) + (w_acc[2] + w_acc[3]);
-    ap[c] = P > 0 ? a / (double)P : __longlong_as_double(0x7FF8000000000000ll);     // NaN: a class without positives
-    if (n_pos) n_pos[c] = P;
-    if (score_sum) {
-      double t = 0.0;
-      for (int sp = 0; sp < splits; ++sp) t += partial[(size_t)sp * C + c];
-      score_sum[c] = t;
+    ap[at] = m > 0 ? a / (double)m : POL::empty();
+    if (n_pos) n_pos[at] = m;
+    if constexpr (!STAGE) {
+      if (score_sum) {
+        double t = 0.0;
+        for (int sp = 0; sp < splits; ++sp) t += partial[(size_t)sp * C + c];
+        score_sum[c] = t;
+      }
     }
   }
 }
@@ -448,66 +531,8 @@ __global__ __launch_bounds__(256) void ap_reduce_kernel(const unsigned* __restri
 // against the list.  Composites are distinct, so a positive is its own lower_bound and the inclusive prefix of cnt at positive i is
 // rank_i, its 1-based position among all n frames.  With tps = i + 1, fps = rank_i - tps, w = (n - P) / P, eps = 2^-52:
 //   cAP = (1 / P) * sum_i tps / (tps + fps / (w + eps) + eps)
-//   cap_reduce   one workgroup per class: running prefix of cnt, the terms accumulated per thread in index order, then the wave
-//                and workgroup trees of ap_reduce: a fixed order, the same bits on every run.
+//   ap_walk<CapWalk>   one workgroup per class: running prefix of cnt, one term per positive.
 // ================================================================================================================================
-#define CAP_EPS 2.220446049250313e-16     // 2^-52, numpy's finfo(float).eps
-
-__device__ __forceinline__ double cap_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
-
-__global__ __launch_bounds__(256) void cap_reduce_kernel(const unsigned* __restrict__ cnt_all, const unsigned* __restrict__ len, long long n,
-                                                         int C, const double* __restrict__ partial, int splits, double* __restrict__ ap,
-                                                         long long* __restrict__ n_pos, double* __restrict__ score_sum) {
-  __shared__ long long w_sum[4];
-  __shared__ double w_acc[4];
-  __shared__ long long carry_cnt;
-  const int c = blockIdx.x;
-  const long long P = (long long)len[c];
-  const unsigned* cnt = cnt_all + (size_t)c * n;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) carry_cnt = 0;
-  __syncthreads();
-  const double wd = (double)(n - P) / (double)P + CAP_EPS;                    // P = 0: no term is formed
-  double acc = 0.0;
-  for (long long base = 0; base < P; base += 1024) {
-    const long long j = base + (long long)tid * 4;
-    long long v[4], mine = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { v[e] = j + e < P ? (long long)cnt[j + e] : 0; mine += v[e]; }
-    long long incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const long long u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
-    if (lane == 63) w_sum[wave] = incl;
-    __syncthreads();
-    long long seen = carry_cnt + incl - mine;                                 // frames in front of my first element
-    for (int w = 0; w < wave; ++w) seen += w_sum[w];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      seen += v[e];                                                           // rank of positive j + e
-      if (j + e < P) {
-        const double tps = (double)(j + e + 1), fps = (double)(seen - (j + e + 1));
-        acc += tps / (tps + fps / wd + CAP_EPS);
-      }
-    }
-    __syncthreads();
-    if (tid == 255) carry_cnt = seen;
-    __syncthreads();
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if (lane == 0) w_acc[wave] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    const double a = (w_acc[0] + w_acc[1]) + (w_acc[2] + w_acc[3]);
-    ap[c] = P > 0 ? a / (double)P : cap_nan();
-    if (n_pos) n_pos[c] = P;
-    if (score_sum) {
-      double t = 0.0;
-      for (int sp = 0; sp < splits; ++sp) t += partial[(size_t)sp * C + c];
-      score_sum[c] = t;
-    }
-  }
-}
 
 // n_frames == 0: NaN, no positives, no score mass
 __global__ void cap_empty_kernel(int C, double* __restrict__ ap, long long* __restrict__ n_pos, double* __restrict__ score_sum) {
@@ -523,19 +548,61 @@ static int ap_splits(int C) {
   return s < 16 ? 16 : (s > AP_SPLITS_MAX ? AP_SPLITS_MAX : s);
 }
 
-size_t perframe_ap_workspace_bytes(long long n, int C) {
-  const size_t ntiles = (size_t)((n + AP_TILE - 1) / AP_TILE);
-  return 4 * (size_t)C * (size_t)n * 4 + (size_t)C * AP_RADIX * ntiles * 4 + (size_t)C * 4 + 8 + (size_t)AP_SPLITS_MAX * C * 8 + 1024;
-}
+// The workspace of an entry, carved once: the four *_workspace_bytes functions return its totals, the launches take their pointers
+// from it.  T: what a list holds per positive (the calibrated metric's 8-byte composites; 8 more bytes align them behind the keys).
+// The per-stage buffers lie behind the per-frame workspace, rounded up to 16 bytes.
+template <typename T>
+struct ApLayout {
+  int ntiles, nblk;                      // radix tiles of n keys; 1024-frame blocks of the run scans
+  unsigned* keys;                        // [C][n] order-reversing keys, class-major
+  T *p0, *p1;                            // [C][n] each: the lists, and where a radix pass scatters them
+  unsigned *cnt, *hist, *cursor;         // [C][n] ap_count's counters; [C][256][ntiles]; [C] positives per class
+  double* partial;                       // [AP_SPLITS_MAX][C] score mass
+  unsigned* st;                          // [PS_STAGES][n] stage counters, the classes back to back
+  int *off, *bl_head, *bl_tail;          // [C] where a class's stage counters start; [nblk] each: the run scans' block carries
+  size_t frame_bytes, stage_bytes;       // what a per-frame / a per-stage entry needs
 
-// the calibrated metric's lists hold 8 bytes per entry (+ 8 to align them behind the keys)
-size_t perframe_cap_workspace_bytes(long long n, int C) { return perframe_ap_workspace_bytes(n, C) + 2 * (size_t)C * (size_t)n * 4 + 8; }
+  ApLayout(void* ws, long long n, int C) : ntiles((int)((n + AP_TILE - 1) / AP_TILE)), nblk((int)((n + PS_BLK - 1) / PS_BLK)) {
+    const size_t cn = (size_t)C * (size_t)n;
+    at = (uintptr_t)ws;
+    keys = take<unsigned>(cn);
+    p0 = take<T>(2 * cn);
+    p1 = p0 + cn;
+    cnt = take<unsigned>(cn);
+    hist = take<unsigned>((size_t)C * AP_RADIX * (size_t)ntiles);
+    cursor = take<unsigned>((size_t)C);
+    partial = take<double>((size_t)AP_SPLITS_MAX * C);
+    frame_bytes = bytes + 1024;
+    bytes = (frame_bytes + 15) & ~(size_t)15;
+    at = (uintptr_t)ws + bytes;
+    st = take<unsigned>((size_t)PS_STAGES * (size_t)n);
+    off = take<int>((size_t)C);
+    bl_head = take<int>((size_t)nblk);
+    bl_tail = take<int>((size_t)nblk);
+    stage_bytes = bytes + 64;
+  }
+
+ private:
+  uintptr_t at;                          // the address reached
+  size_t bytes = 0;                      // the bytes budgeted so far: every buffer, and 8 for the gap in front of an 8-byte-aligned one
+  template <typename U> U* take(size_t count) {
+    if (sizeof(U) == 8) { at = (at + 7) & ~(uintptr_t)7; bytes += 8; }
+    U* p = (U*)at;
+    at += count * sizeof(U);
+    bytes += count * sizeof(U);
+    return p;
+  }
+};
+
+size_t perframe_ap_workspace_bytes(long long n, int C) { return ApLayout<unsigned>(nullptr, n, C).frame_bytes; }
+size_t perframe_cap_workspace_bytes(long long n, int C) { return ApLayout<ap_u64>(nullptr, n, C).frame_bytes; }
+size_t perstage_ap_workspace_bytes(long long n, int C) { return ApLayout<unsigned>(nullptr, n, C).stage_bytes; }
+size_t perstage_cap_workspace_bytes(long long n, int C) { return ApLayout<ap_u64>(nullptr, n, C).stage_bytes; }
 
 // what the per-frame and the per-stage metric share: keys, every class's positives sorted, every score counted against them
 // (T = unsigned: by key, AP; T = ap_u64: by (key, frame), cAP)
 template <typename T>
 struct ApRanked {
-  unsigned* keys;      // [C][n] order-reversing keys, class-major
   T* q;                // [C][n] class c: its len[c] positives ascending (descending score)
   unsigned* cnt;       // [C][n] class c: cnt[b] = entries whose lower_bound in q is b (AP: nonzero at the first member of a tie run only)
   unsigned* len;       // [C] positives per class
@@ -544,22 +611,16 @@ struct ApRanked {
 };
 
 template <typename T>
-static ApRanked<T> ap_rank_positives(const float* scores, const float* target, const int* labels, long long n, int C, void* ws, hipStream_t s) {
+static ApRanked<T> ap_rank_positives(const float* scores, const float* target, const int* labels, long long n, int C, const ApLayout<T>& L,
+                                     hipStream_t s) {
   static DeviceOnce once;
   once.run([] { (void)hipFuncSetAttribute((const void*)ap_count_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, AP_TAB * 4 + 128); });
-  const int ntiles = (int)((n + AP_TILE - 1) / AP_TILE);
-  const size_t cn = (size_t)C * (size_t)n;
-  unsigned* keys = (unsigned*)ws;
-  T* p0 = (T*)(((uintptr_t)(keys + cn) + sizeof(T) - 1) & ~(uintptr_t)(sizeof(T) - 1));
-  T* p1 = p0 + cn;
-  unsigned* cnt = (unsigned*)(p1 + cn);
-  unsigned* hist = cnt + cn;
-  unsigned* cursor = hist + (size_t)C * AP_RADIX * ntiles;
-  double* partial = (double*)(((uintptr_t)(cursor + C) + 7) & ~(uintptr_t)7);
-  (void)hipMemsetAsync(cursor, 0, (size_t)C * 4, s);
+  const int ntiles = L.ntiles;
+  T *p0 = L.p0, *p1 = L.p1;
+  (void)hipMemsetAsync(L.cursor, 0, (size_t)C * 4, s);
   const dim3 xg((unsigned)((n + AP_XF - 1) / AP_XF), (unsigned)((C + AP_XC - 1) / AP_XC));
-  if (labels) ap_extract_kernel<true, T><<<xg, 256, 0, s>>>(scores, nullptr, labels, n, C, keys, p0, cursor);
-  else ap_extract_kernel<false, T><<<xg, 256, 0, s>>>(scores, target, nullptr, n, C, keys, p0, cursor);
+  if (labels) ap_extract_kernel<true, T><<<xg, 256, 0, s>>>(scores, nullptr, labels, n, C, L.keys, p0, L.cursor);
+  else ap_extract_kernel<false, T><<<xg, 256, 0, s>>>(scores, target, nullptr, n, C, L.keys, p0, L.cursor);
   const int tg = ntiles < AP_TGRID ? ntiles : AP_TGRID;
   // digit shifts, least significant first: the key's four, below them (composites) the digits that frame indices up to n - 1 have
   int shifts[8], np = 0;
@@ -570,14 +631,14 @@ static ApRanked<T> ap_rank_positives(const float* scores, const float* target, c
     for (int p = 0; p < AP_PASSES; ++p) shifts[np++] = 8 * p;
   }
   for (int p = 0; p < np; ++p) {
-    ap32_hist_kernel<T><<<dim3(tg, C), 64, 0, s>>>(p0, cursor, n, ntiles, shifts[p], hist, p == 0 ? cnt : nullptr);
-    ap32_scan_kernel<<<C, 256, 0, s>>>(hist, cursor, ntiles);
-    ap32_scatter_kernel<T><<<dim3(tg, C), 64, 0, s>>>(p0, p1, cursor, n, ntiles, shifts[p], hist);
+    ap32_hist_kernel<T><<<dim3(tg, C), 64, 0, s>>>(p0, L.cursor, n, ntiles, shifts[p], L.hist, p == 0 ? L.cnt : nullptr);
+    ap32_scan_kernel<<<C, 256, 0, s>>>(L.hist, L.cursor, ntiles);
+    ap32_scatter_kernel<T><<<dim3(tg, C), 64, 0, s>>>(p0, p1, L.cursor, n, ntiles, shifts[p], L.hist);
     T* t = p0; p0 = p1; p1 = t;
   }
   const int splits = ap_splits(C);
-  ap_count_kernel<T><<<dim3(splits, C), 1024, AP_TAB * 4 + 128, s>>>(keys, p0, cursor, n, C, cnt, partial);
-  return ApRanked<T>{keys, p0, cnt, cursor, partial, splits};
+  ap_count_kernel<T><<<dim3(splits, C), 1024, AP_TAB * 4 + 128, s>>>(L.keys, p0, L.cursor, n, C, L.cnt, L.partial);
+  return ApRanked<T>{p0, L.cnt, L.cursor, L.partial, splits};
 }
 
 // Returns 0, or -1 on a bad argument.  ws must hold perframe_ap_workspace_bytes(n, C) bytes.  Positives: target != 0, or (labels != NULL)
@@ -585,8 +646,8 @@ static ApRanked<T> ap_rank_positives(const float* scores, const float* target, c
 int launch_perframe_ap(const float* scores, const float* target, const int* labels, long long n, int C, double* ap, long long* n_pos,
                        double* score_sum, void* ws, hipStream_t s) {
   if (n <= 0 || C <= 0 || C > 65535 || n >= (1ll << 31)) return -1;    // per-class cursors are 32-bit
-  const ApRanked<unsigned> r = ap_rank_positives<unsigned>(scores, target, labels, n, C, ws, s);
-  ap_reduce_kernel<<<C, 256, 0, s>>>(r.q, r.cnt, r.len, n, C, r.partial, r.splits, ap, n_pos, score_sum);
+  const ApRanked<unsigned> r = ap_rank_positives(scores, target, labels, n, C, ApLayout<unsigned>(ws, n, C), s);
+  ap_walk_kernel<ApWalk><<<C, 256, 0, s>>>(r.q, r.cnt, r.len, n, C, nullptr, nullptr, r.partial, r.splits, ap, n_pos, score_sum);
   return 0;
 }
 
@@ -598,8 +659,8 @@ int launch_perframe_cap(const float* scores, const float* target, const int* lab
     cap_empty_kernel<<<(C + 255) / 256, 256, 0, s>>>(C, ap, n_pos, score_sum);
     return 0;
   }
-  const ApRanked<ap_u64> r = ap_rank_positives<ap_u64>(scores, target, labels, n, C, ws, s);
-  cap_reduce_kernel<<<C, 256, 0, s>>>(r.cnt, r.len, n, C, r.partial, r.splits, ap, n_pos, score_sum);
+  const ApRanked<ap_u64> r = ap_rank_positives(scores, target, labels, n, C, ApLayout<ap_u64>(ws, n, C), s);
+  ap_walk_kernel<CapWalk><<<C, 256, 0, s>>>(nullptr, r.cnt, r.len, n, C, nullptr, nullptr, r.partial, r.splits, ap, n_pos, score_sum);
   return 0;
 }
 
@@ -619,30 +680,46 @@ int launch_perframe_cap(const float* scores, const float* target, const int* lab
 //                of each class's counters (exclusive sum of the positives per class: the labels are single, so they sum to <= n)
 //   ps_stage     per frame: run start (forward max-scan of the heads) and run end (backward min-scan of the tails); a positive derives
 //                its 10-bit stage mask from (i - a, len), finds its key's lower_bound in q_c and adds 1 to st_cs[b] of its stages
-//   ps_reduce    one workgroup per (class, stage) walks q_c, cnt_c and st_cs once: two running prefixes, the tie-run ends of q, fp64
-//                accumulation of (stage positives in the run) * (stage positives so far) / (samples so far) in ap_reduce's order.
+//   ap_walk<PsWalk>   one workgroup per (class, stage) walks q_c, cnt_c and st_cs once: two running prefixes, the tie-run ends of q, fp64
+//                accumulation of (stage positives in the run) * (stage positives so far) / (samples so far).
 // Integer atomics only (any order gives the same counters); the one floating-point sum has a fixed order: the same bits on every run.
+//
+// Per-stage calibrated average precision (metrics='cAP'), T = the (key, frame) composite: the lower_bound of a positive is its own
+// index, so st_cs holds the stage's member flags and cnt_c the ranks in the stable order.  ap_walk<CpsWalk> counts the members P_cs
+// first (w = (n - P_c) / P_cs) and accumulates, for a member at index i with rank r, tps / (tps + fps / (w + eps) + eps) with
+// tps = the members up to i and fps = r - (i + 1), the negatives in front of it.
 // ================================================================================================================================
-#define PS_STAGES 10
-#define PS_BLK 1024           // frames per block of the run scans (256 threads x 4)
+
+// the labels around a thread's four frames i0 .. i0 + 3 (lab[e + 1]: frame i0 + e; 0 outside [0, n)), which of the four start (head) or
+// end (tail) a run of equal labels, the thread's last head h (-1: none) and its first tail t (0x7FFFFFFF: none)
+struct PsRunEdges {
+  int lab[6];
+  bool head[4], tail[4];
+  int h, t;
+};
+__device__ __forceinline__ PsRunEdges ps_run_edges(const int* __restrict__ labels, long long n, long long i0) {
+  PsRunEdges r;
+  r.h = -1;
+  r.t = 0x7FFFFFFF;
+#pragma unroll
+  for (int e = 0; e < 6; ++e) { const long long i = i0 - 1 + e; r.lab[e] = (i >= 0 && i < n) ? labels[i] : 0; }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const long long i = i0 + e;
+    r.head[e] = i < n && (i == 0 || r.lab[e + 1] != r.lab[e]);
+    r.tail[e] = i < n && (i == n - 1 || r.lab[e + 1] != r.lab[e + 2]);
+    if (r.head[e]) r.h = (int)i;
+    if (r.tail[e] && r.t == 0x7FFFFFFF) r.t = (int)i;
+  }
+  return r;
+}
 
 __global__ __launch_bounds__(256) void ps_edges_kernel(const int* __restrict__ labels, long long n, int* __restrict__ bl_head,
                                                        int* __restrict__ bl_tail) {
   __shared__ int wh[4], wt[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long long i0 = (long long)blockIdx.x * PS_BLK + (long long)tid * 4;
-  int lab[6];
-#pragma unroll
-  for (int e = 0; e < 6; ++e) { const long long i = i0 - 1 + e; lab[e] = (i >= 0 && i < n) ? labels[i] : 0; }
-  int h = -1, t = 0x7FFFFFFF;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const long long i = i0 + e;
-    if (i < n) {
-      if (i == 0 || lab[e + 1] != lab[e]) h = (int)i;
-      if ((i == n - 1 || lab[e + 1] != lab[e + 2]) && t == 0x7FFFFFFF) t = (int)i;
-    }
-  }
+  const PsRunEdges r = ps_run_edges(labels, n, (long long)blockIdx.x * PS_BLK + (long long)tid * 4);
+  int h = r.h, t = r.t;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { h = max(h, __shfl_xor(h, o, 64)); t = min(t, __shfl_xor(t, o, 64)); }
   if (lane == 0) { wh[wave] = h; wt[wave] = t; }
@@ -653,43 +730,14 @@ __global__ __launch_bounds__(256) void ps_edges_kernel(const int* __restrict__ l
   }
 }
 
-template <int OP> __device__ __forceinline__ int ps_comb(int a, int b) { return OP == 0 ? max(a, b) : OP == 1 ? min(a, b) : a + b; }
-
-// exclusive scan of v[0 .. m) in place by one 256-thread workgroup; REV: from the back
-template <int OP, bool REV>
-__device__ void ps_block_scan(int* v, int m, int identity, int* wsum, int* carry) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) *carry = identity;
-  __syncthreads();
-  for (int base = 0; base < m; base += 256) {
-    const int idx = base + tid;
-    const int pos = REV ? m - 1 - idx : idx;
-    const int x = idx < m ? v[pos] : identity;
-    int incl = x;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o, 64); if (lane >= o) incl = ps_comb<OP>(incl, u); }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int off = *carry;
-    for (int w = 0; w < wave; ++w) off = ps_comb<OP>(off, wsum[w]);
-    int before = __shfl_up(incl, 1, 64);
-    if (lane == 0) before = identity;
-    if (idx < m) v[pos] = ps_comb<OP>(off, before);
-    __syncthreads();
-    if (tid == 255) *carry = ps_comb<OP>(off, incl);
-    __syncthreads();
-  }
-}
-
 __global__ __launch_bounds__(256) void ps_carry_kernel(int* __restrict__ bl_head, int* __restrict__ bl_tail, int nblk,
                                                        const unsigned* __restrict__ len, int C, int* __restrict__ off) {
-  __shared__ int wsum[4];
-  __shared__ int carry;
-  ps_block_scan<0, false>(bl_head, nblk, -1, wsum, &carry);             // -> the last head in front of the block
-  ps_block_scan<1, true>(bl_tail, nblk, 0x7FFFFFFF, wsum, &carry);      // -> the first tail behind the block
+  __shared__ int wsum[2][4];
+  wg_scan_array<ScanMax, false, 1>(bl_head, nblk, -1, wsum);            // -> the last head in front of the block
+  wg_scan_array<ScanMin, true, 1>(bl_tail, nblk, 0x7FFFFFFF, wsum);     // -> the first tail behind the block
   for (int c = threadIdx.x; c < C; c += 256) off[c] = (int)len[c];
   __syncthreads();
-  ps_block_scan<2, false>(off, C, 0, wsum, &carry);                     // positives of the classes in front (their sum is <= n < 2^31)
+  wg_scan_array<ScanSum, false, 1>(off, C, 0, wsum);                    // positives of the classes in front (their sum is <= n < 2^31)
 }
 
 // T = the (key, frame) composite (cAP): the lower_bound of a positive is its own index, st_cs marks the stage's members
@@ -701,20 +749,8 @@ __global__ __launch_bounds__(256) void ps_stage_kernel(const float* __restrict__
   __shared__ int wh[4], wt[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long i0 = (long long)blockIdx.x * PS_BLK + (long long)tid * 4;
-  int lab[6];
-#pragma unroll
-  for (int e = 0; e < 6; ++e) { const long long i = i0 - 1 + e; lab[e] = (i >= 0 && i < n) ? labels[i] : 0; }
-  bool head[4], tail[4];
-  int h = -1, t = 0x7FFFFFFF;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const long long i = i0 + e;
-    head[e] = i < n && (i == 0 || lab[e + 1] != lab[e]);
-    tail[e] = i < n && (i == n - 1 || lab[e + 1] != lab[e + 2]);
-    if (head[e]) h = (int)i;
-    if (tail[e] && t == 0x7FFFFFFF) t = (int)i;
-  }
-  int hs = h, ts = t;                                       // inclusive scans over the wave: heads from the front, tails from the back
+  const PsRunEdges r = ps_run_edges(labels, n, i0);
+  int hs = r.h, ts = r.t;                                   // inclusive scans over the wave: heads from the front, tails from the back
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
     const int u = __shfl_up(hs, o, 64), d = __shfl_down(ts, o, 64);
@@ -735,13 +771,13 @@ __global__ __launch_bounds__(256) void ps_stage_kernel(const float* __restrict__
   }
   int a[4], b[4];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) { if (head[e]) a_run = (int)(i0 + e); a[e] = a_run; }
+  for (int e = 0; e < 4; ++e) { if (r.head[e]) a_run = (int)(i0 + e); a[e] = a_run; }
 #pragma unroll
-  for (int e = 3; e >= 0; --e) { if (tail[e]) b_run = (int)(i0 + e); b[e] = b_run; }
+  for (int e = 3; e >= 0; --e) { if (r.tail[e]) b_run = (int)(i0 + e); b[e] = b_run; }
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const long long i = i0 + e;
-    const int c = lab[e + 1];
+    const int c = r.lab[e + 1];
     if (i >= n || c < 0 || c >= C) continue;
     const double rl = (double)(b[e] - a[e]);
     const long long at = i - a[e];
@@ -765,181 +801,6 @@ __global__ __launch_bounds__(256) void ps_stage_kernel(const float* __restrict__
   }
 }
 
-// one workgroup per (class, stage): ap_reduce_kernel with a second running prefix, the stage positives
-__global__ __launch_bounds__(256) void ps_reduce_kernel(const unsigned* __restrict__ q_all, const unsigned* __restrict__ cnt_all,
-                                                        const unsigned* __restrict__ len, long long n, int C, const unsigned* __restrict__ st_all,
-                                                        const int* __restrict__ off, double* __restrict__ ap, long long* __restrict__ n_pos) {
-  __shared__ long long w_sum[4], w_st[4], w_max[4];
-  __shared__ double w_acc[4];
-  __shared__ long long carry_cnt, carry_st, carry_end;
-  const int c = blockIdx.x, sg = blockIdx.y;
-  const long long P = (long long)len[c];
-  const unsigned* q = q_all + (size_t)c * n;
-  const unsigned* cnt = cnt_all + (size_t)c * n;
-  const unsigned* st = st_all + (size_t)sg * n + (size_t)off[c];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) { carry_cnt = 0; carry_st = 0; carry_end = 0; }
-  __syncthreads();
-  double acc = 0.0;
-  for (long long base = 0; base < P; base += 1024) {
-    const long long j = base + (long long)tid * 4;
-    unsigned k[5];
-    long long v[4], u[4], mine = 0, mine_st = 0;
-#pragma unroll
-    for (int e = 0; e < 5; ++e) k[e] = j + e < P ? q[j + e] : 0u;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      v[e] = j + e < P ? (long long)cnt[j + e] : 0;
-      u[e] = j + e < P ? (long long)st[j + e] : 0;
-      mine += v[e];
-      mine_st += u[e];
-    }
-    long long incl = mine, incl_st = mine_st;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const long long x = __shfl_up(incl, o, 64), y = __shfl_up(incl_st, o, 64);
-      if (lane >= o) { incl += x; incl_st += y; }
-    }
-    if (lane == 63) { w_sum[wave] = incl; w_st[wave] = incl_st; }
-    __syncthreads();
-    long long seen = carry_cnt + incl - mine;               // column scores at or above the score in front of my first element
-    long long tps = carry_st + incl_st - mine_st;           // stage positives at or above it
-    for (int w = 0; w < wave; ++w) { seen += w_sum[w]; tps += w_st[w]; }
-    long long s_after[4], t_after[4], end_local = 0;        // stage positives at my last run end (0 = none: the prefix is monotone)
-    bool is_end[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      seen += v[e];
-      tps += u[e];
-      s_after[e] = seen;
-      t_after[e] = tps;
-      is_end[e] = (j + e < P) && ((j + e + 1 >= P) || (k[e] != k[e + 1]));
-      if (is_end[e]) end_local = tps;
-    }
-    long long mx = end_local;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const long long x = __shfl_up(mx, o, 64); if (lane >= o && x > mx) mx = x; }
-    if (lane == 63) w_max[wave] = mx;
-    __syncthreads();
-    long long prev = __shfl_up(mx, 1, 64);                  // stage positives at the most recent run end before my first element
-    if (lane == 0) prev = 0;
-    if (carry_end > prev) prev = carry_end;
-    for (int w = 0; w < wave; ++w) if (w_max[w] > prev) prev = w_max[w];
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (is_end[e]) {
-        const long long d = t_after[e] - prev;              // stage positives of this tie run (counted at its first member)
-        if (d > 0) {
-          const long long samples = s_after[e] - (j + e + 1) + t_after[e];
-          acc += (double)d * ((double)t_after[e] / (double)samples);
-          prev = t_after[e];
-        }
-      }
-    __syncthreads();
-    if (tid == 255) {
-      carry_cnt = seen;
-      carry_st = tps;
-      long long mm = carry_end;
-      for (int w = 0; w < 4; ++w) if (w_max[w] > mm) mm = w_max[w];
-      carry_end = mm;
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if (lane == 0) w_acc[wave] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    const long long Ps = carry_st;
-    const double a = (w_acc[0] + w_acc[1]) + (w_acc[2] + w_acc[3]);
-    ap[(size_t)sg * C + c] = Ps > 0 ? a / (double)Ps : 0.0;               // a class without a run: 0.0, as the reference reports it
-    if (n_pos) n_pos[(size_t)sg * C + c] = Ps;
-  }
-}
-
-// Per-stage calibrated average precision (metrics='cAP'): one workgroup per (class, stage) over cnt_c (ranks in the stable order) and
-// the stage's member flags st_cs.  A first walk counts the members P_cs (w = (n - P_c) / P_cs needs it before the first term); the
-// second keeps two running prefixes and accumulates, for a member at index i with rank r, tps / (tps + fps / (w + eps) + eps) with
-// tps = the members up to i and fps = r - (i + 1), the negatives in front of it - per thread in index order, then fixed trees.
-__global__ __launch_bounds__(256) void cps_reduce_kernel(const unsigned* __restrict__ cnt_all, const unsigned* __restrict__ len, long long n,
-                                                         int C, const unsigned* __restrict__ st_all, const int* __restrict__ off,
-                                                         double* __restrict__ ap, long long* __restrict__ n_pos) {
-  __shared__ long long w_sum[4], w_st[4];
-  __shared__ double w_acc[4];
-  __shared__ long long carry_cnt, carry_st, members;
-  const int c = blockIdx.x, sg = blockIdx.y;
-  const long long P = (long long)len[c];
-  const unsigned* cnt = cnt_all + (size_t)c * n;
-  const unsigned* st = st_all + (size_t)sg * n + (size_t)off[c];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  long long ms = 0;
-  for (long long j = tid; j < P; j += 256) ms += (long long)st[j];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) ms += __shfl_xor(ms, o, 64);
-  if (lane == 0) w_sum[wave] = ms;
-  if (tid == 0) { carry_cnt = 0; carry_st = 0; }
-  __syncthreads();
-  if (tid == 0) members = (w_sum[0] + w_sum[1]) + (w_sum[2] + w_sum[3]);
-  __syncthreads();
-  const long long Ps = members;
-  const double wd = (double)(n - P) / (double)Ps + CAP_EPS;                   // Ps = 0: no term is formed
-  double acc = 0.0;
-  for (long long base = 0; base < P; base += 1024) {
-    const long long j = base + (long long)tid * 4;
-    long long v[4], u[4], mine = 0, mine_st = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      v[e] = j + e < P ? (long long)cnt[j + e] : 0;
-      u[e] = j + e < P ? (long long)st[j + e] : 0;
-      mine += v[e];
-      mine_st += u[e];
-    }
-    long long incl = mine, incl_st = mine_st;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const long long x = __shfl_up(incl, o, 64), y = __shfl_up(incl_st, o, 64);
-      if (lane >= o) { incl += x; incl_st += y; }
-    }
-    if (lane == 63) { w_sum[wave] = incl; w_st[wave] = incl_st; }
-    __syncthreads();
-    long long seen = carry_cnt + incl - mine;               // frames of the column in front of my first element
-    long long tps = carry_st + incl_st - mine_st;           // stage members in front of it
-    for (int w = 0; w < wave; ++w) { seen += w_sum[w]; tps += w_st[w]; }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      seen += v[e];
-      tps += u[e];
-      if (u[e]) {
-        const double t = (double)tps, fps = (double)(seen - (j + e + 1));
-        acc += t / (t + fps / wd + CAP_EPS);
-      }
-    }
-    __syncthreads();
-    if (tid == 255) { carry_cnt = seen; carry_st = tps; }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if (lane == 0) w_acc[wave] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    const double a = (w_acc[0] + w_acc[1]) + (w_acc[2] + w_acc[3]);
-    ap[(size_t)sg * C + c] = Ps > 0 ? a / (double)Ps : cap_nan();           // no member: NaN, as the host form
-    if (n_pos) n_pos[(size_t)sg * C + c] = Ps;
-  }
-}
-
-template <typename T> static size_t ps_base_bytes(long long n, int C) {
-  return ((sizeof(T) == 4 ? perframe_ap_workspace_bytes(n, C) : perframe_cap_workspace_bytes(n, C)) + 15) & ~(size_t)15;
-}
-template <typename T> static size_t ps_workspace_bytes(long long n, int C) {
-  const size_t nblk = (size_t)((n + PS_BLK - 1) / PS_BLK);
-  return ps_base_bytes<T>(n, C) + (size_t)PS_STAGES * (size_t)n * 4 + (size_t)C * 4 + 2 * nblk * 4 + 64;
-}
-
-size_t perstage_ap_workspace_bytes(long long n, int C) { return ps_workspace_bytes<unsigned>(n, C); }
-size_t perstage_cap_workspace_bytes(long long n, int C) { return ps_workspace_bytes<ap_u64>(n, C); }
-
 template <typename T>
 static int perstage_launch(const float* scores, const int* labels, long long n, int C, double* ap, long long* n_pos, void* ws, hipStream_t s) {
   if (n < 0 || C <= 0 || C > 65535 || n >= (1ll << 31)) return -1;
@@ -948,18 +809,15 @@ static int perstage_launch(const float* scores, const int* labels, long long n, 
     if (n_pos) (void)hipMemsetAsync(n_pos, 0, (size_t)PS_STAGES * C * 8, s);
     return 0;
   }
-  const int nblk = (int)((n + PS_BLK - 1) / PS_BLK);
-  unsigned* st = (unsigned*)((char*)ws + ps_base_bytes<T>(n, C));
-  int* off = (int*)(st + (size_t)PS_STAGES * (size_t)n);
-  int* bl_head = off + C;
-  int* bl_tail = bl_head + nblk;
-  const ApRanked<T> r = ap_rank_positives<T>(scores, nullptr, labels, n, C, ws, s);
-  (void)hipMemsetAsync(st, 0, (size_t)PS_STAGES * (size_t)n * 4, s);
-  ps_edges_kernel<<<nblk, 256, 0, s>>>(labels, n, bl_head, bl_tail);
-  ps_carry_kernel<<<1, 256, 0, s>>>(bl_head, bl_tail, nblk, r.len, C, off);
-  ps_stage_kernel<T><<<nblk, 256, 0, s>>>(scores, labels, n, C, bl_head, bl_tail, r.q, r.len, off, st);
-  if constexpr (sizeof(T) == 4) ps_reduce_kernel<<<dim3(C, PS_STAGES), 256, 0, s>>>(r.q, r.cnt, r.len, n, C, st, off, ap, n_pos);
-  else cps_reduce_kernel<<<dim3(C, PS_STAGES), 256, 0, s>>>(r.cnt, r.len, n, C, st, off, ap, n_pos);
+  const ApLayout<T> L(ws, n, C);
+  const ApRanked<T> r = ap_rank_positives(scores, nullptr, labels, n, C, L, s);
+  (void)hipMemsetAsync(L.st, 0, (size_t)PS_STAGES * (size_t)n * 4, s);
+  ps_edges_kernel<<<L.nblk, 256, 0, s>>>(labels, n, L.bl_head, L.bl_tail);
+  ps_carry_kernel<<<1, 256, 0, s>>>(L.bl_head, L.bl_tail, L.nblk, r.len, C, L.off);
+  ps_stage_kernel<T><<<L.nblk, 256, 0, s>>>(scores, labels, n, C, L.bl_head, L.bl_tail, r.q, r.len, L.off, L.st);
+  const dim3 grid(C, PS_STAGES);
+  if constexpr (sizeof(T) == 4) ap_walk_kernel<PsWalk><<<grid, 256, 0, s>>>(r.q, r.cnt, r.len, n, C, L.st, L.off, nullptr, 0, ap, n_pos, nullptr);
+  else ap_walk_kernel<CpsWalk><<<grid, 256, 0, s>>>(nullptr, r.cnt, r.len, n, C, L.st, L.off, nullptr, 0, ap, n_pos, nullptr);
   return 0;
 }
 

@@ -154,6 +154,53 @@ def _postprocess_device(what, prediction, ground_truth, postprocessing, n_valid)
     return res[1], res[0], (res.check if n_valid is not None else None)
 
 
+def _need_cuda(what, *tensors):
+    from ._lib import PregoError
+    if not all(t.is_cuda for t in tensors):
+        raise PregoError(f"{what} needs CUDA tensors; there is no CPU fallback (host arrays: {what[:-len('_device')]})")
+
+
+def _device_metric(what, kind, prediction, truth, class_names, postprocessing, n_valid, cal, rows, n_out, report, defer, raw):
+    """What the two device functions share behind their own argument checks: the post-processing, fp32 scores and the targets as the
+    entry wants them, the shape check, workspace and outputs, the call of prego_<kind>_ap / _cap (`cal`) (`_labels`: one id per
+    frame) on the current stream, and the function that collects the result.  The entry writes `n_out` arrays of shape `rows` +
+    (classes,) - the metric, the positives (int64), per frame also the score mass -; an empty set gives zeros without a call.
+    raw: those arrays; else report(*arrays, class_names).  defer: the collecting function is returned instead of called."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    from ._lib import PregoError, check
+    prediction, truth, count_check = _postprocess_device(what, prediction, truth, postprocessing, n_valid)
+    _need_cuda(what, prediction, truth)
+    pred = prediction.detach().to(torch.float32).contiguous()
+    by_label = truth.dim() == 1 and not truth.dtype.is_floating_point      # one class id per frame
+    truth = truth.detach().to(torch.int32 if by_label else torch.float32).contiguous()
+    if pred.dim() != 2 or pred.shape[1] != len(class_names) or (truth.shape != pred.shape[:1] if by_label else truth.shape != pred.shape):
+        raise PregoError(f"{what}: shapes {tuple(pred.shape)} / {tuple(truth.shape)} for {len(class_names)} classes")
+    n, ncls = pred.shape
+    out = ws = None
+    if n > 0:                                           # an empty eval set: same empty report as the host path
+        lib = _lib.load()
+        dev = pred.device
+        stem = f"prego_{kind}_{'cap' if cal else 'ap'}"
+        ws = torch.empty(getattr(lib, stem + "_workspace_bytes")(n, ncls), dtype=torch.uint8, device=dev)
+        out = torch.empty((n_out,) + rows + (ncls,), dtype=torch.float64, device=dev)      # the positives as int64 bits
+        p = lambda t: C.c_void_p(t.data_ptr())
+        with torch.cuda.device(dev):
+            check(getattr(lib, stem + ("_labels" if by_label else ""))(p(pred), p(truth), n, ncls, *[p(o) for o in out], p(ws), ws.numel(),
+                                                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+    def finish(_keep=(pred, truth, ws)):
+        host = out.cpu().numpy() if n > 0 else np.zeros((n_out,) + rows + (ncls,))
+        if count_check is not None:
+            count_check()
+        arrays = [h.view(np.int64) if i == 1 else h for i, h in enumerate(host)]
+        return tuple(a.copy() for a in arrays) if raw else report(*arrays, class_names)
+    return finish if defer else finish()
+
+
 def perframe_average_precision_device(prediction, ground_truth, class_names, postprocessing=None, metrics="AP", defer=False, raw=False,
                                       n_valid=None):
     """Device path: prediction / ground_truth fp32 CUDA tensors [frames, classes] - or ground_truth = an integer CUDA tensor [frames],
@@ -167,56 +214,11 @@ def perframe_average_precision_device(prediction, ground_truth, class_names, pos
     compared when the result is collected (PregoError on a mismatch); without it the count is read back before the metric is enqueued.
     defer=True: the kernels are only ENQUEUED and a function is returned that waits for them and builds the report (Evaluate writes
     its output file while the GPU sorts)."""
-    import ctypes as C
-
-    import torch
-
-    from . import _lib
-    from ._lib import PregoError, check
+    from ._lib import PregoError
     if metrics not in ("AP", "cAP"):
         raise PregoError("perframe_average_precision_device: metric 'AP' or 'cAP' only")
-    prediction, ground_truth, count_check = _postprocess_device("perframe_average_precision_device", prediction, ground_truth,
-                                                                postprocessing, n_valid)
-    cal = metrics == "cAP"
-    if not (prediction.is_cuda and ground_truth.is_cuda):
-        raise PregoError("perframe_average_precision_device needs CUDA tensors; there is no CPU fallback "
-                         "(host arrays: perframe_average_precision)")
-    pred = prediction.detach().to(torch.float32).contiguous()
-    by_label = ground_truth.dim() == 1 and not ground_truth.dtype.is_floating_point      # one class id per frame (prego_perframe_ap_labels)
-    truth = ground_truth.detach().to(torch.int32 if by_label else torch.float32).contiguous()
-    if pred.dim() != 2 or pred.shape[1] != len(class_names) or (truth.shape != pred.shape[:1] if by_label else truth.shape != pred.shape):
-        raise PregoError(f"perframe_average_precision_device: shapes {tuple(pred.shape)} / {tuple(truth.shape)} for {len(class_names)} classes")
-    n, ncls = pred.shape
-    if n == 0:                                          # an empty eval set: same empty report as the host path
-        z = (np.zeros(ncls), np.zeros(ncls, np.int64), np.zeros(ncls))
-        rep = z if raw else _report(*z, class_names)
-
-        def empty():
-            if count_check is not None:
-                count_check()
-            return rep
-        return empty if defer else empty()
-    lib = _lib.load()
-    dev = pred.device
-    need = lib.prego_perframe_cap_workspace_bytes if cal else lib.prego_perframe_ap_workspace_bytes
-    ws = torch.empty(need(n, ncls), dtype=torch.uint8, device=dev)
-    out = torch.empty((3, ncls), dtype=torch.float64, device=dev)          # AP | positives (int64 bits) | score sums
-    with torch.cuda.device(dev):
-        if cal:
-            fn = lib.prego_perframe_cap_labels if by_label else lib.prego_perframe_cap
-        else:
-            fn = lib.prego_perframe_ap_labels if by_label else lib.prego_perframe_ap
-        check(fn(C.c_void_p(pred.data_ptr()), C.c_void_p(truth.data_ptr()), n, ncls, C.c_void_p(out[0].data_ptr()),
-                 C.c_void_p(out[1].data_ptr()), C.c_void_p(out[2].data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
-                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-    def finish(_keep=(pred, truth, ws)):
-        host = out.cpu().numpy()
-        if count_check is not None:
-            count_check()
-        if raw:
-            return host[0].copy(), host[1].view(np.int64).copy(), host[2].copy()
-        return _report(host[0], host[1].view(np.int64), host[2], class_names)
-    return finish if defer else finish()
+    return _device_metric("perframe_average_precision_device", "perframe", prediction, ground_truth, class_names, postprocessing, n_valid,
+                          metrics == "cAP", (), 3, _report, defer, raw)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -317,51 +319,14 @@ def perstage_average_precision_device(prediction, labels, class_names, defer=Fal
     defer=True: the kernels are only ENQUEUED and a function is returned that waits for them and builds the result.
     postprocessing / n_valid: None or a `ThumosPostprocessing` and its hint, as perframe_average_precision_device (the runs are those
     of the frames that are left: removing a frame makes its neighbours adjacent)."""
-    import ctypes as C
-
     import torch
 
-    from . import _lib
-    from ._lib import PregoError, check
+    from ._lib import PregoError
     if metrics not in ("AP", "cAP"):
         raise PregoError(f"perstage_average_precision_device: metrics {metrics!r} ('AP' or 'cAP')")
-    cal = metrics == "cAP"
-    if not (prediction.is_cuda and labels.is_cuda):
-        raise PregoError("perstage_average_precision_device needs CUDA tensors; there is no CPU fallback "
-                         "(host arrays: perstage_average_precision)")
+    _need_cuda("perstage_average_precision_device", prediction, labels)
     if labels.dim() != 1 or labels.dtype.is_floating_point or labels.dtype == torch.bool:
         raise PregoError("perstage_average_precision_device: labels must be one integer class id per frame [frames] "
                          "(dense target matrices: perstage_average_precision on the host)")
-    prediction, labels, count_check = _postprocess_device("perstage_average_precision_device", prediction, labels, postprocessing, n_valid)
-    pred = prediction.detach().to(torch.float32).contiguous()
-    ids = labels.detach().to(torch.int32).contiguous()
-    if pred.dim() != 2 or pred.shape[1] != len(class_names) or ids.shape != pred.shape[:1]:
-        raise PregoError(f"perstage_average_precision_device: shapes {tuple(pred.shape)} / {tuple(ids.shape)} for {len(class_names)} classes")
-    n, ncls = pred.shape
-    if n == 0:
-        z = (np.zeros((N_STAGES, ncls)), np.zeros((N_STAGES, ncls), np.int64))
-        rep = z if raw else perstage_report(z[0], class_names)
-
-        def empty():
-            if count_check is not None:
-                count_check()
-            return rep
-        return empty if defer else empty()
-    lib = _lib.load()
-    dev = pred.device
-    need = lib.prego_perstage_cap_workspace_bytes if cal else lib.prego_perstage_ap_workspace_bytes
-    ws = torch.empty(need(n, ncls), dtype=torch.uint8, device=dev)
-    out = torch.empty((2, N_STAGES, ncls), dtype=torch.float64, device=dev)          # AP | positives (int64 bits)
-    with torch.cuda.device(dev):
-        fn = lib.prego_perstage_cap_labels if cal else lib.prego_perstage_ap_labels
-        check(fn(C.c_void_p(pred.data_ptr()), C.c_void_p(ids.data_ptr()), n, ncls, C.c_void_p(out[0].data_ptr()),
-                 C.c_void_p(out[1].data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
-                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-    def finish(_keep=(pred, ids, ws)):
-        host = out.cpu().numpy()
-        if count_check is not None:
-            count_check()
-        if raw:
-            return host[0].copy(), host[1].view(np.int64).copy()
-        return perstage_report(host[0], class_names)
-    return finish if defer else finish()
+    return _device_metric("perstage_average_precision_device", "perstage", prediction, labels, class_names, postprocessing, n_valid,
+                          metrics == "cAP", (N_STAGES,), 2, lambda ap, n_pos, names: perstage_report(ap, names), defer, raw)

@@ -71,6 +71,50 @@ def test_tile_edges_vs_host(n, ncls):
     assert np.abs(ap - host_ap).max() < TOL
 
 
+def long_list_case(levels):
+    """(scores [5000, 3], ids): class 1 holds about 3000 frames in runs of 1..300, class 2 about 1000, class 0 none (id -1: a negative
+    of every class); levels = 3: every column three long tie runs, levels = 0: tie-free"""
+    from .test_cap_cpu import edge_scores
+    n, ncls = 5000, 3
+    rng = np.random.default_rng(50 + levels)
+    scores = edge_scores(rng, n, ncls, levels)
+    runs = []
+    while sum(len(r) for r in runs) < n:
+        runs.append(np.full(int(rng.integers(1, 301)), int(rng.choice([1, 1, 1, 2, -1])), np.int32))
+    return scores, np.concatenate(runs)[:n]
+
+
+@pytest.mark.parametrize("levels", [0, 3])
+def test_long_lists_with_tie_runs_over_chunk_borders(levels):
+    """A class with more than 2048 positives: its list takes three 1024-element chunks of the walk (csrc/metrics.hip, ap_walk_kernel),
+    so the carries between chunks, every wave border and tie runs that span them are reached (by ids the edge shapes above give a class
+    a few hundred positives).  All four entries by ids against the host forms within (P + 16) * 2^-52, P = the positives in that sum
+    (tests/test_cap_cpu.py says why); equal positive counts; NaN exactly where the host form has it (class 0, which has no frame)."""
+    from prego_amd.metrics import average_precision_columns, calibrated_average_precision_columns, perframe_ap_raw_device
+    from .test_cap_cpu import close, onehot
+    scores, labels = long_list_case(levels)
+    ncls = scores.shape[1]
+    names = [f"c{i}" for i in range(ncls)]
+    pos = onehot(labels, ncls) != 0
+    assert pos[:, 1].sum() > 2048 and pos[:, 2].sum() > 0 and pos[:, 0].sum() == 0
+    pr, ids = torch.from_numpy(scores).cuda(), torch.from_numpy(labels).cuda()
+    for metric, columns in (("AP", average_precision_columns), ("cAP", calibrated_average_precision_columns)):
+        got, n_pos, _ = perframe_ap_raw_device(pr, ids, metric)
+        want = columns(scores, pos)
+        ok, dev = close(got, want, pos.sum(0))
+        print(f"levels {levels} {metric}: per-frame max |device - host| {dev:.3e}")
+        assert np.isnan(want[0]) and np.isfinite(want[1:]).all()
+        assert np.array_equal(n_pos, pos.sum(0))
+        assert ok, (metric, got, want)
+        got, n_pos = perstage_average_precision_device(pr, ids, names, raw=True, metrics=metric)
+        want, want_pos = perstage_ap_raw(scores, labels, metric)
+        ok, dev = close(got, want, want_pos)
+        print(f"levels {levels} {metric}: per-stage max |device - host| {dev:.3e}")
+        assert np.isfinite(want[:, 1:]).all() and (want_pos[:, 1:] > 0).all()
+        assert np.array_equal(n_pos, want_pos)
+        assert ok, (metric, got, want)
+
+
 def test_worst_case_lists_stay_inside_the_queried_workspace():
     """every run one frame long: every positive is in all ten stages, the largest the per-stage counters get"""
     from prego_amd import _lib
