@@ -460,6 +460,37 @@ int prego_format_ids(const int32_t* ids, int64_t n, uint32_t* text, int32_t* bad
  * between calls converts its fp32 features with, once. */
 int prego_cast_features(const float* src, void* dst, int64_t n, int dtype, prego_stream_t stream);
 
+/* One training batch cut from a training set that stays in device memory: what the loader's default_collate stacks from the items of
+ * datasets/dataset.py:96-132 (StepRecognitionDataset: rgb, flow, target of a window) or :138-231 (AnticipationDataset: also ant_target),
+ * written by ONE launch on `stream`.  Allocates nothing, waits for nothing.  An addition to ABI 7 (existing signatures unchanged).
+ *
+ * Resident set, device memory: the UNPADDED videos one after the other - rgb_rows [n_rows][d_rgb] fp32, flow_rows [n_rows][d_flow] fp32
+ * (NULL for a dataset without flow; flow_out is then NULL as well), and EITHER labels int32 [n_rows] (the row's class id, -1 for an
+ * all-zero row: target rows are built as zeros with 1.0f at the class) OR dense_targets [n_rows][n_classes] fp32 (rows are copied).
+ * vid_row0 int64 [n_videos]: a video's first resident row; vid_len int32 [n_videos]: its frames.
+ *
+ * Windows, device memory: table int32 [n_windows][2] = (video index, start row) per window, the start in the datasets' PADDED
+ * coordinates (window_size - 1 zero rows in front of every video, dataset.py:53-55); bit 31 of the video word marks a PAD entry
+ * (features of the window, all-zero target and ant_target).  order int32 [n_order]: indices into table in the order the sampler drew them;
+ * the batch is order[first .. first + n).
+ *
+ * Outputs, device fp32 contiguous, each nullable: rgb_out [n][window_size][d_rgb], flow_out [n][window_size][d_flow],
+ * target_out [n][window_size][n_classes], ant_target_out [n][ant_len][n_classes].
+ *
+ * Row rule: row r of a window with start s is padded row p = s + r of its video; ant_target row l is padded row p = s + window_size + l.
+ * p < window_size - 1 or p >= vid_len[v] + window_size - 1 gives a row of zeros (nothing is read), every other p reads resident row
+ * vid_row0[v] + p - (window_size - 1).  No table content makes the kernel read outside the resident arrays: an order entry outside
+ * [0, n_windows), a video index outside [0, n_videos) or a resident row outside [0, n_rows) gives zeros.
+ *
+ * PREGO_EINVAL with a message, nothing launched: d_rgb or d_flow not a multiple of 4; rgb_rows, flow_rows or an output not 16-byte
+ * aligned (a table not aligned to its element); n < 1; both or neither of labels / dense_targets; window_size < 1; ant_len < 0;
+ * ant_target_out with ant_len == 0; an output without its resident rows; a NULL table; n_classes < 1; first / n outside order; a batch
+ * of 2^31 or more rows or target elements. */
+int prego_gather_windows(const float* rgb_rows, const float* flow_rows, int64_t n_rows, int d_rgb, int d_flow, const int32_t* labels,
+                         const float* dense_targets, const int64_t* vid_row0, const int32_t* vid_len, int n_videos, const int32_t* table,
+                         int n_windows, const int32_t* order, int64_t n_order, int64_t first, int n, int window_size, int n_classes,
+                         int ant_len, float* rgb_out, float* flow_out, float* target_out, float* ant_target_out, prego_stream_t stream);
+
 /* utils/metrics.py:25-62 on the device: sklearn.metrics.average_precision_score of every class column of the per-frame score
  * matrix the eval loop collects (trainer/eval.py:48-57; main.py:101 runs it after every epoch).  scores / target: device fp32
  * [n_frames][n_classes] row-major (target != 0 marks a positive).  Thresholds are the distinct score values (ties share one),

@@ -42,7 +42,7 @@ SYMBOLS = [
     "prego_miniroad_set_anticipation_grads", "prego_miniroad_adamw_step_anticipation",
     "prego_miniroad_step_anticipation",
     "prego_miniroad_step_wide_workspace_bytes", "prego_miniroad_step_wide", "prego_miniroad_step_wide_anticipation",
-    "prego_cast_features",
+    "prego_cast_features", "prego_gather_windows",
     "prego_stream_pool_bytes", "prego_stream_pool_create", "prego_stream_pool_destroy", "prego_miniroad_step_pool_workspace_bytes",
     "prego_miniroad_step_pool", "prego_stream_pool_vote", "prego_stream_pool_flush", "prego_stream_pool_reset", "prego_stream_pool_record",
     "prego_miniroad_step_frames_workspace_bytes", "prego_miniroad_step_frames", "prego_miniroad_step_frames_anticipation",
@@ -167,6 +167,7 @@ def _open(path: str, debug: bool) -> C.CDLL:
     lib.prego_window_vote.argtypes = [vp, i64, i32, i32, vp, vp]
     lib.prego_format_ids.argtypes = [vp, i64, vp, vp, vp]
     lib.prego_cast_features.argtypes = [vp, vp, i64, i32, vp]
+    lib.prego_gather_windows.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.prego_perframe_ap_workspace_bytes.argtypes = [i64, i32]
     lib.prego_perframe_ap_workspace_bytes.restype = sz
     lib.prego_perframe_ap.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, sz, vp]

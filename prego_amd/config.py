@@ -16,6 +16,12 @@ FEATURE_SIZES = {
 }
 
 
+# Keys the reference does not have, with the value a cfg without them gets (read with cfg.get: a reference yaml stays valid).
+#   train_cache_device     the training set stays in device memory and every batch is cut there by one launch (train_cache.py)
+#   train_cache_max_bytes  its byte budget; None = half of the free device memory when the cache is filled
+TRAIN_CACHE_DEFAULTS = {"train_cache_device": False, "train_cache_max_bytes": None}
+
+
 def rgb_dim(cfg: dict) -> int:
     return 0 if cfg.get("no_rgb", False) else FEATURE_SIZES[cfg["rgb_type"]]
 

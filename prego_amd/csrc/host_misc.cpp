@@ -1,5 +1,8 @@
 // Handle-free entry points of the C ABI (include/prego_amd.h): post-processing, metrics and label preparation around the models.
 #include "host_common.h"
+#ifdef PREGO_DEBUG_ABI
+#include "miniroad_handle.h"      // the allocation / wait counters of prego_debug_alloc_count cover this file's entries as well
+#endif
 
 #include <algorithm>
 #include <thread>
@@ -39,6 +42,54 @@ extern "C" int prego_cast_features(const float* src, void* dst, int64_t n, int d
   HIPCHK(hipGetDevice(&dev));
   HIPCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
   launch_cast_features(dtype == PREGO_F16, src, dst, n, n_cu, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+// ================================================================================================
+// the training set in device memory: one batch of windows per launch (train_cache.hip)
+// ================================================================================================
+extern "C" int prego_gather_windows(const float* rgb_rows, const float* flow_rows, int64_t n_rows, int d_rgb, int d_flow, const int32_t* labels,
+                                    const float* dense_targets, const int64_t* vid_row0, const int32_t* vid_len, int n_videos,
+                                    const int32_t* table, int n_windows, const int32_t* order, int64_t n_order, int64_t first, int n,
+                                    int window_size, int n_classes, int ant_len, float* rgb_out, float* flow_out, float* target_out,
+                                    float* ant_target_out, prego_stream_t stream) {
+  if (n < 1) return prego_fail_(PREGO_EINVAL, "gather_windows: n %d (>= 1)", n);
+  if (window_size < 1) return prego_fail_(PREGO_EINVAL, "gather_windows: window_size %d (>= 1)", window_size);
+  if (ant_len < 0) return prego_fail_(PREGO_EINVAL, "gather_windows: ant_len %d (>= 0)", ant_len);
+  if (ant_target_out && ant_len == 0) return prego_fail_(PREGO_EINVAL, "gather_windows: ant_target_out with ant_len 0");
+  if ((labels != nullptr) == (dense_targets != nullptr))
+    return prego_fail_(PREGO_EINVAL, "gather_windows: exactly one of labels and dense_targets");
+  if (d_rgb < 0 || d_rgb % 4 || d_flow < 0 || d_flow % 4)
+    return prego_fail_(PREGO_EINVAL, "gather_windows: d_rgb %d, d_flow %d (multiples of 4)", d_rgb, d_flow);
+  if ((rgb_out && (!rgb_rows || d_rgb == 0)) || (flow_out && (!flow_rows || d_flow == 0)))
+    return prego_fail_(PREGO_EINVAL, "gather_windows: an output without its resident rows");
+  if (!vid_row0 || !vid_len || !table || !order || n_videos < 0 || n_windows < 0 || n_rows < 0)
+    return prego_fail_(PREGO_EINVAL, "gather_windows: NULL table, or a negative count");
+  if (n_classes < 1) return prego_fail_(PREGO_EINVAL, "gather_windows: n_classes %d (>= 1)", n_classes);
+  if (first < 0 || n_order < 0 || first > n_order - n)
+    return prego_fail_(PREGO_EINVAL, "gather_windows: entries [%lld, %lld + %d) of an order of %lld", (long long)first, (long long)first, n,
+                       (long long)n_order);
+  const int64_t lim = (int64_t)1 << 31, rows = (int64_t)n * window_size;
+  if (rows >= lim || rows * n_classes >= lim || (int64_t)n * ant_len * n_classes >= lim)
+    return prego_fail_(PREGO_EINVAL, "gather_windows: a batch of %d windows of %d rows, %d classes, ant_len %d has 2^31 elements or more", n,
+                       window_size, n_classes, ant_len);
+  if (((uintptr_t)rgb_rows | (uintptr_t)flow_rows | (uintptr_t)rgb_out | (uintptr_t)flow_out | (uintptr_t)target_out |
+       (uintptr_t)ant_target_out) % 16)
+    return prego_fail_(PREGO_EINVAL, "gather_windows: feature rows and outputs must be 16-byte aligned");
+  if (((uintptr_t)labels | (uintptr_t)dense_targets | (uintptr_t)vid_len | (uintptr_t)table | (uintptr_t)order) % 4 || (uintptr_t)vid_row0 % 8)
+    return prego_fail_(PREGO_EINVAL, "gather_windows: a table is not aligned to its element");
+  if (!rgb_out && !flow_out && !target_out && !ant_target_out) return PREGO_OK;
+  int dev = 0, n_cu = 0;
+  HIPCHK(hipGetDevice(&dev));
+  HIPCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+  GatherWindows a;
+  a.rgb_rows = rgb_rows; a.flow_rows = flow_rows; a.labels = (const int*)labels; a.dense_targets = dense_targets;
+  a.vid_row0 = (const long long*)vid_row0; a.vid_len = (const int*)vid_len; a.table = (const int*)table; a.order = (const int*)order;
+  a.n_rows = n_rows; a.first = first; a.n_videos = n_videos; a.n_windows = n_windows; a.n = n; a.window = window_size;
+  a.n_classes = n_classes; a.ant_len = ant_len; a.d_rgb = d_rgb; a.d_flow = d_flow;
+  a.rgb_out = rgb_out; a.flow_out = flow_out; a.target_out = target_out; a.ant_out = ant_target_out;
+  launch_gather_windows(a, n_cu, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return PREGO_OK;
 }

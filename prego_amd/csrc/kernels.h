@@ -308,6 +308,21 @@ int launch_thumos_postprocess(const float* scores, long long ld_scores, const fl
 // Evaluate's feature cache (feature_cache.hip): n fp32 values -> bf16 / fp16 (f16) with the pack kernels' conversion; n % 8 == 0, n > 0
 void launch_cast_features(bool f16, const float* src, void* dst, long long n, int n_cu, hipStream_t s);
 
+// training windows cut from the resident training set (train_cache.hip); the fields are prego_gather_windows' arguments (prego_amd.h)
+struct GatherWindows {
+  const float *rgb_rows, *flow_rows;       // [n_rows][d_rgb], [n_rows][d_flow]; NULL with a NULL output
+  const int* labels;                       // [n_rows] class id, -1 for an all-zero row - or
+  const float* dense_targets;              // [n_rows][n_classes]
+  const long long* vid_row0;               // [n_videos]
+  const int *vid_len, *table, *order;      // [n_videos], [n_windows][2], [>= first + n]
+  long long n_rows, first;
+  int n_videos, n_windows, n, window, n_classes, ant_len, d_rgb, d_flow;
+  float *rgb_out, *flow_out, *target_out, *ant_out;      // nullable
+};
+// the caller has checked: n >= 1, window >= 1, n * window, n * window * n_classes and n * ant_len * n_classes below 2^31, d % 4 == 0,
+// 16-byte aligned feature and output pointers, first + n within order
+void launch_gather_windows(const GatherWindows& a, int n_cu, hipStream_t s);
+
 // stream pool (stream_pool.hip): slot-addressed GRU state rows and per-slot vote records in the caller's device block
 constexpr int kPoolMaxActive = 256;      // slots one call may name
 constexpr int kPoolRecHeader = 4;        // record words in front of the counts: frames, last vote + 1, n_events, overflow

@@ -87,6 +87,9 @@ def main(argv=None):
         logger.info(f'{cfg["task"]} result: {mAP * 100:.2f} m{cfg["metric"]}')
         return mAP
     trainloader = build_data_loader(cfg, mode="train")
+    if cfg.get("train_cache_device", False):   # not a reference key: the training set stays in device memory, batches are cut there (train_cache.py)
+        from .train_cache import device_loader
+        trainloader = device_loader(trainloader, device, cfg, logger)
     criterion = build_criterion(cfg, device)
     train_one_epoch = build_trainer(cfg)
     if cfg["optimizer"] == "AdamW":          # main.py:62-67, arithmetic on the HIP path (one fused launch, csrc/optim.hip)
