@@ -79,7 +79,7 @@ class OnlineRecord:
             self._close_window(self.frames - self.window)
 
     def push_frames(self, ids):
-        """a burst: the host model of the pool's K-frame commit (csrc/stream_pool.hip: pool_commit_frames) - the slot's lane takes the
+        """a burst: the host model of the pool's K-frame commit (csrc/stream_pool.hip: pool_commit) - the slot's lane takes the
         ids in frame order, so a window may end inside the burst any number of times"""
         for i in ids:
             self.push(i)

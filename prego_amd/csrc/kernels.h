@@ -335,9 +335,9 @@ struct PoolGeom {
 struct PoolSlots { int s[kPoolMaxActive]; };      // the slot list of one call, by value in the kernel arguments
 // slots: HOST, n in 1..256, every slot in [0, capacity) and named once (the caller checks duplicates); -1 = refused, nothing launched
 int launch_pool_gather(const PoolGeom& g, const int* slots, int n, float* h_ws, hipStream_t s);
-int launch_pool_commit(const PoolGeom& g, const int* slots, int n, const float* h_ws, const int* argmax, hipStream_t s);
-// the commit of a burst: the state row once, then argmax[i K + t], t = 0 .. K - 1, voted in frame order by the slot's lane
-int launch_pool_commit_frames(const PoolGeom& g, const int* slots, int n, int K, const float* h_ws, const int* argmax, hipStream_t s);
+// the commit of K frames per slot (1..32, n K <= 256; K = 1: the one-frame call): the state row once, then argmax[i K + t], t = 0 .. K - 1,
+// voted in frame order by the slot's lane
+int launch_pool_commit(const PoolGeom& g, const int* slots, int n, int K, const float* h_ws, const int* argmax, hipStream_t s);
 int launch_pool_vote(const PoolGeom& g, const int* slots, int n, const int* ids, hipStream_t s);
 int launch_pool_flush(const PoolGeom& g, const int* slots, int n, hipStream_t s);
 int launch_pool_reset(const PoolGeom& g, const int* slots, int n, hipStream_t s);
@@ -495,12 +495,11 @@ __host__ __device__ inline unsigned ragged_count(unsigned e) { return e >> 24; }
 int launch_frames_recur_ragged(const void* whh, const float* gi, const float* b_hn, const float* h0, float* hist, void* hr, float* h_state,
                                const RaggedMap& walk, int n, int rows, int n_t, int t, bool single_frame, int H, hipStream_t s,
                                bool f16 = false);
-// stream_pool.hip, the commit of a ragged burst: the state row once, then the ids argmax[off .. off + count) of rows.e[i] (the caller's order: entry i =
-// slots[i]) voted in frame order by the slot's lane; off + count <= n_rows <= 256 for every entry, or nothing is launched
+// stream_pool.hip, a ragged burst: entry i of `rows` (the caller's order: slots[i]) gives the slot's ids, [off, off + count) of the packed
+// rows, voted in frame order by the slot's lane - after the state row (commit) or alone (vote); off + count <= n_rows <= 256 for every
+// entry, or nothing is launched
 int launch_pool_commit_ragged(const PoolGeom& g, const int* slots, int n, const RaggedMap& rows, int n_rows, const float* h_ws,
                               const int* argmax, hipStream_t s);
-// stream_pool.hip, the vote alone for packed ids: slot slots[i]'s lane votes ids[off .. off + count) of rows.e[i] in frame order; the same
-// bounds on the entries as launch_pool_commit_ragged, or nothing is launched
 int launch_pool_vote_ragged(const PoolGeom& g, const int* slots, int n, const RaggedMap& rows, int n_rows, const int* ids, hipStream_t s);
 
 // Transformer stream pool, bursts (vit_stream.hip): slot slots[i] takes count[i] frames (1..min(32, T)), its encoded rows enc[off[i] ..

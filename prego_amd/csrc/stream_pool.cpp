@@ -37,58 +37,58 @@ int check_slots(prego_stream_pool* p, const char* who, int n, const int32_t* slo
   return check_slot_list(p->stamps, p->g.capacity, who, n, slots);
 }
 
-// the step calls' workspace: dense state [n][hid] fp32 | argmax [n] (the burst call: [n K]) int32 | the dense call's own workspace.
-// burst = false (K = 1): the one-frame call through step_wide (its workspace is 0 bytes up to 16 streams: step's launches on the
-// handle's scratch); burst = true: K frames through step_frames
+// what the three step entries differ in: the dense call behind them and, with it, the ids slot i votes.  kOne: one frame through
+// step_wide (its workspace is 0 bytes up to 16 streams: step's launches on the handle's scratch), ids [i]; kFrames: K frames per slot
+// through step_frames, ids [i K, i K + K); kRagged: a count per slot through step_ragged, ids in packed rows (RaggedPlan)
+enum class Burst { kOne, kFrames, kRagged };
+
+// the step calls' workspace: dense state [n][hid] fp32 | argmax [rows] int32 | the dense call's own workspace.  per: kFrames: K (rows =
+// n K), kRagged: the rows, kOne: unused (rows = n)
 struct StepPoolLayout { size_t am, wide, wide_bytes, total; };
-StepPoolLayout step_pool_layout(const prego_miniroad* h, int n, bool burst, int K) {
+StepPoolLayout step_pool_layout(const prego_miniroad* h, Burst kind, int n, int per) {
   StepPoolLayout l{};
   WsCarver c;
   c.take((size_t)n * h->hid * 4);
-  l.am = c.take((size_t)n * K * 4);
+  l.am = c.take((size_t)(kind == Burst::kOne ? n : kind == Burst::kFrames ? n * per : per) * 4);
   l.wide = c.o;
-  l.wide_bytes = burst ? prego_miniroad_step_frames_workspace_bytes(h, n, K) : prego_miniroad_step_wide_workspace_bytes(h, n);
-  l.total = l.wide + l.wide_bytes;
-  return l;
-}
-// the ragged burst: argmax [rows], the dense call is prego_miniroad_step_ragged
-StepPoolLayout step_pool_ragged_layout(const prego_miniroad* h, int n, int rows) {
-  StepPoolLayout l{};
-  WsCarver c;
-  c.take((size_t)n * h->hid * 4);
-  l.am = c.take((size_t)rows * 4);
-  l.wide = c.o;
-  l.wide_bytes = prego_miniroad_step_ragged_workspace_bytes(h, n, rows);
+  l.wide_bytes = kind == Burst::kOne      ? prego_miniroad_step_wide_workspace_bytes(h, n)
+                 : kind == Burst::kFrames ? prego_miniroad_step_frames_workspace_bytes(h, n, per)
+                                          : prego_miniroad_step_ragged_workspace_bytes(h, n, per);
   l.total = l.wide + l.wide_bytes;
   return l;
 }
 
-// prego_miniroad_step_pool (burst = false, K = 1) and prego_miniroad_step_pool_frames (burst = true, K = n_frames): gather the slots'
+// prego_miniroad_step_pool (kOne, K = 1), _frames (kFrames, K = n_frames) and _ragged (kRagged, n_frames[i] per slot): gather the slots'
 // states into the workspace, make the dense call a caller without a pool would make, through the same entry point (the pool adds no
-// arithmetic), commit
-int step_pool_impl(const char* who, prego_miniroad* h, prego_stream_pool* p, int n_active, bool burst, int K, const int32_t* slots,
-                   const float* rgb, const float* flow, float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax, int flags, void* workspace,
-                   size_t workspace_bytes, prego_stream_t stream) {
+// arithmetic), commit.  The refusals of all three are decided before the gather
+int step_pool_impl(const char* who, Burst kind, prego_miniroad* h, prego_stream_pool* p, int n_active, int K, const int32_t* n_frames,
+                   const int32_t* slots, const float* rgb, const float* flow, float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax,
+                   int flags, void* workspace, size_t workspace_bytes, prego_stream_t stream) {
   const bool ant = ant_out != nullptr || ant_argmax != nullptr;
   StepPoolLayout l{};
+  RaggedPlan plan;                                            // kRagged only
   {
     HandleScope scope_(h);
     if (!p) return prego_fail_(PREGO_EINVAL, "%s: pool is NULL", who);
-    if (burst && (K < 1 || K > 32)) return prego_fail_(PREGO_EINVAL, "%s: %d frames per stream (1..32 per call)", who, K);
-    if (burst && n_active >= 1 && (long long)n_active * K > kPoolMaxActive)
+    if (kind == Burst::kFrames && (K < 1 || K > 32)) return prego_fail_(PREGO_EINVAL, "%s: %d frames per stream (1..32 per call)", who, K);
+    if (kind == Burst::kFrames && n_active >= 1 && (long long)n_active * K > kPoolMaxActive)
       return prego_fail_(PREGO_EINVAL, "%s: %d streams x %d frames = %lld rows (at most %d per call: use forward() with h0 / h_last)", who,
                          n_active, K, (long long)n_active * K, kPoolMaxActive);
+    if (kind == Burst::kRagged)
+      if (int rc = ragged_plan(who, n_active, n_frames, &plan)) return rc;
     // everything the dense call would refuse, before the gather is launched (the state it will be handed is the workspace's dense copy)
     if (int rc = step_refusals(h, n_active, kPoolMaxActive, rgb, flow, p->g.h, ant)) return rc;
     if (p->g.hid != h->hid || p->g.ncls != h->ncls)
       return prego_fail_(PREGO_EINVAL, "%s: the pool was created for hidden_dim %d / %d classes, the handle has %d / %d", who, p->g.hid,
                          p->g.ncls, h->hid, h->ncls);
     if (int rc = check_slots(p, who, n_active, slots)) return rc;
-    l = step_pool_layout(h, n_active, burst, K);
-    if (int rc = burst ? workspace_refusal(who, "prego_miniroad_step_pool_frames_workspace_bytes", workspace, workspace_bytes, l.total,
-                                           "%d active streams x %d frames", n_active, K)
-                       : workspace_refusal(who, "prego_miniroad_step_pool_workspace_bytes", workspace, workspace_bytes, l.total,
-                                           "%d active streams", n_active)) return rc;
+    l = step_pool_layout(h, kind, n_active, kind == Burst::kRagged ? plan.rows : K);
+    if (int rc = kind == Burst::kOne      ? workspace_refusal(who, "prego_miniroad_step_pool_workspace_bytes", workspace, workspace_bytes, l.total,
+                                                              "%d active streams", n_active)
+                 : kind == Burst::kFrames ? workspace_refusal(who, "prego_miniroad_step_pool_frames_workspace_bytes", workspace, workspace_bytes,
+                                                              l.total, "%d active streams x %d frames", n_active, K)
+                                          : workspace_refusal(who, "prego_miniroad_step_pool_ragged_workspace_bytes", workspace, workspace_bytes,
+                                                              l.total, "%d active streams with %d frames in all", n_active, plan.rows)) return rc;
   }
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
@@ -96,14 +96,20 @@ int step_pool_impl(const char* who, prego_miniroad* h, prego_stream_pool* p, int
   int32_t* am = argmax ? argmax : (int32_t*)(ws + l.am);      // the vote always has its ids
   if (launch_pool_gather(p->g, slots, n_active, h_ws, s)) return prego_fail_(PREGO_EINVAL, "%s: gather refused its arguments", who);
   void* dws = ws + l.wide;
-  const int rc = burst ? (ant ? prego_miniroad_step_frames_anticipation(h, n_active, K, rgb, flow, h_ws, out, am, ant_out, ant_argmax, flags, dws,
-                                                                        l.wide_bytes, stream)
-                              : prego_miniroad_step_frames(h, n_active, K, rgb, flow, h_ws, out, am, flags, dws, l.wide_bytes, stream))
-                       : (ant ? prego_miniroad_step_wide_anticipation(h, n_active, rgb, flow, h_ws, out, am, ant_out, ant_argmax, flags, dws,
-                                                                      l.wide_bytes, stream)
-                              : prego_miniroad_step_wide(h, n_active, rgb, flow, h_ws, out, am, flags, dws, l.wide_bytes, stream));
+  const size_t db = l.wide_bytes;
+  int rc;
+  if (kind == Burst::kOne)
+    rc = ant ? prego_miniroad_step_wide_anticipation(h, n_active, rgb, flow, h_ws, out, am, ant_out, ant_argmax, flags, dws, db, stream)
+             : prego_miniroad_step_wide(h, n_active, rgb, flow, h_ws, out, am, flags, dws, db, stream);
+  else if (kind == Burst::kFrames)
+    rc = ant ? prego_miniroad_step_frames_anticipation(h, n_active, K, rgb, flow, h_ws, out, am, ant_out, ant_argmax, flags, dws, db, stream)
+             : prego_miniroad_step_frames(h, n_active, K, rgb, flow, h_ws, out, am, flags, dws, db, stream);
+  else
+    rc = ant ? prego_miniroad_step_ragged_anticipation(h, n_active, n_frames, rgb, flow, h_ws, out, am, ant_out, ant_argmax, flags, dws, db, stream)
+             : prego_miniroad_step_ragged(h, n_active, n_frames, rgb, flow, h_ws, out, am, flags, dws, db, stream);
   if (rc) return rc;                                          // the pool itself is untouched: only the commit writes it
-  if (burst ? launch_pool_commit_frames(p->g, slots, n_active, K, h_ws, am, s) : launch_pool_commit(p->g, slots, n_active, h_ws, am, s))
+  if (kind == Burst::kRagged ? launch_pool_commit_ragged(p->g, slots, n_active, plan.by_stream, plan.rows, h_ws, am, s)
+                             : launch_pool_commit(p->g, slots, n_active, K, h_ws, am, s))
     return prego_fail_(PREGO_EINVAL, "%s: commit refused its arguments", who);
   HIPCHK(hipGetLastError());
   return PREGO_OK;
@@ -146,71 +152,40 @@ extern "C" void prego_stream_pool_destroy(prego_stream_pool* p) { delete p; }
 
 extern "C" size_t prego_miniroad_step_pool_workspace_bytes(const prego_miniroad* h, int n_active) {
   if (!h || n_active < 1 || n_active > kPoolMaxActive) return 0;
-  return step_pool_layout(h, n_active, false, 1).total;
+  return step_pool_layout(h, Burst::kOne, n_active, 1).total;
 }
 
 extern "C" int prego_miniroad_step_pool(prego_miniroad* h, prego_stream_pool* p, int n_active, const int32_t* slots, const float* rgb,
                                         const float* flow, float* out, int32_t* argmax, float* ant_out, int32_t* ant_argmax, int flags,
                                         void* workspace, size_t workspace_bytes, prego_stream_t stream) {
-  return step_pool_impl("step_pool", h, p, n_active, false, 1, slots, rgb, flow, out, argmax, ant_out, ant_argmax, flags, workspace, workspace_bytes,
-                        stream);
+  return step_pool_impl("step_pool", Burst::kOne, h, p, n_active, 1, nullptr, slots, rgb, flow, out, argmax, ant_out, ant_argmax, flags, workspace,
+                        workspace_bytes, stream);
 }
 
 extern "C" size_t prego_miniroad_step_pool_frames_workspace_bytes(const prego_miniroad* h, int n_active, int n_frames) {
   if (!h || prego_miniroad_step_frames_workspace_bytes(h, n_active, n_frames) == 0) return 0;
-  return step_pool_layout(h, n_active, true, n_frames).total;
+  return step_pool_layout(h, Burst::kFrames, n_active, n_frames).total;
 }
 
 extern "C" int prego_miniroad_step_pool_frames(prego_miniroad* h, prego_stream_pool* p, int n_active, int n_frames, const int32_t* slots,
                                                const float* rgb, const float* flow, float* out, int32_t* argmax, float* ant_out,
                                                int32_t* ant_argmax, int flags, void* workspace, size_t workspace_bytes,
                                                prego_stream_t stream) {
-  return step_pool_impl("step_pool_frames", h, p, n_active, true, n_frames, slots, rgb, flow, out, argmax, ant_out, ant_argmax, flags,
-                        workspace, workspace_bytes, stream);
+  return step_pool_impl("step_pool_frames", Burst::kFrames, h, p, n_active, n_frames, nullptr, slots, rgb, flow, out, argmax, ant_out, ant_argmax,
+                        flags, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t prego_miniroad_step_pool_ragged_workspace_bytes(const prego_miniroad* h, int n_active, int n_rows) {
   if (!h || prego_miniroad_step_ragged_workspace_bytes(h, n_active, n_rows) == 0) return 0;
-  return step_pool_ragged_layout(h, n_active, n_rows).total;
+  return step_pool_layout(h, Burst::kRagged, n_active, n_rows).total;
 }
 
-// prego_miniroad_step_pool_frames with a frame count per slot: gather, prego_miniroad_step_ragged (_anticipation) through its own entry
-// point, pool_commit_ragged.  The refusals of all three are decided before the gather
 extern "C" int prego_miniroad_step_pool_ragged(prego_miniroad* h, prego_stream_pool* p, int n_active, const int32_t* n_frames,
                                                const int32_t* slots, const float* rgb, const float* flow, float* out, int32_t* argmax,
                                                float* ant_out, int32_t* ant_argmax, int flags, void* workspace, size_t workspace_bytes,
                                                prego_stream_t stream) {
-  const char* who = "step_pool_ragged";
-  const bool ant = ant_out != nullptr || ant_argmax != nullptr;
-  StepPoolLayout l{};
-  RaggedPlan plan;
-  {
-    HandleScope scope_(h);
-    if (!p) return prego_fail_(PREGO_EINVAL, "%s: pool is NULL", who);
-    if (int rc = ragged_plan(who, n_active, n_frames, &plan)) return rc;
-    if (int rc = step_refusals(h, n_active, kPoolMaxActive, rgb, flow, p->g.h, ant)) return rc;
-    if (p->g.hid != h->hid || p->g.ncls != h->ncls)
-      return prego_fail_(PREGO_EINVAL, "%s: the pool was created for hidden_dim %d / %d classes, the handle has %d / %d", who, p->g.hid,
-                         p->g.ncls, h->hid, h->ncls);
-    if (int rc = check_slots(p, who, n_active, slots)) return rc;
-    l = step_pool_ragged_layout(h, n_active, plan.rows);
-    if (int rc = workspace_refusal(who, "prego_miniroad_step_pool_ragged_workspace_bytes", workspace, workspace_bytes, l.total,
-                                   "%d active streams with %d frames in all", n_active, plan.rows)) return rc;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  float* h_ws = (float*)ws;
-  int32_t* am = argmax ? argmax : (int32_t*)(ws + l.am);      // the vote always has its ids
-  if (launch_pool_gather(p->g, slots, n_active, h_ws, s)) return prego_fail_(PREGO_EINVAL, "%s: gather refused its arguments", who);
-  void* dws = ws + l.wide;
-  const int rc = ant ? prego_miniroad_step_ragged_anticipation(h, n_active, n_frames, rgb, flow, h_ws, out, am, ant_out, ant_argmax, flags, dws,
-                                                               l.wide_bytes, stream)
-                     : prego_miniroad_step_ragged(h, n_active, n_frames, rgb, flow, h_ws, out, am, flags, dws, l.wide_bytes, stream);
-  if (rc) return rc;                                          // the pool itself is untouched: only the commit writes it
-  if (launch_pool_commit_ragged(p->g, slots, n_active, plan.by_stream, plan.rows, h_ws, am, s))
-    return prego_fail_(PREGO_EINVAL, "%s: commit refused its arguments", who);
-  HIPCHK(hipGetLastError());
-  return PREGO_OK;
+  return step_pool_impl("step_pool_ragged", Burst::kRagged, h, p, n_active, 0, n_frames, slots, rgb, flow, out, argmax, ant_out, ant_argmax, flags,
+                        workspace, workspace_bytes, stream);
 }
 
 extern "C" int prego_stream_pool_vote(prego_stream_pool* p, int n, const int32_t* slots, const int32_t* ids, prego_stream_t stream) {

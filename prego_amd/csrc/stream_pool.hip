@@ -3,11 +3,10 @@
 // any subset of the slots by one frame.  The kernels here only move state rows and count votes; the frame itself is the unchanged wide
 // step on a dense copy of the active rows (stream_wide.hip), so the pool adds no arithmetic.
 //   pool_gather   h_ws[i] <- pool.h[slots[i]]                       one workgroup per active stream, 16-byte accesses
-//   pool_commit   pool.h[slots[i]] <- h_ws[i], then lane 0 of workgroup i votes argmax[i] into the slot's record
-//   pool_commit_frames  pool_commit after a burst of K frames per slot: the state once, K votes in frame order by the slot's lane
-//   pool_commit_ragged  pool_commit after a ragged burst: a frame count per slot, the ids in packed rows (RaggedMap, by value as the slots)
-//   pool_vote     the vote alone, ids from the caller's device vector  (one lane per stream)
-//   pool_vote_ragged  the vote alone for a ragged burst: a frame count per slot, the ids in packed rows (the Transformer pool's bursts)
+//   pool_commit<Span>  pool.h[slots[i]] <- h_ws[i], then lane 0 of workgroup i votes the ids of slot i in frame order into its record
+//   pool_vote<Span>    the vote alone, ids from the caller's device vector  (one lane per stream)
+//     Span says which ids belong to active stream i: UniformSpan [i K, i K + K) - K by value, K = 1 the one-frame call, no table in the
+//     kernel arguments - or RaggedSpan [off, off + count) of a RaggedMap entry (packed rows, by value as the slots)
 //   pool_flush    votes a slot's unfinished window (the reference's shorter last window, aggregate.py:57-58)
 //   pool_reset    zeroes a slot's state row and record
 // The slot list travels by value in the kernel arguments (PoolSlots, 1 KB): no staging buffer, no H2D copy, nothing for the caller to
@@ -64,57 +63,39 @@ __global__ __launch_bounds__(256) void pool_gather_kernel(PoolGeom g, PoolSlots 
   for (int k = threadIdx.x; k < (g.hid >> 2); k += 256) dst[k] = src[k];
 }
 
-__global__ __launch_bounds__(256) void pool_commit_kernel(PoolGeom g, PoolSlots sl, const float* __restrict__ h_ws,
+// which ids of a call belong to active stream i, the policy of pool_commit and pool_vote (as UniformRows / RaggedRows of stream_frames.hip)
+struct UniformSpan {                     // K ids per stream, stream-major; a window boundary may fall inside a burst any number of times
+  int K;
+  __device__ __forceinline__ int off(int i) const { return i * K; }
+  __device__ __forceinline__ int count(int) const { return K; }
+};
+struct RaggedSpan {                      // entry i of the table: packed rows in the caller's order
+  RaggedMap rows;
+  __device__ __forceinline__ int off(int i) const { return (int)ragged_off(rows.e[i]); }
+  __device__ __forceinline__ int count(int i) const { return (int)ragged_count(rows.e[i]); }
+};
+
+template <class Span>
+__device__ __forceinline__ void pool_vote_span(const PoolGeom& g, int slot, const Span& span, int i, const int* __restrict__ ids) {
+  int* rec = pool_record(g, slot);
+  const int off = span.off(i), K = span.count(i);
+  for (int t = 0; t < K; ++t) pool_vote_update(rec, g, ids[off + t]);
+}
+
+template <class Span>
+__global__ __launch_bounds__(256) void pool_commit_kernel(PoolGeom g, PoolSlots sl, Span span, const float* __restrict__ h_ws,
                                                           const int* __restrict__ argmax) {
   const int i = blockIdx.x, slot = sl.s[i];
   const f32x4* src = (const f32x4*)(h_ws + (size_t)i * g.hid);
   f32x4* dst = (f32x4*)(g.h + (size_t)slot * g.hid);
   for (int k = threadIdx.x; k < (g.hid >> 2); k += 256) dst[k] = src[k];
-  if (threadIdx.x == 0) pool_vote_update(pool_record(g, slot), g, argmax[i]);
+  if (threadIdx.x == 0) pool_vote_span(g, slot, span, i, argmax);
 }
 
-// pool_commit for a burst of K frames per slot: the ids of slot i are argmax[i K .. i K + K), voted in frame order by one lane, so a window
-// boundary may fall inside the burst any number of times
-__global__ __launch_bounds__(256) void pool_commit_frames_kernel(PoolGeom g, PoolSlots sl, int K, const float* __restrict__ h_ws,
-                                                                 const int* __restrict__ argmax) {
-  const int i = blockIdx.x, slot = sl.s[i];
-  const f32x4* src = (const f32x4*)(h_ws + (size_t)i * g.hid);
-  f32x4* dst = (f32x4*)(g.h + (size_t)slot * g.hid);
-  for (int k = threadIdx.x; k < (g.hid >> 2); k += 256) dst[k] = src[k];
-  if (threadIdx.x == 0) {
-    int* rec = pool_record(g, slot);
-    for (int t = 0; t < K; ++t) pool_vote_update(rec, g, argmax[(size_t)i * K + t]);
-  }
-}
-
-// pool_commit for a ragged burst: the ids of slot i are argmax[off .. off + count) of its table entry (packed rows, the caller's order)
-__global__ __launch_bounds__(256) void pool_commit_ragged_kernel(PoolGeom g, PoolSlots sl, RaggedMap rows, const float* __restrict__ h_ws,
-                                                                 const int* __restrict__ argmax) {
-  const int i = blockIdx.x, slot = sl.s[i];
-  const f32x4* src = (const f32x4*)(h_ws + (size_t)i * g.hid);
-  f32x4* dst = (f32x4*)(g.h + (size_t)slot * g.hid);
-  for (int k = threadIdx.x; k < (g.hid >> 2); k += 256) dst[k] = src[k];
-  if (threadIdx.x == 0) {
-    int* rec = pool_record(g, slot);
-    const unsigned e = rows.e[i];
-    const int off = (int)ragged_off(e), K = (int)ragged_count(e);
-    for (int t = 0; t < K; ++t) pool_vote_update(rec, g, argmax[off + t]);
-  }
-}
-
-__global__ __launch_bounds__(64) void pool_vote_kernel(PoolGeom g, PoolSlots sl, int n, const int* __restrict__ ids) {
+template <class Span>
+__global__ __launch_bounds__(64) void pool_vote_kernel(PoolGeom g, PoolSlots sl, Span span, int n, const int* __restrict__ ids) {
   const int i = blockIdx.x * 64 + threadIdx.x;
-  if (i < n) pool_vote_update(pool_record(g, sl.s[i]), g, ids[i]);
-}
-
-// pool_vote for a ragged burst: lane i votes ids[off .. off + count) of its table entry in frame order
-__global__ __launch_bounds__(64) void pool_vote_ragged_kernel(PoolGeom g, PoolSlots sl, RaggedMap rows, int n, const int* __restrict__ ids) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  if (i >= n) return;
-  int* rec = pool_record(g, sl.s[i]);
-  const unsigned e = rows.e[i];
-  const int off = (int)ragged_off(e), K = (int)ragged_count(e);
-  for (int t = 0; t < K; ++t) pool_vote_update(rec, g, ids[off + t]);
+  if (i < n) pool_vote_span(g, sl.s[i], span, i, ids);
 }
 
 __global__ __launch_bounds__(64) void pool_flush_kernel(PoolGeom g, PoolSlots sl, int n) {
@@ -155,44 +136,49 @@ int launch_pool_gather(const PoolGeom& g, const int* slots, int n, float* h_ws, 
   return 0;
 }
 
-int launch_pool_commit(const PoolGeom& g, const int* slots, int n, const float* h_ws, const int* argmax, hipStream_t s) {
+// a ragged call's table: 1..32 ids per entry, every span inside the n_rows <= 256 packed rows
+static bool ragged_span(const RaggedMap& rows, int n, int n_rows, RaggedSpan* span) {
+  if (n_rows < n || n_rows > kPoolMaxActive) return false;
+  for (int i = 0; i < n; ++i)
+    if (ragged_count(rows.e[i]) < 1u || ragged_count(rows.e[i]) > 32u || ragged_off(rows.e[i]) + ragged_count(rows.e[i]) > (unsigned)n_rows) return false;
+  span->rows = rows;
+  return true;
+}
+
+template <class Span>
+static int pool_commit(const PoolGeom& g, const int* slots, int n, const Span& span, const float* h_ws, const int* argmax, hipStream_t s) {
   PoolSlots sl;
   if (!h_ws || !argmax || !pool_slots(g, slots, n, &sl)) return -1;
-  pool_commit_kernel<<<n, 256, 0, s>>>(g, sl, h_ws, argmax);
+  pool_commit_kernel<Span><<<n, 256, 0, s>>>(g, sl, span, h_ws, argmax);
   return 0;
 }
 
-int launch_pool_commit_frames(const PoolGeom& g, const int* slots, int n, int K, const float* h_ws, const int* argmax, hipStream_t s) {
+template <class Span>
+static int pool_vote(const PoolGeom& g, const int* slots, int n, const Span& span, const int* ids, hipStream_t s) {
   PoolSlots sl;
-  if (!h_ws || !argmax || K < 1 || K > 32 || n * K > kPoolMaxActive || !pool_slots(g, slots, n, &sl)) return -1;
-  pool_commit_frames_kernel<<<n, 256, 0, s>>>(g, sl, K, h_ws, argmax);
+  if (!ids || !pool_slots(g, slots, n, &sl)) return -1;
+  pool_vote_kernel<Span><<<(n + 63) / 64, 64, 0, s>>>(g, sl, span, n, ids);
   return 0;
+}
+
+int launch_pool_commit(const PoolGeom& g, const int* slots, int n, int K, const float* h_ws, const int* argmax, hipStream_t s) {
+  if (K < 1 || K > 32 || n < 1 || n > kPoolMaxActive || n * K > kPoolMaxActive) return -1;
+  return pool_commit(g, slots, n, UniformSpan{K}, h_ws, argmax, s);
 }
 
 int launch_pool_commit_ragged(const PoolGeom& g, const int* slots, int n, const RaggedMap& rows, int n_rows, const float* h_ws,
                               const int* argmax, hipStream_t s) {
-  PoolSlots sl;
-  if (!h_ws || !argmax || n_rows < n || n_rows > kPoolMaxActive || !pool_slots(g, slots, n, &sl)) return -1;
-  for (int i = 0; i < n; ++i)
-    if (ragged_count(rows.e[i]) < 1u || ragged_count(rows.e[i]) > 32u || ragged_off(rows.e[i]) + ragged_count(rows.e[i]) > (unsigned)n_rows) return -1;
-  pool_commit_ragged_kernel<<<n, 256, 0, s>>>(g, sl, rows, h_ws, argmax);
-  return 0;
+  RaggedSpan span;
+  return ragged_span(rows, n, n_rows, &span) ? pool_commit(g, slots, n, span, h_ws, argmax, s) : -1;
 }
 
 int launch_pool_vote(const PoolGeom& g, const int* slots, int n, const int* ids, hipStream_t s) {
-  PoolSlots sl;
-  if (!ids || !pool_slots(g, slots, n, &sl)) return -1;
-  pool_vote_kernel<<<(n + 63) / 64, 64, 0, s>>>(g, sl, n, ids);
-  return 0;
+  return pool_vote(g, slots, n, UniformSpan{1}, ids, s);
 }
 
 int launch_pool_vote_ragged(const PoolGeom& g, const int* slots, int n, const RaggedMap& rows, int n_rows, const int* ids, hipStream_t s) {
-  PoolSlots sl;
-  if (!ids || n_rows < n || n_rows > kPoolMaxActive || !pool_slots(g, slots, n, &sl)) return -1;
-  for (int i = 0; i < n; ++i)
-    if (ragged_count(rows.e[i]) < 1u || ragged_count(rows.e[i]) > 32u || ragged_off(rows.e[i]) + ragged_count(rows.e[i]) > (unsigned)n_rows) return -1;
-  pool_vote_ragged_kernel<<<(n + 63) / 64, 64, 0, s>>>(g, sl, rows, n, ids);
-  return 0;
+  RaggedSpan span;
+  return ragged_span(rows, n, n_rows, &span) ? pool_vote(g, slots, n, span, ids, s) : -1;
 }
 
 int launch_pool_flush(const PoolGeom& g, const int* slots, int n, hipStream_t s) {

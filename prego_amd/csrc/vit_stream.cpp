@@ -93,6 +93,37 @@ int burst_plan(const char* who, int window, int n, const int32_t* counts, BurstP
   return 0;
 }
 
+// what both step entries refuse first, in this order: NULL arguments, an fp32-operand handle (that sentence names the symbol, prego_<who>),
+// missing weights, missing input, a pool of another geometry, the slot list
+int vit_step_refusals(const char* who, const prego_vit* h, prego_vit_stream_pool* p, int n_active, const int32_t* slots,
+                      const float* rgb, const float* flow, const float* out_logits) {
+  if (!h || !p || !out_logits) return prego_fail_(PREGO_EINVAL, "%s: NULL argument", who);
+  if (h->f32) return prego_fail_(PREGO_EINVAL, "prego_%s on an fp32-operand handle: the parity mode covers prego_vit_forward", who);
+  if (!h->have_weights) return prego_fail_(PREGO_EINVAL, "%s before set_weights", who);
+  if ((h->d_rgb > 0 && !rgb) || (h->d_rgb == 0 && !flow)) return prego_fail_(PREGO_EINVAL, "%s: missing input", who);
+  if (p->r.T != h->window || p->r.E != h->emb || p->g.ncls != h->ncls)
+    return prego_fail_(PREGO_EINVAL, "%s: the pool was created for window_size %d / embedding_dim %d / %d classes, the handle has %d / %d / %d",
+                       who, p->r.T, p->r.E, p->g.ncls, h->window, h->emb, h->ncls);
+  return check_slot_list(p->stamps, p->r.capacity, who, n_active, slots);
+}
+
+// the caller's workspace, refused when NULL, misaligned or small (rows: the burst entry's, 0 = the one-frame entry: each words its own size
+// refusal), carved as f lays it out: ws = the per-batch arena, as prego_vit_forward's; am = the caller's argmax or the workspace's
+struct VitStepBufs { char *xb, *ws; float* enc; int32_t* am; };
+int vit_step_carve(const char* who, void* workspace, size_t workspace_bytes, const VitStepWs& f, int n_active, int rows, int32_t* argmax,
+                   VitStepBufs* b) {
+  if (!workspace) return prego_fail_(PREGO_EINVAL, "%s: workspace is NULL", who);
+  if ((uintptr_t)workspace & 255) return prego_fail_(PREGO_EINVAL, "%s: the workspace must be 256-byte aligned", who);
+  if (workspace_bytes < f.total)
+    return rows ? prego_fail_(PREGO_EWORKSPACE, "%s: workspace %zu < %zu for %d rows of %d active streams (prego_vit_step_pool_bursts_workspace_bytes)",
+                              who, workspace_bytes, f.total, rows, n_active)
+                : prego_fail_(PREGO_EWORKSPACE, "%s: workspace %zu < %zu for %d active streams (prego_vit_step_pool_workspace_bytes)", who,
+                              workspace_bytes, f.total, n_active);
+  char* base = (char*)workspace;
+  *b = VitStepBufs{base + f.xb, base + f.win, (float*)(base + f.enc), argmax ? argmax : (int32_t*)(base + f.am)};
+  return 0;
+}
+
 int slot_in_pool(const prego_vit_stream_pool* p, const char* who, int slot) {
   if (slot < 0 || slot >= p->r.capacity) return prego_fail_(PREGO_EINVAL, "%s: slot %d is outside the pool (capacity %d)", who, slot, p->r.capacity);
   return 0;
@@ -148,38 +179,25 @@ extern "C" int prego_vit_step_pool(prego_vit* h, prego_vit_stream_pool* p, int n
                                    const float* flow, float* out_logits, int32_t* argmax, int flags, void* workspace, size_t workspace_bytes,
                                    prego_stream_t stream) {
   const char* who = "vit_step_pool";
-  if (!h || !p || !out_logits) return prego_fail_(PREGO_EINVAL, "%s: NULL argument", who);
-  if (h->f32) return prego_fail_(PREGO_EINVAL, "prego_vit_step_pool on an fp32-operand handle: the parity mode covers prego_vit_forward");
-  if (!h->have_weights) return prego_fail_(PREGO_EINVAL, "%s before set_weights", who);
-  if ((h->d_rgb > 0 && !rgb) || (h->d_rgb == 0 && !flow)) return prego_fail_(PREGO_EINVAL, "%s: missing input", who);
-  if (p->r.T != h->window || p->r.E != h->emb || p->g.ncls != h->ncls)
-    return prego_fail_(PREGO_EINVAL, "%s: the pool was created for window_size %d / embedding_dim %d / %d classes, the handle has %d / %d / %d",
-                       who, p->r.T, p->r.E, p->g.ncls, h->window, h->emb, h->ncls);
-  if (int rc = check_slot_list(p->stamps, p->r.capacity, who, n_active, slots)) return rc;
+  if (int rc = vit_step_refusals(who, h, p, n_active, slots, rgb, flow, out_logits)) return rc;
   const VitStepWs f = vit_step_ws(h, n_active);
-  if (!workspace) return prego_fail_(PREGO_EINVAL, "%s: workspace is NULL", who);
-  if ((uintptr_t)workspace & 255) return prego_fail_(PREGO_EINVAL, "%s: the workspace must be 256-byte aligned", who);
-  if (workspace_bytes < f.total)
-    return prego_fail_(PREGO_EWORKSPACE, "%s: workspace %zu < %zu for %d active streams (prego_vit_step_pool_workspace_bytes)", who,
-                       workspace_bytes, f.total, n_active);
+  VitStepBufs b;
+  if (int rc = vit_step_carve(who, workspace, workspace_bytes, f, n_active, 0, argmax, &b)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  char* base = (char*)workspace;
-  char* ws = base + f.win;                      // the per-batch arena, laid out as prego_vit_forward's
+  char* ws = b.ws;
   const VitWs& w = f.w;
   const int n = n_active, E = h->emb, din = h->d_rgb + h->d_flow;
   const int causal = (flags & 1) ? 1 : 0;
-  float* enc = (float*)(base + f.enc);
-  int32_t* am = argmax ? argmax : (int32_t*)(base + f.am);      // the vote always has its ids
-  launch_cat_convert(rgb, flow, n, h->d_rgb, h->d_flow, base + f.xb, s, h->f16);
-  launch_gemm_bf16_nt(base + f.xb, din, h->enc_w, din, h->enc_b, enc, E, n, E, din, s, h->f16);       // ViT.py:124, once per frame
-  if (launch_vit_ring_commit(p->r, slots, n, enc, s)) return prego_fail_(PREGO_EINVAL, "%s: ring commit refused its arguments", who);
+  launch_cat_convert(rgb, flow, n, h->d_rgb, h->d_flow, b.xb, s, h->f16);
+  launch_gemm_bf16_nt(b.xb, din, h->enc_w, din, h->enc_b, b.enc, E, n, E, din, s, h->f16);       // ViT.py:124, once per frame
+  if (launch_vit_ring_commit(p->r, slots, n, b.enc, s)) return prego_fail_(PREGO_EINVAL, "%s: ring commit refused its arguments", who);
   const bool fused = h->layers == 1;            // one layer: the token kernel writes LayerNorm1(x) and x0; x is never materialised
   const VitLayer& l0 = h->L[0];
   if (launch_vit_ring_tokens(p->r, slots, n, h->enc_b, h->cls, h->pe, fused ? nullptr : (float*)(ws + w.x), l0.ln1_w, l0.ln1_b,
                              fused ? ws + w.xn : nullptr, fused ? (float*)(ws + w.x0) : nullptr, s, h->f16))
     return prego_fail_(PREGO_EINVAL, "%s: ring tokens refused its arguments", who);
-  if (int rc = blocks_and_head(h, who, ws, w, n, causal, fused, out_logits, am, s)) return rc;
-  if (launch_pool_vote(p->g, slots, n, (const int*)am, s)) return prego_fail_(PREGO_EINVAL, "%s: vote refused its arguments", who);
+  if (int rc = blocks_and_head(h, who, ws, w, n, causal, fused, out_logits, b.am, s)) return rc;
+  if (launch_pool_vote(p->g, slots, n, (const int*)b.am, s)) return prego_fail_(PREGO_EINVAL, "%s: vote refused its arguments", who);
   HIPCHK(hipGetLastError());
   return PREGO_OK;
 }
@@ -197,41 +215,28 @@ extern "C" int prego_vit_step_pool_bursts(prego_vit* h, prego_vit_stream_pool* p
                                           const float* rgb, const float* flow, float* out_logits, int32_t* argmax, int flags, void* workspace,
                                           size_t workspace_bytes, prego_stream_t stream) {
   const char* who = "vit_step_pool_bursts";
-  if (!h || !p || !out_logits) return prego_fail_(PREGO_EINVAL, "%s: NULL argument", who);
-  if (h->f32) return prego_fail_(PREGO_EINVAL, "prego_vit_step_pool_bursts on an fp32-operand handle: the parity mode covers prego_vit_forward");
-  if (!h->have_weights) return prego_fail_(PREGO_EINVAL, "%s before set_weights", who);
-  if ((h->d_rgb > 0 && !rgb) || (h->d_rgb == 0 && !flow)) return prego_fail_(PREGO_EINVAL, "%s: missing input", who);
-  if (p->r.T != h->window || p->r.E != h->emb || p->g.ncls != h->ncls)
-    return prego_fail_(PREGO_EINVAL, "%s: the pool was created for window_size %d / embedding_dim %d / %d classes, the handle has %d / %d / %d",
-                       who, p->r.T, p->r.E, p->g.ncls, h->window, h->emb, h->ncls);
-  if (int rc = check_slot_list(p->stamps, p->r.capacity, who, n_active, slots)) return rc;
+  if (int rc = vit_step_refusals(who, h, p, n_active, slots, rgb, flow, out_logits)) return rc;      // the slot list before the counts
   BurstPlan bp;
   if (int rc = burst_plan(who, h->window, n_active, counts, &bp)) return rc;
   const int n = n_active, R = bp.rows, E = h->emb, din = h->d_rgb + h->d_flow;
   const VitStepWs f = vit_step_ws(h, R);
-  if (!workspace) return prego_fail_(PREGO_EINVAL, "%s: workspace is NULL", who);
-  if ((uintptr_t)workspace & 255) return prego_fail_(PREGO_EINVAL, "%s: the workspace must be 256-byte aligned", who);
-  if (workspace_bytes < f.total)
-    return prego_fail_(PREGO_EWORKSPACE, "%s: workspace %zu < %zu for %d rows of %d active streams (prego_vit_step_pool_bursts_workspace_bytes)",
-                       who, workspace_bytes, f.total, R, n);
+  VitStepBufs b;
+  if (int rc = vit_step_carve(who, workspace, workspace_bytes, f, n, R, argmax, &b)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  char* base = (char*)workspace;
-  char* ws = base + f.win;
+  char* ws = b.ws;
   const VitWs& w = f.w;
   const int causal = (flags & 1) ? 1 : 0;
-  float* enc = (float*)(base + f.enc);
-  int32_t* am = argmax ? argmax : (int32_t*)(base + f.am);
-  launch_cat_convert(rgb, flow, R, h->d_rgb, h->d_flow, base + f.xb, s, h->f16);
-  launch_gemm_bf16_nt(base + f.xb, din, h->enc_w, din, h->enc_b, enc, E, R, E, din, s, h->f16);       // ViT.py:124, once per frame
+  launch_cat_convert(rgb, flow, R, h->d_rgb, h->d_flow, b.xb, s, h->f16);
+  launch_gemm_bf16_nt(b.xb, din, h->enc_w, din, h->enc_b, b.enc, E, R, E, din, s, h->f16);       // ViT.py:124, once per frame
   const bool fused = h->layers == 1;
   const VitLayer& l0 = h->L[0];
-  if (launch_vit_burst_tokens(p->r, slots, n, bp.by_slot, bp.by_row, R, enc, h->enc_b, h->cls, h->pe, fused ? nullptr : (float*)(ws + w.x),
+  if (launch_vit_burst_tokens(p->r, slots, n, bp.by_slot, bp.by_row, R, b.enc, h->enc_b, h->cls, h->pe, fused ? nullptr : (float*)(ws + w.x),
                               l0.ln1_w, l0.ln1_b, fused ? ws + w.xn : nullptr, fused ? (float*)(ws + w.x0) : nullptr, s, h->f16))
     return prego_fail_(PREGO_EINVAL, "%s: burst tokens refused its arguments", who);
-  if (launch_vit_ring_commit_burst(p->r, slots, n, bp.by_slot, R, enc, s))
+  if (launch_vit_ring_commit_burst(p->r, slots, n, bp.by_slot, R, b.enc, s))
     return prego_fail_(PREGO_EINVAL, "%s: ring commit refused its arguments", who);
-  if (int rc = blocks_and_head(h, who, ws, w, R, causal, fused, out_logits, am, s)) return rc;
-  if (launch_pool_vote_ragged(p->g, slots, n, bp.by_slot, R, (const int*)am, s))
+  if (int rc = blocks_and_head(h, who, ws, w, R, causal, fused, out_logits, b.am, s)) return rc;
+  if (launch_pool_vote_ragged(p->g, slots, n, bp.by_slot, R, (const int*)b.am, s))
     return prego_fail_(PREGO_EINVAL, "%s: vote refused its arguments", who);
   HIPCHK(hipGetLastError());
   return PREGO_OK;

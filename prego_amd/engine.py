@@ -9,6 +9,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import _lib
+from . import _stream_call as SC
 from ._lib import PregoError, check, ptr_array
 
 _PARAM_ORDER = [
@@ -77,6 +78,7 @@ class MiniRoadEngine:
         self.num_layers = int(num_layers)
         self.max_clips = self.lib.prego_miniroad_max_clips(self.h)
         self._ws: Optional[torch.Tensor] = None
+        self._ws_wide, self._ws_frames = SC.Workspace(), SC.Workspace()      # step_wide's; step_frames' and step_ragged's
         self._res: Optional[torch.Tensor] = None          # whole-call relu(h) buffer (prego_miniroad_set_resident): torch's allocator owns it
         # fp16x2 rows are 34 KB (fp32 intermediates, split operands): 32 768 rows measured best there (262.6 against 269.4 ms per pass
         # at 49 152; scripts/probes/chunk_sweep3.sh); the 16-bit modes are flat between 32 768 and 49 152 (120.2 / 120.4 ms)
@@ -309,6 +311,18 @@ class MiniRoadEngine:
                 flags, C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(_stream_ptr(self.device))))
 
     # -- streaming (online use) ------------------------------------------------
+    # the steps the four entries share are prego_amd/_stream_call.py's; what stands here is each entry's own
+    def _stream_call(self, sym, lead, rgb, flow, h, outs, want_ant, softmax, ws=False):
+        """The C call of a streaming entry: `sym` or, with want_ant, `sym`_anticipation (handle, *lead, rgb, flow, h, *outs, flags[,
+        workspace, bytes], stream).  ws False: `step`, whose symbols take no workspace.  Returns outs, the entry's tuple."""
+        p = SC.ptr
+        ws_args = () if ws is False else (p(ws), ws.numel() if ws is not None else 0)
+        with torch.cuda.device(self.device):
+            check(getattr(self.lib, sym + ("_anticipation" if want_ant else ""))(
+                self.h, *lead, p(rgb if self.dims[0] > 0 else None), p(flow), p(h), *[p(t) for t in outs],
+                _lib.FWD_SOFTMAX if softmax else 0, *ws_args, C.c_void_p(_stream_ptr(self.device))))
+        return outs
+
     def step(self, rgb: Optional[torch.Tensor], flow: Optional[torch.Tensor], h: torch.Tensor, softmax: bool = True,
              out: Optional[torch.Tensor] = None, argmax: Optional[torch.Tensor] = None, want_ant: bool = False,
              ant_out: Optional[torch.Tensor] = None, ant_argmax: Optional[torch.Tensor] = None):
@@ -320,61 +334,25 @@ class MiniRoadEngine:
         want_ant (MiniROADA, after set_anticipation): the anticipation head on the new state as well (prego_miniroad_step_anticipation, two
         more launches; the general forward where the fast path does not apply) - returns (out, argmax, ant_out [n, L, C] probabilities
         or logits as `softmax`, ant_argmax int32 [n, L]); pass `ant_out` / `ant_argmax` to reuse buffers."""
-        if want_ant and not getattr(self, "ant_len", 0):
-            raise PregoError("step(want_ant=True) before set_anticipation")
+        want_ant = SC.resolve_ant("step", bool(want_ant), getattr(self, "ant_len", 0))
         d_rgb, d_flow, emb, hid, ncls = self.dims
-        src = rgb if d_rgb > 0 else flow
-        if src is None:
-            raise PregoError("step: a --no_rgb model needs the flow frame" if d_rgb == 0 else "step: rgb is None")
-        n = src.shape[0]
+        n = SC.frame_source("step", d_rgb, rgb, flow).shape[0]
         general = self.compute_dtype in ("fp32", "fp16x2") or hid != 1024 or self.num_layers != 1     # what the streaming kernels are not built for
-        for t, d in ((rgb if d_rgb > 0 else None, d_rgb), (flow, d_flow)):
-            if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (n, d)):
-                raise PregoError(f"step: expected contiguous fp32 cuda [{n}, {d}], got {tuple(t.shape)} {t.dtype} on {t.device}")
+        # `step` words its shape refusals its own way, and it does not check out / argmax
+        SC.check("step", SC.in_specs((n,), d_rgb, d_flow, rgb, flow), "contiguous fp32 cuda {shape}")
         h_shape = (n, hid) if self.num_layers == 1 else (self.num_layers, n, hid)
-        if not h.is_cuda or h.dtype != torch.float32 or not h.is_contiguous() or tuple(h.shape) != h_shape:
-            raise PregoError(f"step: expected the GRU state as contiguous fp32 cuda {list(h_shape)}, got {tuple(h.shape)} {h.dtype} on {h.device}")
-        if out is None:
-            out = torch.empty((n, ncls), dtype=torch.float32, device=self.device)
-        if argmax is None:
-            argmax = torch.empty((n,), dtype=torch.int32, device=self.device)
-        if want_ant:
-            L = self.ant_len
-            if ant_out is None:
-                ant_out = torch.empty((n, L, ncls), dtype=torch.float32, device=self.device)
-            if ant_argmax is None:
-                ant_argmax = torch.empty((n, L), dtype=torch.int32, device=self.device)
-            for t, shape, dt in ((ant_out, (n, L, ncls), torch.float32), (ant_argmax, (n, L), torch.int32)):
-                if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape:
-                    raise PregoError(f"step: expected a contiguous {dt} cuda {list(shape)} anticipation buffer, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        SC.check("step", [(h, h_shape, SC.F32, None)], "the GRU state as contiguous fp32 cuda {shape}")
+        outs, specs = SC.outputs(self.device, (n,), ncls, self.ant_len if want_ant else 0, out, argmax, ant_out, ant_argmax)
+        SC.check("step", specs[2:], "a contiguous {dt} cuda {shape} anticipation buffer")
         if general:
             rl = [rgb[i:i + 1] for i in range(n)] if d_rgb > 0 else None
             fl = [flow[i:i + 1] for i in range(n)] if flow is not None else None
-            if want_ant:
-                o, a, hl, ao, aa = self.forward_ragged(rl, fl, softmax=softmax, want_out=True, want_argmax=True, h0=h, want_h_last=True,
-                                                       want_ant=True)
-                ant_out.copy_(torch.cat(ao))
-                ant_argmax.copy_(torch.cat(aa))
-            else:
-                o, a, hl = self.forward_ragged(rl, fl, softmax=softmax, want_out=True, want_argmax=True, h0=h, want_h_last=True)
-            h.copy_(hl)
-            out.copy_(torch.cat(o))
-            argmax.copy_(torch.cat(a))
-            return (out, argmax, ant_out, ant_argmax) if want_ant else (out, argmax)
-        if want_ant:
-            with torch.cuda.device(self.device):
-                check(self.lib.prego_miniroad_step_anticipation(
-                    self.h, n, C.c_void_p(rgb.data_ptr()) if (rgb is not None and d_rgb > 0) else None,
-                    C.c_void_p(flow.data_ptr()) if flow is not None else None, C.c_void_p(h.data_ptr()), C.c_void_p(out.data_ptr()),
-                    C.c_void_p(argmax.data_ptr()), C.c_void_p(ant_out.data_ptr()), C.c_void_p(ant_argmax.data_ptr()),
-                    _lib.FWD_SOFTMAX if softmax else 0, C.c_void_p(_stream_ptr(self.device))))
-            return out, argmax, ant_out, ant_argmax
-        with torch.cuda.device(self.device):
-            check(self.lib.prego_miniroad_step(
-                self.h, n, C.c_void_p(rgb.data_ptr()) if (rgb is not None and d_rgb > 0) else None,
-                C.c_void_p(flow.data_ptr()) if flow is not None else None, C.c_void_p(h.data_ptr()), C.c_void_p(out.data_ptr()),
-                C.c_void_p(argmax.data_ptr()), _lib.FWD_SOFTMAX if softmax else 0, C.c_void_p(_stream_ptr(self.device))))
-        return out, argmax
+            res = self.forward_ragged(rl, fl, softmax=softmax, want_out=True, want_argmax=True, h0=h, want_h_last=True, want_ant=want_ant)
+            h.copy_(res[2])
+            for dst, clips in zip(outs, res[:2] + res[3:]):      # out, argmax and, with want_ant, the anticipation pair
+                dst.copy_(torch.cat(clips))
+            return outs
+        return self._stream_call("prego_miniroad_step", (n,), rgb, flow, h, outs, want_ant, softmax)
 
     def step_wide(self, rgb: Optional[torch.Tensor], flow: Optional[torch.Tensor], h: torch.Tensor, softmax: bool = True,
                   out: Optional[torch.Tensor] = None, argmax: Optional[torch.Tensor] = None, want_ant: bool = False,
@@ -387,41 +365,12 @@ class MiniRoadEngine:
         d_rgb, d_flow, emb, hid, ncls = self.dims
         if self.compute_dtype in ("fp32", "fp16x2") or hid != 1024 or self.num_layers != 1:
             return self.step(rgb, flow, h, softmax=softmax, out=out, argmax=argmax, want_ant=want_ant, ant_out=ant_out, ant_argmax=ant_argmax)
-        if want_ant and not getattr(self, "ant_len", 0):
-            raise PregoError("step_wide(want_ant=True) before set_anticipation")
-        src = rgb if d_rgb > 0 else flow
-        if src is None:
-            raise PregoError("step_wide: a --no_rgb model needs the flow frame" if d_rgb == 0 else "step_wide: rgb is None")
-        n = src.shape[0]
-        L = self.ant_len if want_ant else 0
-        if out is None:
-            out = torch.empty((n, ncls), dtype=torch.float32, device=self.device)
-        if argmax is None:
-            argmax = torch.empty((n,), dtype=torch.int32, device=self.device)
-        if want_ant and ant_out is None:
-            ant_out = torch.empty((n, L, ncls), dtype=torch.float32, device=self.device)
-        if want_ant and ant_argmax is None:
-            ant_argmax = torch.empty((n, L), dtype=torch.int32, device=self.device)
-        checks = [(rgb if d_rgb > 0 else None, (n, d_rgb), torch.float32, "rgb"), (flow, (n, d_flow), torch.float32, "flow"),
-                  (h, (n, hid), torch.float32, "GRU state"), (out, (n, ncls), torch.float32, "out"), (argmax, (n,), torch.int32, "argmax")]
-        if want_ant:
-            checks += [(ant_out, (n, L, ncls), torch.float32, "anticipation out"), (ant_argmax, (n, L), torch.int32, "anticipation argmax")]
-        for t, shape, dt, what in checks:
-            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
-                raise PregoError(f"step_wide: expected {what} as contiguous {dt} cuda {list(shape)}, got {tuple(t.shape)} {t.dtype} on {t.device}")
-        need = self.lib.prego_miniroad_step_wide_workspace_bytes(self.h, n)
-        if need and (getattr(self, "_ws_wide", None) is None or self._ws_wide.numel() < need):
-            self._ws_wide = torch.empty(need, dtype=torch.uint8, device=self.device)
-        ws = self._ws_wide if need else None
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        tail = (_lib.FWD_SOFTMAX if softmax else 0, p(ws), ws.numel() if ws is not None else 0, C.c_void_p(_stream_ptr(self.device)))
-        with torch.cuda.device(self.device):
-            if want_ant:
-                check(self.lib.prego_miniroad_step_wide_anticipation(self.h, n, p(rgb if d_rgb > 0 else None), p(flow), p(h), p(out), p(argmax),
-                                                                     p(ant_out), p(ant_argmax), *tail))
-                return out, argmax, ant_out, ant_argmax
-            check(self.lib.prego_miniroad_step_wide(self.h, n, p(rgb if d_rgb > 0 else None), p(flow), p(h), p(out), p(argmax), *tail))
-        return out, argmax
+        want_ant = SC.resolve_ant("step_wide", bool(want_ant), getattr(self, "ant_len", 0))
+        n = SC.frame_source("step_wide", d_rgb, rgb, flow).shape[0]
+        outs, specs = SC.outputs(self.device, (n,), ncls, self.ant_len if want_ant else 0, out, argmax, ant_out, ant_argmax)
+        SC.check("step_wide", SC.in_specs((n,), d_rgb, d_flow, rgb, flow) + [(h, (n, hid), SC.F32, "GRU state")] + specs)
+        ws = self._ws_wide.fit(self.lib.prego_miniroad_step_wide_workspace_bytes(self.h, n), self.device, none_if_zero=True)
+        return self._stream_call("prego_miniroad_step_wide", (n,), rgb, flow, h, outs, want_ant, softmax, ws)
 
     def step_frames(self, rgb: Optional[torch.Tensor], flow: Optional[torch.Tensor], h: torch.Tensor, softmax: bool = True,
                     want_ant=None, out: Optional[torch.Tensor] = None, argmax: Optional[torch.Tensor] = None,
@@ -434,48 +383,16 @@ class MiniRoadEngine:
         unfused LayerNorm route, also for n <= 4).  The weights off the sequential path are read once per call, W_hh once per frame from
         the L2.  Raises on engines the streaming kernels are not built for (fp32, fp16x2, hidden sizes other than 1024, two layers)."""
         d_rgb, d_flow, emb, hid, ncls = self.dims
-        if self.compute_dtype in ("fp32", "fp16x2") or hid != 1024 or self.num_layers != 1:
-            raise PregoError(f"step_frames: the streaming kernels are built for bf16 / fp16 operands, hidden_dim 1024, one GRU layer (this engine: "
-                             f"{self.compute_dtype}, hidden_dim {hid}, {self.num_layers} layers); use forward() with h0 / h_last")
-        if want_ant is None:
-            want_ant = bool(getattr(self, "ant_len", 0))
-        if want_ant and not getattr(self, "ant_len", 0):
-            raise PregoError("step_frames(want_ant=True) before set_anticipation")
-        src = rgb if d_rgb > 0 else flow
-        if src is None:
-            raise PregoError("step_frames: a --no_rgb model needs the flow frames" if d_rgb == 0 else "step_frames: rgb is None")
+        SC.refuse_general("step_frames", self.compute_dtype, hid, self.num_layers, "use forward() with h0 / h_last")
+        want_ant = SC.resolve_ant("step_frames", want_ant, getattr(self, "ant_len", 0))
+        src = SC.frame_source("step_frames", d_rgb, rgb, flow, "frames")
         if src.dim() != 3:
             raise PregoError(f"step_frames: expected frames as [n, K, d], got {tuple(src.shape)}")
         n, K = int(src.shape[0]), int(src.shape[1])
-        L = self.ant_len if want_ant else 0
-        if out is None:
-            out = torch.empty((n, K, ncls), dtype=torch.float32, device=self.device)
-        if argmax is None:
-            argmax = torch.empty((n, K), dtype=torch.int32, device=self.device)
-        if want_ant and ant_out is None:
-            ant_out = torch.empty((n, K, L, ncls), dtype=torch.float32, device=self.device)
-        if want_ant and ant_argmax is None:
-            ant_argmax = torch.empty((n, K, L), dtype=torch.int32, device=self.device)
-        checks = [(rgb if d_rgb > 0 else None, (n, K, d_rgb), torch.float32, "rgb"), (flow, (n, K, d_flow), torch.float32, "flow"),
-                  (h, (n, hid), torch.float32, "GRU state"), (out, (n, K, ncls), torch.float32, "out"), (argmax, (n, K), torch.int32, "argmax")]
-        if want_ant:
-            checks += [(ant_out, (n, K, L, ncls), torch.float32, "anticipation out"), (ant_argmax, (n, K, L), torch.int32, "anticipation argmax")]
-        for t, shape, dt, what in checks:
-            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
-                raise PregoError(f"step_frames: expected {what} as contiguous {dt} cuda {list(shape)}, got {tuple(t.shape)} {t.dtype} on {t.device}")
-        need = self.lib.prego_miniroad_step_frames_workspace_bytes(self.h, n, K)      # 0: the C call refuses the shape with its message
-        if need and (getattr(self, "_ws_frames", None) is None or self._ws_frames.numel() < need):
-            self._ws_frames = torch.empty(need, dtype=torch.uint8, device=self.device)
-        ws = self._ws_frames if need else None
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        tail = (_lib.FWD_SOFTMAX if softmax else 0, p(ws), ws.numel() if ws is not None else 0, C.c_void_p(_stream_ptr(self.device)))
-        with torch.cuda.device(self.device):
-            if want_ant:
-                check(self.lib.prego_miniroad_step_frames_anticipation(self.h, n, K, p(rgb if d_rgb > 0 else None), p(flow), p(h), p(out),
-                                                                       p(argmax), p(ant_out), p(ant_argmax), *tail))
-                return out, argmax, ant_out, ant_argmax
-            check(self.lib.prego_miniroad_step_frames(self.h, n, K, p(rgb if d_rgb > 0 else None), p(flow), p(h), p(out), p(argmax), *tail))
-        return out, argmax
+        outs, specs = SC.outputs(self.device, (n, K), ncls, self.ant_len if want_ant else 0, out, argmax, ant_out, ant_argmax)
+        SC.check("step_frames", SC.in_specs((n, K), d_rgb, d_flow, rgb, flow) + [(h, (n, hid), SC.F32, "GRU state")] + specs)
+        ws = self._ws_frames.fit(self.lib.prego_miniroad_step_frames_workspace_bytes(self.h, n, K), self.device, none_if_zero=True)
+        return self._stream_call("prego_miniroad_step_frames", (n, K), rgb, flow, h, outs, want_ant, softmax, ws)
 
     def step_ragged(self, rgb: Optional[torch.Tensor], flow: Optional[torch.Tensor], counts, h: torch.Tensor, softmax: bool = True,
                     want_ant=None, out: Optional[torch.Tensor] = None, argmax: Optional[torch.Tensor] = None,
@@ -489,54 +406,19 @@ class MiniRoadEngine:
         launch per frame index up to max(counts), each over the streams that still have a frame.  `counts` is read before the call
         returns.  Raises on engines the streaming kernels are not built for (fp32, fp16x2, hidden sizes other than 1024, two layers)."""
         d_rgb, d_flow, emb, hid, ncls = self.dims
-        if self.compute_dtype in ("fp32", "fp16x2") or hid != 1024 or self.num_layers != 1:
-            raise PregoError(f"step_ragged: the streaming kernels are built for bf16 / fp16 operands, hidden_dim 1024, one GRU layer (this engine: "
-                             f"{self.compute_dtype}, hidden_dim {hid}, {self.num_layers} layers); use forward() with h0 / h_last")
-        if want_ant is None:
-            want_ant = bool(getattr(self, "ant_len", 0))
-        if want_ant and not getattr(self, "ant_len", 0):
-            raise PregoError("step_ragged(want_ant=True) before set_anticipation")
-        src = rgb if d_rgb > 0 else flow
-        if src is None:
-            raise PregoError("step_ragged: a --no_rgb model needs the flow frames" if d_rgb == 0 else "step_ragged: rgb is None")
-        if isinstance(counts, torch.Tensor):
-            if counts.is_cuda or counts.is_floating_point() or counts.dim() != 1:
-                raise PregoError(f"step_ragged: counts is a sequence of ints or a 1-d CPU int tensor, got {tuple(counts.shape)} {counts.dtype} on {counts.device}")
-            counts = counts.tolist()
-        counts = [int(k) for k in counts]
+        SC.refuse_general("step_ragged", self.compute_dtype, hid, self.num_layers, "use forward() with h0 / h_last")
+        want_ant = SC.resolve_ant("step_ragged", want_ant, getattr(self, "ant_len", 0))
+        src = SC.frame_source("step_ragged", d_rgb, rgb, flow, "frames")
+        counts = SC.counts_list("step_ragged", counts, refuse_cuda=True)
         n, R = len(counts), sum(counts)
         if src.dim() != 2 or src.shape[0] != R:
             raise PregoError(f"step_ragged: expected packed frames as [sum(counts) = {R}, d], got {tuple(src.shape)}")
-        L = self.ant_len if want_ant else 0
-        if out is None:
-            out = torch.empty((R, ncls), dtype=torch.float32, device=self.device)
-        if argmax is None:
-            argmax = torch.empty((R,), dtype=torch.int32, device=self.device)
-        if want_ant and ant_out is None:
-            ant_out = torch.empty((R, L, ncls), dtype=torch.float32, device=self.device)
-        if want_ant and ant_argmax is None:
-            ant_argmax = torch.empty((R, L), dtype=torch.int32, device=self.device)
-        checks = [(rgb if d_rgb > 0 else None, (R, d_rgb), torch.float32, "rgb"), (flow, (R, d_flow), torch.float32, "flow"),
-                  (h, (n, hid), torch.float32, "GRU state"), (out, (R, ncls), torch.float32, "out"), (argmax, (R,), torch.int32, "argmax")]
-        if want_ant:
-            checks += [(ant_out, (R, L, ncls), torch.float32, "anticipation out"), (ant_argmax, (R, L), torch.int32, "anticipation argmax")]
-        for t, shape, dt, what in checks:
-            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
-                raise PregoError(f"step_ragged: expected {what} as contiguous {dt} cuda {list(shape)}, got {tuple(t.shape)} {t.dtype} on {t.device}")
-        need = self.lib.prego_miniroad_step_ragged_workspace_bytes(self.h, n, R)      # 0: the C call refuses the shape with its message
-        if need and (getattr(self, "_ws_frames", None) is None or self._ws_frames.numel() < need):
-            self._ws_frames = torch.empty(need, dtype=torch.uint8, device=self.device)      # grown here, outside the C call
-        ws = self._ws_frames if need else None
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        tail = (_lib.FWD_SOFTMAX if softmax else 0, p(ws), ws.numel() if ws is not None else 0, C.c_void_p(_stream_ptr(self.device)))
-        arr = (C.c_int32 * max(n, 1))(*[min(max(k, -(2 ** 31)), 2 ** 31 - 1) for k in counts])
-        with torch.cuda.device(self.device):
-            if want_ant:
-                check(self.lib.prego_miniroad_step_ragged_anticipation(self.h, n, arr, p(rgb if d_rgb > 0 else None), p(flow), p(h), p(out),
-                                                                       p(argmax), p(ant_out), p(ant_argmax), *tail))
-                return out, argmax, ant_out, ant_argmax
-            check(self.lib.prego_miniroad_step_ragged(self.h, n, arr, p(rgb if d_rgb > 0 else None), p(flow), p(h), p(out), p(argmax), *tail))
-        return out, argmax
+        outs, specs = SC.outputs(self.device, (R,), ncls, self.ant_len if want_ant else 0, out, argmax, ant_out, ant_argmax)
+        SC.check("step_ragged", SC.in_specs((R,), d_rgb, d_flow, rgb, flow) + [(h, (n, hid), SC.F32, "GRU state")] + specs)
+        ws = self._ws_frames.fit(self.lib.prego_miniroad_step_ragged_workspace_bytes(self.h, n, R), self.device, none_if_zero=True)
+        arr = (C.c_int32 * max(n, 1))(*SC.clamp_i32(counts))
+        return self._stream_call("prego_miniroad_step_ragged", (n, arr), rgb, flow, h, outs, want_ant, softmax, ws)
+
 
     # -- training ------------------------------------------------------------------------
     def set_dropout(self, p: float, seed: int):

@@ -16,6 +16,7 @@ from typing import NamedTuple
 
 import torch
 
+from . import _stream_call as SC
 from ._lib import PregoError
 from .aggregate import OVERFLOW_BAD_ID, OVERFLOW_FULL
 
@@ -133,6 +134,22 @@ class _RecordPool:
     @staticmethod
     def _slot_array(slots):
         return (C.c_int32 * len(slots))(*slots)
+
+    def _step_call(self, who, sym, handle, rows, ws_bytes, lead, slots, rgb, flow, bufs, flags, ant_len=None, note=""):
+        """What a push entry of either pool does once it knows the row shape of its outputs (the shared steps are prego_amd/_stream_call.py's):
+        outputs, checks, workspace and the C call `sym`(handle, pool, n, *lead, slots, rgb, flow, *outs, flags, workspace, bytes, stream).
+        ant_len None: the Transformer pool, whose symbols take no anticipation outputs; 0: NULL for them.  note: push_bursts' on its
+        packed rows.  A subclass sets _dims = (d_rgb, d_flow, n_classes)."""
+        d_rgb, d_flow, ncls = self._dims
+        outs, specs = SC.outputs(self.device, rows, ncls, ant_len or 0, *bufs)
+        SC.check(who, SC.in_specs(rows, d_rgb, d_flow, rgb, flow) + specs, "{what} as contiguous {dt} cuda {shape}" + note)
+        ws = self._ws.fit(ws_bytes, self.device)                 # 0 bytes: the C call refuses the shape with its message
+        c_outs = outs if ant_len is None else (outs + (None, None))[:4]
+        with torch.cuda.device(self.device):
+            self._check(getattr(self.lib, sym)(handle, self.p, len(slots), *lead, self._slot_array(slots), SC.ptr(rgb if d_rgb > 0 else None),
+                                               SC.ptr(flow), *[SC.ptr(t) for t in c_outs], flags, SC.ptr(ws), ws.numel(),
+                                               C.c_void_p(self._stream_ptr(self.device))))
+        return outs
 
     # -- reading a slot ------------------------------------------------------------------------
     def _record(self, slot: int):
@@ -625,13 +642,12 @@ class StreamPool(_RecordPool):
         self.slots = SlotTable(capacity)
         self._stream_ptr = _stream_ptr
         d_rgb, d_flow, emb, hid, ncls = eng.dims
-        self._hid, self._ncls, self._ncls_pad = hid, ncls, (ncls + 3) // 4 * 4
-        self._fast = eng.compute_dtype in ("bf16", "fp16") and hid == 1024 and eng.num_layers == 1
+        self._hid, self._ncls, self._ncls_pad, self._dims = hid, ncls, (ncls + 3) // 4 * 4, (d_rgb, d_flow, ncls)
         need = self.lib.prego_stream_pool_bytes(eng.h, int(capacity), self.max_events)
         if need == 0:
             raise PregoError(f"stream pool: capacity {capacity}, max_events {max_events} (each 1..{1 << 20})")
         self._block = torch.empty(need, dtype=torch.uint8, device=self.device)
-        self._ws = None
+        self._ws = SC.Workspace()
         p = C.c_void_p()
         with torch.cuda.device(self.device):
             rc = self.lib.prego_stream_pool_create(C.byref(p), eng.h, int(capacity), self.window, self.max_events, C.c_void_p(self._block.data_ptr()),
@@ -639,54 +655,23 @@ class StreamPool(_RecordPool):
         self._check(rc)
         self.p = p
 
-    # -- one frame for a subset of the streams ---------------------------------------------------
+    # -- frames for a subset of the streams ---------------------------------------------------------
+    _ADVICE = "run the general forward and feed its ids to vote()"
+
     def push(self, slots, rgb, flow=None, softmax: bool = True, want_ant=None, out=None, argmax=None, ant_out=None, ant_argmax=None):
         """One new frame for each open slot of `slots`: rgb [n, d_rgb] / flow [n, d_flow] (None = zero flow) fp32 cuda contiguous, rows in
         `slots` order.  Returns step_wide's tuple - (out [n, C], argmax int32 [n]) and, with want_ant (default: the model has an
         anticipation head), (ant_out [n, L, C], ant_argmax int32 [n, L]) - bit for bit what step_wide returns for a dense call of these
         streams; each slot's state is advanced and its record takes the frame's argmax.  Pass buffers to reuse them."""
-        eng = self.engine
-        if not self._fast:
-            raise PregoError(f"stream pool push: the streaming kernels are built for bf16 / fp16 operands, hidden_dim 1024, one GRU layer "
-                             f"(this engine: {eng.compute_dtype}, hidden_dim {self._hid}, {eng.num_layers} layers); run the general forward "
-                             "and feed its ids to vote()")
+        eng, who = self.engine, "stream pool push"
+        SC.refuse_general(who, eng.compute_dtype, self._hid, eng.num_layers, self._ADVICE)
         slots = self.slots.check(slots, "push")
         n = len(slots)
-        d_rgb, d_flow, emb, hid, ncls = eng.dims
-        if want_ant is None:
-            want_ant = bool(getattr(eng, "ant_len", 0))
-        if want_ant and not getattr(eng, "ant_len", 0):
-            raise PregoError("stream pool push(want_ant=True) before set_anticipation")
-        if (rgb if d_rgb > 0 else flow) is None:
-            raise PregoError("stream pool push: a --no_rgb model needs the flow frame" if d_rgb == 0 else "stream pool push: rgb is None")
-        L = eng.ant_len if want_ant else 0
-        if out is None:
-            out = torch.empty((n, ncls), dtype=torch.float32, device=self.device)
-        if argmax is None:
-            argmax = torch.empty((n,), dtype=torch.int32, device=self.device)
-        if want_ant and ant_out is None:
-            ant_out = torch.empty((n, L, ncls), dtype=torch.float32, device=self.device)
-        if want_ant and ant_argmax is None:
-            ant_argmax = torch.empty((n, L), dtype=torch.int32, device=self.device)
-        checks = [(rgb if d_rgb > 0 else None, (n, d_rgb), torch.float32, "rgb"), (flow, (n, d_flow), torch.float32, "flow"),
-                  (out, (n, ncls), torch.float32, "out"), (argmax, (n,), torch.int32, "argmax")]
-        if want_ant:
-            checks += [(ant_out, (n, L, ncls), torch.float32, "anticipation out"), (ant_argmax, (n, L), torch.int32, "anticipation argmax")]
-        for t, shape, dt, what in checks:
-            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
-                raise PregoError(f"stream pool push: expected {what} as contiguous {dt} cuda {list(shape)}, got {tuple(t.shape)} {t.dtype} on {t.device}")
-        need = self.lib.prego_miniroad_step_pool_workspace_bytes(eng.h, n)
-        if self._ws is None or self._ws.numel() < need:          # grown here, outside the C call
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        with torch.cuda.device(self.device):
-            rc = self.lib.prego_miniroad_step_pool(eng.h, self.p, n, self._slot_array(slots), p(rgb if d_rgb > 0 else None), p(flow), p(out),
-                                                   p(argmax), p(ant_out) if want_ant else None, p(ant_argmax) if want_ant else None,
-                                                   1 if softmax else 0, p(self._ws), self._ws.numel(), C.c_void_p(self._stream_ptr(self.device)))
-        self._check(rc)
-        return (out, argmax, ant_out, ant_argmax) if want_ant else (out, argmax)
+        want_ant = SC.resolve_ant(who, want_ant, getattr(eng, "ant_len", 0))
+        SC.frame_source(who, eng.dims[0], rgb, flow)
+        return self._step_call(who, "prego_miniroad_step_pool", eng.h, (n,), self.lib.prego_miniroad_step_pool_workspace_bytes(eng.h, n), (), slots,
+                               rgb, flow, (out, argmax, ant_out, ant_argmax), 1 if softmax else 0, eng.ant_len if want_ant else 0)
 
-    # -- a burst of K frames for a subset of the streams --------------------------------------------
     def push_frames(self, slots, rgb, flow=None, softmax: bool = True, want_ant=None, out=None, argmax=None, ant_out=None, ant_argmax=None):
         """K new frames for each open slot of `slots` in one call (prego_miniroad_step_pool_frames): rgb [n, K, d_rgb] / flow [n, K, d_flow]
         (None = zero flow) fp32 cuda contiguous, 1 <= K <= 32 the same for every slot, n K <= 256 - slots with different backlogs: `push_ragged`;
@@ -694,110 +679,38 @@ class StreamPool(_RecordPool):
         argmax int32 [n, K]) and, with want_ant, (ant_out [n, K, L, C], ant_argmax int32 [n, K, L]); every frame's bits are `push`'s for a
         call of 5..256 slots.  Each slot's state is advanced by K frames and its record is word for word the record after K `push`
         calls: the K ids are voted in frame order, window boundaries inside the burst included."""
-        eng = self.engine
-        if not self._fast:
-            raise PregoError(f"stream pool push_frames: the streaming kernels are built for bf16 / fp16 operands, hidden_dim 1024, one GRU layer "
-                             f"(this engine: {eng.compute_dtype}, hidden_dim {self._hid}, {eng.num_layers} layers); run the general forward "
-                             "and feed its ids to vote()")
+        eng, who = self.engine, "stream pool push_frames"
+        SC.refuse_general(who, eng.compute_dtype, self._hid, eng.num_layers, self._ADVICE)
         slots = self.slots.check(slots, "push_frames")
         n = len(slots)
-        d_rgb, d_flow, emb, hid, ncls = eng.dims
-        if want_ant is None:
-            want_ant = bool(getattr(eng, "ant_len", 0))
-        if want_ant and not getattr(eng, "ant_len", 0):
-            raise PregoError("stream pool push_frames(want_ant=True) before set_anticipation")
-        src = rgb if d_rgb > 0 else flow
-        if src is None:
-            raise PregoError("stream pool push_frames: a --no_rgb model needs the flow frames" if d_rgb == 0 else "stream pool push_frames: rgb is None")
+        want_ant = SC.resolve_ant(who, want_ant, getattr(eng, "ant_len", 0))
+        src = SC.frame_source(who, eng.dims[0], rgb, flow, "frames")
         if src.dim() != 3 or src.shape[0] != n:
             raise PregoError(f"stream pool push_frames: expected frames as [{n}, K, d], got {tuple(src.shape)}")
         K = int(src.shape[1])
-        L = eng.ant_len if want_ant else 0
-        if out is None:
-            out = torch.empty((n, K, ncls), dtype=torch.float32, device=self.device)
-        if argmax is None:
-            argmax = torch.empty((n, K), dtype=torch.int32, device=self.device)
-        if want_ant and ant_out is None:
-            ant_out = torch.empty((n, K, L, ncls), dtype=torch.float32, device=self.device)
-        if want_ant and ant_argmax is None:
-            ant_argmax = torch.empty((n, K, L), dtype=torch.int32, device=self.device)
-        checks = [(rgb if d_rgb > 0 else None, (n, K, d_rgb), torch.float32, "rgb"), (flow, (n, K, d_flow), torch.float32, "flow"),
-                  (out, (n, K, ncls), torch.float32, "out"), (argmax, (n, K), torch.int32, "argmax")]
-        if want_ant:
-            checks += [(ant_out, (n, K, L, ncls), torch.float32, "anticipation out"), (ant_argmax, (n, K, L), torch.int32, "anticipation argmax")]
-        for t, shape, dt, what in checks:
-            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
-                raise PregoError(f"stream pool push_frames: expected {what} as contiguous {dt} cuda {list(shape)}, got {tuple(t.shape)} {t.dtype} on {t.device}")
-        need = self.lib.prego_miniroad_step_pool_frames_workspace_bytes(eng.h, n, K)      # 0: the C call refuses the shape with its message
-        if self._ws is None or self._ws.numel() < need:          # grown here, outside the C call
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        with torch.cuda.device(self.device):
-            rc = self.lib.prego_miniroad_step_pool_frames(eng.h, self.p, n, K, self._slot_array(slots), p(rgb if d_rgb > 0 else None), p(flow),
-                                                          p(out), p(argmax), p(ant_out) if want_ant else None,
-                                                          p(ant_argmax) if want_ant else None, 1 if softmax else 0, p(self._ws),
-                                                          self._ws.numel(), C.c_void_p(self._stream_ptr(self.device)))
-        self._check(rc)
-        return (out, argmax, ant_out, ant_argmax) if want_ant else (out, argmax)
+        return self._step_call(who, "prego_miniroad_step_pool_frames", eng.h, (n, K), self.lib.prego_miniroad_step_pool_frames_workspace_bytes(eng.h, n, K),
+                               (K,), slots, rgb, flow, (out, argmax, ant_out, ant_argmax), 1 if softmax else 0, eng.ant_len if want_ant else 0)
 
-    # -- a burst of its own length for each of a subset of the streams -------------------------------
     def push_ragged(self, slots, counts, rgb, flow=None, softmax: bool = True, want_ant=None, out=None, argmax=None, ant_out=None, ant_argmax=None):
         """counts[i] new frames (1..32, R = sum(counts) <= 256) for open slot slots[i] in one call (prego_miniroad_step_pool_ragged): rgb
         [R, d_rgb] / flow [R, d_flow] (None = zero flow) fp32 cuda contiguous, packed in `slots` order (`pack_bursts`).  Returns `push`'s
         tuple over the packed rows: (out [R, C], argmax int32 [R]) and, with want_ant, (ant_out [R, L, C], ant_argmax int32 [R, L]); every
         row's bits are `push_frames`'s.  Slot i's state is advanced by counts[i] frames and its record is word for word the record after
         counts[i] `push` calls."""
-        eng = self.engine
-        if not self._fast:
-            raise PregoError(f"stream pool push_ragged: the streaming kernels are built for bf16 / fp16 operands, hidden_dim 1024, one GRU layer "
-                             f"(this engine: {eng.compute_dtype}, hidden_dim {self._hid}, {eng.num_layers} layers); run the general forward "
-                             "and feed its ids to vote()")
+        eng, who = self.engine, "stream pool push_ragged"
+        SC.refuse_general(who, eng.compute_dtype, self._hid, eng.num_layers, self._ADVICE)
         slots = self.slots.check(slots, "push_ragged")
         n = len(slots)
-        if isinstance(counts, torch.Tensor):
-            counts = counts.tolist()
-        counts = [int(k) for k in counts]
-        if len(counts) != n:
-            raise PregoError(f"stream pool push_ragged: {n} slots, {len(counts)} counts")
+        counts = SC.counts_list(who, counts, n)
         R = sum(counts)
-        d_rgb, d_flow, emb, hid, ncls = eng.dims
-        if want_ant is None:
-            want_ant = bool(getattr(eng, "ant_len", 0))
-        if want_ant and not getattr(eng, "ant_len", 0):
-            raise PregoError("stream pool push_ragged(want_ant=True) before set_anticipation")
-        src = rgb if d_rgb > 0 else flow
-        if src is None:
-            raise PregoError("stream pool push_ragged: a --no_rgb model needs the flow frames" if d_rgb == 0 else "stream pool push_ragged: rgb is None")
+        want_ant = SC.resolve_ant(who, want_ant, getattr(eng, "ant_len", 0))
+        src = SC.frame_source(who, eng.dims[0], rgb, flow, "frames")
         if src.dim() != 2 or src.shape[0] != R:
             raise PregoError(f"stream pool push_ragged: expected packed frames as [sum(counts) = {R}, d], got {tuple(src.shape)}")
-        L = eng.ant_len if want_ant else 0
-        if out is None:
-            out = torch.empty((R, ncls), dtype=torch.float32, device=self.device)
-        if argmax is None:
-            argmax = torch.empty((R,), dtype=torch.int32, device=self.device)
-        if want_ant and ant_out is None:
-            ant_out = torch.empty((R, L, ncls), dtype=torch.float32, device=self.device)
-        if want_ant and ant_argmax is None:
-            ant_argmax = torch.empty((R, L), dtype=torch.int32, device=self.device)
-        checks = [(rgb if d_rgb > 0 else None, (R, d_rgb), torch.float32, "rgb"), (flow, (R, d_flow), torch.float32, "flow"),
-                  (out, (R, ncls), torch.float32, "out"), (argmax, (R,), torch.int32, "argmax")]
-        if want_ant:
-            checks += [(ant_out, (R, L, ncls), torch.float32, "anticipation out"), (ant_argmax, (R, L), torch.int32, "anticipation argmax")]
-        for t, shape, dt, what in checks:
-            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
-                raise PregoError(f"stream pool push_ragged: expected {what} as contiguous {dt} cuda {list(shape)}, got {tuple(t.shape)} {t.dtype} on {t.device}")
-        need = self.lib.prego_miniroad_step_pool_ragged_workspace_bytes(eng.h, n, R)      # 0: the C call refuses the shape with its message
-        if self._ws is None or self._ws.numel() < need:          # grown here, outside the C call
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        with torch.cuda.device(self.device):
-            rc = self.lib.prego_miniroad_step_pool_ragged(eng.h, self.p, n, self._slot_array(counts), self._slot_array(slots),
-                                                          p(rgb if d_rgb > 0 else None), p(flow), p(out), p(argmax),
-                                                          p(ant_out) if want_ant else None, p(ant_argmax) if want_ant else None,
-                                                          1 if softmax else 0, p(self._ws), self._ws.numel(),
-                                                          C.c_void_p(self._stream_ptr(self.device)))
-        self._check(rc)
-        return (out, argmax, ant_out, ant_argmax) if want_ant else (out, argmax)
+        return self._step_call(who, "prego_miniroad_step_pool_ragged", eng.h, (R,), self.lib.prego_miniroad_step_pool_ragged_workspace_bytes(eng.h, n, R),
+                               (self._slot_array(counts),), slots, rgb, flow, (out, argmax, ant_out, ant_argmax), 1 if softmax else 0,
+                               eng.ant_len if want_ant else 0)
+
 
     def vote(self, slots, ids):
         """Aggregation alone: ids (int32 cuda [n], or a host sequence) are the new frame's step ids of `slots`, from whatever produced them."""
@@ -892,12 +805,13 @@ class TransformerStreamPool(_RecordPool):
         self._stream_ptr = _stream_ptr
         self._T, self._E = int(vit.img_dim), int(vit.embedding_dim)
         self._ncls, self._ncls_pad = int(vit.out_dim), (int(vit.out_dim) + 3) // 4 * 4
+        self._dims = (vit.d_rgb, vit.d_flow, self._ncls)
         need = lib.prego_vit_stream_pool_bytes(hnd, int(capacity), self.max_events)
         if need == 0:
             raise PregoError(f"transformer stream pool: capacity {capacity} (>= 1), max_events {max_events} (1..{1 << 20}), or a block "
                              "beyond size_t")
         self._block = torch.empty(need, dtype=torch.uint8, device=dev)
-        self._ws = None
+        self._ws = SC.Workspace()
         p = C.c_void_p()
         with torch.cuda.device(dev):
             rc = lib.prego_vit_stream_pool_create(C.byref(p), hnd, int(capacity), self.vote_window, self.max_events,
@@ -924,35 +838,12 @@ class TransformerStreamPool(_RecordPool):
         `slots` order.  Returns (logits [n, C] fp32 - raw, ViTEnc applies no softmax -, argmax int32 [n]): row i is the model's forward on
         the window_size frames of slot slots[i] ending at this frame.  Each slot's ring takes the frame and its record the argmax.
         Pass buffers to reuse them."""
-        m = self.model
         hnd = self._handle("push")
         slots = self.slots.check(slots, "push")
         n = len(slots)
-        d_rgb, d_flow, ncls = m.d_rgb, m.d_flow, self._ncls
-        if (rgb if d_rgb > 0 else flow) is None:
-            raise PregoError("transformer stream pool push: a --no_rgb model needs the flow frame" if d_rgb == 0 else
-                             "transformer stream pool push: rgb is None")
-        if d_flow == 0:
-            flow = None
-        if out is None:
-            out = torch.empty((n, ncls), dtype=torch.float32, device=self.device)
-        if argmax is None:
-            argmax = torch.empty((n,), dtype=torch.int32, device=self.device)
-        for t, shape, dt, what in [(rgb if d_rgb > 0 else None, (n, d_rgb), torch.float32, "rgb"), (flow, (n, d_flow), torch.float32, "flow"),
-                                   (out, (n, ncls), torch.float32, "out"), (argmax, (n,), torch.int32, "argmax")]:
-            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
-                raise PregoError(f"transformer stream pool push: expected {what} as contiguous {dt} cuda {list(shape)}, got {tuple(t.shape)} "
-                                 f"{t.dtype} on {t.device}")
-        need = self.lib.prego_vit_step_pool_workspace_bytes(hnd, n)
-        if self._ws is None or self._ws.numel() < need:          # grown here, outside the C call
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        with torch.cuda.device(self.device):
-            rc = self.lib.prego_vit_step_pool(hnd, self.p, n, self._slot_array(slots), p(rgb if d_rgb > 0 else None), p(flow), p(out),
-                                              p(argmax), 1 if m.causal else 0, p(self._ws), self._ws.numel(),
-                                              C.c_void_p(self._stream_ptr(self.device)))
-        self._check(rc)
-        return out, argmax
+        SC.frame_source("transformer stream pool push", self.model.d_rgb, rgb, flow)
+        return self._step_call("transformer stream pool push", "prego_vit_step_pool", hnd, (n,), self.lib.prego_vit_step_pool_workspace_bytes(hnd, n),
+                               (), slots, rgb, flow if self._dims[1] else None, (out, argmax), 1 if self.model.causal else 0)
 
     def push_bursts(self, slots, counts, rgb, flow=None, out=None, argmax=None):
         """counts[i] new frames (1..min(32, window_size); one int = the same for every slot; R = sum(counts) <= 256) for open slot
@@ -961,18 +852,10 @@ class TransformerStreamPool(_RecordPool):
         window_size frames of slot slots[i] ending at its burst frame k.  Afterwards each slot's ring and record are what counts[i]
         `push` calls leave; the logits agree with those calls at the tolerance that holds `push` against `forward_frames` (the GEMM
         kernels are chosen by row count), bit for bit when every count is 1.  A longer backlog is the caller's to split."""
-        m = self.model
+        who = "transformer stream pool push_bursts"
         hnd = self._handle("push_bursts")
         slots = self.slots.check(slots, "push_bursts")
-        n = len(slots)
-        if isinstance(counts, torch.Tensor):
-            counts = counts.tolist()
-        try:
-            counts = [int(k) for k in counts]
-        except TypeError:                                        # one number: the same count for every slot
-            counts = [int(counts)] * n
-        if len(counts) != n:
-            raise PregoError(f"transformer stream pool push_bursts: {n} slots, {len(counts)} counts")
+        counts = SC.counts_list(who, counts, len(slots), one_int=True)
         k_max = min(32, self._T)
         for i, k in enumerate(counts):
             if not 1 <= k <= k_max:
@@ -981,31 +864,11 @@ class TransformerStreamPool(_RecordPool):
         R = sum(counts)
         if R > MAX_ACTIVE:
             raise PregoError(f"transformer stream pool push_bursts: the counts sum to {R} rows (at most {MAX_ACTIVE} windows per call)")
-        d_rgb, d_flow, ncls = m.d_rgb, m.d_flow, self._ncls
-        if (rgb if d_rgb > 0 else flow) is None:
-            raise PregoError("transformer stream pool push_bursts: a --no_rgb model needs the flow frames" if d_rgb == 0 else
-                             "transformer stream pool push_bursts: rgb is None")
-        if d_flow == 0:
-            flow = None
-        if out is None:
-            out = torch.empty((R, ncls), dtype=torch.float32, device=self.device)
-        if argmax is None:
-            argmax = torch.empty((R,), dtype=torch.int32, device=self.device)
-        for t, shape, dt, what in [(rgb if d_rgb > 0 else None, (R, d_rgb), torch.float32, "rgb"), (flow, (R, d_flow), torch.float32, "flow"),
-                                   (out, (R, ncls), torch.float32, "out"), (argmax, (R,), torch.int32, "argmax")]:
-            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
-                raise PregoError(f"transformer stream pool push_bursts: expected {what} as contiguous {dt} cuda {list(shape)} "
-                                 f"(sum(counts) = {R} packed rows), got {tuple(t.shape)} {t.dtype} on {t.device}")
-        need = self.lib.prego_vit_step_pool_bursts_workspace_bytes(hnd, n, R)
-        if self._ws is None or self._ws.numel() < need:          # grown here, outside the C call
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        with torch.cuda.device(self.device):
-            rc = self.lib.prego_vit_step_pool_bursts(hnd, self.p, n, self._slot_array(counts), self._slot_array(slots),
-                                                     p(rgb if d_rgb > 0 else None), p(flow), p(out), p(argmax), 1 if m.causal else 0,
-                                                     p(self._ws), self._ws.numel(), C.c_void_p(self._stream_ptr(self.device)))
-        self._check(rc)
-        return out, argmax
+        SC.frame_source(who, self.model.d_rgb, rgb, flow, "frames")
+        return self._step_call(who, "prego_vit_step_pool_bursts", hnd, (R,), self.lib.prego_vit_step_pool_bursts_workspace_bytes(hnd, len(slots), R),
+                               (self._slot_array(counts),), slots, rgb, flow if self._dims[1] else None, (out, argmax),
+                               1 if self.model.causal else 0, note=f" (sum(counts) = {R} packed rows)")
+
 
     def window(self, slot: int):
         """([window_size, E] fp32 tensor, fill): the slot's encoded frames, oldest first - linear_encoding's rows, its bias where the
