@@ -56,9 +56,21 @@ int prego_debug_ant_full_span(int on);
 int prego_debug_hog(int kind, int xcd_lo, int ms, const void* read_buf, void* write_buf, size_t bytes, float* sink, prego_stream_t stream);
 
 /* Debug / microbenchmark only: C[M,N] fp32 = A[M,K] bf16 . B[N,K]^T bf16 + bias with a chosen kernel variant
- * (0 = 128x128, 1 = 256x128 three-stage, 9 = 256x256 two-stage, 12 = the ping-pong kernel = the production kernel of the projections; scripts/gemm_bench.py).  N % 128 == 0 (256 for variants >= 9), K % 64 == 0. */
+ * (0 = 128x128, 1 = 256x128 three-stage, 9 = 256x256 two-stage, 12 = the ping-pong kernel = the production kernel of the projections,
+ * 30 = the eight-wave split-K workgroup; scripts/gemm_bench.py).  N % 128 == 0, K % 64 == 0.  A variant forces its kernel: on a shape
+ * that kernel does not take (N % 256 or K < 128 for 9 / 12, more than 256 tiles for 30) nothing is launched and 0 is returned.
+ * PREGO_EINVAL for any other variant. */
 int prego_debug_gemm_bf16(int variant, const void* A, const void* B, const float* bias, float* C, int M, int N, int K,
                           prego_stream_t stream);
+
+/* Unit test only (tests/test_gemm_dispatch_cpu.py): which kernel an NT product runs on - the answer of the one chooser behind
+ * launch_gemm_bf16_nt, launch_gemm_bf16_nt_epi and the MiniROAD projections, without touching a device.  entry: 0 = launch_gemm_bf16_nt,
+ * 1 = launch_gemm_bf16_nt_epi, 2 = the MiniROAD forward's projection with fp16 operands or a 16-bit C.  mode: the epilogue (0 store fp32,
+ * 1 residual, 2 gelu 16-bit, 3 store 16-bit, 4 qkv, 5 tokens); dh, emb: the qkv epilogue's head and embedding widths.  knobs: bit 0
+ * PREGO_GEMM_NO_BIG, bit 1 PREGO_GEMM_NO_SPLITK, bit 2 PREGO_GEMM_NO_PINGPONG.  Returns -1 nothing launched (M <= 0), 0 the 128x128
+ * kernel, 1 256x128 three-stage, 2 256x256 two-stage, 3 ping-pong, 4 the eight-wave split-K workgroup. */
+int prego_debug_gemm_nt_choice(int entry, int M, int N, int K, int lda, int ldb, int has_bias, int f16, int train_splitk, int mode, int dh,
+                               int emb, int knobs);
 
 /* Unit test only (tests/test_gpu_gemm_tn.py): the training GEMMs on k-major operands exactly as the training steps launch them
  * (launch_gemm_bf16_tn chooses between the split-K and the plain kernel itself).  C[M,N] = op(A) . op(B) (+ bias[n]); ta: A is stored

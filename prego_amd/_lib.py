@@ -67,7 +67,7 @@ THUMOS_TILE_ROWS = 128                       # PREGO_THUMOS_TILE_ROWS: rows per 
 DEBUG_SYMBOLS = ["prego_miniroad_debug_stamps", "prego_debug_gemm_bf16", "prego_debug_attention_bwd", "prego_debug_attention_fwd",
                  "prego_debug_recurrence_only", "prego_debug_gemm_worker", "prego_debug_head_only",
                  "prego_debug_split_fault", "prego_debug_split_state", "prego_debug_set_abort", "prego_debug_alloc_count", "prego_debug_hog",
-                 "prego_debug_ant_full_span", "prego_debug_gemm_tn", "prego_debug_gemm_nt", "prego_debug_vit_ring_tokens",
+                 "prego_debug_ant_full_span", "prego_debug_gemm_tn", "prego_debug_gemm_nt", "prego_debug_gemm_nt_choice", "prego_debug_vit_ring_tokens",
                  "prego_debug_vit_burst_tokens", "prego_debug_vit_burst_commit", "prego_debug_pool_image_fault"]
 
 
@@ -267,6 +267,7 @@ def _open(path: str, debug: bool) -> C.CDLL:
         lib.prego_debug_gemm_bf16.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, vp]
         lib.prego_debug_gemm_tn.argtypes = [i32, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
         lib.prego_debug_gemm_nt.argtypes = [i32, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp]
+        lib.prego_debug_gemm_nt_choice.argtypes = [i32] * 13
         lib.prego_debug_split_fault.argtypes = [vp, i32]
         lib.prego_debug_split_state.argtypes = [vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(i64), C.POINTER(i32)]
         lib.prego_debug_set_abort.argtypes = [vp, C.c_uint32, vp]

@@ -31,20 +31,15 @@
 // (2 s of s_memrealtime: a timeout raises the abort word that ends both kernels - no hung GPU), but behind a successful handshake every
 // producer of every wait is resident and running.
 //
-// Arithmetic: the tile loop is the ping-pong K loop of gemm_pp.hip (same fragment order, same MFMA order), the row jobs are the
+// Arithmetic: the tile loop IS the ping-pong K loop of the GEMM (gemm_tile.h: pp_tile_loop, the same code), the row jobs are the
 // bodies of pack_rows_kernel / ln_relu_rows_kernel (rowwise.hip) on a wave per row: every GI element is bit-identical to the
 // chunked pass.
 #include "common.h"
 #include "kernels.h"
+#include "gemm_tile.h"
 #include "pass_handshake.h"
 
-#define FBK 64
-#define FHALF 16384
-#define FBUF 65536
-#define FF_WAIT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 #define FF_TIMEOUT_TICKS 200000000ull          // s_memrealtime runs at 100 MHz: 2 s
-
-__device__ __forceinline__ int ffp_key_b(int r) { return ((r >> 1) & 1) | (((r >> 3) & 3) << 1); }
 
 // tid 0 only: wait until *p >= need.  false = aborted (by this wait's timeout or by someone else)
 __device__ __forceinline__ bool ffp_wait_ge(const unsigned* p, unsigned need, unsigned* abort_word, unsigned code) {
@@ -64,8 +59,8 @@ __device__ __forceinline__ bool ffp_wait_ge(const unsigned* p, unsigned need, un
   }
 }
 
-// One 256 x 256 output tile: C[rows <= 256, 256] (16-bit) = A[rows, K] . B[256, K]^T + bias, the 8-phase ping-pong loop of gemm_pp.hip
-// (see there for the schedule).  A, B, bias, C point at the tile's first row / column.  SC1OUT: the stores are write-through (the tile
+// One 256 x 256 output tile: C[rows <= 256, 256] (16-bit) = A[rows, K] . B[256, K]^T + bias through pp_tile_loop
+// (gemm_tile.h, with the schedule).  A, B, bias, C point at the tile's first row / column.  SC1OUT: the stores are write-through (the tile
 // is read on another XCD).
 template <typename OT, bool SC1OUT>
 __device__ __forceinline__ void ffp_tile(char* smem, const bf16_t* __restrict__ A, int lda, int rows, const bf16_t* __restrict__ B, int ldb,
@@ -76,53 +71,11 @@ __device__ __forceinline__ void ffp_tile(char* smem, const bf16_t* __restrict__ 
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int grp = wave >> 2, wc = wave & 3;
-  const int nk = K / FBK;
-  const int sr = lane >> 3, scp = lane & 7;
   int a_off[2], b_off[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int r = (wave * 2 + i) * 8 + sr;
-    a_off[i] = r * lda * 2 + ((scp ^ ((r >> 1) & 7)) << 4);
-    b_off[i] = r * ldb * 2 + ((scp ^ ffp_key_b(r)) << 4);
-  }
+  pp_lane_offsets<false>(wave, lane, lda, ldb, 0, 0, a_off, b_off);
   const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)A, 0, rows * lda * 2, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)B, 0, 256 * ldb * 2, 0x00020000);
-  auto stage_a = [&](int hf, int kt) {
-    char* dst = smem + (kt & 1) * FBUF + hf * FHALF + wave * 2048;
-    const int so = hf * 128 * lda * 2 + kt * (FBK * 2);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, a_off[i], so, 0, 0);
-  };
-  auto stage_b = [&](int hf, int kt) {
-    char* dst = smem + (kt & 1) * FBUF + (2 + hf) * FHALF + wave * 2048;
-    const int so = hf * 128 * ldb * 2 + kt * (FBK * 2);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_b, (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, b_off[i], so, 0, 0);
-  };
   const int fr = lane & 15, fq = lane >> 4;
-  bf16x8 a0[2][4], a1[2][4], b0[2][2], b1[2][2];
-  auto read_a = [&](bf16x8 (&af)[2][4], int slot, int kt) {
-    const char* base = smem + (kt & 1) * FBUF + slot * FHALF;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int r = grp * 64 + i * 16 + fr;
-        af[ks][i] = *(const bf16x8*)(base + r * 128 + (((ks * 4 + fq) ^ ((r >> 1) & 7)) << 4));
-      }
-  };
-  auto read_b = [&](bf16x8 (&bf)[2][2], int slot, int kt) {
-    const char* base = smem + (kt & 1) * FBUF + slot * FHALF;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int r = wc * 32 + (fr >> 2) * 8 + j * 4 + (fr & 3);
-        bf[ks][j] = *(const bf16x8*)(base + r * 128 + (((ks * 4 + fq) ^ ffp_key_b(r)) << 4));
-      }
-  };
   f32x4 acc[2][2][4][2];
 #pragma unroll
   for (int x = 0; x < 2; ++x)
@@ -132,55 +85,7 @@ __device__ __forceinline__ void ffp_tile(char* smem, const bf16_t* __restrict__ 
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[x][y][i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  auto mma = [&](f32x4 (&c)[4][2], const bf16x8 (&af)[2][4], const bf16x8 (&bf)[2][2]) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) c[i][j] = op16<OT>::mfma(bf[ks][j], af[ks][i], c[i][j]);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  auto bar = [&]() {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  stage_a(0, 0); stage_b(0, 0); stage_b(1, 0); stage_a(1, 0);
-  stage_a(0, 1); stage_b(0, 1); stage_b(1, 1);
-  FF_WAIT(10);
-  bar();
-  read_a(a0, 0, 0);
-  if (grp == 1) bar();
-  for (int kt = 0; kt < nk; ++kt) {
-    const bool full = kt + 2 < nk;
-    read_b(b0, 2, kt);
-    if (kt + 1 < nk) stage_a(1, kt + 1);
-    if (full) FF_WAIT(10); else FF_WAIT(0);
-    bar();
-    mma(acc[0][0], a0, b0);
-    bar();
-    read_b(b1, 3, kt);
-    if (full) { stage_a(0, kt + 2); FF_WAIT(10); } else FF_WAIT(0);
-    bar();
-    mma(acc[0][1], a0, b1);
-    bar();
-    read_a(a1, 1, kt);
-    if (full) { stage_b(0, kt + 2); FF_WAIT(10); } else FF_WAIT(0);
-    bar();
-    mma(acc[1][1], a1, b1);
-    bar();
-    if (kt + 1 < nk) read_a(a0, 0, kt + 1);
-    if (full) { stage_b(1, kt + 2); FF_WAIT(10); } else FF_WAIT(0);
-    bar();
-    mma(acc[1][0], a1, b0);
-    bar();
-  }
-  if (grp == 0) bar();
+  pp_tile_loop<OT, false>((lds_char*)smem, rs_a, rs_b, a_off, b_off, lda, ldb, K / kPpBK, wave, lane, acc);
   float4 bv[2][2];
 #pragma unroll
   for (int y = 0; y < 2; ++y)
@@ -676,14 +581,14 @@ __global__ __launch_bounds__(512, 2) void ff_pass_kernel(FfPassArgs a) {
 
 // 0 on success, -1 = shape not supported.  One launch per pass; `grid` workgroups (256: one per CU, an eighth lands on every XCD).
 int launch_ff_pass(const FfPassArgs& a, hipStream_t s) {
-  if (a.E % 512 || a.E > 4096 || a.kx % FBK || a.kx < 2 * FBK || a.n3 % 256 || a.xcd_lo < 1 || a.xcd_lo > 7) return -1;
+  if (a.E % 512 || a.E > 4096 || a.kx % kPpBK || a.kx < 2 * kPpBK || a.n3 % 256 || a.xcd_lo < 1 || a.xcd_lo > 7) return -1;
   if (a.sg < 1 || a.ring_units % (8 - a.xcd_lo) || (a.gi_ring_units & (a.gi_ring_units - 1)) || a.nt1 != a.E / 256 || a.nt2 != a.n3 / 256) return -1;
   static DeviceOnce once;
   once.run([&] {
-    (void)hipFuncSetAttribute((const void*)ff_pass_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * FBUF);
-    (void)hipFuncSetAttribute((const void*)ff_pass_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * FBUF);
+    (void)hipFuncSetAttribute((const void*)ff_pass_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kPpBuf);
+    (void)hipFuncSetAttribute((const void*)ff_pass_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kPpBuf);
   });
-  if (a.f16) ff_pass_kernel<f16_t><<<256, 512, 2 * FBUF, s>>>(a);
-  else ff_pass_kernel<bf16_t><<<256, 512, 2 * FBUF, s>>>(a);
+  if (a.f16) ff_pass_kernel<f16_t><<<256, 512, 2 * kPpBuf, s>>>(a);
+  else ff_pass_kernel<bf16_t><<<256, 512, 2 * kPpBuf, s>>>(a);
   return 0;
 }

@@ -17,6 +17,7 @@
 // latency it removes (two workgroups per CU already cover for each other).
 #include "common.h"
 #include "kernels.h"
+#include "gemm_tile.h"     // xcd_remap
 
 #define TBM 128
 #define TBN 128
@@ -25,10 +26,6 @@
 typedef short tn_v4s __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) tn_v4s* tn_lds_v4s;
 
-__device__ __forceinline__ int tn_xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
 // image (b): byte offset of 16-byte chunk ch (0..15) of row `row` of a [rows][128 x 16-bit] tile
 __device__ __forceinline__ int tn_key(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 
@@ -52,7 +49,7 @@ __global__ __launch_bounds__(SPLITK ? 512 : 256, SPLITK ? 1 : 2) void gemm_bf16_
   char* smem = smem_all + grp * 65536;
   const int wm = wave >> 1, wn = wave & 1;
   const int ntn = (N + TBN - 1) / TBN, ntm = (M + TBM - 1) / TBM;
-  const int tile = tn_xcd_remap(blockIdx.x, ntm * ntn);
+  const int tile = xcd_remap(blockIdx.x, ntm * ntn);
   const int m0 = (tile / ntn) * TBM, n0 = (tile % ntn) * TBN;
 
   // ---- LDS-DMA sources.  Row-major operand ([rows of the tile][64 k], 128-byte rows): 8 rows x 128 B per piece, chunk XOR (r >> 1) & 7.

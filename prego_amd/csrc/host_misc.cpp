@@ -289,15 +289,35 @@ extern "C" int prego_debug_gemm_worker(const void* A, const void* B, const float
 }
 
 // debug / microbenchmark: C[M,N] (fp32) = A[M,K] . B[N,K]^T + bias with a chosen bf16 kernel variant
-// (0 = 128x128 two-stage, 1 = 256x128 three-stage counted-vmcnt, 9 = 256x256 two-stage, 12 = ping-pong), scripts/gemm_bench.py
-void launch_gemm_bf16_variant(int variant, const void* A, int lda, const void* B, int ldb, const float* bias, float* C, int ldc,
-                              int M, int N, int K, hipStream_t s);
+// (0 = 128x128 two-stage, 1 = 256x128 three-stage counted-vmcnt, 9 = 256x256 two-stage, 12 = ping-pong, 30 = the eight-wave split-K
+// workgroup), scripts/gemm_bench.py.  A variant forces its kernel; on a shape that kernel does not take nothing is launched and the
+// call still returns 0 (tests/test_gpu_gemm.py sees it by its canary)
 extern "C" int prego_debug_gemm_bf16(int variant, const void* A, const void* B, const float* bias, float* C, int M, int N, int K,
                                      prego_stream_t stream) {
   if (!A || !B || !C || M <= 0 || N % 128 || K % 64) return prego_fail_(PREGO_EINVAL, "debug gemm: bad arguments");
-  launch_gemm_bf16_variant(variant, A, K, B, K, bias, C, N, M, N, K, (hipStream_t)stream);
+  GemmNtKernel kind;
+  switch (variant) {
+    case 0: kind = GEMM_NT_128; break;
+    case 1: kind = GEMM_NT_256X128; break;
+    case 9: kind = GEMM_NT_256SQ; break;
+    case 12: kind = GEMM_NT_PINGPONG; break;
+    case 30: kind = GEMM_NT_SPLITK; break;
+    default: return prego_fail_(PREGO_EINVAL, "debug gemm: unknown variant %d", variant);
+  }
+  GemmEpi epi{};
+  epi.mode = EPI_STORE;
+  if (!(variant == 12 && !bias))     // odd: this hook's ping-pong variant has never taken a NULL bias
+    (void)launch_gemm_nt_kernel(kind, A, K, B, K, bias, C, N, M, N, K, epi, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return PREGO_OK;
+}
+
+// unit test (tests/test_gemm_dispatch_cpu.py): gemm_nt_choose's answer (GemmNtKernel as an int) - no device is touched.  entry: GemmNtEntry;
+// knobs: bit 0 PREGO_GEMM_NO_BIG, bit 1 _NO_SPLITK, bit 2 _NO_PINGPONG, as arguments here because the environment is read once per process
+extern "C" int prego_debug_gemm_nt_choice(int entry, int M, int N, int K, int lda, int ldb, int has_bias, int f16, int train_splitk, int mode,
+                                          int dh, int emb, int knobs) {
+  const GemmNtQuery q = {entry, M, N, K, lda, ldb, has_bias != 0, f16 != 0, train_splitk != 0, mode, dh, emb};
+  return (int)gemm_nt_choose(q, GemmNtKnobs{(knobs & 1) != 0, (knobs & 2) != 0, (knobs & 4) != 0});
 }
 
 // unit test (tests/test_gpu_gemm_tn.py): launch_gemm_bf16_tn as the training steps call it - the launcher's own choice of kernel runs

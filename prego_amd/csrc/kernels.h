@@ -176,8 +176,42 @@ struct GemmEpi {
   int split_a_lo, split_b_lo;      // SPLIT instantiation (fp16x2 operands): element column of the lo half in the A / B rows
   const float* acc_scale;          // SPLIT: device pointer to 1 / (power-of-two scale of the weights); NULL = 1
 };
-void launch_gemm_bf16_nt_epi(const void* A, int lda, const void* B, int ldb, const float* bias, float* C, int ldc, int M,
-                             int N, int K, GemmEpi epi, hipStream_t s);
+
+// ---- which kernel an NT product C[M,N] = epilogue(A[M,K] . B[N,K]^T + bias) runs on (gemm.hip): ONE chooser, ONE launcher ----
+enum GemmNtKernel {
+  GEMM_NT_NONE = -1,           // nothing to launch (M <= 0)
+  GEMM_NT_128 = 0,             // 128 x 128 two-stage (gemm.hip): every epilogue, both operand types, any shape
+  GEMM_NT_256X128 = 1,         // 256 x 128 three-stage counted-vmcnt (gemm.hip): bf16, fp32 C
+  GEMM_NT_256SQ = 2,           // 256 x 256 two-stage (gemm.hip): bf16, fp32 C, N % 256 == 0
+  GEMM_NT_PINGPONG = 3,        // 256 x 256 ping-pong (gemm_pp.hip): every epilogue, both operand types, gemm_pingpong_takes
+  GEMM_NT_SPLITK = 4           // eight-wave split-K workgroup (gemm_tn.hip): bf16, fp32 C, at most 256 tiles
+};
+// who asks: the three call paths differ in what they try (the differences are historical and kept; see gemm_nt_choose)
+enum GemmNtEntry {
+  GEMM_NT_PLAIN = 0,           // launch_gemm_bf16_nt: a projection with fp32 C and no epilogue
+  GEMM_NT_EPI = 1,             // launch_gemm_bf16_nt_epi: any epilogue
+  GEMM_NT_PROJ16 = 2           // the MiniROAD forward's projection with fp16 operands or a 16-bit C
+};
+struct GemmNtKnobs { bool no_big, no_splitk, no_pingpong; };   // PREGO_GEMM_NO_BIG / _NO_SPLITK / _NO_PINGPONG (debug library only)
+struct GemmNtQuery {
+  int entry, M, N, K, lda, ldb;
+  bool has_bias, f16, train_splitk;
+  int mode, dh, emb;           // epilogue mode; EPI_QKV: head width and embedding width
+};
+// pure: no device, no global
+GemmNtKernel gemm_nt_choose(const GemmNtQuery& q, GemmNtKnobs knobs);
+bool gemm_pingpong_takes(int M, int N, int K, bool has_bias, int mode, int dh, int emb);    // gemm_pp.hip
+// runs `kind`; -1 = that kernel does not take the shape or the epilogue (nothing launched).  C: fp32 destination (EPI_STORE,
+// EPI_RESIDUAL, EPI_TOKENS); the 16-bit destinations are in epi
+int launch_gemm_nt_kernel(GemmNtKernel kind, const void* A, int lda, const void* B, int ldb, const float* bias, float* C, int ldc, int M,
+                          int N, int K, GemmEpi epi, hipStream_t s);
+// choose, then launch
+void launch_gemm_nt(int entry, const void* A, int lda, const void* B, int ldb, const float* bias, float* C, int ldc, int M, int N, int K,
+                    GemmEpi epi, bool train_splitk, hipStream_t s);
+inline void launch_gemm_bf16_nt_epi(const void* A, int lda, const void* B, int ldb, const float* bias, float* C, int ldc, int M,
+                                    int N, int K, GemmEpi epi, hipStream_t s) {
+  launch_gemm_nt(GEMM_NT_EPI, A, lda, B, ldb, bias, C, ldc, M, N, K, epi, false, s);
+}
 
 void launch_pack_rows(bool bf16, const float* const* rgb_ptrs, const float* const* flow_ptrs, const SlotPlan& plan,
                       int row0, int nrows, int d_rgb, int d_flow, void* X, hipStream_t s, int grid_limit = 0,
@@ -190,9 +224,7 @@ void launch_ln_relu(bool bf16, const void* Y, const float* gamma, const float* b
 void launch_f32_to_bf16(const float* src, void* dst, size_t n, hipStream_t s);
 void launch_pad_convert(bool bf16, const float* src, int rows_src, int cols_src, int ld_src, void* dst, int rows_dst,
                         int cols_dst, hipStream_t s, bool f16 = false);
-// 256x256x64 ping-pong (8-phase) kernel, csrc/gemm_pp.hip; -1 = shape not supported (N % 256, K % 64, K >= 128)
-int launch_gemm_bf16_pingpong_mode(int mode, const void* A, int lda, const void* B, int ldb, const float* bias, void* C, int ldc,
-                                   int M, int N, int K, bool out_bf16, hipStream_t s, bool f16 = false);
+// 256x256x64 ping-pong (8-phase) kernel, csrc/gemm_pp.hip; -1 = shape not supported (gemm_pingpong_takes)
 int launch_gemm_bf16_pingpong_epi(const void* A, int lda, const void* B, int ldb, const float* bias, void* C, int ldc, int M, int N,
                                   int K, GemmEpi epi, hipStream_t s);
 int launch_gemm_bf16_pingpong_worker(const void* A, int lda, const void* B, int ldb, const float* bias, void* C, int ldc, int M, int N,
@@ -208,12 +240,14 @@ void launch_ln_relu_x2(const float* Y, const float* gamma, const float* beta, in
 int launch_gru_recurrence_x2(int hid, int nct, GruArgs a, const float* inv_scale, hipStream_t s);
 size_t gru_x2_hx_bytes(int hid, int G);
 GruArm gru_x2_arm_desc(int hid, int G, void* hx, unsigned* sync);
-int launch_gemm_bf16_pingpong(const void* A, int lda, const void* B, int ldb, const float* bias, float* C, int ldc, int M, int N,
-                              int K, hipStream_t s);
-void launch_gemm_bf16_nt(const void* A, int lda, const void* B, int ldb, const float* bias, float* C, int ldc, int M,
-                         int N, int K, hipStream_t s, bool f16 = false,
-                         bool train_splitk = false /* bf16, at most 256 tiles of 128 x 128: the eight-wave split-K workgroup of gemm_tn.hip
-                                                      (another summation order over k than every other NT kernel: training forward only) */);
+inline void launch_gemm_bf16_nt(const void* A, int lda, const void* B, int ldb, const float* bias, float* C, int ldc, int M,
+                                int N, int K, hipStream_t s, bool f16 = false,
+                                bool train_splitk = false /* bf16, at most 256 tiles of 128 x 128: the eight-wave split-K workgroup of gemm_tn.hip
+                                                             (another summation order over k than every other NT kernel: training forward only) */) {
+  GemmEpi epi{};
+  epi.mode = EPI_STORE; epi.f16 = f16 ? 1 : 0;
+  launch_gemm_nt(GEMM_NT_PLAIN, A, lda, B, ldb, bias, C, ldc, M, N, K, epi, train_splitk, s);
+}
 void launch_gemm_f32_nt(const float* A, int lda, const float* B, int ldb, const float* bias, float* C, int ldc, int M,
                         int N, int K, hipStream_t s);
 int launch_gru_recurrence(bool bf16, int hid, int nct, GruArgs a, hipStream_t s);

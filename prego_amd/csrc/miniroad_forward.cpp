@@ -241,12 +241,11 @@ static int run_chunked_pass(prego_miniroad* h, const FwdCall& c, const SlotPlan&
       return;
     }
     if (!h->bf16) { launch_gemm_f32_nt((const float*)A, lda, (const float*)Wt, ldb, bias, (float*)Cout, ldc, M, N, K, s); return; }
-    if (!i16 && !h->f16) { launch_gemm_bf16_nt(A, lda, Wt, ldb, bias, (float*)Cout, ldc, M, N, K, s, false, (flags & PREGO_FWD_KEEP) != 0); return; }
-    if (M >= 4096 && launch_gemm_bf16_pingpong_mode(0, A, lda, Wt, ldb, bias, Cout, ldc, M, N, K, i16, s, h->f16) == 0) return;
     GemmEpi epi{};
     epi.f16 = h->f16 ? 1 : 0;
     if (i16) { epi.mode = EPI_STORE_BF16; epi.out_b = Cout; } else epi.mode = EPI_STORE;
-    launch_gemm_bf16_nt_epi(A, lda, Wt, ldb, bias, i16 ? nullptr : (float*)Cout, ldc, M, N, K, epi, s);
+    launch_gemm_nt(!i16 && !h->f16 ? GEMM_NT_PLAIN : GEMM_NT_PROJ16, A, lda, Wt, ldb, bias, i16 ? nullptr : (float*)Cout, ldc, M, N, K, epi,
+                   (flags & PREGO_FWD_KEEP) != 0, s);
   };
   const bool keep = (flags & PREGO_FWD_KEEP) != 0;
   if (keep) {

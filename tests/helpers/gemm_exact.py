@@ -81,7 +81,7 @@ _WGRAD = [
     (200, 300, 320, 300, 208, 304, True),     # ragged in both, padded leading dimensions, NaN in the pad columns
     (1, 8, 64, 1, 8, 0, False),               # smallest: 1 tile
     (129, 129, 128, 128, 136, 136, False),    # one element past a tile in both directions
-    (128, 384, 128, 128, 0, 0, False),        # 3 tiles   } tn_xcd_remap at counts that are not multiples of 8: the canary shows a
+    (128, 384, 128, 128, 0, 0, False),        # 3 tiles   } xcd_remap at counts that are not multiples of 8: the canary shows a
     (300, 300, 192, 192, 0, 0, False),        # 9 tiles   } tile visited twice or never
     (381, 640, 128, 128, 0, 0, False),        # 15 tiles  }
     (1913, 2170, 128, 100, 0, 0, False),      # 255 tiles }
@@ -115,6 +115,87 @@ TN_REAL = [TnCase(1, 1, 200, 300, 320, 300, 208, 304, colsum=True, bias=True), T
 NT_VARIANT_SHAPES = [(300, 256, 128), (4113, 512, 1024), (70001, 256, 192), (65536, 2048, 256)]      # prego_debug_gemm_bf16's shapes
 NT_DISPATCH = [(M, N, K) for M in (2047, 2048, 4095, 4096, 4097) for N in (256, 384) for K in (64, 128, 1088)]      # launch_gemm_bf16_nt's thresholds
 NT_TRAIN_SPLITK = [(2048, 1024, 1024), (2048, 1024, 960), (2048, 4096 + 128, 1024)]
+
+
+# ---- which kernel an NT product ran on BEFORE the chooser existed (tests/test_gemm_dispatch_cpu.py): a transcription, function by
+# function, of the launcher chain as it stood in the commit before gemm_nt_choose - gemm.hip (launch_gemm_bf16_nt, launch_gemm_bf16_nt_epi),
+# gemm_pp.hip (launch_gemm_bf16_pingpong_epi / _mode / launch_gemm_bf16_pingpong), gemm_tn.hip (launch_gemm_bf16_tn) and the `proj` lambda
+# of miniroad_forward.cpp.  It is the record of that chain: it is not to be brought into line with the chooser.
+K128, K256X128, K256SQ, KPINGPONG, KSPLITK, KNONE = 0, 1, 2, 3, 4, -1                      # GemmNtKernel (csrc/kernels.h)
+EPI_STORE, EPI_RESIDUAL, EPI_GELU_BF16, EPI_STORE_BF16, EPI_QKV, EPI_TOKENS = range(6)     # csrc/kernels.h
+ENTRY_PLAIN, ENTRY_EPI, ENTRY_PROJ16 = 0, 1, 2                                             # GemmNtEntry (csrc/kernels.h)
+KNOB_NO_BIG, KNOB_NO_SPLITK, KNOB_NO_PINGPONG = 1, 2, 4
+
+
+def _old_tn_launches_nt(M, N, K, lda, ldb):
+    """launch_gemm_bf16_tn(false, false, ..., k_valid = K, colsum_out = NULL) == 0"""
+    if K % 64 or K <= 0 or M <= 0 or N <= 0 or lda % 8 or ldb % 8:
+        return False
+    ldmax = max(lda, ldb)
+    if lda <= 0 or ldb <= 0 or K * ldmax * 2 > 0x7fffffff or M * lda * 2 > 0x7fffffff or (128 + 1) * ldmax * 2 + K * 2 > 0x7fffffff:
+        return False
+    ntm, ntn = (M + 127) // 128, (N + 127) // 128
+    return not (ntm * ntn > 256 or K < 2 * 64)                   # the !tb branch; k_valid == K here
+
+
+def _old_pingpong_epi_launches(N, K, has_bias, mode, dh, emb):
+    """launch_gemm_bf16_pingpong_epi(...) == 0"""
+    if N % 256 or K % 64 or K < 2 * 64 or (not has_bias and N > 8192):
+        return False
+    return not (mode == EPI_QKV and (dh % 8 or emb % 8))
+
+
+def _old_pingpong_mode_launches(N, K, has_bias, out16):
+    """launch_gemm_bf16_pingpong_mode(...) == 0 (and launch_gemm_bf16_pingpong with out16 = False)"""
+    if not has_bias:
+        return False
+    return _old_pingpong_epi_launches(N, K, True, EPI_STORE_BF16 if out16 else EPI_STORE, 0, 0)
+
+
+def _old_nt_epi(M, N, K, has_bias, mode, dh, emb, knobs):
+    """launch_gemm_bf16_nt_epi"""
+    if M <= 0:
+        return KNONE
+    if M >= 4096 and not knobs & KNOB_NO_PINGPONG:
+        if _old_pingpong_epi_launches(N, K, has_bias, mode, dh, emb):
+            return KPINGPONG
+    return K128                                                   # the f16 switch and the bf16 switch: the same kernel template
+
+
+def _old_nt(M, N, K, lda, ldb, has_bias, f16, train_splitk, knobs):
+    """launch_gemm_bf16_nt"""
+    if f16:
+        return _old_nt_epi(M, N, K, has_bias, EPI_STORE, 0, 0, knobs)
+    if (train_splitk and not knobs & KNOB_NO_SPLITK and ((M + 127) // 128) * ((N + 127) // 128) <= 256 and K >= 1024 and K % 64 == 0
+            and _old_tn_launches_nt(M, N, K, lda, ldb)):
+        return KSPLITK
+    if M >= 4096 and N % 256 == 0 and not knobs & KNOB_NO_BIG:
+        if knobs & KNOB_NO_PINGPONG or not _old_pingpong_mode_launches(N, K, has_bias, False):
+            return K256SQ                                         # launch_gemm_bf16_experimental(9, ...): N % 256 == 0 holds here
+        return KPINGPONG
+    if M >= 2048 and not knobs & KNOB_NO_BIG:
+        return K256X128
+    return _old_nt_epi(M, N, K, has_bias, EPI_STORE, 0, 0, knobs)
+
+
+def _old_proj(M, N, K, lda, ldb, has_bias, f16, out16, keep, knobs):
+    """the 16-bit-operand branches of miniroad_forward.cpp's proj (h->bf16 set, no x2)"""
+    if not out16 and not f16:
+        return _old_nt(M, N, K, lda, ldb, has_bias, False, keep, knobs)
+    if M >= 4096 and _old_pingpong_mode_launches(N, K, has_bias, out16):
+        return KPINGPONG
+    return _old_nt_epi(M, N, K, has_bias, EPI_STORE_BF16 if out16 else EPI_STORE, 0, 0, knobs)
+
+
+def old_nt_choice(entry, M, N, K, lda, ldb, has_bias, f16, train_splitk, mode, dh, emb, knobs):
+    """the kernel the old chain ran for what prego_debug_gemm_nt_choice is asked, by the entry's old function"""
+    if entry == ENTRY_PLAIN:
+        assert mode == EPI_STORE
+        return _old_nt(M, N, K, lda, ldb, has_bias, f16, train_splitk, knobs)
+    if entry == ENTRY_PROJ16:
+        assert mode in (EPI_STORE, EPI_STORE_BF16) and (f16 or mode == EPI_STORE_BF16)
+        return _old_proj(M, N, K, lda, ldb, has_bias, f16, mode == EPI_STORE_BF16, train_splitk, knobs)
+    return _old_nt_epi(M, N, K, has_bias, mode, dh, emb, knobs)
 
 
 @dataclass

@@ -27,7 +27,7 @@ NT_SMALL = sorted({s for s in gx.NT_VARIANT_SHAPES + gx.NT_DISPATCH + gx.NT_TRAI
 def test_case_lists_cover_what_they_claim():
     assert len(TN_SMALL) >= 25 and len(NT_SMALL) >= 15
     tiles = {c.tiles() for c in gx.TN_WGRAD}
-    assert {1, 3, 9, 15, 255, 256, 257, 272} <= tiles                       # tn_xcd_remap at counts that are not multiples of 8; the launcher's boundary
+    assert {1, 3, 9, 15, 255, 256, 257, 272} <= tiles                       # xcd_remap at counts that are not multiples of 8; the launcher's boundary
     for c in gx.TN_CASES + gx.TN_REAL:
         lda, ldb = c.ld()
         assert lda % 8 == 0 and ldb % 8 == 0 and c.K % 64 == 0 and 0 < c.k_valid <= c.K
