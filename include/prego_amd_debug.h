@@ -72,6 +72,23 @@ int prego_debug_gemm_bf16(int variant, const void* A, const void* B, const float
 int prego_debug_gemm_nt_choice(int entry, int M, int N, int K, int lda, int ldb, int has_bias, int f16, int train_splitk, int mode, int dh,
                                int emb, int knobs);
 
+/* Unit test only (tests/test_gru_choice_cpu.py): which recurrence kernel a launch would run, without touching a device (gru_choose,
+ * csrc/gru_recurrence.hip).  entry: 0 = launch_gru_recurrence, 1 = launch_gru_recurrence_x2, 2 = launch_gru_recurrence_pass.  operand:
+ * 0 bf16, 1 fp16, 2 fp32 (ignored by entry 1).  train: the launch keeps gate activations / raw state.  stamps: a stamp buffer is
+ * given.  mt_spec: the value of PREGO_GRU_MT_SPEC (-1 = unset; an argument here because the environment is read once per process).
+ * ready: entry 1: the scale pointer is given; entry 2: chunk counters and rendezvous words are given.  Returns -1 = refused, -2 = a
+ * choice the launch table has no kernel for (a bug: the chooser's range is the table), otherwise
+ * family (0 classic, 1 multi-tile, 2 fp16x2, 3 pass) | operand << 2 | UT << 4 | NCT << 6 | TRAIN << 9 | GI16 << 10 | SPEC << 11 |
+ * hid << 12; *grid and *lds (nullable) receive the launch's workgroups and dynamic LDS bytes. */
+int prego_debug_gru_choice(int entry, int operand, int hid, int nct, int G, int gi_bf16, int train, int no_mt, int stamps, int rows,
+                           int mt_spec, int Gd, int ready, int* grid, int* lds);
+/* Unit test only: the recurrence's exchange layout and sizes (csrc/gru_tile.h), the functions the kernels and the host both use.
+ * what 0: byte offset of (clip column a, contraction index b, tile c) in a group's plane laid out for `tiles` tiles of `wb`-byte
+ * elements; 1: the contraction index held at (fragment a, lane b, byte c); 2: the clip column of lane b; 3: bytes of one plane for
+ * hidden size a.  what 10 .. 14: gru_hx_bytes(bf16 = wb == 2, hid = a, G = b), gru_x2_hx_bytes(a, b), gru_group_size(wb == 2, a),
+ * gru_hidden_supported(wb == 2, a), slots a handle of b groups plans for (c != 0: an fp16x2 handle). */
+long long prego_debug_gru_hx_offset(int what, int wb, int tiles, int a, int b, int c);
+
 /* Unit test only (tests/test_gpu_gemm_tn.py): the training GEMMs on k-major operands exactly as the training steps launch them
  * (launch_gemm_bf16_tn chooses between the split-K and the plain kernel itself).  C[M,N] = op(A) . op(B) (+ bias[n]); ta: A is stored
  * [K][M] with lda elements per k row, else [M][K]; tb: B is stored [K][N], else [N][K]; 16-bit operands are bf16.  k_valid <= K: the

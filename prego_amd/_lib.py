@@ -68,7 +68,7 @@ DEBUG_SYMBOLS = ["prego_miniroad_debug_stamps", "prego_debug_gemm_bf16", "prego_
                  "prego_debug_recurrence_only", "prego_debug_gemm_worker", "prego_debug_head_only",
                  "prego_debug_split_fault", "prego_debug_split_state", "prego_debug_set_abort", "prego_debug_alloc_count", "prego_debug_hog",
                  "prego_debug_ant_full_span", "prego_debug_gemm_tn", "prego_debug_gemm_nt", "prego_debug_gemm_nt_choice", "prego_debug_vit_ring_tokens",
-                 "prego_debug_vit_burst_tokens", "prego_debug_vit_burst_commit", "prego_debug_pool_image_fault"]
+                 "prego_debug_gru_choice", "prego_debug_gru_hx_offset", "prego_debug_vit_burst_tokens", "prego_debug_vit_burst_commit", "prego_debug_pool_image_fault"]
 
 
 class PregoError(RuntimeError):
@@ -268,6 +268,9 @@ def _open(path: str, debug: bool) -> C.CDLL:
         lib.prego_debug_gemm_tn.argtypes = [i32, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
         lib.prego_debug_gemm_nt.argtypes = [i32, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp]
         lib.prego_debug_gemm_nt_choice.argtypes = [i32] * 13
+        lib.prego_debug_gru_choice.argtypes = [i32] * 13 + [C.POINTER(i32), C.POINTER(i32)]
+        lib.prego_debug_gru_hx_offset.argtypes = [i32] * 6
+        lib.prego_debug_gru_hx_offset.restype = C.c_longlong
         lib.prego_debug_split_fault.argtypes = [vp, i32]
         lib.prego_debug_split_state.argtypes = [vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(i64), C.POINTER(i32)]
         lib.prego_debug_set_abort.argtypes = [vp, C.c_uint32, vp]

@@ -27,6 +27,7 @@
 // Training batches are small (16 windows x 128 frames in the reference, one clip tile of one group), so this kernel is
 // written for low launch count first: the 128-step loop drops from 3.5 ms to < 0.5 ms (train step 6.2 -> 2.7 ms).
 #include "common.h"
+#include "gru_tile.h"
 #include "kernels.h"
 
 #define BPTT_SPIN_LIMIT (1u << 22)
@@ -39,12 +40,11 @@ __global__ __launch_bounds__(256, 1) void gru_bptt_kernel(BpttArgs a) {
   constexpr int UNITS = 16 * UT;              // output units (columns of dh) owned by this workgroup
   constexpr int K3 = 3 * HID;                 // contraction length
   constexpr int KQ = K3 / 4;                  // K range per wave
-  constexpr int KF = BF ? 32 : 16;            // k per fragment
-  constexpr int EPL = BF ? 8 : 4;             // elements per lane and fragment
+  constexpr int KF = gru_kf((int)sizeof(WT)); // k per fragment (gru_tile.h: the forward's exchange layout over k = gate * H + unit)
+  constexpr int EPL = gru_epl((int)sizeof(WT)); // elements per lane and fragment
   constexpr int NKS = KQ / KF;                // fragments per wave and clip tile
-  constexpr int NFR = K3 / KF;                // fragments of one clip tile's dGH
   constexpr int OWN_R = UT == 2 ? 2 : 1;
-  constexpr int GROUP_BYTES = NFR * BPTT_MAX_TILES * 1024;
+  constexpr int GROUP_BYTES = gru_plane_bytes((int)sizeof(WT), K3, BPTT_MAX_TILES);
   constexpr int P = HID / UNITS;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256, 1) void gru_bptt_kernel(BpttArgs a) {
   // byte offset of my element (clip l15 of tile ct, k = gate * H + my unit) inside a buffer
   auto elem_off = [&](int ct, int gate) -> int {
     const int k = gate * HID + ucol;
-    return ((k / KF) * BPTT_MAX_TILES + ct) * 1024 + ((((k % KF) / EPL) << 4) + l15) * 16 + (k % EPL) * (int)sizeof(WT);
+    return GRU_HX_OFFSET(KF, EPL, (int)sizeof(WT), BPTT_MAX_TILES, l15, k, ct);
   };
 
   // plan tables through the scalar path (constant address space), one step ahead: vector loads here put a vmcnt(0) and an
@@ -202,11 +202,11 @@ __global__ __launch_bounds__(256, 1) void gru_bptt_kernel(BpttArgs a) {
           if (local) {
 #pragma unroll
             for (int ks = 0; ks < NKS; ++ks)
-              hb[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs, rbuf * buf_stride + ((q * NKS + ks) * BPTT_MAX_TILES + ct) * 1024 + lane_off, 0, AUX_NT);
+              hb[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs, rbuf * buf_stride + GRU_HX_FRAG(BPTT_MAX_TILES, q * NKS + ks, ct) + lane_off, 0, AUX_NT);
           } else {
 #pragma unroll
             for (int ks = 0; ks < NKS; ++ks)
-              hb[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs, rbuf * buf_stride + ((q * NKS + ks) * BPTT_MAX_TILES + ct) * 1024 + lane_off, 0, AUX_SC1);
+              hb[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs, rbuf * buf_stride + GRU_HX_FRAG(BPTT_MAX_TILES, q * NKS + ks, ct) + lane_off, 0, AUX_SC1);
           }
           unsigned mx = 0u;
 #pragma unroll
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(256, 1) void gru_bptt_kernel(BpttArgs a) {
   }
 }
 
-size_t gru_bptt_hx_bytes(bool bf16, int hid, int G) { return (size_t)BPTT_BUFS * G * (3 * hid / (bf16 ? 32 : 16)) * BPTT_MAX_TILES * 1024; }
+size_t gru_bptt_hx_bytes(bool bf16, int hid, int G) { return (size_t)BPTT_BUFS * G * gru_plane_bytes(bf16 ? 2 : 4, 3 * hid, BPTT_MAX_TILES); }
 
 // returns 0 on success, -1 for an unsupported shape (the caller falls back to the step-by-step loop).  Hidden sizes 1024 and 512, bf16
 // (32 units per workgroup) or fp32 (16) operands.  hidden_dim 2048 trains through the step-by-step loop: its workgroups would own 16

@@ -37,6 +37,7 @@
 //  * gi for step t+1 is prefetched during step t; clip tiles whose clips have all ended are skipped.
 //  * every spin is bounded; a timeout raises an abort word that ends the launch (no hung GPU).
 #include "common.h"
+#include "gru_tile.h"
 #include "kernels.h"
 #include "pass_handshake.h"
 #include <cstdlib>
@@ -45,10 +46,7 @@
 #ifndef GRU_NSEG
 #define GRU_NSEG 2                           // segments of the gather validated and multiplied one after the other (A/B at the end of round 2, per launch: 1: 1.434, 2: 1.413, 4: 1.434, 8: 1.588 ms)
 #endif
-#define GRU_MAX_TILES 8                      // clip tiles per group the exchange buffer is laid out for (128 slots)
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 
 // operand tag of the weight type: the 16-bit types name themselves, fp32 weights never reach the 16-bit conversions
 template <typename WT> struct gru_ot { typedef bf16_t type; };
@@ -65,22 +63,18 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_kernel(GruArgs a) {
   static_assert(!PASS || (GI16 && !TRAIN && NCT == 1 && sizeof(WT) == 2), "pass mode: 16-bit operands and GI, one clip tile, inference");
   constexpr bool BF = (sizeof(WT) == 2);          // 16-bit operands: bf16_t or f16_t (same layout, same tag bit 14: |h| < 2 in both)
   typedef typename gru_ot<WT>::type OT;
-  constexpr int UNITS = 16 * UT;              // hidden units owned by this workgroup
-  constexpr int KQ = HID / 4;                 // K range per wave
+  typedef GruGeom<(int)sizeof(WT), HID, UT, GRU_MAX_TILES> Geo;      // geometry and exchange layout: gru_tile.h
+  constexpr int UNITS = Geo::UNITS;           // hidden units owned by this workgroup
+  constexpr int KQ = Geo::KQ;                 // K range per wave
   constexpr int OWN_R = UT == 2 ? 2 : 1;      // accumulator registers a lane owns per clip tile (4 waves share UT tiles)
-  constexpr int NKS = BF ? KQ / 32 : KQ / 16; // fragments per clip tile (bf16: 32 k each; f32: 16 k each)
-  constexpr unsigned TAGM = BF ? 0x40004000u : 0x40000000u;
-  // Exchange layout = MFMA B-fragment order: [k-step of 32 (bf16) / 16 (f32)][clip tile 0..7][lane 0..63][16 B], so a
-  // consumer's fragment load is ONE contiguous 1 KiB (rows at a 2 KiB stride all fell on the same L2 channel and
-  // ran at 10 B/clk/CU).  Element (clip slot c, hidden unit k): fragment (k / KF, c / 16), lane ((k % KF) / EPL) * 16
-  // + c % 16, byte (k % EPL) * sizeof(WT), with KF = k per fragment, EPL = elements per lane.
-  constexpr int KF = BF ? 32 : 16;
-  constexpr int EPL = BF ? 8 : 4;
-  constexpr int GROUP_BYTES = (HID / KF) * GRU_MAX_TILES * 1024;     // one buffer of one group
+  constexpr int NKS = Geo::NKS;               // fragments per clip tile (bf16: 32 k each; f32: 16 k each)
+  constexpr unsigned TAGM = Geo::TAGM;
+  constexpr int KF = Geo::KF, EPL = Geo::EPL;  // k per fragment, elements per lane
+  constexpr int GROUP_BYTES = Geo::GROUP_BYTES;     // one buffer of one group
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   f32x4* red = (f32x4*)smem;                  // [2 parities][4 waves][3 gates][UT][64 lanes]
-  constexpr int RED_STRIDE = 4 * 3 * UT * 64;
+  constexpr int RED_STRIDE = Geo::RED_STRIDE;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int q = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -90,7 +84,7 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_kernel(GruArgs a) {
   __builtin_amdgcn_s_setprio(GRU_PRIO);
 #endif
   // ---- placement rendezvous: group := XCD when every XCD holds exactly P workgroups ------------
-  constexpr int P = HID / UNITS;
+  constexpr int P = Geo::P;
   __shared__ int s_place[4];
   if (tid == 0) {
     int gg = blockIdx.x % a.G, ww = blockIdx.x / a.G, loc = 0;
@@ -258,24 +252,9 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_kernel(GruArgs a) {
 #pragma unroll
     for (int e = 0; e < OWN_R; ++e) hreg[ct][e] = (sidx[ct] < a.n_clips) ? a.h_state[(size_t)sidx[ct] * HID + ucol + e] : 0.f;
   }
-  // continuous batching: a slot runs several clips back to back; h restarts from 0 where the next clip begins
-  int nstart[NCT], segp[NCT], sege[NCT];
+  int nstart[NCT], segp[NCT], sege[NCT];      // continuous batching: the segment cursor of gru_tile.h
 #pragma unroll
-  for (int ct = 0; ct < NCT; ++ct) {
-    nstart[ct] = 0x7fffffff; segp[ct] = 0; sege[ct] = 0;
-    if (a.seg_start != nullptr && sidx[ct] < a.n_clips) {
-      int k = a.seg_off[sidx[ct]];
-      sege[ct] = a.seg_off[sidx[ct] + 1];
-      while (k < sege[ct] && a.seg_start[k] < a.t0) ++k;
-      if (k < sege[ct] && a.seg_start[k] == a.t0 && a.t0 > 0) {        // a clip starts on this launch's first step
-#pragma unroll
-        for (int e = 0; e < OWN_R; ++e) hreg[ct][e] = 0.f;
-      }
-      while (k < sege[ct] && a.seg_start[k] <= a.t0) ++k;
-      segp[ct] = k;
-      nstart[ct] = k < sege[ct] ? a.seg_start[k] : 0x7fffffff;
-    }
-  }
+  for (int ct = 0; ct < NCT; ++ct) { GRU_SEG_INIT(ct, _Pragma("unroll") for (int e = 0; e < OWN_R; ++e) hreg[ct][e] = 0.f;) }
 
   // exchange buffers: [2][G][GROUP_BYTES]; one descriptor per group, buffer index in the offset
   const int buf_stride = a.G * GROUP_BYTES;
@@ -283,18 +262,13 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_kernel(GruArgs a) {
   __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)hx_base, 0, buf_stride + GROUP_BYTES, 0x00020000);
 
   // tagged MFMA-operand copy of one state element
-  auto tag_bf = [](float x, unsigned tag) -> unsigned {
-    x = fminf(fmaxf(x, -1.9921875f), 1.9921875f);
-    return ((unsigned)f2bf(x) & 0xBFFFu) | (tag << 14);
-  };
   auto tag_f32 = [](float x, unsigned tag) -> unsigned {
     x = fminf(fmaxf(x, -1.9999998f), 1.9999998f);
     return (__float_as_uint(x) & 0xBFFFFFFFu) | (tag << 30);
   };
   // publish this lane's slice of tile ct; no waiting
   auto publish = [&](int ct, int buf, unsigned tag, bool zero) {
-    const int off = buf * buf_stride + ((ucol / KF) * GRU_MAX_TILES + ct) * 1024 + ((((ucol % KF) / EPL) << 4) + l15) * 16 +
-                    (ucol % EPL) * (int)sizeof(WT);
+    const int off = buf * buf_stride + GRU_HX_OFFSET(KF, EPL, (int)sizeof(WT), GRU_MAX_TILES, l15, ucol, ct);
     if constexpr (BF && OWN_R == 2) {
       f32x2 hv = {zero ? 0.f : hreg[ct][0], zero ? 0.f : hreg[ct][1]};
       hv[0] = __builtin_amdgcn_fmed3f(hv[0], -1.9921875f, 1.9921875f);
@@ -358,17 +332,7 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_kernel(GruArgs a) {
   unsigned long long st_acc[6] = {0, 0, 0, 0, 0, 0};
   unsigned long long st_t = 0;
 #define STAMP(i) do { if (stamp) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); st_acc[i] += n_ - st_t; st_t = n_; } } while (0)
-  // the plan tables are read-only for the whole launch: constant address space = scalar (s_load) path, so the
-  // look-ahead never touches the vector-memory queue (a vector load here drags a vmcnt wait through every step)
-  typedef const __attribute__((address_space(4))) int* cint_p;
-  cint_p nact_c = (cint_p)a.nact;
-  cint_p rowoff_c = (cint_p)a.rowoff;
-  const int nsteps = a.t1 - a.t0;
-  // plan scalars one step ahead of their use (s_load latency off the critical path)
-  // (rowoff is carried RAW and row_base subtracted where it is used: a subtraction next to the look-ahead s_load makes
-  // hipcc wait for that load at the top of every step)
-  int na_c = nact_c[a.t0], rb_c = rowoff_c[a.t0];                      // step tl
-  int na_n = nsteps > 1 ? nact_c[a.t0 + 1] : 0, rb_n = nsteps > 1 ? rowoff_c[a.t0 + 1] : 0;   // step tl+1
+  GRU_PLAN_INIT                               // nact_c, rowoff_c, nsteps; na_c / rb_c of step tl, na_n / rb_n of step tl + 1 (gru_tile.h)
   // prologue: h_{t0-1} -> buffer 1 with the tag of step "-1" (= 1); gi of the first step
   float giA[NCT][3][OWN_R], giB[NCT][3][OWN_R];                         // ping-pong: no register copies
   u32x3 gvA[NCT], gvB[NCT];                                             // pass mode: the same as one register triple per tile
@@ -388,13 +352,11 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_kernel(GruArgs a) {
     const int na = na_c;
     const int rbase = rb_c - a.row_base;
     const bool more = tl + 1 < nsteps;
-    const int t2 = (tl + 2 < nsteps) ? t + 2 : t;                       // look-ahead index (clamped)
-    const int na_2 = nact_c[t2], rb_2 = rowoff_c[t2];
+    GRU_PLAN_PEEK                                                       // na_2, rb_2 of step tl + 2 (index clamped)
     const int re_n = PASS ? rowoff_c[more ? t + 2 : t + 1] : 0;         // pass mode: end of step t + 1's rows
     const int rbuf = (tl + 1) & 1;
     const unsigned etag = (unsigned)(((tl - 1) >> 1) & 1);              // tag of the step that produced h_{t-1}
     const unsigned eword = etag ? TAGM : 0u;
-    const unsigned untag = etag ? ~TAGM : 0xFFFFFFFFu;
     if (stamp) st_t = __builtin_amdgcn_s_memtime();
 
 #pragma unroll
@@ -422,11 +384,11 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_kernel(GruArgs a) {
         if (local) {
 #pragma unroll
           for (int ks = 0; ks < NKS; ++ks)
-            hb[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs, rbuf * buf_stride + ((q * NKS + ks) * GRU_MAX_TILES + ct) * 1024 + lane_off, 0, AUX_NT);
+            hb[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs, rbuf * buf_stride + GRU_HX_FRAG(GRU_MAX_TILES, q * NKS + ks, ct) + lane_off, 0, AUX_NT);
         } else {
 #pragma unroll
           for (int ks = 0; ks < NKS; ++ks)
-            hb[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs, rbuf * buf_stride + ((q * NKS + ks) * GRU_MAX_TILES + ct) * 1024 + lane_off, 0, AUX_SC1);
+            hb[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs, rbuf * buf_stride + GRU_HX_FRAG(GRU_MAX_TILES, q * NKS + ks, ct) + lane_off, 0, AUX_SC1);
         }
 #pragma unroll
         for (int sg = 0; sg < NSEG; ++sg) {
@@ -454,11 +416,11 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_kernel(GruArgs a) {
               if (local && spins < 6u) {
 #pragma unroll
                 for (int ks = sg * SEGK; ks < NKS; ++ks)
-                  hb[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs, rbuf * buf_stride + ((q * NKS + ks) * GRU_MAX_TILES + ct) * 1024 + lane_off, 0, AUX_NT);
+                  hb[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs, rbuf * buf_stride + GRU_HX_FRAG(GRU_MAX_TILES, q * NKS + ks, ct) + lane_off, 0, AUX_NT);
               } else {
 #pragma unroll
                 for (int ks = sg * SEGK; ks < NKS; ++ks)
-                  hb[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs, rbuf * buf_stride + ((q * NKS + ks) * GRU_MAX_TILES + ct) * 1024 + lane_off, 0, AUX_SC1);
+                  hb[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs, rbuf * buf_stride + GRU_HX_FRAG(GRU_MAX_TILES, q * NKS + ks, ct) + lane_off, 0, AUX_SC1);
               }
               if (!seg_stale()) break;
             }
@@ -531,22 +493,7 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_kernel(GruArgs a) {
         // ---- (3) gates + state update for the registers this lane owns
         {
           if constexpr (OWN_R == 2) {
-            // this lane owns registers {own_r0, own_r0+1} of its tile: 8-byte LDS reads at immediate offsets, and the two
-            // elements go through the gate math as one f32x2 (v_pk_add/mul/fma_f32): the step runs one wave per SIMD,
-            // so every VALU instruction is ~4 cycles of its critical path
-            const f32x2* rp = (const f32x2*)((const float*)&redw[own_ut * 64 + lane] + own_r0);
-            f32x2 part[3][4];
-#pragma unroll
-            for (int gate = 0; gate < 3; ++gate)
-#pragma unroll
-              for (int qq = 0; qq < 4; ++qq) part[gate][qq] = rp[((qq * 3 + gate) * UT) * 64 * 2];
-            // all twelve reads in flight before the first add (left alone, hipcc recycles registers and serialises the
-            // LDS round trips: read 2, wait, add, read 2, wait, ...)
-            asm volatile("" : "+v"(part[0][0]), "+v"(part[0][1]), "+v"(part[0][2]), "+v"(part[0][3]), "+v"(part[1][0]), "+v"(part[1][1]),
-                              "+v"(part[1][2]), "+v"(part[1][3]), "+v"(part[2][0]), "+v"(part[2][1]), "+v"(part[2][2]), "+v"(part[2][3]));
-            f32x2 gh[3];
-#pragma unroll
-            for (int gate = 0; gate < 3; ++gate) gh[gate] = (part[gate][0] + part[gate][1]) + (part[gate][2] + part[gate][3]);
+            GRU_RED_READ2                      // f32x2 gh[3]: this lane's register pair, summed over the four K-quarters (gru_tile.h)
             if (sidx[ct] < na) {
               const f32x2 one = {1.f, 1.f};
               f32x2 gr, gz, gn;
@@ -559,16 +506,7 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_kernel(GruArgs a) {
               } else {
                 gr = (f32x2){gir[ct][0][0], gir[ct][0][1]}; gz = (f32x2){gir[ct][1][0], gir[ct][1][1]}; gn = (f32x2){gir[ct][2][0], gir[ct][2][1]};
               }
-              const f32x2 hp = {hreg[ct][0], hreg[ct][1]}, bh = {bhn[0], bhn[1]};
-              const f32x2 xr = gr + gh[0], xz = gz + gh[1];
-              f32x2 r, z, n;
-              r[0] = sigmoidf_(xr[0]); r[1] = sigmoidf_(xr[1]);
-              z[0] = sigmoidf_(xz[0]); z[1] = sigmoidf_(xz[1]);
-              const f32x2 ghn = gh[2] + bh;
-              const f32x2 xn = gn + r * ghn;
-              n[0] = tanhf_(xn[0]); n[1] = tanhf_(xn[1]);
-              const f32x2 hn = (one - z) * n + z * hp;
-              hreg[ct][0] = hn[0]; hreg[ct][1] = hn[1];
+              GRU_GATES2(ct)                   // r, z, n, ghn and the new hreg[ct] from gr, gz, gn, gh (gru_tile.h)
               if constexpr (TRAIN) {
                 if (a.keep_r) {                                      // training: gate activations for BPTT
                   const size_t ko = (size_t)(rbase + sidx[ct]) * HID + ucol;
@@ -637,14 +575,12 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_kernel(GruArgs a) {
         if (restart) {
 #pragma unroll
           for (int e = 0; e < OWN_R; ++e) hreg[ct][e] = 0.f;
-          ++segp[ct];
-          nstart[ct] = segp[ct] < sege[ct] ? a.seg_start[segp[ct]] : 0x7fffffff;
-          asm volatile("" : "+v"(nstart[ct]));      // take the (rare) load's wait here, not as a vmcnt(0) in every step
+          GRU_SEG_ADVANCE(ct)
         }
         STAMP(4);
       }
     }
-    na_c = na_n; rb_c = rb_n; na_n = na_2; rb_n = rb_2;
+    GRU_PLAN_SHIFT
     return true;
   };
   const unsigned long long rt0 = stamp ? __builtin_amdgcn_s_memrealtime() : 0ull;       // 100 MHz: with the cycle sums below = this XCD's shader clock
@@ -699,17 +635,17 @@ template <typename WT, int HID, int NCT, bool SPEC>
 __global__ __launch_bounds__(256, 1) void gru_recurrence_mt_kernel(GruArgs a) {
   static_assert(sizeof(WT) == 2 && NCT >= 2, "multi-tile kernel: 16-bit operands, two or more clip tiles");
   typedef typename gru_ot<WT>::type OT;
-  constexpr int UT = 2, UNITS = 16 * UT, KQ = HID / 4, NKS = KQ / 32, KF = 32, EPL = 8;
-  constexpr unsigned TAGM = 0x40004000u;
-  constexpr int GROUP_BYTES = (HID / KF) * GRU_MAX_TILES * 1024;
+  constexpr int UT = 2;
+  typedef GruGeom<2, HID, UT, GRU_MAX_TILES> Geo;
+  constexpr int UNITS = Geo::UNITS, KQ = Geo::KQ, NKS = Geo::NKS, KF = Geo::KF, EPL = Geo::EPL, GROUP_BYTES = Geo::GROUP_BYTES;
+  constexpr unsigned TAGM = Geo::TAGM;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   f32x4* red = (f32x4*)smem;                  // [2 parities][4 waves][3 gates][UT][64 lanes]
-  constexpr int RED_STRIDE = 4 * 3 * UT * 64;
-  constexpr int RED_BYTES = 2 * RED_STRIDE * 16;
+  constexpr int RED_STRIDE = Geo::RED_STRIDE, RED_BYTES = Geo::RED_BYTES;
   char* gsm = smem + RED_BYTES;               // gather images [2 buffers][4 waves][NKS fragments][64 lanes][16 B]
   const unsigned gsm_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)gsm;
-  constexpr int GATHER_BYTES = 2 * 4 * NKS * 1024;
+  constexpr int GATHER_BYTES = gru_mt_gather_bytes(NKS);
   // gi rows (16-bit pairs of my two units) also arrive by LDS-DMA: [2 step parities][NCT][3 gates][256 threads] dwords.  With
   // no compiler-visible vector load left in the loop, hipcc inserts no vmcnt wait of its own (its conservative vmcnt(0) in
   // front of the loop-carried gi registers would wait for the gather prefetch too: measured in the first build of this kernel)
@@ -780,18 +716,7 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_mt_kernel(GruArgs a) {
   }
   int nstart[NCT], segp[NCT], sege[NCT];
 #pragma unroll
-  for (int ct = 0; ct < NCT; ++ct) {
-    nstart[ct] = 0x7fffffff; segp[ct] = 0; sege[ct] = 0;
-    if (a.seg_start != nullptr && sidx[ct] < a.n_clips) {
-      int k = a.seg_off[sidx[ct]];
-      sege[ct] = a.seg_off[sidx[ct] + 1];
-      while (k < sege[ct] && a.seg_start[k] < a.t0) ++k;
-      if (k < sege[ct] && a.seg_start[k] == a.t0 && a.t0 > 0) { hreg[ct][0] = 0.f; hreg[ct][1] = 0.f; }
-      while (k < sege[ct] && a.seg_start[k] <= a.t0) ++k;
-      segp[ct] = k;
-      nstart[ct] = k < sege[ct] ? a.seg_start[k] : 0x7fffffff;
-    }
-  }
+  for (int ct = 0; ct < NCT; ++ct) { GRU_SEG_INIT(ct, hreg[ct][0] = 0.f; hreg[ct][1] = 0.f;) }
 
   // ---- exchange buffers; relu(h) output through a buffer resource (dead lanes: offset past num_records, instruction still issued)
   const int buf_stride = a.G * GROUP_BYTES;
@@ -800,7 +725,7 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_mt_kernel(GruArgs a) {
   __amdgpu_buffer_rsrc_t rs_hr = __builtin_amdgcn_make_buffer_rsrc(a.h_relu_out, 0, 0x7FFFFFF0, 0x00020000);
   constexpr int OOR = 0x7FFFFFF8;                 // >= num_records of both resources
   auto publish = [&](int ct, int buf, unsigned tag, bool zero, bool cond) {
-    const int off = buf * buf_stride + ((ucol / KF) * GRU_MAX_TILES + ct) * 1024 + ((((ucol % KF) / EPL) << 4) + l15) * 16 + (ucol % EPL) * 2;
+    const int off = buf * buf_stride + GRU_HX_OFFSET(KF, EPL, 2, GRU_MAX_TILES, l15, ucol, ct);
     f32x2 hv = {zero ? 0.f : hreg[ct][0], zero ? 0.f : hreg[ct][1]};
     hv[0] = __builtin_amdgcn_fmed3f(hv[0], -1.9921875f, 1.9921875f);
     hv[1] = __builtin_amdgcn_fmed3f(hv[1], -1.9921875f, 1.9921875f);
@@ -839,12 +764,7 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_mt_kernel(GruArgs a) {
     for (int ks = 0; ks < NKS; ++ks) hbr[ks] = p[ks * 64];
   };
 
-  typedef const __attribute__((address_space(4))) int* cint_p;
-  cint_p nact_c = (cint_p)a.nact;
-  cint_p rowoff_c = (cint_p)a.rowoff;
-  const int nsteps = a.t1 - a.t0;
-  int na_c = nact_c[a.t0], rb_c = rowoff_c[a.t0];
-  int na_n = nsteps > 1 ? nact_c[a.t0 + 1] : 0, rb_n = nsteps > 1 ? rowoff_c[a.t0 + 1] : 0;
+  GRU_PLAN_INIT
 #pragma unroll
   for (int ct = 0; ct < NCT; ++ct)
     if (tfirst[ct] < na_c) {
@@ -869,12 +789,10 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_mt_kernel(GruArgs a) {
     const int na = na_c;
     const int rbase = rb_c - a.row_base;
     const bool more = tl + 1 < nsteps;
-    const int t2 = (tl + 2 < nsteps) ? t + 2 : t;
-    const int na_2 = nact_c[t2], rb_2 = rowoff_c[t2];
+    GRU_PLAN_PEEK
     const int rbuf = (tl + 1) & 1;
     const unsigned etag = (unsigned)(((tl - 1) >> 1) & 1);
     const unsigned eword = etag ? TAGM : 0u;
-    const unsigned untag = etag ? ~TAGM : 0xFFFFFFFFu;
     // what the NEXT step's tile-0 gather expects (issued at the end of this step when two or more tiles are alive)
     const int rbuf_n = tl & 1;
 #pragma unroll
@@ -1001,17 +919,7 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_mt_kernel(GruArgs a) {
         MSTAMP(4);
         // ---- (5) gates + state update
         {
-          const f32x2* rp = (const f32x2*)((const float*)&redw[own_ut * 64 + lane] + own_r0);
-          f32x2 part[3][4];
-#pragma unroll
-          for (int gate = 0; gate < 3; ++gate)
-#pragma unroll
-            for (int qq = 0; qq < 4; ++qq) part[gate][qq] = rp[((qq * 3 + gate) * UT) * 64 * 2];
-          asm volatile("" : "+v"(part[0][0]), "+v"(part[0][1]), "+v"(part[0][2]), "+v"(part[0][3]), "+v"(part[1][0]), "+v"(part[1][1]),
-                            "+v"(part[1][2]), "+v"(part[1][3]), "+v"(part[2][0]), "+v"(part[2][1]), "+v"(part[2][2]), "+v"(part[2][3]));
-          f32x2 gh[3];
-#pragma unroll
-          for (int gate = 0; gate < 3; ++gate) gh[gate] = (part[gate][0] + part[gate][1]) + (part[gate][2] + part[gate][3]);
+          GRU_RED_READ2
           if (col_live) {
             const f32x2 one = {1.f, 1.f};
             f32x2 gr, gz, gn;
@@ -1020,16 +928,7 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_mt_kernel(GruArgs a) {
             gr = (f32x2){op16<OT>::lo(ur), op16<OT>::hi(ur)};
             gz = (f32x2){op16<OT>::lo(uz), op16<OT>::hi(uz)};
             gn = (f32x2){op16<OT>::lo(un), op16<OT>::hi(un)};
-            const f32x2 hp = {hreg[ct][0], hreg[ct][1]}, bh = {bhn[0], bhn[1]};
-            const f32x2 xr = gr + gh[0], xz = gz + gh[1];
-            f32x2 r, z, n;
-            r[0] = sigmoidf_(xr[0]); r[1] = sigmoidf_(xr[1]);
-            z[0] = sigmoidf_(xz[0]); z[1] = sigmoidf_(xz[1]);
-            const f32x2 ghn = gh[2] + bh;
-            const f32x2 xn = gn + r * ghn;
-            n[0] = tanhf_(xn[0]); n[1] = tanhf_(xn[1]);
-            const f32x2 hn = (one - z) * n + z * hp;
-            hreg[ct][0] = hn[0]; hreg[ct][1] = hn[1];
+            GRU_GATES2(ct)
           }
         }
         MSTAMP(5);
@@ -1043,14 +942,12 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_mt_kernel(GruArgs a) {
         }
         if (restart) {
           hreg[ct][0] = 0.f; hreg[ct][1] = 0.f;
-          ++segp[ct];
-          nstart[ct] = segp[ct] < sege[ct] ? a.seg_start[segp[ct]] : 0x7fffffff;
-          asm volatile("" : "+v"(nstart[ct]));
+          GRU_SEG_ADVANCE(ct)
         }
         MSTAMP(6);
       }
     }
-    na_c = na_n; rb_c = rb_n; na_n = na_2; rb_n = rb_2;
+    GRU_PLAN_SHIFT
     return true;
   };
   for (int tl = 0; tl < nsteps; ++tl) {
@@ -1075,16 +972,22 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_mt_kernel(GruArgs a) {
 // to this file's kernels.  7.62 us per four-tile step against the pipelined kernel's 7.25 on the same device (synth512: 27.7 vs 28.3 M
 // frames/s): what a tile costs is moving its 32 KB through the CU's vector-memory path in the wave's own time (~850 cycles) and the serial
 // reduce / gate / store phases, not the L2 round trip the batching amortises - and 411-469 registers put the fragments in AGPRs.)
-// Returns 0 on success, -1 for unsupported (hid, nct).
-// a.hx must hold [2][G][GROUP_BYTES] bytes (gru_hx_bytes); both buffers are re-armed here (stream ordered):
-// buffer 0 := tag 1 everywhere (first expected tag there is 0), buffer 1 := tag 0 (first expected tag is 1).
-size_t gru_hx_bytes(bool bf16, int hid, int G) {
-  return (size_t)2 * G * (bf16 ? hid / 32 : hid / 16) * GRU_MAX_TILES * 1024;
-}
-int gru_max_tiles() { return 4; }   // kernels are instantiated for 1, 2 and 4 live tiles (8 spills registers)
+
+// ---- host: sizes, arm, ONE chooser, ONE launch table -------------------------------------------------------------------------
+// a.hx must hold [2][G][GROUP_BYTES] bytes (gru_hx_bytes).  Sizes come from gru_tile.h's geometry, the expressions the kernels index with.
+static int op_bytes(bool bf16) { return bf16 ? 2 : 4; }
+size_t gru_hx_bytes(bool bf16, int hid, int G) { return (size_t)2 * G * gru_plane_bytes(op_bytes(bf16), hid, GRU_MAX_TILES); }
+int gru_max_slots(int G, bool x2) { return G * 16 * (x2 ? GRU_X2_RUN_TILES : GRU_RUN_TILES); }
+// workgroups per recurrence group for (operand type, hidden size): H / (16 UT)
+int gru_group_size(bool bf16, int hid) { return hid / (16 * gru_ut(op_bytes(bf16), hid)); }
+// What decides is the weight slice a workgroup keeps in registers (3 gates x 16 UT rows x H / 4 per wave): 16-bit operands H = 512 and
+// 1024 (UT = 2: 96 / 192 registers) and H = 2048 (UT = 1: 192, 128 workgroups per group = two groups of four XCDs, sc1 hand-off); fp32
+// operands H = 512 and 1024 (UT = 1: 96 / 192).  rnn.py:31: any cfg['hidden_dim']
+bool gru_hidden_supported(bool bf16, int hid) { return hid == 1024 || hid == 512 || (bf16 && hid == 2048); }
 
 // re-arm both exchange buffers and the rendezvous words in ONE launch (three hipMemsetAsync calls per recurrence launch were
-// 0.7 ms per pass of fill kernels plus their launch gaps): buffer 0 := tag 1 everywhere, buffer 1 := 0, sync[0..15] := 0
+// 0.7 ms per pass of fill kernels plus their launch gaps): buffer 0 := tag 1 everywhere (first expected tag there is 0), buffer 1 := 0
+// (first expected tag is 1), sync[0..15] := 0
 __global__ void gru_arm_kernel(unsigned* __restrict__ hx, size_t words_per_buf, unsigned pattern, unsigned* __restrict__ sync) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
@@ -1094,138 +997,130 @@ __global__ void gru_arm_kernel(unsigned* __restrict__ hx, size_t words_per_buf, 
   }
   if (sync != nullptr && i < 16) sync[i] = 0u;
 }
-
 GruArm gru_arm_desc(bool bf16, int hid, int G, void* hx, unsigned* sync) {
   return GruArm{(unsigned*)hx, (unsigned long long)(gru_hx_bytes(bf16, hid, G) / 2 / 4), bf16 ? 0x40004000u : 0x40000000u, sync};
 }
-
-// The recurrence of a whole split pass: XCDs 0 .. a.Gd - 1 (needs the verified placement of an earlier full-width launch: rendezvous
-// word 20), one clip tile per group, GI ring + chunk counters of GruArgs' pass fields.  -1: unsupported.
-// The exchange buffers / rendezvous words must have been armed by launch_gru_arm EARLIER in the stream, before the feed-forward launch of
+// Split pass: the exchange buffers / rendezvous words must be armed EARLIER in the stream, before the feed-forward launch of
 // the pass is released: an ordinary kernel queued between the two persistent launches would need workgroups on CUs the feed-forward
 // kernel fills completely (2 x 256 registers per SIMD) and would hold the recurrence up until the feed-forward has finished - which
 // waits for the recurrence.
-void launch_gru_arm(bool bf16, int hid, int G, void* hx, unsigned* sync, hipStream_t s) {
-  gru_arm_kernel<<<256, 256, 0, s>>>((unsigned*)hx, gru_hx_bytes(bf16, hid, G) / 2 / 4, bf16 ? 0x40004000u : 0x40000000u, sync);
-}
-int launch_gru_recurrence_pass(int hid, GruArgs a, hipStream_t s) {
-  if (hid != 1024 || a.G != 8 || a.Gd < 1 || a.Gd >= 8 || !a.gi_bf16 || !a.gi_cnt || !a.rec_cnt || a.sync == nullptr) return -1;
-  const size_t lds = (size_t)2 * 4 * 3 * 2 * 64 * 16;
-  if (a.f16) gru_recurrence_kernel<f16_t, 1024, 2, 1, false, true, true><<<256, 256, lds, s>>>(a);
-  else gru_recurrence_kernel<bf16_t, 1024, 2, 1, false, true, true><<<256, 256, lds, s>>>(a);
-  return 0;
+void launch_gru_arm(const GruArm& arm, hipStream_t s) {
+  gru_arm_kernel<<<256, 256, 0, s>>>(arm.hx, (size_t)arm.words_per_buf, arm.pattern, arm.sync);
 }
 
-// other hidden sizes (rnn.py:31: any cfg['hidden_dim']): the classic kernel, inference instantiations only.  What decides is the
-// weight slice a workgroup keeps in registers (3 gates x 16 UT rows x H / 4 per wave): 16-bit operands H = 512 (UT = 2: 96 registers) and
-// H = 2048 (UT = 1: 192, 128 workgroups per group = two groups of four XCDs, sc1 hand-off); fp32 operands H = 512 (UT = 1: 96)
-template <int HID>
-static int launch_gru_recurrence_other(bool bf16, int nct, const GruArgs& a, int grid, hipStream_t s) {
-#define LAUNCH_O(WT, UT, NCT)                                                                                    \
-  do {                                                                                                             \
-    const size_t lds = (size_t)2 * 4 * 3 * UT * 64 * 16;                                                           \
-    if (a.gi_bf16) gru_recurrence_kernel<WT, HID, UT, NCT, false, true><<<grid, 256, lds, s>>>(a);                \
-    else gru_recurrence_kernel<WT, HID, UT, NCT, false><<<grid, 256, lds, s>>>(a);                                \
-  } while (0)
-  constexpr int UTB = HID <= 1024 ? 2 : 1;
-  // training (round 6: rnn.py:31-38 takes any hidden_dim, and so does trainer/train.py): the instantiation that keeps the gate
-  // activations / raw state for BPTT (fp32 GI; bf16 or - H = 512 - exact-fp32 operands)
-  if (a.keep_r != nullptr || a.h_raw_out != nullptr) {
-#define LAUNCH_T(WT, UT, NCT)                                                                                    \
-    do {                                                                                                           \
-      const size_t lds = (size_t)2 * 4 * 3 * UT * 64 * 16;                                                         \
-      gru_recurrence_kernel<WT, HID, UT, NCT, true><<<grid, 256, lds, s>>>(a);                                    \
-    } while (0)
-    if (a.gi_bf16 || a.f16) return -1;
-    if (bf16) { if (nct == 1) LAUNCH_T(bf16_t, UTB, 1); else if (nct == 2) LAUNCH_T(bf16_t, UTB, 2); else if (nct <= 4) LAUNCH_T(bf16_t, UTB, 4); else return -1; }
-    else {
-      if constexpr (HID > 512) return -1;
-      else { if (nct == 1) LAUNCH_T(float, 1, 1); else if (nct == 2) LAUNCH_T(float, 1, 2); else if (nct <= 4) LAUNCH_T(float, 1, 4); else return -1; }
-    }
-#undef LAUNCH_T
-    return 0;
+GruChoice gru_choose(const GruQuery& q) {
+  const GruChoice no{};
+  auto pick = [](int family, int op, int hid, int nct, bool train, bool gi16, bool spec, int grid, size_t more_lds) {
+    const int ut = op == GRU_OP_X2 ? 1 : gru_ut(op == GRU_OP_F32 ? 4 : 2, hid);
+    return GruChoice{true, family, op, hid, ut, nct, train, gi16, spec, grid, (size_t)gru_red_bytes(3, ut) + more_lds};
+  };
+  if (q.entry == GRU_ENTRY_X2) {             // more tiles would spill (2 x 96 weight registers): the planner keeps fp16x2 handles at <= 2 tiles
+    if (q.hid != 1024 || q.G < 1 || q.G > 4 || !q.ready || (q.nct != 1 && q.nct != 2)) return no;
+    return pick(GRU_X2, GRU_OP_X2, 1024, q.nct, false, false, false, q.G * (1024 / 16), 0);
   }
-  if (bf16) {
-    if (!a.gi_bf16) return -1;                 // 16-bit operands run with 16-bit GI (inference)
-    if (a.f16) { if (nct == 1) LAUNCH_O(f16_t, UTB, 1); else if (nct == 2) LAUNCH_O(f16_t, UTB, 2); else if (nct <= 4) LAUNCH_O(f16_t, UTB, 4); else return -1; }
-    else { if (nct == 1) LAUNCH_O(bf16_t, UTB, 1); else if (nct == 2) LAUNCH_O(bf16_t, UTB, 2); else if (nct <= 4) LAUNCH_O(bf16_t, UTB, 4); else return -1; }
-  } else {
-    if constexpr (HID > 512) return -1;
-    else { if (a.gi_bf16) return -1; if (nct == 1) LAUNCH_O(float, 1, 1); else if (nct == 2) LAUNCH_O(float, 1, 2); else if (nct <= 4) LAUNCH_O(float, 1, 4); else return -1; }
+  if (q.entry == GRU_ENTRY_PASS) {
+    if (q.hid != 1024 || q.G != 8 || q.Gd < 1 || q.Gd >= 8 || !q.gi_bf16 || !q.ready) return no;
+    return pick(GRU_PASS, q.f16 ? GRU_OP_F16 : GRU_OP_BF16, 1024, 1, false, true, false, 256, 0);
   }
-#undef LAUNCH_O
-  return 0;
-}
-// workgroups per recurrence group for (operand type, hidden size): H / (16 UT)
-int gru_group_size(bool bf16, int hid) { return hid / (bf16 && hid <= 1024 ? 32 : 16); }
-bool gru_hidden_supported(bool bf16, int hid) { return hid == 1024 || hid == 512 || (bf16 && hid == 2048); }
-
-int launch_gru_recurrence(bool bf16, int hid, int nct, GruArgs a, hipStream_t s) {
-  if (hid != 1024) {
-    if (!gru_hidden_supported(bf16, hid)) return -1;
-    if (!a.armed) gru_arm_kernel<<<256, 256, 0, s>>>((unsigned*)a.hx, gru_hx_bytes(bf16, hid, a.G) / 2 / 4, bf16 ? 0x40004000u : 0x40000000u, a.sync);
-    const int grid = a.G * gru_group_size(bf16, hid);
-    return hid == 512 ? launch_gru_recurrence_other<512>(bf16, nct, a, grid, s) : launch_gru_recurrence_other<2048>(bf16, nct, a, grid, s);
+  if (!gru_hidden_supported(q.op16, q.hid)) return no;
+  const int grid = q.G * gru_group_size(q.op16, q.hid);
+  const int inst = q.nct == 1 ? 1 : q.nct == 2 ? 2 : 4;         // kernels exist for 1, 2 and 4 live tiles: three run the four-tile one
+  if (q.hid != 1024) {
+    // other hidden sizes: the classic kernel.  Training (rnn.py:31-38 takes any hidden_dim, and so does trainer/train.py): fp32 GI; bf16
+    // or - H = 512 - exact-fp32 operands.  Inference: 16-bit operands run with 16-bit GI, fp32 operands with fp32 GI
+    if (q.train ? (q.gi_bf16 || q.f16) : (q.op16 != q.gi_bf16)) return no;
+    if (q.nct > 4) return no;
+    return pick(GRU_CLASSIC, !q.op16 ? GRU_OP_F32 : q.f16 ? GRU_OP_F16 : GRU_OP_BF16, q.hid, inst, q.train, !q.train && q.op16, false, grid, 0);
   }
-  const int P = bf16 ? 32 : 64;
-  const size_t buf_bytes = gru_hx_bytes(bf16, hid, a.G) / 2;
-  if (!a.armed) gru_arm_kernel<<<256, 256, 0, s>>>((unsigned*)a.hx, buf_bytes / 4, bf16 ? 0x40004000u : 0x40000000u, a.sync);
-  const int grid = a.G * P;
-  const bool train = a.keep_r != nullptr || a.h_raw_out != nullptr;
   // two or more clip tiles per group, inference: the software-pipelined multi-tile kernel (PREGO_GRU_NO_MT=1: the classic kernel, A/B)
-  const bool no_mt = a.no_mt != 0;
 #ifdef GRU_MT_STAMPS
   const bool stamps_ok = true;
 #else
-  const bool stamps_ok = a.stamps == nullptr;       // PREGO_GRU_STAMPS=1 on a production build: the classic kernel carries the stamps
+  const bool stamps_ok = !q.stamps;       // PREGO_GRU_STAMPS=1 on a production build: the classic kernel carries the stamps
 #endif
   // the pipelined kernel stores relu(h) through a buffer resource (32-bit byte offsets): launches over more than 2^31 bytes of rows
   // (a caller-chosen chunk of a million rows) stay on the classic kernel and its 64-bit addressing
-  const bool rows_ok = a.rows > 0 && (long long)a.rows * hid * 2 < (1ll << 31) - 65536;
-  if (bf16 && a.gi_bf16 && nct >= 2 && nct <= 4 && !train && !no_mt && stamps_ok && rows_ok) {
-    static const int spec_env = prego_tune_env("PREGO_GRU_MT_SPEC") ? atoi(prego_tune_env("PREGO_GRU_MT_SPEC")) : -1;     // A/B: tag check inside (1) / before (0) the multiply
-    const bool spec = spec_env >= 0 ? spec_env != 0 : nct >= 3;
-    // reduction buffers + two gather images per wave + the gi rows of two steps
-    const size_t lds = (size_t)2 * 4 * 3 * 2 * 64 * 16 + (size_t)2 * 4 * 8 * 1024 + (size_t)2 * (nct == 2 ? 2 : 4) * 3 * 1024;
-#define LAUNCH_MT(WT, NCT)                                                                                   \
-    do {                                                                                                       \
-      static DeviceOnce once;                                                                                  \
-      once.run([&] {                                                                                           \
-        (void)hipFuncSetAttribute((const void*)gru_recurrence_mt_kernel<WT, 1024, NCT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);  \
-        (void)hipFuncSetAttribute((const void*)gru_recurrence_mt_kernel<WT, 1024, NCT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      });                                                                                                      \
-      if (spec) gru_recurrence_mt_kernel<WT, 1024, NCT, true><<<grid, 256, lds, s>>>(a);                       \
-      else gru_recurrence_mt_kernel<WT, 1024, NCT, false><<<grid, 256, lds, s>>>(a);                           \
-    } while (0)
-    if (a.f16) { if (nct == 2) LAUNCH_MT(f16_t, 2); else LAUNCH_MT(f16_t, 4); }
-    else { if (nct == 2) LAUNCH_MT(bf16_t, 2); else LAUNCH_MT(bf16_t, 4); }
-#undef LAUNCH_MT
+  const bool rows_ok = q.rows > 0 && (long long)q.rows * q.hid * 2 < (1ll << 31) - 65536;
+  if (q.op16 && q.gi_bf16 && q.nct >= 2 && q.nct <= 4 && !q.train && !q.no_mt && stamps_ok && rows_ok) {
+    const bool spec = q.mt_spec >= 0 ? q.mt_spec != 0 : q.nct >= 3;      // A/B: tag check inside / before the multiply
+    const int n = q.nct == 2 ? 2 : 4;
+    return pick(GRU_MULTI_TILE, q.f16 ? GRU_OP_F16 : GRU_OP_BF16, 1024, n, false, true, spec, grid,
+                (size_t)gru_mt_gather_bytes(1024 / 4 / 32) + gru_mt_gi_bytes(n));
+  }
+  const int op = !q.op16 ? GRU_OP_F32 : q.f16 ? GRU_OP_F16 : GRU_OP_BF16;
+  if ((op == GRU_OP_F16 && q.train) || q.nct > 4) return no;      // fp16 operands: inference only (training runs on bf16 / fp32 handles)
+  // the ONE answer that differs from the launcher chain this replaced: fp32 operands with 16-bit GI ran the classic GI16 kernel.  No
+  // caller can ask (inter16() needs 16-bit operands), the kernel is not instantiated, and the chooser's range is the launch table
+  if (op == GRU_OP_F32 && q.gi_bf16 && !q.train) return no;
+  return pick(GRU_CLASSIC, op, 1024, inst, q.train, !q.train && q.gi_bf16, false, grid, 0);
+}
+
+// the launch table: every kernel a caller can reach (DESIGN 5a lists why each row is there), keyed by GruChoice::packed()
+typedef void (*GruKernel)(GruArgs);
+struct GruRow { int key; GruKernel fn; };
+template <typename WT> struct gru_op_of { static constexpr int v = sizeof(WT) == 4 ? GRU_OP_F32 : op16<typename gru_ot<WT>::type>::is_f16 ? GRU_OP_F16 : GRU_OP_BF16; };
+#define GRU_ROW(WT, HID, UT, NCT, TRAIN, GI16) \
+  {gru_choice_key(GRU_CLASSIC, gru_op_of<WT>::v, UT, NCT, TRAIN, GI16, false, HID), gru_recurrence_kernel<WT, HID, UT, NCT, TRAIN, GI16>}
+#define GRU_ROWS(WT, HID, UT, TRAIN, GI16) GRU_ROW(WT, HID, UT, 1, TRAIN, GI16), GRU_ROW(WT, HID, UT, 2, TRAIN, GI16), GRU_ROW(WT, HID, UT, 4, TRAIN, GI16)
+#define GRU_ROWS_MT(WT, NCT) \
+  {gru_choice_key(GRU_MULTI_TILE, gru_op_of<WT>::v, 2, NCT, false, true, true, 1024), gru_recurrence_mt_kernel<WT, 1024, NCT, true>}, \
+  {gru_choice_key(GRU_MULTI_TILE, gru_op_of<WT>::v, 2, NCT, false, true, false, 1024), gru_recurrence_mt_kernel<WT, 1024, NCT, false>}
+static const GruRow kGruRows[] = {
+    // inference, 16-bit GI | inference, fp32 GI (PREGO_FP32_INTERMEDIATES; fp32 handles) | kept training forward, fp32 GI
+    GRU_ROWS(bf16_t, 1024, 2, false, true), GRU_ROWS(bf16_t, 1024, 2, false, false), GRU_ROWS(bf16_t, 1024, 2, true, false),
+    GRU_ROWS(f16_t, 1024, 2, false, true), GRU_ROWS(f16_t, 1024, 2, false, false),
+    GRU_ROWS(float, 1024, 1, false, false), GRU_ROWS(float, 1024, 1, true, false),
+    GRU_ROWS(bf16_t, 512, 2, false, true), GRU_ROWS(bf16_t, 512, 2, true, false), GRU_ROWS(f16_t, 512, 2, false, true),
+    GRU_ROWS(float, 512, 1, false, false), GRU_ROWS(float, 512, 1, true, false),
+    GRU_ROWS(bf16_t, 2048, 1, false, true), GRU_ROWS(bf16_t, 2048, 1, true, false), GRU_ROWS(f16_t, 2048, 1, false, true),
+    {gru_choice_key(GRU_PASS, GRU_OP_BF16, 2, 1, false, true, false, 1024), gru_recurrence_kernel<bf16_t, 1024, 2, 1, false, true, true>},
+    {gru_choice_key(GRU_PASS, GRU_OP_F16, 2, 1, false, true, false, 1024), gru_recurrence_kernel<f16_t, 1024, 2, 1, false, true, true>},
+    GRU_ROWS_MT(bf16_t, 2), GRU_ROWS_MT(bf16_t, 4), GRU_ROWS_MT(f16_t, 2), GRU_ROWS_MT(f16_t, 4),
+};
+#undef GRU_ROW
+#undef GRU_ROWS
+#undef GRU_ROWS_MT
+
+bool gru_choice_has_kernel(const GruChoice& c) {       // unit test: the chooser's range is the table (the fp16x2 entry launches its own two)
+  if (!c.ok || c.family == GRU_X2) return c.ok;
+  for (const GruRow& r : kGruRows)
+    if (r.key == c.packed()) return true;
+  return false;
+}
+// -1: refused (nothing is launched, the caller reports the error)
+static int gru_launch(const GruChoice& c, GruArgs& a, hipStream_t s) {
+  if (!c.ok) return -1;
+  const int key = c.packed();
+  for (const GruRow& r : kGruRows) {
+    if (r.key != key) continue;
+    if (c.family == GRU_MULTI_TILE) {      // more than 64 KiB of LDS: the limit is raised once per device, for every multi-tile kernel
+      static DeviceOnce once;
+      once.run([&] {
+        for (const GruRow& m : kGruRows)
+          if ((m.key & 3) == GRU_MULTI_TILE)
+            (void)hipFuncSetAttribute((const void*)m.fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      gru_red_bytes(3, 2) + gru_mt_gather_bytes(1024 / 4 / 32) + gru_mt_gi_bytes((m.key >> 6) & 7));
+      });
+    }
+    if (!a.armed && c.family != GRU_PASS) launch_gru_arm(gru_arm_desc(c.op != GRU_OP_F32, c.hid, a.G, a.hx, a.sync), s);
+    void* args[] = {&a};
+    (void)hipLaunchKernel((const void*)r.fn, dim3(c.grid), dim3(256), args, c.lds, s);      // a launch error surfaces at the caller's hipGetLastError
     return 0;
   }
-#define LAUNCH(WT, UT, NCT)                                                                            \
-  do {                                                                                                 \
-    const size_t lds = (size_t)2 * 4 * 3 * UT * 64 * 16;                                               \
-    if (train) gru_recurrence_kernel<WT, 1024, UT, NCT, true><<<grid, 256, lds, s>>>(a);              \
-    else if (a.gi_bf16) gru_recurrence_kernel<WT, 1024, UT, NCT, false, true><<<grid, 256, lds, s>>>(a); \
-    else gru_recurrence_kernel<WT, 1024, UT, NCT, false><<<grid, 256, lds, s>>>(a);                    \
-  } while (0)
-  if (bf16 && a.f16) {
-    if (train) return -1;                    // fp16 operands: inference only (training runs on bf16 / fp32 handles)
-    if (nct == 1) LAUNCH(f16_t, 2, 1);
-    else if (nct == 2) LAUNCH(f16_t, 2, 2);
-    else if (nct <= 4) LAUNCH(f16_t, 2, 4);
-    else return -1;
-  } else if (bf16) {
-    if (nct == 1) LAUNCH(bf16_t, 2, 1);
-    else if (nct == 2) LAUNCH(bf16_t, 2, 2);
-    else if (nct <= 4) LAUNCH(bf16_t, 2, 4);
-    else return -1;
-  } else {
-    if (nct == 1) LAUNCH(float, 1, 1);
-    else if (nct == 2) LAUNCH(float, 1, 2);
-    else if (nct <= 4) LAUNCH(float, 1, 4);
-    else return -1;
-  }
-#undef LAUNCH
-  return 0;
+  return -1;
+}
+
+static GruQuery gru_query(int entry, bool op16, int hid, int nct, const GruArgs& a) {
+  static const int spec_env = prego_tune_env("PREGO_GRU_MT_SPEC") ? atoi(prego_tune_env("PREGO_GRU_MT_SPEC")) : -1;
+  return GruQuery{entry, op16, a.f16 != 0, hid, nct, a.G, a.gi_bf16 != 0, a.keep_r != nullptr || a.h_raw_out != nullptr, a.no_mt != 0,
+                  a.stamps != nullptr, a.rows, spec_env, a.Gd, a.gi_cnt && a.rec_cnt && a.sync != nullptr};
+}
+// Returns 0 on success, -1 for unsupported (hid, nct).  Both exchange buffers are re-armed here (stream ordered) unless a.armed.
+int launch_gru_recurrence(bool bf16, int hid, int nct, GruArgs a, hipStream_t s) {
+  return gru_launch(gru_choose(gru_query(GRU_ENTRY_MAIN, bf16, hid, nct, a)), a, s);
+}
+// The recurrence of a whole split pass: XCDs 0 .. a.Gd - 1 (needs the verified placement of an earlier full-width launch: rendezvous
+// word 20), one clip tile per group, GI ring + chunk counters of GruArgs' pass fields.  -1: unsupported.  Armed by launch_gru_arm (there).
+int launch_gru_recurrence_pass(int hid, GruArgs a, hipStream_t s) {
+  return gru_launch(gru_choose(gru_query(GRU_ENTRY_PASS, true, hid, 1, a)), a, s);
 }

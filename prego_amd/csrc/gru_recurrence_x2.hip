@@ -17,27 +17,29 @@
 // On any other placement everything goes through region R with sc1 on both sides.  The tags decide validity either way:
 // placement only changes speed.
 #include "common.h"
+#include "gru_tile.h"
 #include "kernels.h"
 #include <cstdlib>
 
 #define X2_SPIN_LIMIT (1u << 22)
-#define X2_TILES 4                              // clip tiles per group the exchange buffer is laid out for (gru_max_tiles)
+#define X2_TILES GRU_X2_TILES                   // clip tiles per group the exchange buffer is laid out for (gru_tile.h)
 #ifndef X2_NSEG
 #define X2_NSEG 2
 #endif
 
 template <int HID, int NCT>
 __global__ __launch_bounds__(256, 1) void gru_recurrence_x2_kernel(GruArgs a, const float* __restrict__ inv_scale_p) {
-  constexpr int UNITS = 16, KQ = HID / 4, NKS = KQ / 32, KF = 32, EPL = 8;
-  constexpr unsigned TAGM = 0x40004000u;
-  constexpr int PLANE_BYTES = (HID / KF) * X2_TILES * 1024;      // one plane (hi or lo) of one group: [k-step][tile][lane][16 B]
-  constexpr int REGION_BYTES = 2 * PLANE_BYTES;                  // hi | lo
-  constexpr int GROUP_BYTES = 2 * REGION_BYTES;                  // region L | region R
-  constexpr int P = HID / UNITS;                                 // 64 workgroups per group
+  typedef GruGeom<2, HID, 1, X2_TILES, 2, 2> Geo;                // fp16 elements; planes hi | lo; regions L | R (gru_tile.h)
+  constexpr int UNITS = Geo::UNITS, KQ = Geo::KQ, NKS = Geo::NKS, KF = Geo::KF, EPL = Geo::EPL;
+  constexpr unsigned TAGM = Geo::TAGM;
+  constexpr int PLANE_BYTES = Geo::PLANE_BYTES;                  // one plane (hi or lo) of one group: [k-step][tile][lane][16 B]
+  constexpr int REGION_BYTES = Geo::REGION_BYTES;                // hi | lo
+  constexpr int GROUP_BYTES = Geo::GROUP_BYTES;                  // region L | region R
+  constexpr int P = Geo::P;                                      // 64 workgroups per group
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   f32x4* red = (f32x4*)smem;                                     // [2 parities][4 waves][3 gates][64 lanes]
-  constexpr int RED_STRIDE = 4 * 3 * 64;
+  constexpr int RED_STRIDE = Geo::RED_STRIDE;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int q = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -105,18 +107,7 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_x2_kernel(GruArgs a, co
   }
   int nstart[NCT], segp[NCT], sege[NCT];
 #pragma unroll
-  for (int ct = 0; ct < NCT; ++ct) {
-    nstart[ct] = 0x7fffffff; segp[ct] = 0; sege[ct] = 0;
-    if (a.seg_start != nullptr && sidx[ct] < a.n_clips) {
-      int k = a.seg_off[sidx[ct]];
-      sege[ct] = a.seg_off[sidx[ct] + 1];
-      while (k < sege[ct] && a.seg_start[k] < a.t0) ++k;
-      if (k < sege[ct] && a.seg_start[k] == a.t0 && a.t0 > 0) hreg[ct] = 0.f;      // a clip starts on this launch's first step
-      while (k < sege[ct] && a.seg_start[k] <= a.t0) ++k;
-      segp[ct] = k;
-      nstart[ct] = k < sege[ct] ? a.seg_start[k] : 0x7fffffff;
-    }
-  }
+  for (int ct = 0; ct < NCT; ++ct) { GRU_SEG_INIT(ct, hreg[ct] = 0.f;) }
 
   // exchange buffers: [2 buffers][G][GROUP_BYTES]; one descriptor per group
   const int buf_stride = a.G * GROUP_BYTES;
@@ -128,7 +119,7 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_x2_kernel(GruArgs a, co
 
   // publish this lane's element of tile ct (hi and lo planes; region R always, region L when paired); no waiting
   auto publish = [&](int ct, int buf, unsigned tag, bool zero) {
-    const int off = buf * buf_stride + ((ucol / KF) * X2_TILES + ct) * 1024 + ((((ucol % KF) / EPL) << 4) + l15) * 16 + (ucol % EPL) * 2;
+    const int off = buf * buf_stride + GRU_HX_OFFSET(KF, EPL, 2, X2_TILES, l15, ucol, ct);
     float hv = zero ? 0.f : hreg[ct];
     hv = __builtin_amdgcn_fmed3f(hv, -1.9990234375f, 1.9990234375f);
     const _Float16 hi = (_Float16)hv;
@@ -150,12 +141,7 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_x2_kernel(GruArgs a, co
     for (int gate = 0; gate < 3; ++gate) dst[gate] = ((const float*)a.gi)[(size_t)r * (3 * HID) + gate * HID + ucol];
   };
 
-  typedef const __attribute__((address_space(4))) int* cint_p;
-  cint_p nact_c = (cint_p)a.nact;
-  cint_p rowoff_c = (cint_p)a.rowoff;
-  const int nsteps = a.t1 - a.t0;
-  int na_c = nact_c[a.t0], rb_c = rowoff_c[a.t0];
-  int na_n = nsteps > 1 ? nact_c[a.t0 + 1] : 0, rb_n = nsteps > 1 ? rowoff_c[a.t0 + 1] : 0;
+  GRU_PLAN_INIT
   float giA[NCT][3], giB[NCT][3];
 #pragma unroll
   for (int ct = 0; ct < NCT; ++ct)
@@ -167,12 +153,10 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_x2_kernel(GruArgs a, co
     const int na = na_c;
     const int rbase = rb_c - a.row_base;
     const bool more = tl + 1 < nsteps;
-    const int t2 = (tl + 2 < nsteps) ? t + 2 : t;
-    const int na_2 = nact_c[t2], rb_2 = rowoff_c[t2];
+    GRU_PLAN_PEEK
     const int rbuf = (tl + 1) & 1;
     const unsigned etag = (unsigned)(((tl - 1) >> 1) & 1);
     const unsigned eword = etag ? TAGM : 0u;
-    const unsigned untag = etag ? ~TAGM : 0xFFFFFFFFu;
 
 #pragma unroll
     for (int ct = 0; ct < NCT; ++ct) {
@@ -185,7 +169,7 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_x2_kernel(GruArgs a, co
         unsigned spins = 0;
         const bool col_live = sidx[ct] < na;
         const int lane_off = col_live ? lane * 16 : 0x7F000000;     // dead columns: past num_records, zeros, no memory access
-        const int base_off = rbuf * buf_stride + rd_region + ((q * NKS) * X2_TILES + ct) * 1024 + lane_off;
+        const int base_off = rbuf * buf_stride + rd_region + GRU_HX_FRAG(X2_TILES, q * NKS, ct) + lane_off;
         if (rd_local) {
 #pragma unroll
           for (int ks = 0; ks < NKS; ++ks) {
@@ -285,13 +269,11 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_x2_kernel(GruArgs a, co
         if (col_live && a.h_relu_out) ((float*)a.h_relu_out)[(size_t)(rbase + sidx[ct]) * HID + ucol] = fmaxf(hreg[ct], 0.f);
         if (restart) {
           hreg[ct] = 0.f;
-          ++segp[ct];
-          nstart[ct] = segp[ct] < sege[ct] ? a.seg_start[segp[ct]] : 0x7fffffff;
-          asm volatile("" : "+v"(nstart[ct]));
+          GRU_SEG_ADVANCE(ct)
         }
       }
     }
-    na_c = na_n; rb_c = rb_n; na_n = na_2; rb_n = rb_2;
+    GRU_PLAN_SHIFT
     return true;
   };
   for (int tl = 0; tl < nsteps; tl += 2) {
@@ -304,31 +286,21 @@ __global__ __launch_bounds__(256, 1) void gru_recurrence_x2_kernel(GruArgs a, co
     if (sidx[ct] < a.n_clips) a.h_state[(size_t)sidx[ct] * HID + ucol] = hreg[ct];
 }
 
-size_t gru_x2_hx_bytes(int hid, int G) { return (size_t)2 * G * 4 * (hid / 32) * X2_TILES * 1024; }
+size_t gru_x2_hx_bytes(int hid, int G) { return (size_t)2 * G * 4 * gru_plane_bytes(2, hid, X2_TILES); }      // 2 buffers x (2 regions x 2 planes)
 
 // what a launch needs re-armed: buffer 0 := tag 1 everywhere, buffer 1 := 0, sync[0..15] := 0 (kernels.h: GruArm)
 GruArm gru_x2_arm_desc(int hid, int G, void* hx, unsigned* sync) {
   return GruArm{(unsigned*)hx, (unsigned long long)(gru_x2_hx_bytes(hid, G) / 2 / 4), 0x40004000u, sync};
 }
 
-__global__ void gru_x2_arm_kernel(unsigned* __restrict__ hx, size_t words_per_buf, unsigned* __restrict__ sync) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t k = i; k < words_per_buf / 4; k += stride) {
-    ((uint4*)hx)[k] = make_uint4(0x40004000u, 0x40004000u, 0x40004000u, 0x40004000u);
-    ((uint4*)(hx + words_per_buf))[k] = make_uint4(0u, 0u, 0u, 0u);
-  }
-  if (sync != nullptr && i < 16) sync[i] = 0u;
-}
-
-// 0 on success, -1 for an unsupported (hid, nct)
+// 0 on success, -1 for an unsupported (hid, nct): gru_choose's x2 entry
 int launch_gru_recurrence_x2(int hid, int nct, GruArgs a, const float* inv_scale, hipStream_t s) {
-  if (hid != 1024 || a.G < 1 || a.G > 4 || !inv_scale) return -1;
-  if (!a.armed) gru_x2_arm_kernel<<<256, 256, 0, s>>>((unsigned*)a.hx, gru_x2_hx_bytes(hid, a.G) / 2 / 4, a.sync);
-  const int grid = a.G * 64;
-  const size_t lds = (size_t)2 * 4 * 3 * 64 * 16;
-  if (nct == 1) gru_recurrence_x2_kernel<1024, 1><<<grid, 256, lds, s>>>(a, inv_scale);
-  else if (nct == 2) gru_recurrence_x2_kernel<1024, 2><<<grid, 256, lds, s>>>(a, inv_scale);
-  else return -1;                 // more tiles would spill (2 x 96 weight registers): the planner keeps fp16x2 handles at <= 2 tiles
+  GruQuery q{};
+  q.entry = GRU_ENTRY_X2; q.hid = hid; q.nct = nct; q.G = a.G; q.ready = inv_scale != nullptr;
+  const GruChoice c = gru_choose(q);
+  if (!c.ok) return -1;
+  if (!a.armed) launch_gru_arm(gru_x2_arm_desc(hid, a.G, a.hx, a.sync), s);
+  if (c.nct == 1) gru_recurrence_x2_kernel<1024, 1><<<c.grid, 256, c.lds, s>>>(a, inv_scale);
+  else gru_recurrence_x2_kernel<1024, 2><<<c.grid, 256, c.lds, s>>>(a, inv_scale);
   return 0;
 }

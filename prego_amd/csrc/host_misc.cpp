@@ -1,5 +1,6 @@
 // Handle-free entry points of the C ABI (include/prego_amd.h): post-processing, metrics and label preparation around the models.
 #include "host_common.h"
+#include "gru_tile.h"
 #ifdef PREGO_DEBUG_ABI
 #include "miniroad_handle.h"      // the allocation / wait counters of prego_debug_alloc_count cover this file's entries as well
 #endif
@@ -318,6 +319,31 @@ extern "C" int prego_debug_gemm_nt_choice(int entry, int M, int N, int K, int ld
                                           int dh, int emb, int knobs) {
   const GemmNtQuery q = {entry, M, N, K, lda, ldb, has_bias != 0, f16 != 0, train_splitk != 0, mode, dh, emb};
   return (int)gemm_nt_choose(q, GemmNtKnobs{(knobs & 1) != 0, (knobs & 2) != 0, (knobs & 4) != 0});
+}
+
+// unit test (tests/test_gru_choice_cpu.py): gru_choose's answer packed (GruChoice::packed) - no device is touched
+extern "C" int prego_debug_gru_choice(int entry, int operand, int hid, int nct, int G, int gi_bf16, int train, int no_mt, int stamps, int rows,
+                                      int mt_spec, int Gd, int ready, int* grid, int* lds) {
+  const GruChoice c = gru_choose(GruQuery{entry, operand != GRU_OP_F32, operand == GRU_OP_F16, hid, nct, G, gi_bf16 != 0, train != 0, no_mt != 0,
+                                          stamps != 0, rows, mt_spec, Gd, ready != 0});
+  if (grid) *grid = c.ok ? c.grid : 0;
+  if (lds) *lds = c.ok ? (int)c.lds : 0;
+  return c.ok && !gru_choice_has_kernel(c) ? -2 : c.packed();
+}
+// unit test: the exchange layout functions and the sizes the host derives from them (gru_tile.h)
+extern "C" long long prego_debug_gru_hx_offset(int what, int wb, int tiles, int a, int b, int c) {
+  switch (what) {
+    case 0: return gru_hx_offset(wb, tiles, a, b, c);
+    case 1: return gru_hx_k_at(wb, a, b, c);
+    case 2: return gru_hx_col_at(b);
+    case 3: return gru_plane_bytes(wb, a, tiles);
+    case 10: return (long long)gru_hx_bytes(wb == 2, a, b);
+    case 11: return (long long)gru_x2_hx_bytes(a, b);
+    case 12: return gru_group_size(wb == 2, a);
+    case 13: return gru_hidden_supported(wb == 2, a) ? 1 : 0;
+    case 14: return gru_max_slots(b, c != 0);
+    default: return -1;
+  }
 }
 
 // unit test (tests/test_gpu_gemm_tn.py): launch_gemm_bf16_tn as the training steps call it - the launcher's own choice of kernel runs

@@ -127,13 +127,46 @@ int launch_ff_pass(const FfPassArgs& a, hipStream_t s);
 int launch_gru_recurrence_pass(int hid, GruArgs a, hipStream_t s);
 int gru_group_size(bool bf16, int hid);            // workgroups per recurrence group
 bool gru_hidden_supported(bool bf16, int hid);     // 1024; 512; 2048 with 16-bit operands
-void launch_gru_arm(bool bf16, int hid, int G, void* hx, unsigned* sync, hipStream_t s);   // must precede it in the stream (see there)
 
 // what a recurrence launch needs re-armed before it starts (gru_recurrence.hip: buffer 0 := tag 1 everywhere, buffer 1 := 0,
 // sync[0..15] := 0).  A LayerNorm launch that runs between two recurrence launches of a stream can do it on the side (one launch
 // and one launch gap fewer per chunk)
 struct GruArm { unsigned* hx; unsigned long long words_per_buf; unsigned pattern; unsigned* sync; };
 GruArm gru_arm_desc(bool bf16, int hid, int G, void* hx, unsigned* sync);
+// the arm as a launch of its own (what the recurrence launchers do for a.armed == 0).  Split pass: it must sit EARLIER in the stream than
+// the feed-forward launch of the pass (gru_recurrence.hip, at the function)
+void launch_gru_arm(const GruArm& arm, hipStream_t s);
+
+// ---- which recurrence kernel a launch runs: ONE pure host function behind the three entry points (gru_recurrence.hip: gru_choose) ----
+enum GruEntry { GRU_ENTRY_MAIN = 0, GRU_ENTRY_X2 = 1, GRU_ENTRY_PASS = 2 };       // launch_gru_recurrence / _x2 / _pass
+enum GruFamily { GRU_CLASSIC = 0, GRU_MULTI_TILE = 1, GRU_X2 = 2, GRU_PASS = 3 };
+enum GruOperand { GRU_OP_BF16 = 0, GRU_OP_F16 = 1, GRU_OP_F32 = 2, GRU_OP_X2 = 3 };
+struct GruQuery {
+  int entry;
+  bool op16, f16;               // the entry's `bf16` argument (16-bit operands) and GruArgs::f16; ignored by the x2 entry
+  int hid, nct, G;
+  bool gi_bf16, train;          // train: the launch keeps gate activations / raw state (a.keep_r or a.h_raw_out)
+  bool no_mt, stamps;           // GruArgs::no_mt, a.stamps != nullptr
+  int rows;
+  int mt_spec;                  // PREGO_GRU_MT_SPEC: -1 unset, 0 tag check before the multiply, otherwise inside it
+  int Gd;                       // pass entry
+  bool ready;                   // x2 entry: inv_scale given; pass entry: gi_cnt, rec_cnt and sync given
+};
+constexpr int gru_choice_key(int family, int op, int ut, int nct, bool train, bool gi16, bool spec, int hid) {
+  return family | op << 2 | ut << 4 | nct << 6 | (int)train << 9 | (int)gi16 << 10 | (int)spec << 11 | hid << 12;
+}
+struct GruChoice {
+  bool ok;                      // false: refused (the entry returns -1 and launches nothing)
+  int family, op, hid, ut, nct; // nct: the instantiation's tile count (1, 2 or 4), not the query's
+  bool train, gi16, spec;
+  int grid;
+  size_t lds;
+  int packed() const {          // what prego_debug_gru_choice returns (-1: refused)
+    return ok ? gru_choice_key(family, op, ut, nct, train, gi16, spec, hid) : -1;
+  }
+};
+GruChoice gru_choose(const GruQuery& q);
+bool gru_choice_has_kernel(const GruChoice& c);
 
 // persistent reverse-time recurrence of BPTT (gru_bptt.hip); all row indices are absolute packed rows of the kept forward
 struct BpttArgs {
@@ -252,7 +285,7 @@ void launch_gemm_f32_nt(const float* A, int lda, const float* B, int ldb, const 
                         int N, int K, hipStream_t s);
 int launch_gru_recurrence(bool bf16, int hid, int nct, GruArgs a, hipStream_t s);
 size_t gru_hx_bytes(bool bf16, int hid, int G);
-int gru_max_tiles();
+int gru_max_slots(int G, bool x2);       // slots a handle of G groups plans for: 16 per tile and group
 int launch_head_softmax(bool bf16, const void* Hrelu, const void* Wc, const float* bc, const SlotPlan& plan,
                         int row0, int nrows, int hid, int C, int apply_softmax,
                         float* const* out_ptrs, int* const* argmax_ptrs, hipStream_t s, const void* rowmap = nullptr, bool f16 = false);

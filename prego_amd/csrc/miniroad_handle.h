@@ -172,7 +172,7 @@ struct HandleScope {
 };
 
 // split-operand recurrence: two clip tiles per group at most (the four-tile instantiation would spill: 2 x 96 weight registers)
-static inline int max_slots_of(const prego_miniroad* h) { return h->G * 16 * (h->x2 ? 2 : gru_max_tiles()); }
+static inline int max_slots_of(const prego_miniroad* h) { return gru_max_slots(h->G, h->x2); }
 #define PREGO_MAX_CLIPS 8192     // clips per call (continuous batching packs them into <= max_slots slots)
 static inline int max_clips_of(const prego_miniroad*) { return PREGO_MAX_CLIPS; }
 

@@ -177,7 +177,7 @@ int forward_split(prego_miniroad* h, const AntOut& ao, int R, int flags, bool wi
   } side_join{h};
   // everything the recurrence launch needs done first goes IN FRONT of the fork: once the feed-forward kernel is resident it fills its CUs
   // completely, and an ordinary kernel of the caller's stream (the arm kernel, a memset) would wait for it - with the recurrence queued behind
-  launch_gru_arm(true, H, h->G, h->hx, h->flags, s);
+  launch_gru_arm(gru_arm_desc(true, H, h->G, h->hx, h->flags), s);
   if (h->perm_stale) {                       // in front of the fork, like the arm kernel: nothing of this stream may sit between the two launches
     launch_permute_gi_rows(h->w_ih, h->bias2, h->w_ih_perm, h->bias2_perm, H, E, s);
     h->perm_stale = false;

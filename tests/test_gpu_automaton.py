@@ -179,7 +179,10 @@ def test_split_pass_other_feature_and_embedding_size():
 
 @pytest.mark.parametrize("switch", ["PREGO_GRU_NO_LOCAL", "PREGO_GRU_NO_MT"])
 def test_ab_switches_of_the_product_library(switch):
-    for rid, dtypes in (("h1024-rgb", ["fp16", "bf16", "fp32"]), ("clips400", ["fp16"])):
+    runs = [("h1024-rgb", ["fp16", "bf16", "fp32"]), ("clips400", ["fp16"])]
+    if switch == "PREGO_GRU_NO_LOCAL":      # the fp16x2 kernel's unpaired hand-off, and the 16-workgroup rendezvous of hidden size 512, off the verified placement
+        runs += [("h1024-rgb", ["fp16x2"]), ("h512-rgb", ["bf16"])]
+    for rid, dtypes in runs:
         case, sd, _, feats, _, res = _ref(rid)
         for dtype in dtypes:
             _forward_equals(_engine(case, sd, dtype, {switch: "1"}), case, feats, res, f"{switch} {rid} {dtype}")
