@@ -136,6 +136,20 @@ int prego_debug_vit_burst_commit(prego_vit_stream_pool* p, int n, const int32_t*
  * of its record.  Returns the clause bits, -1 for a NULL argument. */
 int prego_debug_pool_image_fault(const int32_t* geometry6, const int32_t* tag, const int32_t* rec);
 
+/* Unit test only (tests/test_vit_tensor_table_cpu.py), no device: entry i of the ViTEnc handle's tensor table, the one enumeration that
+ * prego_vit_set_weights, the gradient list and the AdamW step walk.  dims: HOST int32 [8] = d_rgb, d_flow, embedding_dim, hidden_dim (mlp),
+ * num_heads, num_layers, window_size, n_classes.  rows x cols as nn.Linear stores a matrix, 1 x n for a vector; is_matrix: the handle keeps
+ * a 16-bit operand copy.  Returns the number of entries (i outside the table writes nothing), -1 for a NULL argument. */
+int prego_debug_vit_tensor(const int32_t* dims, int i, int32_t* rows, int32_t* cols, int32_t* is_matrix);
+
+/* Unit test only (tests/test_vit_layout_cpu.py), no device: the blocks of a Transformer workspace layout, in order.  dims as above
+ * (the attention layer's kinds read embedding_dim as d_model and num_heads).  kind 0: prego_vit_forward in 16 bits, a = batch; 1: the same
+ * on a PREGO_F32 handle; 2: prego_vit_forward_frames, a = n_frames, b = windows_per_batch; 3: prego_vit_step_pool, a = n_active; 4: ViTEnc
+ * training, a = batch; 5 / 6: the attention handle's forward in 16 bits / PREGO_F32, a = batch, b = len; 7: the attention handle's
+ * training; 8: the stateless attention op.  offsets: HOST uint64 [cap]: offset and bytes asked for of block i at [2i], [2i + 1], then the
+ * total.  Returns the number of blocks; -1: a NULL argument, an unknown kind, or cap below 2 * blocks + 1. */
+int prego_debug_vit_layout(int kind, const int32_t* dims, int a, int b, uint64_t* offsets, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,7 +68,8 @@ DEBUG_SYMBOLS = ["prego_miniroad_debug_stamps", "prego_debug_gemm_bf16", "prego_
                  "prego_debug_recurrence_only", "prego_debug_gemm_worker", "prego_debug_head_only",
                  "prego_debug_split_fault", "prego_debug_split_state", "prego_debug_set_abort", "prego_debug_alloc_count", "prego_debug_hog",
                  "prego_debug_ant_full_span", "prego_debug_gemm_tn", "prego_debug_gemm_nt", "prego_debug_gemm_nt_choice", "prego_debug_vit_ring_tokens",
-                 "prego_debug_gru_choice", "prego_debug_gru_hx_offset", "prego_debug_vit_burst_tokens", "prego_debug_vit_burst_commit", "prego_debug_pool_image_fault"]
+                 "prego_debug_gru_choice", "prego_debug_gru_hx_offset", "prego_debug_vit_burst_tokens", "prego_debug_vit_burst_commit", "prego_debug_pool_image_fault",
+                 "prego_debug_vit_tensor", "prego_debug_vit_layout"]
 
 
 class PregoError(RuntimeError):
@@ -281,6 +282,8 @@ def _open(path: str, debug: bool) -> C.CDLL:
         lib.prego_debug_vit_burst_tokens.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, vp]
         lib.prego_debug_vit_burst_commit.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp]
         lib.prego_debug_pool_image_fault.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        lib.prego_debug_vit_tensor.argtypes = [C.POINTER(C.c_int32), i32] + [C.POINTER(C.c_int32)] * 3
+        lib.prego_debug_vit_layout.argtypes = [i32, C.POINTER(C.c_int32), i32, i32, C.POINTER(C.c_uint64), i32]
     return lib
 
 

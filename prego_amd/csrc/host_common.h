@@ -18,3 +18,20 @@ int prego_fail_(int code, const char* fmt, ...);
   } while (0)
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Bump allocator over a caller's workspace: put() returns the block's offset, every block starts on a 256-byte boundary, off is the
+// total so far.  log (prego_debug_vit_layout only): (offset, bytes asked for) of every block, in order
+struct ArenaLog { size_t* v; int cap, n; };
+struct Arena {
+  size_t off = 0;
+  ArenaLog* log = nullptr;
+  size_t put(size_t bytes) {
+    const size_t o = off;
+    off += align_up(bytes, 256);
+    if (log) {
+      if (log->n < log->cap) { log->v[2 * log->n] = o; log->v[2 * log->n + 1] = bytes; }
+      ++log->n;
+    }
+    return o;
+  }
+};

@@ -38,35 +38,6 @@ bool vit_pool_layout(const prego_vit* h, int capacity, int max_events, VitPoolLa
   return true;
 }
 
-// the step call's workspace: xb [n][din] 16-bit | enc [n][E] fp32 | argmax [n] int32 | the per-batch arena of n windows (vit_ws)
-struct VitStepWs { size_t xb, enc, am, win; VitWs w; size_t total; };
-VitStepWs vit_step_ws(const prego_vit* h, int n) {
-  VitStepWs f{};
-  const size_t E = h->emb, din = h->d_rgb + h->d_flow;
-  size_t off = 0;
-  auto put = [&](size_t bytes) { size_t o = off; off += align_up(bytes, 256); return o; };
-  f.xb = put((size_t)n * din * 2); f.enc = put((size_t)n * E * 4); f.am = put((size_t)n * 4);
-  f.w = vit_ws(h, n);
-  f.win = put(f.w.total);
-  f.total = off;
-  return f;
-}
-
-// the encoder blocks on B windows whose tokens the token kernel has written (fused: LayerNorm1(x) and x0 instead of x), then the head
-// with its argmax: what prego_vit_forward_frames runs for a batch of B windows
-int blocks_and_head(const prego_vit* h, const char* who, char* ws, const VitWs& w, int B, int causal, bool fused, float* out_logits,
-                    int32_t* am, hipStream_t s) {
-  const int N = h->window + 1;
-  for (int li = 0; li < h->layers; ++li) {
-    const bool last = li + 1 == h->layers;
-    const int rc = last ? encoder_block_token0(h, h->L[li], (const float*)(ws + w.x), ws, w, B, N, causal, s, fused)
-                        : encoder_block(h, h->L[li], (float*)(ws + w.x), ws, w, B, N, causal, s);
-    if (rc) return prego_fail_(PREGO_EINVAL, "%s: encoder block launch failed", who);
-  }
-  launch_vit_head((const float*)(ws + w.x0), B, 1, h->emb, h->lnf_w, h->lnf_b, h->head_w, h->head_b, h->ncls, out_logits, s, (int*)am);
-  return 0;
-}
-
 // a burst call's host arrays turned into kernel arguments: by_slot = entry i for slots[i], by_row = the owner's entry for every packed
 // row, rows = the sum of the counts.  n is already known to be in 1..256.  0 = fine, else PREGO_EINVAL with a message
 struct BurstPlan { RaggedMap by_slot, by_row; int rows; };
@@ -170,7 +141,7 @@ extern "C" void prego_vit_stream_pool_destroy(prego_vit_stream_pool* p) { delete
 
 extern "C" size_t prego_vit_step_pool_workspace_bytes(const prego_vit* h, int n_active) {
   if (!h || n_active < 1 || n_active > kPoolMaxActive) return 0;
-  return vit_step_ws(h, n_active).total;
+  return vit_step_ws(*h, n_active, n_active, true).total;
 }
 
 // One new frame for the slots named: cat + convert, the encoding GEMM on n_active rows, the rows into their rings, one window per slot out
@@ -180,7 +151,7 @@ extern "C" int prego_vit_step_pool(prego_vit* h, prego_vit_stream_pool* p, int n
                                    prego_stream_t stream) {
   const char* who = "vit_step_pool";
   if (int rc = vit_step_refusals(who, h, p, n_active, slots, rgb, flow, out_logits)) return rc;
-  const VitStepWs f = vit_step_ws(h, n_active);
+  const VitStepWs f = vit_step_ws(*h, n_active, n_active, true);
   VitStepBufs b;
   if (int rc = vit_step_carve(who, workspace, workspace_bytes, f, n_active, 0, argmax, &b)) return rc;
   hipStream_t s = (hipStream_t)stream;
@@ -205,7 +176,7 @@ extern "C" int prego_vit_step_pool(prego_vit* h, prego_vit_stream_pool* p, int n
 extern "C" size_t prego_vit_step_pool_bursts_workspace_bytes(const prego_vit* h, int n_active, int n_rows) {
   if (!h || n_active < 1 || n_active > kPoolMaxActive || n_rows < n_active || n_rows > kPoolMaxActive) return 0;
   if ((long long)n_rows > (long long)n_active * (h->window < 32 ? h->window : 32)) return 0;
-  return vit_step_ws(h, n_rows).total;
+  return vit_step_ws(*h, n_rows, n_rows, true).total;
 }
 
 // counts[i] new frames for slots[i], R packed rows: cat + convert and the encoding GEMM on R rows, one window per packed row out of the
@@ -219,7 +190,7 @@ extern "C" int prego_vit_step_pool_bursts(prego_vit* h, prego_vit_stream_pool* p
   BurstPlan bp;
   if (int rc = burst_plan(who, h->window, n_active, counts, &bp)) return rc;
   const int n = n_active, R = bp.rows, E = h->emb, din = h->d_rgb + h->d_flow;
-  const VitStepWs f = vit_step_ws(h, R);
+  const VitStepWs f = vit_step_ws(*h, R, R, true);
   VitStepBufs b;
   if (int rc = vit_step_carve(who, workspace, workspace_bytes, f, n, R, argmax, &b)) return rc;
   hipStream_t s = (hipStream_t)stream;
