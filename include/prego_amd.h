@@ -810,6 +810,52 @@ int prego_vit_stream_pool_snapshot(prego_vit_stream_pool* p, const prego_stream_
 int prego_vit_stream_pool_restore(prego_vit_stream_pool* p, prego_stream_pool_feed* feed /* nullable */, int n, const int32_t* slots,
                                   const void* images, size_t bytes, int32_t* status /* nullable */, prego_stream_t stream);
 
+/* Procedure model (an addition to ABI 7, existing signatures unchanged): online mistake detection from a corpus of correct step
+ * transcripts - the symbolic, integer-exact stand-in for step_anticipation's LLM branch.  Definitions:
+ *   symbols   step ids 0 .. n_classes - 1 (1 <= n_classes <= 128); a virtual START stands in front of every sequence.
+ *   corpus    transcripts, each with a group id >= 0 (the toy class), its symbols and a target flag per position.  A target position p
+ *             is an EXAMPLE: context START, s_0 .. s_{p-1}, next symbol s_p.
+ *   query     a history START, e_0 .. e_{i-1}, the current step e_i and a group q; q = -1: every group.  A queried symbol outside
+ *             [0, n_classes) equals nothing.  A group without examples (or outside the corpus's groups) has none.
+ *   match     for 1 <= j <= order (1..8) an example matches at j when both contexts hold at least j symbols, START included, and their
+ *             last j symbols are equal.  tot_j: the matching examples of the group; cnt_j(c): those whose next symbol is c.
+ *   j*        the largest j <= min(order, i + 1) with tot_j > 0; none: the verdict is UNKNOWN (not a mistake).
+ *   allowed   class c, when cnt(c) > 0 and cnt(c) * den >= tot * num at j* (64-bit products; 0 <= num <= den <= 32768).  MISTAKE: e_i
+ *             is not allowed.  order 1 with num/den = 1/N is the rule of step_anticipation/src/data/frequentist_baseline.py.
+ *   verdict   8 int32 words (two 16-byte stores): flags | cnt(e_i) | tot | group used | allowed mask, bits 0..31 | 32..63 | 64..95 |
+ *             96..127.  flags: 1 JUDGED, 2 MISTAKE, 4 UNKNOWN, 8 SKIPPED, j* in bits 8..15.  A SKIPPED verdict is 8 | 0 | 0 | -1 | 0 ...
+ * prego_procedure_model_create: validates the corpus on the host - transcripts t = 0 .. n_transcripts - 1 (HOST arrays) with group
+ * groups[t] in 0..2^20 - 1, symbols[offsets[t] .. offsets[t + 1]) each in [0, n_classes), targets (nullable: every position) one byte per
+ * symbol -, sorts it by group and enqueues ONE copy of the laid-out corpus into device_block: device memory, 256-byte aligned, at least
+ * prego_procedure_model_bytes(n_groups = 1 + the largest group, n_transcripts, n_symbols, n_examples) bytes, the caller's, only read
+ * afterwards.  Caps, from the word widths: n_symbols + n_transcripts <= 2^30 (a position is an int32 word), n_examples <= 2^24 (counts
+ * are int32 words; cnt * den fits 64 bits), 2^20 groups.  The model object holds host memory only; the block must outlive it.
+ * prego_procedure_judge (the offline / evaluation entry): sequence s = symbols[offsets[s] .. offsets[s + 1]) with group groups[s], all
+ * DEVICE int32 (offsets [n_sequences + 1] ascending from 0 to n_positions); verdict t judges symbols[t] after its sequence's symbols in
+ * front of it.  verdicts: device, 256-byte aligned, n_positions * 32 bytes.
+ * prego_stream_pool_feed_judge / prego_vit_stream_pool_feed_judge: `report` is what prego_stream_pool_feed_drain wrote earlier on the
+ * same stream, still on the device; its count is read there.  Verdict k judges entry k: e_i = the entry's step id, the history the
+ * slot's record event_id[.. index - 1], the group slot_groups[slot] (DEVICE int32 [capacity], the caller's).  An overflow entry
+ * (index -1), a slot outside the pool or an index at or beyond the record's n_events (clamped to 0..max_events) is SKIPPED.  verdicts:
+ * device, 256-byte aligned, max_out * 32 bytes; nothing is written behind verdict `count`.  The pool's block, the report and the model
+ * are only read.
+ * One launch each, one wave per judged item over a bounded grid; integers only, no global atomics (a verdict is a function of the
+ * inputs alone), no device allocation, no host wait.  PREGO_EINVAL / PREGO_EWORKSPACE (a block or buffer too small) with a message,
+ * nothing copied or launched: a NULL argument, an unaligned block, report or verdict buffer, n_classes, order, threshold, a group or a
+ * symbol out of range, descending offsets, a corpus beyond the caps. */
+typedef struct prego_procedure_model prego_procedure_model;
+size_t prego_procedure_model_bytes(int n_groups, int64_t n_transcripts, int64_t n_symbols, int64_t n_examples);
+int prego_procedure_model_create(prego_procedure_model** out, int n_classes, int order, int thr_num, int thr_den, int n_transcripts,
+                                 const int32_t* groups, const int64_t* offsets, const int32_t* symbols, const uint8_t* targets /* nullable */,
+                                 void* device_block, size_t bytes, prego_stream_t stream);
+void prego_procedure_model_destroy(prego_procedure_model* m);
+int prego_procedure_judge(const prego_procedure_model* m, int n_sequences, int n_positions, const int32_t* offsets, const int32_t* symbols,
+                          const int32_t* groups, void* verdicts, size_t verdict_bytes, prego_stream_t stream);
+int prego_stream_pool_feed_judge(const prego_stream_pool_feed* f, const prego_procedure_model* m, const void* report, size_t report_bytes,
+                                 const int32_t* slot_groups, void* verdicts, size_t verdict_bytes, prego_stream_t stream);
+int prego_vit_stream_pool_feed_judge(const prego_stream_pool_feed* f, const prego_procedure_model* m, const void* report, size_t report_bytes,
+                                     const int32_t* slot_groups, void* verdicts, size_t verdict_bytes, prego_stream_t stream);
+
 /* Training of the "Transformer" registry entry: trainer/train.py:20-24 (fwd, loss, backward) over ViTEnc (ViT.py:117-143,
  * Transformer.py:5-82, Attention.py:21-41).  forward_train is ViTEnc.forward in training mode with every dropout rate 0
  * (cfg['dropout'] == cfg['attn_dropout_rate'] == 0; non-zero rates are rejected by the host module) and keeps the activations

@@ -60,6 +60,8 @@ SYMBOLS = [
     "prego_perframe_cap_workspace_bytes", "prego_perframe_cap", "prego_perframe_cap_labels",
     "prego_perstage_cap_workspace_bytes", "prego_perstage_cap_labels",
     "prego_thumos_postprocess_workspace_bytes", "prego_thumos_postprocess", "prego_thumos_postprocess_labels",
+    "prego_procedure_model_bytes", "prego_procedure_model_create", "prego_procedure_model_destroy", "prego_procedure_judge",
+    "prego_stream_pool_feed_judge", "prego_vit_stream_pool_feed_judge",
 ]
 THUMOS_SMOOTH, THUMOS_SWITCH = 1, 2          # PREGO_THUMOS_SMOOTH / _SWITCH
 THUMOS_TILE_ROWS = 128                       # PREGO_THUMOS_TILE_ROWS: rows per scatter tile of prego_thumos_postprocess
@@ -229,7 +231,15 @@ def _open(path: str, debug: bool) -> C.CDLL:
     lib.prego_stream_pool_feed_destroy.restype = None
     lib.prego_stream_pool_feed_drain.argtypes = [vp, vp, sz, vp]
     lib.prego_stream_pool_feed_forget.argtypes = [vp, i32, C.POINTER(C.c_int32), vp]
+    lib.prego_procedure_model_bytes.argtypes = [i32, i64, i64, i64]
+    lib.prego_procedure_model_bytes.restype = sz
+    lib.prego_procedure_model_create.argtypes = [C.POINTER(vp), i32, i32, i32, i32, i32, C.POINTER(C.c_int32), C.POINTER(i64), C.POINTER(C.c_int32),
+                                                 C.POINTER(C.c_uint8), vp, sz, vp]
+    lib.prego_procedure_model_destroy.argtypes = [vp]
+    lib.prego_procedure_model_destroy.restype = None
+    lib.prego_procedure_judge.argtypes = [vp, i32, i32, vp, vp, vp, vp, sz, vp]
     for pre in ("prego_stream_pool", "prego_vit_stream_pool"):
+        getattr(lib, pre + "_feed_judge").argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
         getattr(lib, pre + "_image_bytes").argtypes = [vp]
         getattr(lib, pre + "_image_bytes").restype = sz
         getattr(lib, pre + "_snapshot").argtypes = [vp, vp, i32, C.POINTER(C.c_int32), vp, sz, vp]

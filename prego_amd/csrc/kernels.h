@@ -422,6 +422,27 @@ int launch_feed_drain(const PoolGeom& g, const FeedGeom& f, int* report, hipStre
 // cursor[slots[i]] <- 0; slots: HOST, n in 1..256, each in [0, capacity); -1 = nothing launched
 int launch_feed_forget(const FeedGeom& f, int capacity, const int* slots, int n, hipStream_t s);
 
+// procedure model (procedure.hip): a grouped corpus of step transcripts in the caller's device block, judged as a back-off n-gram model
+constexpr int kProcMaxOrder = 8, kProcMaxClasses = 128, kProcMaxDen = 32768;
+constexpr int kProcStart = 0xff;         // the virtual first symbol of every transcript in `sym`
+constexpr int kProcNoMatch = 0xfe;       // a queried symbol outside [0, ncls): equal to nothing in `sym`
+constexpr int kProcJudged = 1, kProcMistake = 2, kProcUnknown = 4, kProcSkipped = 8, kProcJstarShift = 8;      // a verdict's flags word
+constexpr int kProcVerdictWords = 8;
+constexpr int kProcWaves = 4;            // judged items per workgroup trip: one wave each
+constexpr int kProcMaxGrid = 1024;       // workgroups of a judging launch; they stride over the items
+struct ProcGeom {
+  const int* goff;                       // [n_groups + 1]: group g's examples are ex[goff[g] .. goff[g + 1])
+  const int* ex;                         // [n_examples]: the position in sym of each example's next symbol, sorted by group
+  const unsigned char* sym;              // per transcript kProcStart, s_0 .. s_{n-1}; sym[0] is a START, so a backward compare ends inside
+  int ncls, order, n_groups, n_examples, n_sym, num, den;       // n_sym: bytes of sym
+};
+// offsets [n_seq + 1], symbols [n_pos], groups [n_seq]: device; verdicts: device, 16-byte aligned, n_pos x 32 bytes; -1 = nothing launched
+int launch_procedure_judge(const ProcGeom& m, int n_seq, int n_pos, const int* offsets, const int* symbols, const int* groups, int* verdicts,
+                           hipStream_t s);
+// report: what launch_feed_drain wrote (its count is read on the device); slot_groups [g.capacity]: device; verdicts: device, 16-byte
+// aligned, max_out x 32 bytes, entry k's verdict at k.  Reads g's records, writes the verdicts alone; -1 = nothing launched
+int launch_feed_judge(const ProcGeom& m, const PoolGeom& g, int max_out, const int* report, const int* slot_groups, int* verdicts, hipStream_t s);
+
 // Transformer stream pool (vit_stream.hip): a ring of encoded frames per slot in the caller's device block.  ring [capacity][T][E] fp32,
 // row f mod T = linear_encoding(frame f); hf [capacity][4] int32 = head (next row to write) | fill (rows that hold a frame) | 0 | 0
 struct VitRing {

@@ -4,7 +4,8 @@ step's bits (prego_miniroad_step_pool: gather, the unchanged prego_miniroad_step
 returns what `aggregate` would return for the stream's per-frame predictions ('pred', 'changes_pred'); no argmax crosses to the host on
 the way.  `SlotTable` is the host bookkeeping (which slots are open), usable without a device.  `EventFeed` (`pool.event_feed()`,
 csrc/stream_feed.hip) tells a live consumer which slots gained an event since it last asked, in one asynchronous report per tick;
-`FeedModel` is its host model.  `pool.snapshot` / `restore` / `detach` (csrc/stream_image.hip) take live slots out of a pool as a
+`FeedModel` is its host model; `MistakeMonitor` (`pool.mistake_monitor(model)`, csrc/procedure.hip) judges every drained event against a
+procedure model on the device, `MonitorModel` is its host model.  `pool.snapshot` / `restore` / `detach` (csrc/stream_image.hip) take live slots out of a pool as a
 `PoolSnapshot` of canonical images and put them into a pool again - another pool, other slot numbers, another device or process -,
 validated on the device before a slot is written; `image_fault`, `image_layout` and `model_image` are their host model."""
 from __future__ import annotations
@@ -197,6 +198,11 @@ class _RecordPool:
         """An `EventFeed` over this pool: `feed.drain()` reports every event that any slot's record gained since the previous drain,
         whatever push variant produced it, in one asynchronous copy of at most `max_out` entries; `depth` reports may be in flight."""
         return EventFeed(self, max_out, depth)
+
+    def mistake_monitor(self, model, max_out: int = 1024, depth: int = 2) -> "MistakeMonitor":
+        """A `MistakeMonitor` over this pool: an event feed of its own whose every drained event is judged on the device against the
+        procedure model `model` (a `ProcedureModel` or its `.to(device)`; prego_amd/procedure.py) before the report leaves it."""
+        return MistakeMonitor(self, model, max_out, depth)
 
     # -- slot images: a live slot as data (csrc/stream_image.hip) ----------------------------------
     def image_geometry(self) -> dict:
@@ -618,6 +624,135 @@ class EventFeed:
         with torch.cuda.device(self.device):
             self.pool._check(self.lib.prego_stream_pool_feed_forget(self.f, len(slots), self.pool._slot_array(slots),
                                                                     C.c_void_p(self.pool._stream_ptr(self.device))))
+
+
+class MonitorModel:
+    """Host model of a `MistakeMonitor`, usable without a device and the counterpart of `FeedModel`: a FeedModel over `records`, a group
+    per slot (-1 until `set_group`; `forget` - what the pool's close does - puts it back) and the `ProcedureModel` that judges.
+    `drain()` returns FeedModel's dict with 'verdicts', one `Verdict` per entry: the entry's step after the slot's events in front of
+    it, in the slot's group; an overflow entry, or an event the record no longer holds, is SKIPPED."""
+
+    def __init__(self, records, model, max_out: int = 1024):
+        self.feed, self.model, self.records = FeedModel(records, max_out), model, records
+        self.groups = [-1] * len(records)
+
+    def set_group(self, slots, groups):
+        for s, g in zip(slots, groups):
+            self.groups[s] = int(g)
+
+    def forget(self, slots):
+        self.feed.forget(slots)
+        for s in slots:
+            self.groups[s] = -1
+
+    def judge_entry(self, entry):
+        from .procedure import SKIPPED_VERDICT
+        slot, index, step, _ = entry
+        rec = self.records[slot]
+        if index < 0 or index >= min(len(rec.event_id), rec.max_events):
+            return SKIPPED_VERDICT
+        return self.model.judge(rec.event_id[:index], step, self.groups[slot])
+
+    def drain(self) -> dict:
+        r = self.feed.drain()
+        r["verdicts"] = [self.judge_entry(e) for e in r["entries"]]
+        return r
+
+
+class _MonitorFeed(EventFeed):
+    """the feed a monitor owns: a slot the pool has it forget (close, detach, a restore that does not name it) loses its group too"""
+    _monitor = None
+
+    def forget(self, slots):
+        super().forget(slots)
+        mon = self._monitor() if self._monitor is not None else None
+        if mon is not None:
+            mon._ungroup([int(s) for s in slots])
+
+
+class MonitorTicket:
+    """One monitor drain in flight: `events()` - the report's entries (slot, index, step, start), overflow entries (index -1) included -
+    and `verdicts()` - one `Verdict` per entry, index-aligned; both wait if they must and hand the buffers back to the monitor.
+    `count`, `pending`, `seq`, `ready()` as `FeedTicket` has them."""
+
+    def __init__(self, monitor, feed_ticket, k: int):
+        self._mon, self._ft, self._k, self._got = monitor, feed_ticket, k, None
+
+    def ready(self) -> bool:
+        return self._got is not None or self._mon._done[self._k].query()
+
+    def _wait(self):
+        if self._got is None:
+            from .procedure import VERDICT_WORDS, Verdict
+            self._mon._done[self._k].synchronize()               # recorded behind the verdict copy: the report has landed as well
+            entries = self._ft.entries                           # hands the report buffer back
+            rows = self._mon._host[self._k][:VERDICT_WORDS * len(entries)].view(len(entries), VERDICT_WORDS).tolist()
+            self._got = (entries, [Verdict.from_words(w) for w in rows])
+        return self._got
+
+    count = property(lambda self: self._ft.count)
+    pending = property(lambda self: self._ft.pending)
+    seq = property(lambda self: self._ft.seq)
+
+    def events(self) -> list:
+        return list(self._wait()[0])
+
+    def verdicts(self) -> list:
+        return list(self._wait()[1])
+
+
+class MistakeMonitor:
+    """MistakeMonitor(pool, model, max_out=1024, depth=2) - `pool.mistake_monitor(model)`: online mistake detection behind the drain
+    (csrc/procedure.hip).  It owns an `EventFeed` (`.feed`), a group per slot on the device (-1: judged against every group) and
+    `depth` pinned verdict buffers.  `drain()` enqueues, on the current stream, the feed's drain, one judging launch over the report
+    where it lies and both copies, and returns a `MonitorTicket` without waiting.  `set_group(slots, groups)` is stream-ordered: it
+    holds for the drains enqueued after it.  When the pool closes a slot its group goes back to -1; slot images carry no group, so a
+    restored slot has -1 until `set_group`."""
+
+    def __init__(self, pool, model, max_out: int = 1024, depth: int = 2):
+        from .procedure import VERDICT_WORDS, ProcedureModel
+        self.pool, self.lib, self.device = pool, pool.lib, pool.device
+        self.model = model.to(self.device, lib=self.lib) if isinstance(model, ProcedureModel) else model
+        if getattr(self.model, "m", None) is None or torch.device(self.model.device) != torch.device(self.device):
+            raise PregoError(f"mistake monitor: expected a ProcedureModel or its .to({self.device}), got {type(model).__name__}")
+        self.feed = _MonitorFeed(pool, max_out, depth)
+        self.feed._monitor = weakref.ref(self)
+        self.max_out, self.depth = self.feed.max_out, self.feed.depth
+        self._judge = getattr(self.lib, pool._C["feed_create"].replace("_feed_create", "_feed_judge"))
+        self._groups = torch.full((pool.capacity,), -1, dtype=torch.int32, device=self.device)
+        self._dev = [torch.empty(self.max_out * VERDICT_WORDS, dtype=torch.int32, device=self.device) for _ in range(self.depth)]
+        self._host = [torch.empty(self.max_out * VERDICT_WORDS, dtype=torch.int32).pin_memory() for _ in range(self.depth)]
+        self._done = [torch.cuda.Event() for _ in range(self.depth)]
+
+    def set_group(self, slots, groups):
+        """group groups[i] (>= -1) for open slot slots[i], from the next drain on"""
+        slots = self.pool._open_slots(slots, "mistake monitor set_group")
+        groups = [int(g) for g in groups]
+        if len(groups) != len(slots) or any(g < -1 for g in groups):
+            raise PregoError(f"mistake monitor set_group: {len(slots)} slots, groups {groups} (one per slot, each >= -1)")
+        self._put(slots, groups)
+
+    def _put(self, slots, groups):
+        with torch.cuda.device(self.device):
+            self._groups.index_copy_(0, torch.tensor(slots, dtype=torch.int64).to(self.device), torch.tensor(groups, dtype=torch.int32).to(self.device))
+
+    def _ungroup(self, slots):
+        self._put(slots, [-1] * len(slots))
+
+    def groups(self) -> list:
+        """the group of every slot; it waits for the stream"""
+        return self._groups.cpu().tolist()
+
+    def drain(self) -> MonitorTicket:
+        k = self.feed._next
+        ft = self.feed.drain()                                   # raises, before anything is launched, when buffer k is unread
+        with torch.cuda.device(self.device):
+            self.pool._check(self._judge(self.feed.f, self.model.m, C.c_void_p(self.feed._dev[k].data_ptr()), self.feed._report_bytes,
+                                         C.c_void_p(self._groups.data_ptr()), C.c_void_p(self._dev[k].data_ptr()), self._dev[k].numel() * 4,
+                                         C.c_void_p(self.pool._stream_ptr(self.device))))
+            self._host[k].copy_(self._dev[k], non_blocking=True)
+            self._done[k].record()
+        return MonitorTicket(self, ft, k)
 
 
 class StreamPool(_RecordPool):
