@@ -856,6 +856,40 @@ int prego_stream_pool_feed_judge(const prego_stream_pool_feed* f, const prego_pr
 int prego_vit_stream_pool_feed_judge(const prego_stream_pool_feed* f, const prego_procedure_model* m, const void* report, size_t report_bytes,
                                      const int32_t* slot_groups, void* verdicts, size_t verdict_bytes, prego_stream_t stream);
 
+/* Next-step forecast from the procedure model (an addition to ABI 7, existing signatures unchanged): the histogram a verdict is read
+ * from, handed out ranked.  Definitions (everything of 13l above holds):
+ *   query     a history START, e_0 .. e_{n-1} with n >= 0 steps, all of them context, and a group q.  len = min(order, n + 1).
+ *   j*        the largest j <= len with tot_j > 0; none: the forecast is UNKNOWN.
+ *   ranked    the candidates - classes with cnt_{j*}(c) > 0 - by count descending, equal counts by ascending class id; the forecast
+ *             holds the first min(8, n_cand).  The allowed mask is the verdict's rule on the same row.
+ *   identity  the forecast after e_0 .. e_{i-1} in group q has the j*, tot and allowed mask of the verdict of e_i after that history.
+ *   forecast  24 int32 words (six 16-byte stores): flags | n_cand | tot | group used | allowed mask [4] | id [8] | cnt [8].  flags: 1 MADE,
+ *             4 UNKNOWN, 8 SKIPPED, j* in bits 8..15, ranked entries (0..8) in bits 16..19; unused ranks hold id -1, cnt 0.
+ *             UNKNOWN: 1|4, 0, 0, group, 0 x 4, -1 x 8, 0 x 8.  SKIPPED: 8, 0, 0, -1, 0 x 4, -1 x 8, 0 x 8.
+ * prego_procedure_forecast (offline): the sequences as prego_procedure_judge takes them, except that n_positions may be 0 (every
+ * sequence empty; symbols still not NULL).  Sequence s with L_s symbols yields L_s + 1 forecasts, after its first p = 0 .. L_s symbols,
+ * at row offsets[s] + s + p: n_positions + n_sequences rows.  Row (s, p) forecasts symbol p; the last row what would follow the sequence.
+ * prego_stream_pool_feed_forecast / prego_vit_stream_pool_feed_forecast: the arguments of _feed_judge.  Forecast k says what comes
+ * after entry k: its history is the slot's event_id[.. index - 1] followed by the entry's own step id.  SKIPPED as _feed_judge; nothing
+ * is written behind forecast `count`.
+ * prego_stream_pool_forecast / prego_vit_stream_pool_forecast: slots (DEVICE int32 [n], 1 <= n <= capacity; a slot may repeat) and
+ * slot_groups (DEVICE int32 [capacity]).  Forecast i says what comes after every event slot slots[i]'s record holds (n_events clamped to
+ * 0..max_events; none: a START-only query); a slot outside the pool is SKIPPED.
+ * forecasts: device, 16-byte aligned, 96 bytes per row.  One launch each, a wave per row; integers only, no global atomics, no device
+ * allocation, no host wait.  PREGO_EINVAL / PREGO_EWORKSPACE (a buffer too small) with a message, nothing launched: a NULL argument, an
+ * unaligned buffer, n or the sequence counts out of range. */
+int prego_procedure_forecast(const prego_procedure_model* m, int n_sequences, int n_positions, const int32_t* offsets, const int32_t* symbols,
+                             const int32_t* groups, void* forecasts, size_t forecast_bytes, prego_stream_t stream);
+int prego_stream_pool_feed_forecast(const prego_stream_pool_feed* f, const prego_procedure_model* m, const void* report, size_t report_bytes,
+                                    const int32_t* slot_groups, void* forecasts, size_t forecast_bytes, prego_stream_t stream);
+int prego_vit_stream_pool_feed_forecast(const prego_stream_pool_feed* f, const prego_procedure_model* m, const void* report,
+                                        size_t report_bytes, const int32_t* slot_groups, void* forecasts, size_t forecast_bytes,
+                                        prego_stream_t stream);
+int prego_stream_pool_forecast(const prego_stream_pool* p, const prego_procedure_model* m, const int32_t* slots, int n,
+                               const int32_t* slot_groups, void* forecasts, size_t forecast_bytes, prego_stream_t stream);
+int prego_vit_stream_pool_forecast(const prego_vit_stream_pool* p, const prego_procedure_model* m, const int32_t* slots, int n,
+                                   const int32_t* slot_groups, void* forecasts, size_t forecast_bytes, prego_stream_t stream);
+
 /* Training of the "Transformer" registry entry: trainer/train.py:20-24 (fwd, loss, backward) over ViTEnc (ViT.py:117-143,
  * Transformer.py:5-82, Attention.py:21-41).  forward_train is ViTEnc.forward in training mode with every dropout rate 0
  * (cfg['dropout'] == cfg['attn_dropout_rate'] == 0; non-zero rates are rejected by the host module) and keeps the activations

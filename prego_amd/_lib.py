@@ -62,6 +62,8 @@ SYMBOLS = [
     "prego_thumos_postprocess_workspace_bytes", "prego_thumos_postprocess", "prego_thumos_postprocess_labels",
     "prego_procedure_model_bytes", "prego_procedure_model_create", "prego_procedure_model_destroy", "prego_procedure_judge",
     "prego_stream_pool_feed_judge", "prego_vit_stream_pool_feed_judge",
+    "prego_procedure_forecast", "prego_stream_pool_feed_forecast", "prego_vit_stream_pool_feed_forecast",
+    "prego_stream_pool_forecast", "prego_vit_stream_pool_forecast",
 ]
 THUMOS_SMOOTH, THUMOS_SWITCH = 1, 2          # PREGO_THUMOS_SMOOTH / _SWITCH
 THUMOS_TILE_ROWS = 128                       # PREGO_THUMOS_TILE_ROWS: rows per scatter tile of prego_thumos_postprocess
@@ -238,8 +240,11 @@ def _open(path: str, debug: bool) -> C.CDLL:
     lib.prego_procedure_model_destroy.argtypes = [vp]
     lib.prego_procedure_model_destroy.restype = None
     lib.prego_procedure_judge.argtypes = [vp, i32, i32, vp, vp, vp, vp, sz, vp]
+    lib.prego_procedure_forecast.argtypes = [vp, i32, i32, vp, vp, vp, vp, sz, vp]
     for pre in ("prego_stream_pool", "prego_vit_stream_pool"):
         getattr(lib, pre + "_feed_judge").argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
+        getattr(lib, pre + "_feed_forecast").argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
+        getattr(lib, pre + "_forecast").argtypes = [vp, vp, vp, i32, vp, vp, sz, vp]
         getattr(lib, pre + "_image_bytes").argtypes = [vp]
         getattr(lib, pre + "_image_bytes").restype = sz
         getattr(lib, pre + "_snapshot").argtypes = [vp, vp, i32, C.POINTER(C.c_int32), vp, sz, vp]

@@ -442,6 +442,20 @@ int launch_procedure_judge(const ProcGeom& m, int n_seq, int n_pos, const int* o
 // report: what launch_feed_drain wrote (its count is read on the device); slot_groups [g.capacity]: device; verdicts: device, 16-byte
 // aligned, max_out x 32 bytes, entry k's verdict at k.  Reads g's records, writes the verdicts alone; -1 = nothing launched
 int launch_feed_judge(const ProcGeom& m, const PoolGeom& g, int max_out, const int* report, const int* slot_groups, int* verdicts, hipStream_t s);
+// next-step forecast: the histogram row a verdict is read from, ranked (count descending, equal counts by ascending class id)
+constexpr int kProcMade = kProcJudged;   // a forecast's flags word: MADE | UNKNOWN | SKIPPED, j* as a verdict, ranked entries in bits 16..19
+constexpr int kProcRankedShift = 16, kProcRanks = 8;
+constexpr int kProcForecastWords = 24;   // flags | n_cand | tot | group | mask [4] | id [8] | cnt [8]
+// offsets [n_seq + 1], symbols [max(n_pos, 1)], groups [n_seq]: device; forecasts: device, 16-byte aligned, (n_pos + n_seq) x 96 bytes, the
+// forecast after the first p symbols of sequence s at row offsets[s] + s + p; n_pos 0: every sequence is empty; -1 = nothing launched
+int launch_procedure_forecast(const ProcGeom& m, int n_seq, int n_pos, const int* offsets, const int* symbols, const int* groups,
+                              int* forecasts, hipStream_t s);
+// as launch_feed_judge; forecast k says what follows entry k: the history is the slot's events in front of it and its own step id
+int launch_feed_forecast(const ProcGeom& m, const PoolGeom& g, int max_out, const int* report, const int* slot_groups, int* forecasts,
+                         hipStream_t s);
+// slots [n] (1 <= n <= g.capacity, any words), slot_groups [g.capacity]: device; forecast i says what follows every event slot slots[i]'s
+// record holds, a slot outside the pool is SKIPPED; forecasts: device, 16-byte aligned, n x 96 bytes; -1 = nothing launched
+int launch_pool_forecast(const ProcGeom& m, const PoolGeom& g, int n, const int* slots, const int* slot_groups, int* forecasts, hipStream_t s);
 
 // Transformer stream pool (vit_stream.hip): a ring of encoded frames per slot in the caller's device block.  ring [capacity][T][E] fp32,
 // row f mod T = linear_encoding(frame f); hf [capacity][4] int32 = head (next row to write) | fill (rows that hold a frame) | 0 | 0

@@ -1,4 +1,5 @@
-// Host side of the procedure model (include/prego_amd.h: prego_procedure_*, prego_stream_pool_feed_judge; kernels: procedure.hip).  Create
+// Host side of the procedure model (include/prego_amd.h: prego_procedure_*, prego_stream_pool_feed_judge, the _forecast entries at the
+// end of this file; kernels: procedure.hip).  Create
 // validates the corpus, sorts it by group and lays it out for the caller's device block; the model object keeps the host image alive for
 // the copy and the geometry for the launches.  Every entry point decides all its refusals before its first copy or launch, so a refused
 // call has written nothing.
@@ -179,4 +180,93 @@ extern "C" int prego_vit_stream_pool_feed_judge(const prego_stream_pool_feed* f,
                                                 size_t report_bytes, const int32_t* slot_groups, void* verdicts, size_t verdict_bytes,
                                                 prego_stream_t stream) {
   return feed_judge("vit_stream_pool_feed_judge", f, m, report, report_bytes, slot_groups, verdicts, verdict_bytes, stream);
+}
+
+// ---- next-step forecast: the same refusals in the same order for the five entries, decided before the launch ------------------------------
+namespace {
+size_t forecast_bytes_for(long long n) { return (size_t)n * kProcForecastWords * 4; }
+
+// the forecast buffer of `rows` rows (`what` names them in the message); 0 = fine
+int forecast_buffer_ok(const char* who, const void* forecasts, size_t forecast_bytes, long long rows, const char* what) {
+  if (!forecasts) return prego_fail_(PREGO_EINVAL, "%s: forecasts is NULL", who);
+  if ((uintptr_t)forecasts & 15) return prego_fail_(PREGO_EINVAL, "%s: the forecasts must be 16-byte aligned", who);
+  const size_t need = forecast_bytes_for(rows);
+  if (forecast_bytes < need)
+    return prego_fail_(PREGO_EWORKSPACE, "%s: forecasts with %zu bytes, %lld %s need %zu (96 each)", who, forecast_bytes, rows, what, need);
+  return 0;
+}
+
+int feed_forecast(const char* who, const prego_stream_pool_feed* f, const prego_procedure_model* m, const void* report, size_t report_bytes,
+                  const int32_t* slot_groups, void* forecasts, size_t forecast_bytes, prego_stream_t stream) {
+  if (!f) return prego_fail_(PREGO_EINVAL, "%s: feed is NULL", who);
+  if (!m) return prego_fail_(PREGO_EINVAL, "%s: model is NULL", who);
+  if (!report) return prego_fail_(PREGO_EINVAL, "%s: report is NULL", who);
+  if ((uintptr_t)report & 255) return prego_fail_(PREGO_EINVAL, "%s: the report must be 256-byte aligned", who);
+  const int max_out = stream_pool_feed_geom(f)->max_out;
+  const size_t need_report = prego_stream_pool_feed_report_bytes(max_out);
+  if (report_bytes < need_report)
+    return prego_fail_(PREGO_EWORKSPACE, "%s: report with %zu bytes, %d entries need %zu (prego_stream_pool_feed_report_bytes)", who, report_bytes,
+                       max_out, need_report);
+  if (!slot_groups) return prego_fail_(PREGO_EINVAL, "%s: slot_groups is NULL", who);
+  if (int rc = forecast_buffer_ok(who, forecasts, forecast_bytes, max_out, "entries")) return rc;
+  if (launch_feed_forecast(m->g, *stream_pool_feed_pool(f), max_out, (const int*)report, slot_groups, (int*)forecasts, (hipStream_t)stream))
+    return prego_fail_(PREGO_EINVAL, "%s: bad arguments", who);
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+int pool_forecast(const char* who, const PoolGeom* g, const prego_procedure_model* m, const int32_t* slots, int n, const int32_t* slot_groups,
+                  void* forecasts, size_t forecast_bytes, prego_stream_t stream) {
+  if (!g) return prego_fail_(PREGO_EINVAL, "%s: pool is NULL", who);
+  if (!m) return prego_fail_(PREGO_EINVAL, "%s: model is NULL", who);
+  if (n < 1 || n > g->capacity) return prego_fail_(PREGO_EINVAL, "%s: %d slots (1..%d, the pool's capacity)", who, n, g->capacity);
+  if (!slots) return prego_fail_(PREGO_EINVAL, "%s: slots is NULL", who);
+  if (!slot_groups) return prego_fail_(PREGO_EINVAL, "%s: slot_groups is NULL", who);
+  if (int rc = forecast_buffer_ok(who, forecasts, forecast_bytes, n, "slots")) return rc;
+  if (launch_pool_forecast(m->g, *g, n, slots, slot_groups, (int*)forecasts, (hipStream_t)stream))
+    return prego_fail_(PREGO_EINVAL, "%s: bad arguments", who);
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+}  // namespace
+
+extern "C" int prego_procedure_forecast(const prego_procedure_model* m, int n_sequences, int n_positions, const int32_t* offsets,
+                                        const int32_t* symbols, const int32_t* groups, void* forecasts, size_t forecast_bytes,
+                                        prego_stream_t stream) {
+  const char* who = "procedure_forecast";
+  if (!m) return prego_fail_(PREGO_EINVAL, "%s: model is NULL", who);
+  if (n_sequences < 1 || n_positions < 0 || (long long)n_positions + n_sequences > kProcMaxSymbols)
+    return prego_fail_(PREGO_EINVAL, "%s: %d sequences with %d positions (1 <= sequences, 0 <= positions, together at most %lld)", who, n_sequences,
+                       n_positions, kProcMaxSymbols);
+  if (!offsets) return prego_fail_(PREGO_EINVAL, "%s: offsets is NULL", who);
+  if (!symbols) return prego_fail_(PREGO_EINVAL, "%s: symbols is NULL", who);
+  if (!groups) return prego_fail_(PREGO_EINVAL, "%s: groups is NULL", who);
+  if (int rc = forecast_buffer_ok(who, forecasts, forecast_bytes, (long long)n_positions + n_sequences, "rows")) return rc;
+  if (launch_procedure_forecast(m->g, n_sequences, n_positions, offsets, symbols, groups, (int*)forecasts, (hipStream_t)stream))
+    return prego_fail_(PREGO_EINVAL, "%s: bad arguments", who);
+  HIPCHK(hipGetLastError());
+  return PREGO_OK;
+}
+
+extern "C" int prego_stream_pool_feed_forecast(const prego_stream_pool_feed* f, const prego_procedure_model* m, const void* report,
+                                               size_t report_bytes, const int32_t* slot_groups, void* forecasts, size_t forecast_bytes,
+                                               prego_stream_t stream) {
+  return feed_forecast("stream_pool_feed_forecast", f, m, report, report_bytes, slot_groups, forecasts, forecast_bytes, stream);
+}
+
+extern "C" int prego_vit_stream_pool_feed_forecast(const prego_stream_pool_feed* f, const prego_procedure_model* m, const void* report,
+                                                   size_t report_bytes, const int32_t* slot_groups, void* forecasts, size_t forecast_bytes,
+                                                   prego_stream_t stream) {
+  return feed_forecast("vit_stream_pool_feed_forecast", f, m, report, report_bytes, slot_groups, forecasts, forecast_bytes, stream);
+}
+
+extern "C" int prego_stream_pool_forecast(const prego_stream_pool* p, const prego_procedure_model* m, const int32_t* slots, int n,
+                                          const int32_t* slot_groups, void* forecasts, size_t forecast_bytes, prego_stream_t stream) {
+  return pool_forecast("stream_pool_forecast", p ? stream_pool_geom(p) : nullptr, m, slots, n, slot_groups, forecasts, forecast_bytes, stream);
+}
+
+extern "C" int prego_vit_stream_pool_forecast(const prego_vit_stream_pool* p, const prego_procedure_model* m, const int32_t* slots, int n,
+                                              const int32_t* slot_groups, void* forecasts, size_t forecast_bytes, prego_stream_t stream) {
+  return pool_forecast("vit_stream_pool_forecast", p ? vit_stream_pool_geom(p) : nullptr, m, slots, n, slot_groups, forecasts, forecast_bytes,
+                       stream);
 }

@@ -8,7 +8,11 @@ agree on every verdict word.
 
 `ProcedureModel` is the host model and the oracle of the kernel; `.to(device)` gives a `DeviceProcedureModel`, whose
 `judge_sequences` is the offline / evaluation entry (prego_procedure_judge) and which `pool.mistake_monitor(model)` judges a stream
-pool's event feed with (prego_stream_pool_feed_judge; prego_amd/stream_pool.py)."""
+pool's event feed with (prego_stream_pool_feed_judge; prego_amd/stream_pool.py).
+
+The same histogram answers "what should come next" (DESIGN section 13m): `ProcedureModel.forecast(history, group)` gives a `Forecast`,
+the first 8 steps seen after the longest known context by count, `forecast_sequences` / `anticipation_metrics` score it offline
+(prego_procedure_forecast on the device) and `pool.forecast_monitor(model)` reports it beside every verdict."""
 from __future__ import annotations
 
 import ctypes as C
@@ -64,6 +68,63 @@ class Verdict(NamedTuple):
 
 
 SKIPPED_VERDICT = Verdict(SKIPPED, 0, 0, -1, 0)          # an overflow entry of a feed, or an event the record no longer holds
+
+MADE = JUDGED                                            # a forecast's flags word: MADE | UNKNOWN | SKIPPED, j* as a verdict's,
+RANKED_SHIFT, RANKS, FORECAST_WORDS = 16, 8, 24          # the ranked entries (0..8) in bits 16..19 (csrc/kernels.h: kProcRank*)
+
+
+class Forecast(NamedTuple):
+    """What may come next after a history: flags (MADE | UNKNOWN | SKIPPED, j* in bits 8..15, ranked entries in
+    bits 16..19), n_cand = the classes seen after the longest known context, tot = their examples, the group the query used, the
+    128-bit mask of the allowed classes (a verdict's rule) and the first 8 candidates by count descending, equal counts by ascending
+    id: `ids` and `cnts`, unused ranks -1 and 0."""
+    flags: int
+    n_cand: int
+    tot: int
+    group: int
+    mask: int
+    ids: tuple
+    cnts: tuple
+
+    @property
+    def made(self) -> bool:
+        return bool(self.flags & MADE)
+
+    @property
+    def unknown(self) -> bool:
+        return bool(self.flags & UNKNOWN)
+
+    @property
+    def skipped(self) -> bool:
+        return bool(self.flags & SKIPPED)
+
+    @property
+    def jstar(self) -> int:
+        return (self.flags >> JSTAR_SHIFT) & 0xFF
+
+    @property
+    def n_ranked(self) -> int:
+        return (self.flags >> RANKED_SHIFT) & 0xF
+
+    def ranked(self) -> list:
+        """[(id, cnt)] of the ranked entries, the likeliest first"""
+        return list(zip(self.ids[:self.n_ranked], self.cnts[:self.n_ranked]))
+
+    def allowed(self) -> list:
+        return [c for c in range(MAX_CLASSES) if self.mask >> c & 1]
+
+    def words(self) -> list:
+        """the 24 int32 words the device writes: flags | n_cand | tot | group | mask [4] | id [8] | cnt [8]"""
+        m = [(self.mask >> (32 * k)) & 0xFFFFFFFF for k in range(4)]
+        return [self.flags, self.n_cand, self.tot, self.group] + [w - (1 << 32) if w >> 31 else w for w in m] + list(self.ids) + list(self.cnts)
+
+    @classmethod
+    def from_words(cls, w) -> "Forecast":
+        w = [int(v) for v in w]
+        return cls(w[0], w[1], w[2], w[3], sum((w[4 + k] & 0xFFFFFFFF) << (32 * k) for k in range(4)), tuple(w[8:16]), tuple(w[16:24]))
+
+
+SKIPPED_FORECAST = Forecast(SKIPPED, 0, 0, -1, 0, (-1,) * RANKS, (0,) * RANKS)     # where a verdict would be SKIPPED_VERDICT; a slot outside the pool
 
 
 class ProcedureModel:
@@ -213,6 +274,55 @@ class ProcedureModel:
         f1 = 2 * precision * recall / (precision + recall) if precision + recall else 0.0
         return {"tp": tp, "fp": fp, "fn": fn, "tn": tn, "unknown": unknown, "precision": precision, "recall": recall, "f1": f1}
 
+    # -- forecasting ---------------------------------------------------------------------------------
+    def forecast(self, history, group: int = -1) -> Forecast:
+        """history: every step so far, all of it context (START is implied); what the corpus saw next after the longest context it
+        knows.  The definition the device implements (group -1: every group); a symbol outside [0, n_classes) matches nothing."""
+        group = int(group)
+        ctx = [START] + [int(s) if 0 <= int(s) < self.n_classes else NO_MATCH for s in history]
+        rows = self._examples().get(None if group == -1 else group, {})
+        for j in range(min(self.order, len(ctx)), 0, -1):
+            row = rows.get(tuple(ctx[len(ctx) - j:]))
+            if row is None:
+                continue
+            tot = sum(row)
+            mask = sum(1 << c for c, n in enumerate(row) if n > 0 and n * self.den >= tot * self.num)
+            cand = sorted((c for c, n in enumerate(row) if n > 0), key=lambda c: (-row[c], c))
+            top = cand[:RANKS]
+            pad = RANKS - len(top)
+            return Forecast(MADE | j << JSTAR_SHIFT | len(top) << RANKED_SHIFT, len(cand), tot, group, mask,
+                            tuple(top) + (-1,) * pad, tuple(row[c] for c in top) + (0,) * pad)
+        return Forecast(MADE | UNKNOWN, 0, 0, group, 0, (-1,) * RANKS, (0,) * RANKS)
+
+    def forecast_sequences(self, sequences, groups=None) -> list:
+        """one list per sequence of len + 1 Forecasts: after its first p = 0 .. len steps.  Entry p forecasts step p, the last one
+        what would follow the sequence."""
+        sequences = [list(s) for s in sequences]
+        groups = [-1] * len(sequences) if groups is None else [int(g) for g in groups]
+        if len(groups) != len(sequences):
+            raise ValueError(f"ProcedureModel.forecast_sequences: {len(sequences)} sequences, {len(groups)} groups")
+        return [[self.forecast(s[:p], g) for p in range(len(s) + 1)] for s, g in zip(sequences, groups)]
+
+    def anticipation_metrics(self, sequences, groups=None, ks=(1, 3, 5), forecasts=None) -> dict:
+        """How often the true next step is among the model's first k: over every position p of every sequence, 'positions', 'unknown'
+        (an UNKNOWN forecast is a miss for every k and counted on its own) and 'top' = {k: the positions whose step is among the first
+        k ranked ids}, k <= 8.  `forecasts`: from elsewhere (the device's), as `forecast_sequences` shapes them."""
+        ks = tuple(int(k) for k in ks)
+        if any(not 1 <= k <= RANKS for k in ks):
+            raise ValueError(f"ProcedureModel.anticipation_metrics: ks {ks} (each 1..{RANKS}: a forecast holds {RANKS} ranks)")
+        sequences = [list(s) for s in sequences]
+        forecasts = self.forecast_sequences(sequences, groups) if forecasts is None else forecasts
+        positions = unknown = 0
+        top = {k: 0 for k in ks}
+        for s, fs in zip(sequences, forecasts):
+            for p, step in enumerate(s):
+                positions += 1
+                unknown += int(fs[p].unknown)
+                ids = [c for c, _ in fs[p].ranked()]
+                for k in ks:
+                    top[k] += int(int(step) in ids[:k])
+        return {"positions": positions, "unknown": unknown, "top": top}
+
     # -- the device ----------------------------------------------------------------------------------
     def flat(self):
         """(groups, offsets, symbols, target flags) of the corpus as prego_procedure_model_create takes them"""
@@ -290,6 +400,43 @@ class DeviceProcedureModel:
                                                 C.c_void_p(self._stream_ptr(self.device)))
         if rc != 0:
             raise PregoError(f"prego_amd error {rc}: {self.lib.prego_last_error().decode()}")
+        return out
+
+    def forecast_words(self, sequences, groups=None):
+        """int32 cuda [n_positions + n_sequences, 24]: the forecast words after the first p = 0 .. len steps of every sequence, in
+        order (prego_procedure_forecast); nothing waits"""
+        import torch
+
+        from ._lib import PregoError
+        sequences = [[int(v) for v in s] for s in sequences]
+        groups = [-1] * len(sequences) if groups is None else [int(g) for g in groups]
+        if len(groups) != len(sequences):
+            raise PregoError(f"procedure forecast: {len(sequences)} sequences, {len(groups)} groups")
+        offsets = [0]
+        for s in sequences:
+            offsets.append(offsets[-1] + len(s))
+        n_pos = offsets[-1]
+        out = torch.empty((n_pos + len(sequences), FORECAST_WORDS), dtype=torch.int32, device=self.device)
+        if not sequences:
+            return out
+        dev = lambda v: torch.tensor(v, dtype=torch.int32).to(self.device)
+        off_d, sym_d, grp_d = dev(offsets), dev([v for s in sequences for v in s] or [0]), dev(groups)
+        with torch.cuda.device(self.device):
+            rc = self.lib.prego_procedure_forecast(self.m, len(sequences), n_pos, C.c_void_p(off_d.data_ptr()), C.c_void_p(sym_d.data_ptr()),
+                                                   C.c_void_p(grp_d.data_ptr()), C.c_void_p(out.data_ptr()), out.numel() * 4,
+                                                   C.c_void_p(self._stream_ptr(self.device)))
+        if rc != 0:
+            raise PregoError(f"prego_amd error {rc}: {self.lib.prego_last_error().decode()}")
+        return out
+
+    def forecast_sequences(self, sequences, groups=None) -> list:
+        """`ProcedureModel.forecast_sequences` on the device: one list of len + 1 Forecasts per sequence.  One D2H copy; it waits."""
+        sequences = [list(s) for s in sequences]
+        rows = self.forecast_words(sequences, groups).cpu().tolist()
+        out, at = [], 0
+        for s in sequences:
+            out.append([Forecast.from_words(w) for w in rows[at:at + len(s) + 1]])
+            at += len(s) + 1
         return out
 
     def judge_sequences(self, sequences, groups=None) -> list:

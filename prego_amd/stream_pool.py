@@ -204,6 +204,11 @@ class _RecordPool:
         procedure model `model` (a `ProcedureModel` or its `.to(device)`; prego_amd/procedure.py) before the report leaves it."""
         return MistakeMonitor(self, model, max_out, depth)
 
+    def forecast_monitor(self, model, max_out: int = 1024, depth: int = 2) -> "ForecastMonitor":
+        """A `ForecastMonitor` over this pool: a mistake monitor whose drain also reports, per event, the steps the procedure model
+        expects next, and whose `forecast_slots(slots)` asks the same of open slots by name."""
+        return ForecastMonitor(self, model, max_out, depth)
+
     # -- slot images: a live slot as data (csrc/stream_image.hip) ----------------------------------
     def image_geometry(self) -> dict:
         """what an image of this pool's slots must match to be restored here (csrc/pool_image.h: tag words 2..7), as plain ints"""
@@ -658,6 +663,28 @@ class MonitorModel:
         r["verdicts"] = [self.judge_entry(e) for e in r["entries"]]
         return r
 
+    def forecast_entry(self, entry):
+        """what a `ForecastMonitor` reports beside the entry's verdict: the forecast after the slot's events in front of it and its own
+        step; SKIPPED where the verdict is"""
+        from .procedure import SKIPPED_FORECAST
+        slot, index, step, _ = entry
+        rec = self.records[slot]
+        if index < 0 or index >= min(len(rec.event_id), rec.max_events):
+            return SKIPPED_FORECAST
+        return self.model.forecast(list(rec.event_id[:index]) + [step], self.groups[slot])
+
+    def forecast_slots(self, slots) -> list:
+        """`ForecastMonitor.forecast_slots`: the forecast after every event a slot's record holds; a slot outside the records is SKIPPED"""
+        from .procedure import SKIPPED_FORECAST
+        out = []
+        for s in slots:
+            if not 0 <= s < len(self.records):
+                out.append(SKIPPED_FORECAST)
+                continue
+            rec = self.records[s]
+            out.append(self.model.forecast(rec.event_id[:min(len(rec.event_id), rec.max_events)], self.groups[s]))
+        return out
+
 
 class _MonitorFeed(EventFeed):
     """the feed a monitor owns: a slot the pool has it forget (close, detach, a restore that does not name it) loses its group too"""
@@ -753,6 +780,107 @@ class MistakeMonitor:
             self._host[k].copy_(self._dev[k], non_blocking=True)
             self._done[k].record()
         return MonitorTicket(self, ft, k)
+
+
+class ForecastTicket(MonitorTicket):
+    """One forecast-monitor drain in flight: a `MonitorTicket` that adds `forecasts()`, one `Forecast` per entry, index-aligned with
+    `events()` and `verdicts()`: what the model expects after that event.  The first read waits for all three copies."""
+
+    def _wait(self):
+        if self._got is None:
+            from .procedure import FORECAST_WORDS, Forecast
+            self._mon._fdone[self._k].synchronize()              # recorded behind the forecast copy: report and verdicts have landed
+            entries, verdicts = super()._wait()
+            rows = self._mon._fhost[self._k][:FORECAST_WORDS * len(entries)].view(len(entries), FORECAST_WORDS).tolist()
+            self._got = (entries, verdicts, [Forecast.from_words(w) for w in rows])
+        return self._got
+
+    def ready(self) -> bool:
+        return self._got is not None or self._mon._fdone[self._k].query()
+
+    def forecasts(self) -> list:
+        return list(self._wait()[2])
+
+
+class SlotForecastTicket:
+    """One `forecast_slots` call in flight: `forecasts()` - one `Forecast` per slot named, in the caller's order; it waits if it must and
+    hands the buffer back to the monitor.  `ready()` as `FeedTicket` has it."""
+
+    def __init__(self, monitor, k: int, n: int):
+        self._mon, self._k, self._n, self._got = monitor, k, n, None
+
+    def ready(self) -> bool:
+        return self._got is not None or self._mon._sdone[self._k].query()
+
+    def forecasts(self) -> list:
+        if self._got is None:
+            from .procedure import FORECAST_WORDS, Forecast
+            self._mon._sdone[self._k].synchronize()
+            rows = self._mon._shost[self._k][:FORECAST_WORDS * self._n].view(self._n, FORECAST_WORDS).tolist()
+            self._got = [Forecast.from_words(w) for w in rows]
+        return list(self._got)
+
+
+class ForecastMonitor(MistakeMonitor):
+    """ForecastMonitor(pool, model, max_out=1024, depth=2) - `pool.forecast_monitor(model)`: a `MistakeMonitor` that also says what should
+    come next (csrc/procedure.hip).  `drain()` enqueues the feed's drain, the judge, one forecasting launch over the
+    same report and the three copies, and returns a `ForecastTicket` without waiting.  `forecast_slots(slots)` asks for open slots by
+    name - whatever their records hold now, drained or not - in one launch and one copy into one of `depth` pinned buffers of its own;
+    it raises, before it launches anything, when all of them hold unread tickets."""
+
+    def __init__(self, pool, model, max_out: int = 1024, depth: int = 2):
+        from .procedure import FORECAST_WORDS
+        super().__init__(pool, model, max_out, depth)
+        self._fw = FORECAST_WORDS
+        stem = pool._C["feed_create"].replace("_feed_create", "")
+        self._forecast, self._slot_forecast = getattr(self.lib, stem + "_feed_forecast"), getattr(self.lib, stem + "_forecast")
+        words = lambda n: torch.empty(n * FORECAST_WORDS, dtype=torch.int32, device=self.device)
+        pinned = lambda n: torch.empty(n * FORECAST_WORDS, dtype=torch.int32).pin_memory()
+        self._fdev, self._fhost = [words(self.max_out) for _ in range(self.depth)], [pinned(self.max_out) for _ in range(self.depth)]
+        self._fdone = [torch.cuda.Event() for _ in range(self.depth)]
+        cap = pool.capacity
+        self._sdev, self._shost = [words(cap) for _ in range(self.depth)], [pinned(cap) for _ in range(self.depth)]
+        self._slots_host = [torch.empty(cap, dtype=torch.int32).pin_memory() for _ in range(self.depth)]
+        self._slots_dev = [torch.empty(cap, dtype=torch.int32, device=self.device) for _ in range(self.depth)]
+        self._sdone = [torch.cuda.Event() for _ in range(self.depth)]
+        self._stickets, self._snext = [None] * self.depth, 0
+
+    def drain(self) -> ForecastTicket:
+        t = super().drain()                                      # raises, before anything is launched, when buffer k is unread
+        k = t._k
+        with torch.cuda.device(self.device):
+            self.pool._check(self._forecast(self.feed.f, self.model.m, C.c_void_p(self.feed._dev[k].data_ptr()), self.feed._report_bytes,
+                                            C.c_void_p(self._groups.data_ptr()), C.c_void_p(self._fdev[k].data_ptr()), self._fdev[k].numel() * 4,
+                                            C.c_void_p(self.pool._stream_ptr(self.device))))
+            self._fhost[k].copy_(self._fdev[k], non_blocking=True)
+            self._fdone[k].record()
+        return ForecastTicket(self, t._ft, k)
+
+    def forecast_slots(self, slots) -> SlotForecastTicket:
+        """what comes next for each of `slots` (open slots, 1..capacity of them, a slot may repeat), in the group `set_group` gave it"""
+        slots = [int(s) for s in slots]
+        if not 1 <= len(slots) <= self.pool.capacity:
+            raise PregoError(f"forecast monitor forecast_slots: {len(slots)} slots (1..{self.pool.capacity}, the pool's capacity)")
+        for s in slots:
+            if not self.pool.slots.is_open(s):
+                raise PregoError(f"forecast monitor forecast_slots: slot {s} is not open")
+        k = self._snext
+        held = self._stickets[k]
+        if held is not None and held._got is None:               # the oldest buffer: if it is unread, all of them are
+            raise PregoError(f"forecast monitor forecast_slots: all {self.depth} forecast buffers hold unread tickets (read one with forecasts())")
+        n = len(slots)
+        self._slots_host[k][:n] = torch.tensor(slots, dtype=torch.int32)
+        with torch.cuda.device(self.device):
+            self._slots_dev[k][:n].copy_(self._slots_host[k][:n], non_blocking=True)
+            self.pool._check(self._slot_forecast(self.pool.p, self.model.m, C.c_void_p(self._slots_dev[k].data_ptr()), n,
+                                                 C.c_void_p(self._groups.data_ptr()), C.c_void_p(self._sdev[k].data_ptr()), self._sdev[k].numel() * 4,
+                                                 C.c_void_p(self.pool._stream_ptr(self.device))))
+            self._shost[k][:n * self._fw].copy_(self._sdev[k][:n * self._fw], non_blocking=True)
+            self._sdone[k].record()
+        ticket = SlotForecastTicket(self, k, n)
+        self._stickets[k] = ticket
+        self._snext = (k + 1) % self.depth
+        return ticket
 
 
 class StreamPool(_RecordPool):
