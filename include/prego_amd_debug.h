@@ -150,6 +150,88 @@ int prego_debug_vit_tensor(const int32_t* dims, int i, int32_t* rows, int32_t* c
  * total.  Returns the number of blocks; -1: a NULL argument, an unknown kind, or cap below 2 * blocks + 1. */
 int prego_debug_vit_layout(int kind, const int32_t* dims, int a, int b, uint64_t* offsets, int cap);
 
+/* ---- Unit test only (tests/test_gpu_rows.py): the element-wise and small-reduction kernels of the training steps, each alone, through the
+ * launch_* function of csrc/kernels.h the training steps call (the launcher picks the instantiation).  Every pointer is a device pointer.
+ * Each entry returns PREGO_EINVAL and launches nothing for a NULL it needs or a shape its kernel is not written for; "reads" / "writes" below
+ * is the contract the tests hold the kernels to: nothing outside what is named is read (NaN there must not reach an output) or written.
+ * A dropout probability p becomes the kernels' threshold (unsigned)((double)p 2^32) and scale 1.f / (1.f - p); the mask of element i is
+ * hash(seed, i) >= threshold (csrc/common.h: dropout_keep_).  Types: 0 fp32, 1 bf16, 2 IEEE fp16; fp16 stores saturate at +-65504. */
+
+/* LayerNorm (biased variance, eps inside the root) [+ ReLU if relu] [+ dropout(drop_p) on element index (row0_abs + r) E + c] of nrows rows
+ * of E values.  E a multiple of 512, <= 4096; (in_type, out_type) one of (0,0) (0,1) (0,2) (1,1) (2,2).  Reads Y [nrows][E], gamma, beta
+ * [E].  Writes out [nrows][E] and, when stats is given, stats [nrows][2] = (mean, 1 / sqrt(var + eps)) per row.  arm_hx non-NULL: also
+ * re-arms a recurrence's exchange buffers as gru_arm_desc(arm_bf16, arm_hid, arm_G) describes them: with W = gru_hx_bytes / 8 words per
+ * buffer, words [0, W) of arm_hx := 0x40004000 (16-bit operands) or 0x40000000 (fp32), words [W, 2 W) := 0, arm_sync [0, 16) := 0. */
+int prego_debug_ln_relu(int in_type, int out_type, const void* Y, const float* gamma, const float* beta, int nrows, int E, float eps, void* out,
+                        float* stats, float drop_p, uint64_t seed, int row0_abs, int relu, int arm_bf16, int arm_hid, int arm_G, void* arm_hx,
+                        uint32_t* arm_sync, prego_stream_t stream);
+/* LayerNorm + ReLU of fp32 rows into split rows: out [nrows][2 E] fp16 = [hi | lo], hi = fp16_sat(v), lo = fp16_sat(v - hi).  Shapes and reads
+ * as above; no dropout, no statistics. */
+int prego_debug_ln_relu_x2(const float* Y, const float* gamma, const float* beta, int nrows, int E, float eps, void* out, prego_stream_t stream);
+/* Dropout / ReLU / LayerNorm backward + the column sums of its partials, as both training steps run them.  With xhat = (Y - mu) rstd from
+ * stats [nrows][2], pre = xhat gamma + beta, d = dE [pre > 0 if relu] [dropout mask and scale as the forward, same (seed, row0_abs)],
+ * dxh = d gamma:  dY (+)= rstd (dxh - mean_E(dxh) - xhat mean_E(dxh xhat)) (accumulate: added to what dY holds), dYb (nullable) = bf16 of
+ * the stored dY, dgb [2 E] = (sum_rows d xhat | sum_rows d).  E a multiple of 256, <= 4096.  Reads dE, Y [nrows][E], stats, gamma, beta,
+ * and dY when accumulate.  Writes dY, dYb [nrows][E], dgb, and part [ceil(nrows / 4)][2][E] (scratch). */
+int prego_debug_ln_relu_bwd(const float* dE, const float* Y, const float* stats, const float* gamma, const float* beta, int nrows, int E,
+                            float drop_p, uint64_t seed, int row0_abs, float* dY, void* dYb, float* part, float* dgb, int relu, int accumulate,
+                            prego_stream_t stream);
+/* out [N] = column sums of src [M][N] (fp32, or bf16 with fp32 accumulation) in a fixed order; part: scratch [ceil(M / 64)][N], written.
+ * _stage2: out [N] = sum over b < nb of part [b][N] (16 contiguous slices of ceil(nb / 16) partials, slice sums added in order). */
+int prego_debug_colsum(int bf16, const void* src, int M, int N, float* part, float* out, prego_stream_t stream);
+int prego_debug_colsum_stage2(const float* part, int nb, int N, float* out, prego_stream_t stream);
+/* dst [N][Mpad] = src [M][ld_src]^T converted (bf16 stores round to nearest even); columns M .. Mpad-1 of dst are ZERO.  Reads rows
+ * [0, M) and columns [0, N) of src only; writes exactly dst [N][Mpad]. */
+int prego_debug_transpose_convert(int in_bf16, int out_bf16, const void* src, int M, int N, int ld_src, void* dst, int Mpad,
+                                  prego_stream_t stream);
+/* Packed time-major rows: rowoff [t_max + 1] the prefix sums of the live clips per step (clips sorted by length, descending), row
+ * rowoff[t] + i = step t of sorted clip i.  gather_dlogits: out [nrows][Cpad] (fp32 or bf16) = dl_ptrs[sorted_clip[i]][t][0 .. C), zeros in
+ * columns C .. Cpad-1.  build_hprev: out [nrows][H] = Hraw [rowoff[t - 1] + i][H] (the same clip one step earlier), zeros at t = 0. */
+int prego_debug_gather_dlogits(int bf16, const float* const* dl_ptrs, const int32_t* rowoff, const int32_t* sorted_clip, int t_max, int nrows,
+                               int C, int Cpad, void* out, prego_stream_t stream);
+int prego_debug_build_hprev(int bf16, const float* Hraw, const int32_t* rowoff, int t_max, int nrows, int H, void* out, prego_stream_t stream);
+/* out [n] = Hraw > 0 ? dHrelu : 0 */
+int prego_debug_relu_mask(const float* dHrelu, const float* Hraw, uint64_t n, float* out, prego_stream_t stream);
+/* One reverse step of BPTT, element-wise part, for clips b < na and units j < H (formulas: csrc/train.hip).  Reads rows row_t .. row_t + na-1
+ * of dHout, R, Z, Nn, GHN [rows][H]; carry_in, dhpart [na_next][H] (rows b >= na_next are NOT read: dh = dHout there); rows row_tm1 ..
+ * of Hraw only when t > 0 (t = 0: hprev = 0, Hraw is not read).  Writes carry_out [na][H], rows row_t .. of dGI, dGH [rows][3 H] fp32 and
+ * of dGIop, dGHop (bf16, or fp32 when !bf16) - nothing else. */
+int prego_debug_gru_bwd_step(int bf16, int t, int na, int na_next, int row_t, int row_tm1, int H, const float* dHout, const float* carry_in,
+                             const float* dhpart, const float* R, const float* Z, const float* Nn, const float* GHN, const float* Hraw,
+                             float* carry_out, float* dGI, float* dGH, void* dGIop, void* dGHop, prego_stream_t stream);
+/* dst [rows_dst][cols_dst] (out_type) = src [rows_src][ld_src] in its rows_src x cols_src corner, zeros elsewhere.  Reads that corner only. */
+int prego_debug_pad_convert(int out_type, const float* src, int rows_src, int cols_src, int ld_src, void* dst, int rows_dst, int cols_dst,
+                            prego_stream_t stream);
+/* dst [n] bf16 = src [n], round to nearest even */
+int prego_debug_f32_to_bf16(const float* src, void* dst, uint64_t n, prego_stream_t stream);
+/* du [n] = mask_scale(df) (Phi(u) + u phi(u)), exact-erf GELU's derivative; du_bf16 [n] = bf16(du).  n a multiple of 4. */
+int prego_debug_gelu_bwd(const float* df, const float* u, uint64_t n, float* du, void* du_bf16, float drop_p, uint64_t seed,
+                         prego_stream_t stream);
+/* out_f32 (nullable) / out_bf16 [n] = src masked and scaled by (drop_p, seed), then by (drop2_p, seed2).  n a multiple of 4. */
+int prego_debug_mask_convert(const float* src, uint64_t n, float* out_f32, void* out_bf16, float drop_p, uint64_t seed, float drop2_p,
+                             uint64_t seed2, prego_stream_t stream);
+/* The Transformer head on token 0 of each of B windows of N tokens: out [B][C] = LN(x[b, 0, :]; lnw, lnb, eps 1e-5) hw^T + hb, argmax
+ * (nullable) [B] = the first maximum.  Reads row 0 of every window only.  (E + 8 + C) floats must fit 64 KiB; E a multiple of 4. */
+int prego_debug_vit_head(const float* x, int B, int N, int E, const float* lnw, const float* lnb, const float* hw, const float* hb, int C,
+                         float* out, int32_t* argmax, prego_stream_t stream);
+/* Its backward, any C the forward takes: dx [b, 0, :] = LayerNorm backward of dlogits[b] hw (rows 1 .. N-1 of dx are NOT written),
+ * g_lnw, g_lnb [E], g_hw [C][E], g_hb [C] summed over the windows in window order; scratch [3][B][E] is written. */
+int prego_debug_vit_head_bwd(const float* x, const float* dlogits, int B, int N, int E, int C, const float* lnw, const float* lnb,
+                             const float* hw, float* dx, float* scratch, float* g_lnw, float* g_lnb, float* g_hw, float* g_hb,
+                             prego_stream_t stream);
+/* x [B][T + 1][E] = mask_scale((n < T ? enc [b][n] : cls) + pe [n]), mask index = the element's index in x.  _bwd, the same mask on dx:
+ * denc [B][T][E] = the masked dx rows n < T, g_pe [T + 1][E] = their sum over b in order, g_cls [E] = g_pe [T]. */
+int prego_debug_vit_tokens(const float* enc, const float* cls, const float* pe, int B, int T, int E, float* x, float drop_p, uint64_t seed,
+                           prego_stream_t stream);
+int prego_debug_vit_tokens_bwd(const float* dx, int B, int T, int E, float* denc, float* g_pe, float* g_cls, float drop_p, uint64_t seed,
+                               prego_stream_t stream);
+/* The loss kernel on DEVICE tables (logit_ptrs, target_ptrs, dlogit_ptrs [n_clips] device pointers, lens [n_clips] int32), any number of
+ * clips: the product entry stages at most 4096, so the kernel's one-wave path for more clips than that is reached from here alone.  Reads
+ * the LAST row of each clip's logits and target [lens][C]; writes loss_out [1] and, when dlogit_ptrs is given, all lens x C values of each
+ * clip's dlogits (zeros in front of the last row).  C in 1..128. */
+int prego_debug_oad_loss(const float* const* logit_ptrs, const float* const* target_ptrs, const int32_t* lens, int n_clips, int C, int sum,
+                         float* loss_out, float* const* dlogit_ptrs, float grad_scale, prego_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

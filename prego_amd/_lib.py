@@ -73,7 +73,13 @@ DEBUG_SYMBOLS = ["prego_miniroad_debug_stamps", "prego_debug_gemm_bf16", "prego_
                  "prego_debug_split_fault", "prego_debug_split_state", "prego_debug_set_abort", "prego_debug_alloc_count", "prego_debug_hog",
                  "prego_debug_ant_full_span", "prego_debug_gemm_tn", "prego_debug_gemm_nt", "prego_debug_gemm_nt_choice", "prego_debug_vit_ring_tokens",
                  "prego_debug_gru_choice", "prego_debug_gru_hx_offset", "prego_debug_vit_burst_tokens", "prego_debug_vit_burst_commit", "prego_debug_pool_image_fault",
-                 "prego_debug_vit_tensor", "prego_debug_vit_layout"]
+                 "prego_debug_vit_tensor", "prego_debug_vit_layout",
+                 # the row-wise training kernels, each alone (csrc/rows_debug.cpp, tests/test_gpu_rows.py)
+                 "prego_debug_ln_relu", "prego_debug_ln_relu_x2", "prego_debug_ln_relu_bwd", "prego_debug_colsum", "prego_debug_colsum_stage2",
+                 "prego_debug_transpose_convert", "prego_debug_gather_dlogits", "prego_debug_build_hprev", "prego_debug_relu_mask",
+                 "prego_debug_gru_bwd_step", "prego_debug_pad_convert", "prego_debug_f32_to_bf16", "prego_debug_gelu_bwd",
+                 "prego_debug_mask_convert", "prego_debug_vit_head", "prego_debug_vit_head_bwd", "prego_debug_vit_tokens",
+                 "prego_debug_vit_tokens_bwd", "prego_debug_oad_loss"]
 
 
 class PregoError(RuntimeError):
@@ -299,6 +305,26 @@ def _open(path: str, debug: bool) -> C.CDLL:
         lib.prego_debug_pool_image_fault.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         lib.prego_debug_vit_tensor.argtypes = [C.POINTER(C.c_int32), i32] + [C.POINTER(C.c_int32)] * 3
         lib.prego_debug_vit_layout.argtypes = [i32, C.POINTER(C.c_int32), i32, i32, C.POINTER(C.c_uint64), i32]
+        u64 = C.c_uint64
+        lib.prego_debug_ln_relu.argtypes = [i32, i32, vp, vp, vp, i32, i32, f32, vp, vp, f32, u64, i32, i32, i32, i32, i32, vp, vp, vp]
+        lib.prego_debug_ln_relu_x2.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp]
+        lib.prego_debug_ln_relu_bwd.argtypes = [vp] * 5 + [i32, i32, f32, u64, i32, vp, vp, vp, vp, i32, i32, vp]
+        lib.prego_debug_colsum.argtypes = [i32, vp, i32, i32, vp, vp, vp]
+        lib.prego_debug_colsum_stage2.argtypes = [vp, i32, i32, vp, vp]
+        lib.prego_debug_transpose_convert.argtypes = [i32, i32, vp, i32, i32, i32, vp, i32, vp]
+        lib.prego_debug_gather_dlogits.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, vp, vp]
+        lib.prego_debug_build_hprev.argtypes = [i32, vp, vp, i32, i32, i32, vp, vp]
+        lib.prego_debug_relu_mask.argtypes = [vp, vp, u64, vp, vp]
+        lib.prego_debug_gru_bwd_step.argtypes = [i32] * 7 + [vp] * 13 + [vp]
+        lib.prego_debug_pad_convert.argtypes = [i32, vp, i32, i32, i32, vp, i32, i32, vp]
+        lib.prego_debug_f32_to_bf16.argtypes = [vp, vp, u64, vp]
+        lib.prego_debug_gelu_bwd.argtypes = [vp, vp, u64, vp, vp, f32, u64, vp]
+        lib.prego_debug_mask_convert.argtypes = [vp, u64, vp, vp, f32, u64, f32, u64, vp]
+        lib.prego_debug_vit_head.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]
+        lib.prego_debug_vit_head_bwd.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.prego_debug_vit_tokens.argtypes = [vp, vp, vp, i32, i32, i32, vp, f32, u64, vp]
+        lib.prego_debug_vit_tokens_bwd.argtypes = [vp, i32, i32, i32, vp, vp, vp, f32, u64, vp]
+        lib.prego_debug_oad_loss.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, f32, vp]
     return lib
 
 

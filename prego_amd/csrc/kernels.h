@@ -517,6 +517,7 @@ void launch_gelu_bwd(const float* df, const float* u, size_t n, float* du, void*
 void launch_mask_convert(const float* src, size_t n, float* out_f32, void* out_bf16, unsigned drop_thresh, float drop_scale,
                          unsigned long long drop_seed, hipStream_t s, unsigned drop2_thresh = 0, float drop2_scale = 1.f,
                          unsigned long long drop2_seed = 0);
+// any C launch_vit_head takes: its copy of a window's dlogits in LDS is sized by C, and g_hb is written for C > E as well
 void launch_vit_head_bwd(const float* x, const float* dlogits, int B, int N, int E, int C, const float* lnw, const float* lnb,
                          const float* hw, float* dx, float* scratch /*[3][B][E]*/, float* g_lnw, float* g_lnb, float* g_hw,
                          float* g_hb, hipStream_t s);

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void vit_head_bwd1_kernel(const float* __restr
                                                             const float* __restrict__ hw, float* __restrict__ dx, float* __restrict__ scratch,
                                                             int B) {
   __shared__ float red[8];
-  __shared__ float sdl[128];
+  extern __shared__ float sdl[];                   // [C] dlogits of window b (sized by the launcher, as vit_head_kernel's logits are)
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* xr = x + (size_t)b * N * E;
   for (int c = tid; c < C; c += 256) sdl[c] = dlogits[(size_t)b * C + c];
@@ -113,6 +113,11 @@ __global__ void vit_head_bwd2_kernel(const float* __restrict__ scratch, const fl
                                      float* __restrict__ g_hb) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   const int k = blockIdx.y;                        // k < C: row k of the head weight; k == C: the LayerNorm parameters
+  if (k == C && c >= E && c < C) {                 // more classes than columns: the bias gradient's own lanes (the grid's x covers max(E, C))
+    float hb = 0.f;
+    for (int b = 0; b < B; ++b) hb += dlogits[(size_t)b * C + c];
+    g_hb[c] = hb;
+  }
   if (c >= E) return;
   if (k == C) {
     float a = 0.f, d = 0.f;
@@ -137,8 +142,8 @@ __global__ void vit_head_bwd2_kernel(const float* __restrict__ scratch, const fl
 void launch_vit_head_bwd(const float* x, const float* dlogits, int B, int N, int E, int C, const float* lnw, const float* lnb,
                          const float* hw, float* dx, float* scratch, float* g_lnw, float* g_lnb, float* g_hw, float* g_hb,
                          hipStream_t s) {
-  vit_head_bwd1_kernel<<<B, 256, 0, s>>>(x, dlogits, N, E, C, lnw, lnb, hw, dx, scratch, B);
-  dim3 g2((E + 255) / 256, C + 1);
+  vit_head_bwd1_kernel<<<B, 256, (size_t)C * sizeof(float), s>>>(x, dlogits, N, E, C, lnw, lnb, hw, dx, scratch, B);
+  dim3 g2(((E > C ? E : C) + 255) / 256, C + 1);
   vit_head_bwd2_kernel<<<g2, 256, 0, s>>>(scratch, dlogits, B, E, C, g_lnw, g_lnb, g_hw, g_hb);
 }
 
