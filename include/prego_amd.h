@@ -585,6 +585,43 @@ int prego_thumos_postprocess(const float* scores, int64_t ld_scores, const float
 int prego_thumos_postprocess_labels(const float* scores, int64_t ld_scores, const int32_t* labels, int64_t n_frames, int n_classes, int flags,
                                     int switch_from, int switch_to, int ambiguous, float* scores_out, int32_t* labels_out, int64_t* n_valid,
                                     void* workspace, size_t workspace_bytes, prego_stream_t stream);
+/* Segmental metrics on the device: what step-recognition results on Assembly101 are reported in - frame accuracy (MoF), segmental
+ * Edit score and segmental F1 at three overlaps - from the transcripts that one class id per frame spells out.
+ * INPUTS.  pred / gt: device int32 [n_frames], one id per frame, n_videos videos one after the other; offsets: device int32
+ * [n_videos + 1], video v owns the frames [offsets[v], offsets[v + 1]).  Every word of offsets is clamped into [0, n_frames] before it
+ * indexes memory and a descending pair is an empty video; the records are defined for ascending offsets (videos that overlap share
+ * workspace: their records are unspecified, nothing is read or written out of bounds).  bg_mask: HOST, 128 bits, bit c set = class c
+ * is background (NULL = no background class, PREGO's data sets).  overlap_num / overlap_den: HOST, three overlaps as rationals,
+ * 0 < num <= den <= 32768 (both NULL = 1/10, 1/4, 1/2).
+ * SEGMENTS of a label sequence of ONE video: the maximal runs of equal id inside that video, in frame order - a run never continues
+ * across a video boundary (prego_perstage_ap_labels does the opposite).  Runs whose id is in [0, 128) and set in the mask are dropped;
+ * two runs of one id separated only by a dropped run stay two segments.  A segment is (id, start, end), end exclusive.  Ids outside
+ * [0, 128) are ordinary ids, compared for equality only, never background.  m, n: the pred and gt segments of the video.
+ * PER VIDEO.  correct = frames with pred == gt, frames = its length (background frames count in both).  dist = the Levenshtein
+ * distance of the two segment-id lists (insert, delete, substitute 1; match 0).  For a pred segment p and a gt segment g of the same
+ * id: inter = min(pe, ge) - max(ps, gs), union = max(pe, ge) - min(ps, gs); the candidates of p are the same-id gt segments with
+ * inter > 0, best(p) the candidate with the largest inter / union (64-bit cross products; equal ratios: the earliest gt segment);
+ * p qualifies at k when inter * den_k >= union * num_k.  tp_k = the gt segments g for which some pred segment has best(p) = g and
+ * qualifies at k; fp_k = m - tp_k, fn_k = n - tp_k.  (The usual sequential rule without its order: walk the pred segments, take the
+ * argmax of IoU x id equality over the gt segments, a true positive if the IoU reaches the overlap and that gt segment is not hit
+ * yet.  Below 2^31 frames two distinct ratios, or a ratio and a threshold, differ by at least 1 / (10 * 2^31): the rational compares
+ * agree with that formulation's fp64 divisions.)
+ * RECORD.  records: device int32 [n_videos][8], 16-byte aligned:  correct | frames | m | n | dist | tp_0 | tp_1 | tp_2.
+ * REPORT (the caller's, fp64, in this operand order): MoF = 100 * sum(correct) / sum(frames) (0.0 without frames); Edit = the mean over
+ * the videos of 100 * (1 - dist / max(m, n, 1)); F1@k = 200 * TP_k / (M + N) over the sums of tp_k, m, n (0.0 when M + N == 0).
+ * One launch, one workgroup per video (csrc/segmental.hip): frame scan and compaction, the Levenshtein table by anti-diagonals - three
+ * diagonals of min(m, n) + 1 ints in LDS while min(m, n) <= PREGO_SEGMENTAL_LDS_SEGMENTS, in the workspace above it (slow; no video
+ * is refused for its size) -, a bisection per pred segment.  Integers only: the same words on every run.  Everything is enqueued on
+ * `stream`; nothing is allocated, nothing waits.  Workspace: prego_segmental_workspace_bytes (40 B per frame + 12 B per video).
+ * n_frames == 0: returns 0, every record is eight zeros, no workspace is needed.  PREGO_EINVAL, decided before the launch (records
+ * and workspace untouched): a NULL pred, gt, offsets or records, a NULL workspace with n_frames > 0, n_videos < 1, n_frames < 0 or
+ * >= 2^31, records not 16-byte aligned, only one of overlap_num / overlap_den, an overlap outside 0 < num <= den <= 32768;
+ * PREGO_EWORKSPACE: workspace_bytes below the query.  An addition to ABI 7 (existing signatures unchanged). */
+#define PREGO_SEGMENTAL_LDS_SEGMENTS 2047
+size_t prego_segmental_workspace_bytes(int64_t n_frames, int n_videos);
+int prego_segmental_scores(const int32_t* pred, const int32_t* gt, const int32_t* offsets, int n_videos, int64_t n_frames,
+                           const uint32_t bg_mask[4], const int32_t overlap_num[3], const int32_t overlap_den[3], int32_t* records,
+                           void* workspace, size_t workspace_bytes, prego_stream_t stream);
 /* HOST function (no device work): the reference's loader yields fp32 target rows [n_frames][n_classes] per video (one-hot for both
  * shipped configs).  targets: n_videos host pointers, n_frames: their row counts; labels: host int32 [sum of n_frames], the videos one
  * after the other, labels[i] = np.argmax(row i) (eval.py:55, the first maximum); onehot[v] = 1 iff every row of video v holds exactly one

@@ -64,8 +64,11 @@ SYMBOLS = [
     "prego_stream_pool_feed_judge", "prego_vit_stream_pool_feed_judge",
     "prego_procedure_forecast", "prego_stream_pool_feed_forecast", "prego_vit_stream_pool_feed_forecast",
     "prego_stream_pool_forecast", "prego_vit_stream_pool_forecast",
+    "prego_segmental_workspace_bytes", "prego_segmental_scores",
 ]
 THUMOS_SMOOTH, THUMOS_SWITCH = 1, 2          # PREGO_THUMOS_SMOOTH / _SWITCH
+SEGMENTAL_LDS_SEGMENTS = 2047                # PREGO_SEGMENTAL_LDS_SEGMENTS: the short side up to which prego_segmental_scores keeps its diagonals in LDS
+SEGMENTAL_CHUNK = 1024                       # frames per scan step of its workgroups (csrc/kernels.h kSegmentalChunk)
 THUMOS_TILE_ROWS = 128                       # PREGO_THUMOS_TILE_ROWS: rows per scatter tile of prego_thumos_postprocess
 # include/prego_amd_debug.h: only in libprego_amd_debug.so
 DEBUG_SYMBOLS = ["prego_miniroad_debug_stamps", "prego_debug_gemm_bf16", "prego_debug_attention_bwd", "prego_debug_attention_fwd",
@@ -197,6 +200,9 @@ def _open(path: str, debug: bool) -> C.CDLL:
     lib.prego_thumos_postprocess_workspace_bytes.restype = sz
     lib.prego_thumos_postprocess.argtypes = [vp, i64, vp, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
     lib.prego_thumos_postprocess_labels.argtypes = [vp, i64, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
+    lib.prego_segmental_workspace_bytes.argtypes = [i64, i32]
+    lib.prego_segmental_workspace_bytes.restype = sz
+    lib.prego_segmental_scores.argtypes = [vp, vp, vp, i32, i64, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, sz, vp]
     lib.prego_onehot_labels.argtypes =[i32, C.POINTER(vp), C.POINTER(i64), i32, vp, C.POINTER(C.c_int32)]
     f32 = C.c_float
     lib.prego_adamw_step.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), i64, f32, f32, f32, f32, f32, vp]

@@ -363,6 +363,14 @@ size_t perstage_cap_workspace_bytes(long long n_frames, int n_classes);
 int launch_perstage_cap(const float* scores, const int* labels, long long n_frames, int n_classes, double* ap, long long* n_pos, void* workspace,
                         hipStream_t s);
 
+// segmental metrics (segmental.hip): MoF, edit distance and F1 at three overlaps per video; one launch, one workgroup per video.
+// records [n_videos][8]; bg: four mask words; num / den: three overlaps; -1 = refused, nothing launched.  ws: the query's bytes
+constexpr int kSegmentalLdsSegments = 2047;     // PREGO_SEGMENTAL_LDS_SEGMENTS of the public header
+constexpr int kSegmentalChunk = 1024;           // frames per scan step of a workgroup
+size_t segmental_workspace_bytes(long long n_frames, int n_videos);
+int launch_segmental(const int* pred, const int* gt, const int* offsets, int n_videos, long long n_frames, const unsigned* bg, const int* num,
+                     const int* den, int* records, void* workspace, hipStream_t s);
+
 // THUMOS post-processing (thumos_post.hip): 5-frame max, column merge, stable removal of the ambiguous rows; count, scan, scatter
 constexpr int kThumosTileRows = 128;     // rows per scatter tile (PREGO_THUMOS_TILE_ROWS of the public header)
 constexpr int kThumosChunkCols = 96;     // columns of a tile staged in LDS at a time

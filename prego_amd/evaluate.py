@@ -25,6 +25,7 @@ from .metrics import (N_STAGES, perframe_ap_raw, perframe_ap_raw_device, perfram
                       perstage_average_precision_device, perstage_report, report_from_raw)
 from .postprocessing import ThumosPostprocessing, thumos_postprocessing_device
 from .registry import EVAL
+from .segmental import segmental_scores_device
 
 
 def _thumos_postprocessing(cfg, is_thumos: bool):
@@ -74,6 +75,13 @@ class Evaluate(nn.Module):
         if self.perstage_metric not in ("AP", "cAP"):
             raise RuntimeError(f"Unknown eval_perstage_metric: {self.perstage_metric}")
         self.last_perstage = None
+        # cfg['eval_segmental'] (not a reference key, off by default): the segmental metrics of the pass - MoF, segmental Edit, segmental
+        # F1@{10,25,50} (`prego_segmental_scores`) - on the per-frame argmax ("frames") and on the sequence the anticipator reads, the
+        # cfg['eval_segmental_window']-frame majority vote expanded back to frames ("vote"); kept in `last_segmental` and logged.  They
+        # are computed from the argmax of the RAW scores: cfg['eval_thumos_postprocessing'] does not feed them.
+        self.segmental = bool(cfg.get("eval_segmental", False))
+        self.segmental_window = int(cfg.get("eval_segmental_window", 200))
+        self.last_segmental = None
         self.last_metric_path = None         # "device" | "host": where the last call computed cfg['metric']
 
     @staticmethod
@@ -443,6 +451,51 @@ class Evaluate(nn.Module):
                 pred_scores.append(p)
                 gt_targets.append(t)
 
+    @staticmethod
+    def _argmax(rec, argmax_ids):
+        """the device argmax of a batch's videos, taken at launch time as _scores takes the scores"""
+        if rec is not None:
+            for _vid, (_p, a, _t) in rec["items"]:
+                argmax_ids.append(a)
+
+    def _enqueue_segmental(self, argmax_ids, gt_targets, dev):
+        """cfg['eval_segmental']: prego_segmental_scores twice on the current stream - over the per-video device argmax and the device
+        class ids as they are, and over the cfg['eval_segmental_window']-frame vote of every video (prego_window_vote) expanded back to
+        frames and cut to the video's length.  Returns the function that collects {"frames": report, "vote": report}; a vote marker of
+        -1 (a window with an id outside the classes) raises there, as in aggregate_device.  cfg['eval_thumos_postprocessing'] does not
+        feed this metric: it works on the argmax of the raw scores, every frame kept."""
+        import ctypes as C
+
+        from . import _lib
+        from ._lib import check
+        lib, w, ncls = _lib.load(), self.segmental_window, len(self.all_class_names)
+        if w < 1 or ncls > 128:
+            raise PregoError(f"cfg['eval_segmental']: eval_segmental_window {w} (>= 1), {ncls} classes (prego_window_vote takes up to 128)")
+        lens = [int(a.shape[0]) for a in argmax_ids]
+        offsets = torch.tensor(np.concatenate(([0], np.cumsum(lens, dtype=np.int64))), dtype=torch.int32).to(dev)
+        pred = torch.cat([a.to(device=dev, dtype=torch.int32) for a in argmax_ids]).contiguous()
+        gt = torch.cat([t.to(device=dev, dtype=torch.int32) for t in gt_targets]).contiguous()
+        votes = torch.empty(sum((n + w - 1) // w for n in lens), dtype=torch.int32, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        voted, o, f = [], 0, 0
+        with torch.cuda.device(dev):
+            for n in lens:
+                k = (n + w - 1) // w
+                if n > 0:
+                    check(lib.prego_window_vote(C.c_void_p(pred[f:f + n].data_ptr()), n, w, ncls, C.c_void_p(votes[o:o + k].data_ptr()), stream))
+                    voted.append(torch.repeat_interleave(votes[o:o + k], w)[:n])
+                o, f = o + k, f + n
+        pred_vote = torch.cat(voted).contiguous() if voted else pred
+        fn_frames = segmental_scores_device(pred, gt, offsets, defer=True)
+        fn_vote = segmental_scores_device(pred_vote, gt, offsets, defer=True)
+
+        def finish():
+            if bool((votes.cpu() < 0).any()):
+                raise PregoError(f"cfg['eval_segmental']: a vote window holds a class id outside [0, {ncls}) (np.bincount of "
+                                 "utils/aggregate.py:60 would raise / count a class the model does not have)")
+            return {"frames": fn_frames(), "vote": fn_vote()}
+        return finish
+
     def _loader_videos(self, model, dataloader, world, rank, skip_flow):
         """this rank's videos as the loop below batches them, one list per loader item: (features, flow or None, target rows, name,
         position in the loader's order, loader item)"""
@@ -479,6 +532,12 @@ class Evaluate(nn.Module):
             raise PregoError("cfg['eval_thumos_postprocessing']: the temporal smoothing runs over the concatenated frames of the whole eval "
                              f"set, across the boundaries of the ranks' frame ranges, and is computed by a single process only; this eval "
                              f"runs on {world} ranks")
+        if self.segmental and world > 1:
+            raise PregoError("cfg['eval_segmental']: the segmental metrics are computed by a single process only (the per-video records "
+                             f"of the ranks are not gathered); this eval runs on {world} ranks")
+        if self.segmental and torch.device(device).type != "cuda":
+            raise PregoError("cfg['eval_segmental']: the segmental metrics of an eval pass run on the device (prego_segmental_scores); host "
+                             "arrays: prego_amd.segmental.segmental_scores")
         if self.perstage and torch.device(device).type != "cuda":
             raise PregoError("cfg['eval_perstage']: the per-stage AP of an eval pass runs on the device (prego_perstage_ap_labels); host "
                              "arrays: prego_amd.metrics.perstage_average_precision")
@@ -525,6 +584,7 @@ class Evaluate(nn.Module):
         self._n_valid = 0 if (self.data_processing is not None and not resident) else None
         with torch.no_grad():
             pred_scores, gt_targets = [], []
+            argmax_ids = []                      # cfg['eval_segmental']: the videos' device argmax, in the order of pred_scores
             per_video = []                       # (loader position, n_frames) to restore the loader's order on rank 0
             t_begin = time.time()
             t0_ = time.perf_counter()
@@ -542,6 +602,7 @@ class Evaluate(nn.Module):
                     mark("loader")
                     rec = self._flush(model, batch, device, resident)       # batch k: enqueued ...
                     self._scores(rec, pred_scores, gt_targets)
+                    self._argmax(rec, argmax_ids)
                     mark("launch")
                     self._collect(pending, pred_scores, gt_targets, output, json_parts)      # ... while the host finishes batch k - 1
                     mark("collect")
@@ -550,6 +611,7 @@ class Evaluate(nn.Module):
             mark("loader")
             rec = self._flush(model, batch, device, resident)
             self._scores(rec, pred_scores, gt_targets)
+            self._argmax(rec, argmax_ids)
             finish_ap = None
             if world == 1 and torch.device(device).type == "cuda" and pred_scores:
                 # the metric in libprego_amd.so (prego_perframe_ap, or prego_perframe_cap for metric 'cAP'), ENQUEUED here behind the last forward and collected behind the
@@ -595,6 +657,25 @@ class Evaluate(nn.Module):
                     ps_fn = perstage_average_precision_device(pred_m, gt_m, self.all_class_names, defer=True, metrics=self.perstage_metric)
 
                 def finish_ps(_fn=ps_fn, _s=self._ap_stream):
+                    with torch.cuda.stream(_s):
+                        return _fn()
+            finish_seg = None
+            self.last_segmental = None
+            if self.segmental and pred_scores:
+                # the segmental records of the same device-resident ids, enqueued behind the other metrics on their stream
+                if not all(t.dim() == 1 for t in gt_targets):
+                    raise PregoError("cfg['eval_segmental']: the segmental metrics need targets that are one class id per frame (one-hot "
+                                     "rows, cfg['eval_label_targets'] on); this eval set has rows that are not (dense multi-label targets "
+                                     "have no transcript)")
+                if self._ap_stream is None:
+                    self._ap_stream = torch.cuda.Stream(torch.device(device))
+                fwd_done = torch.cuda.Event()
+                fwd_done.record(torch.cuda.current_stream(torch.device(device)))
+                with torch.cuda.stream(self._ap_stream):
+                    self._ap_stream.wait_event(fwd_done)
+                    seg_fn = self._enqueue_segmental(argmax_ids, gt_targets, torch.device(device))
+
+                def finish_seg(_fn=seg_fn, _s=self._ap_stream):
                     with torch.cuda.stream(_s):
                         return _fn()
             mark("launch")
@@ -663,6 +744,12 @@ class Evaluate(nn.Module):
                 mark("perstage_done")
                 for stage, rep_ in self.last_perstage.items():
                     logger.info(f"per-stage mAP {stage}: {rep_['mean_AP'] * 100:.2f}")
+            if finish_seg is not None:
+                self.last_segmental = finish_seg()
+                mark("segmental_done")
+                for key in [k for k in self.last_segmental["frames"] if k not in ("videos", "per_video")]:      # MoF, Edit, three F1
+                    logger.info(f"segmental {key}: frames {self.last_segmental['frames'][key]:.2f}, "
+                                f"vote({self.segmental_window}) {self.last_segmental['vote'][key]:.2f}")
         return result["mean_AP"]
 
     def _sharded_ap(self, pred, gt, world, rank):
