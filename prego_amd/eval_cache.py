@@ -21,10 +21,21 @@ from __future__ import annotations
 
 import ctypes as C
 import weakref
+from typing import NamedTuple, Optional
 
 import torch
 
 _NAMES = {torch.float16: "fp16", torch.bfloat16: "bf16", torch.float32: "fp32"}
+
+
+class EvalVideo(NamedTuple):
+    """one video as Evaluate batches it: from the loader (host tensors) or from this cache (device tensors)"""
+    features: torch.Tensor               # [T, D]
+    flow: Optional[torch.Tensor]         # [T, D], or None: the flow half is all zeros and never shipped
+    target: torch.Tensor                 # the loader's rows [T, C]; in the cache the device form (class ids [T] where the rows are one-hot)
+    name: str
+    pos: int                             # position in the loader's order
+    item: int                            # the loader item it came in
 
 
 class EvalFeatureCache:
@@ -37,7 +48,7 @@ class EvalFeatureCache:
         """release everything; `state` 'disabled' keeps the key, so that calls on the same loader do not fill again"""
         self.state, self.reason = state, reason
         self.filling = False
-        self.entries = []              # (features, flow or None, target, name, loader position, loader item) - a batch item of Evaluate
+        self.entries = []              # EvalVideo, device tensors
         self.gt_ids = {}               # name -> int array: the "gt" list of the output JSON
         self.bytes, self.frames, self.dtype, self.budget = 0, 0, None, None
         if state != "disabled":
@@ -83,7 +94,7 @@ class EvalFeatureCache:
         """the cached videos as Evaluate's loop takes them: one list per loader item"""
         group = []
         for e in self.entries:
-            if group and group[-1][5] != e[5]:
+            if group and group[-1].item != e.item:
                 yield group
                 group = []
             group.append(e)
@@ -116,12 +127,12 @@ class EvalFeatureCache:
             fl = None if flow is None else flow[i]
             feats = [rgb[i]] + ([fl] if fl is not None else [])
             if any(x.dtype != self.dtype and (x.dtype != torch.float32 or x.numel() % 8 or x.data_ptr() % 16) for x in feats):
-                return self._disable(f"video {it[3]!r}: {rgb[i].dtype} features that prego_cast_features does not take")
+                return self._disable(f"video {it.name!r}: {rgb[i].dtype} features that prego_cast_features does not take")
             need = sum(x.numel() for x in feats) * size + targets[i].numel() * targets[i].element_size()
             if self.bytes + need > self.budget:
-                return self._disable(f"budget: video {it[3]!r} needs {need} bytes on top of {self.bytes}, eval_cache_max_bytes is {self.budget}")
+                return self._disable(f"budget: video {it.name!r} needs {need} bytes on top of {self.bytes}, eval_cache_max_bytes is {self.budget}")
             kept = [self._kept(x, device) for x in feats]
-            self.entries.append((kept[0], kept[1] if fl is not None else None, targets[i]) + tuple(it[3:]))
+            self.entries.append(it._replace(features=kept[0], flow=kept[1] if fl is not None else None, target=targets[i]))
             self.bytes += need
             self.frames += int(rgb[i].shape[0])
 

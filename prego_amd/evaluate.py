@@ -10,17 +10,23 @@ taken on the device.  The FPS log line is computed correctly (the reference shad
 loader's `start` field, eval.py:35-36,77-80)."""
 from __future__ import annotations
 
+import ctypes as C
 import json
 import os
 import time
+from collections import namedtuple
+from dataclasses import dataclass, field
+from typing import Callable, Optional
 
 import numpy as np
 import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from .eval_cache import EvalFeatureCache
-from ._lib import PregoError
+from . import _lib
+from .aggregate import aggregate_device
+from .eval_cache import EvalFeatureCache, EvalVideo
+from ._lib import PregoError, check
 from .metrics import (N_STAGES, perframe_ap_raw, perframe_ap_raw_device, perframe_average_precision, perframe_average_precision_device,
                       perstage_average_precision_device, perstage_report, report_from_raw)
 from .postprocessing import ThumosPostprocessing, thumos_postprocessing_device
@@ -41,19 +47,81 @@ def _thumos_postprocessing(cfg, is_thumos: bool):
     return ThumosPostprocessing(bool(cfg.get("eval_thumos_smooth", False)), bool(cfg.get("eval_thumos_switch", False))) if on else None
 
 
+def split_by_length(frames, element_size, fraction=None):
+    """The parts (lists of batch indices) a batch that is copied and then forwarded goes in.  A batch runs as long as its longest video's
+    recurrence and its H2D copy would sit in front of that, so a batch of 16 or more videos goes in two parts ordered by length: the few
+    longest videos first (little to copy, the long critical path), then the bulk of the bytes, whose copy runs under the first part's
+    recurrence.  fraction: share of the frames in the first part - its forward should last about as long as the second part's copy.
+    Measured on the 60-video bench set (scripts/eval_e2e_bench.py): fp32 features 0.2: 4.23, 0.5: 4.72, 0.6: 4.41 M frames/s;
+    16-bit features (half the bytes) 0.2: 5.87, 0.5: 5.62 - the defaults by element size."""
+    order = list(range(len(frames)))
+    if len(frames) < 16:
+        return [order]
+    order.sort(key=lambda i: -frames[i])
+    if fraction is None:
+        fraction = 0.5 if element_size >= 4 else 0.2
+    budget, k, acc = float(fraction) * sum(frames), 0, 0
+    while k < len(order) - 1 and acc + frames[order[k]] <= budget:
+        acc += frames[order[k]]
+        k += 1
+    return [order[:k], order[k:]] if k >= 1 else [order]
+
+
+# what each of the three enqueue paths returns, lists in the order of the videos it was given: the forward's outputs, the targets in their
+# device form, the features as the forward read them on the device (flow: None, or per video a tensor or None), _targets_to_device's count
+# of post-processing-kept rows, and what must stay alive until the launch has run (pinned sources of async copies, feed events)
+_Enqueued = namedtuple("_Enqueued", "probs argmax targets rgb flow n_valid keep")
+
+
+@dataclass
+class _Launched:
+    """a batch whose launch is out (_flush) and whose host half (_collect) is due one batch later"""
+    videos: list                         # per video, in the loader's order: (name, probs, argmax, target)
+    link_fed: bool
+    n_valid: Optional[int] = 0           # the rows of this batch the THUMOS post-processing keeps, counted on the host; None: not known
+    ids: Optional[torch.Tensor] = None   # [pred | gt][frame]: pinned, valid behind `ids_ready` (a CPU box: the tensor itself, no event)
+    ids_ready: Optional[torch.cuda.Event] = None
+    text: Optional[torch.Tensor] = None  # the ids' JSON text made on the device (prego_format_ids), pinned; text_bad[0] != 0: not usable
+    text_bad: Optional[torch.Tensor] = None
+    fed: list = field(default_factory=list)      # a cache-filling call: per video (rgb, flow or None) on the device, until _collect
+    # alive until the record goes, behind _collect: the loader's tensors, device sources of async copies, pinned label buffers, feed events
+    keep: list = field(default_factory=list)
+
+
+@dataclass
+class _Pass:
+    """what one eval pass accumulates between its batches and hands to its ending"""
+    mark: Callable                       # mark(name): phase_log entry
+    t_begin: float
+    json_parts: Optional[list]           # per-video JSON text, formatted batch by batch; None: written from `output` at the end
+    n_valid: Optional[int]               # the THUMOS post-processing's row hint: the batches' counts summed; None: no hint
+    output: dict = field(default_factory=dict)
+    # the [T, C] score and target matrices of the videos, taken at launch time: they stay torch tensors on the model's device (one entry
+    # per video, concatenated once at the end; the reference extends Python lists by one row object per frame, eval.py:46-49), so the
+    # metric's kernels can be enqueued behind the last forward before the host waits for anything
+    pred_scores: list = field(default_factory=list)
+    gt_targets: list = field(default_factory=list)
+    argmax_ids: list = field(default_factory=list)      # cfg['eval_segmental']: the videos' device argmax, in the order of pred_scores
+    per_video: list = field(default_factory=list)       # (loader position, n_frames) to restore the loader's order on rank 0
+    pending: Optional[_Launched] = None  # the batch whose launch is out and whose host half (_collect) is still due
+    metric_inputs: Optional[tuple] = None
+    finish_ap: Optional[Callable] = None
+    finish_ps: Optional[Callable] = None
+    finish_seg: Optional[Callable] = None
+
+
 @EVAL.register("OAD")
 class Evaluate(nn.Module):
     def __init__(self, cfg):
         super().__init__()
         # thumos_postprocessing applies to THUMOS only (eval.py:19-21): None, or a ThumosPostprocessing under cfg['eval_thumos_postprocessing']
         self.data_processing = _thumos_postprocessing(cfg, "THUMOS" in cfg["data_name"])
-        self._n_valid = None                 # the frames the post-processing keeps, counted from the loader's host targets (_targets_to_device)
         self.metric = cfg["metric"]
         if self.metric not in ("AP", "cAP"):          # known before the eval pass runs, not after it (utils/metrics.py:38-44)
             raise RuntimeError(f"Unknown metrics: {self.metric}")
         self.cfg = cfg
         self.all_class_names = json.load(open(cfg["video_list_path"]))[cfg["data_name"].split("_")[0]]["class_index"]
-        # frames per forward.  The loop is pipelined one batch deep (eval: _flush / _collect): while batch k's features cross the link and
+        # frames per forward.  The loop is pipelined one batch deep (_step: _flush / _collect): while batch k's features cross the link and
         # its forward runs, the host waits for batch k - 1's ids and formats their JSON text.  Measured on the 182-video bench set
         # (2.3 M frames, 16-bit features): ONE batch 226 ms, two batches of 1.2 M frames 238 ms - every forward pays its own fill and tail
         # (~12 ms) and the text it hides is 6 ms -, so the default keeps an eval set of this size in one forward
@@ -140,21 +208,16 @@ class Evaluate(nn.Module):
         one-hot targets (what the reference's dataset yields) travel as ONE class id per frame: `prego_onehot_labels` reduces them in the
         loader's memory (a few host threads, while the GPU is busy with the features) and says per video whether the ids tell everything
         the rows do - 4 bytes per frame over the link instead of 4 x classes (0.79 GB for the 182-video eval set: 14 ms of a 200 ms
-        pass).  Such a video's entry is an int32 vector [T]; any other video's rows are copied as they are ([T, C])."""
-        out = [None] * len(targets)
-        if self.data_processing is not None and self._n_valid is not None:
+        pass).  Such a video's entry is an int32 vector [T]; any other video's rows are copied as they are ([T, C]).  Returns the entries,
+        what must stay alive until the copies have run, and the rows the THUMOS post-processing keeps of them (None: not counted)."""
+        out, keep, n_valid = [None] * len(targets), [], None
+        if self.data_processing is not None and all(t.device.type == "cpu" and t.dim() == 2 for t in targets):
             # the frames the THUMOS post-processing keeps, counted while the rows are in host memory: with this hint the device
             # post-processing and the metric behind it are enqueued without a wait for the count (a device target: no hint)
-            if all(t.device.type == "cpu" and t.dim() == 2 for t in targets):
-                self._n_valid += sum(self.data_processing.count_valid(t.numpy()) for t in targets)
-            else:
-                self._n_valid = None
+            n_valid = sum(self.data_processing.count_valid(t.numpy()) for t in targets)
         host = [i for i, t in enumerate(targets) if t.device.type == "cpu" and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()
                 and t.shape[1] == len(self.all_class_names)]
         if host and self.cfg.get("eval_label_targets", True):
-            import ctypes as C
-            from . import _lib
-            from ._lib import check
             nv = len(host)
             ptrs = (C.c_void_p * nv)(*[targets[i].data_ptr() for i in host])
             rows = (C.c_int64 * nv)(*[int(targets[i].shape[0]) for i in host])
@@ -163,7 +226,7 @@ class Evaluate(nn.Module):
             flags = (C.c_int32 * nv)()
             check(_lib.load().prego_onehot_labels(nv, ptrs, rows, len(self.all_class_names), C.c_void_p(labels.data_ptr()), flags))
             labels_dev = labels.to(dev, non_blocking=True)
-            self._keep_labels = labels                       # the pinned source of an async copy
+            keep.append(labels)                              # the pinned source of an async copy
             o = 0
             for k, i in enumerate(host):
                 n = int(targets[i].shape[0])
@@ -173,7 +236,7 @@ class Evaluate(nn.Module):
         for i, t in enumerate(targets):
             if out[i] is None:
                 out[i] = t.to(dev, non_blocking=True)
-        return out
+        return out, keep, n_valid
 
     def _gt_matrix(self, t):
         """a video's ground truth as the [T, C] matrix the loader gave (class-id vectors of _targets_to_device expanded again)"""
@@ -186,7 +249,7 @@ class Evaluate(nn.Module):
     def _enqueue(self, model, sub, device):
         """H2D of one sub-batch on the copy stream + its forward on the compute stream; nothing here waits for the GPU"""
         dev = torch.device(device)
-        flows = [b[1] for b in sub]
+        flows = [b.flow for b in sub]
         if all(f is None for f in flows):
             flows = None
         if dev.type == "cuda":
@@ -196,30 +259,30 @@ class Evaluate(nn.Module):
                 self._copy_stream = self._new_copy_stream(dev)
             cur = torch.cuda.current_stream(dev)
             with torch.cuda.stream(self._copy_stream):
-                rgb = [b[0].to(dev, non_blocking=True) for b in sub]
+                rgb = [b.features.to(dev, non_blocking=True) for b in sub]
                 flow = None if flows is None else [None if f is None else f.to(dev, non_blocking=True) for f in flows]
-                tgt = self._targets_to_device([b[2] for b in sub], dev)
+                tgt, keep, n_valid = self._targets_to_device([b.target for b in sub], dev)
                 ready = torch.cuda.Event()
                 ready.record(self._copy_stream)
             cur.wait_event(ready)
             for t in rgb + [f for f in (flow or []) if f is not None] + tgt:
                 t.record_stream(cur)         # allocated on the copy stream, consumed on the compute stream
         else:
-            rgb = [b[0].to(device) for b in sub]
+            rgb = [b.features.to(device) for b in sub]
             flow = None if flows is None else [None if f is None else f.to(device) for f in flows]
-            tgt = self._targets_to_device([b[2] for b in sub], dev)
+            tgt, keep, n_valid = self._targets_to_device([b.target for b in sub], dev)
         probs, args, _ = model.forward_clips(rgb, flow, want_probs=True, want_argmax=True)
-        return probs, args, tgt, rgb, flow
+        return _Enqueued(probs, args, tgt, rgb, flow, n_valid, keep)
 
     @staticmethod
-    def _enqueue_resident(model, batch):
+    def _enqueue_resident(model, batch, device=None):
         """a batch cut from the feature cache: ONE forward on the resident tensors, whatever the batch's size - nothing to copy, so nothing
         to hide behind a first part (forward_ragged provides the resident buffer and the library picks the pass, as for any
-        device-resident call)"""
-        flow = [b[1] for b in batch]
-        probs, args, _ = model.forward_clips([b[0] for b in batch], None if all(f is None for f in flow) else flow, want_probs=True,
-                                             want_argmax=True)
-        return probs, args, [b[2] for b in batch]
+        device-resident call); the targets are in their device form already, and were never counted on the host"""
+        rgb, flow = [b.features for b in batch], [b.flow for b in batch]
+        flow = None if all(f is None for f in flow) else flow
+        probs, args, _ = model.forward_clips(rgb, flow, want_probs=True, want_argmax=True)
+        return _Enqueued(probs, args, [b.target for b in batch], rgb, flow, None, [])
 
     # link-fed eval: frames per H2D piece; one feed event per ~EVENT_BYTES copied.  A copy costs ~10 us of fixed time whatever its size, so
     # large pieces keep the link busier (182-video set, 16-bit features: 2 048 frames 226 ms to the last id, 4 096: 220, 8 192: 215.5) -
@@ -254,22 +317,22 @@ class Evaluate(nn.Module):
         if self._copy_stream is None:
             self._copy_stream = self._new_copy_stream(dev)
         cur = torch.cuda.current_stream(dev)
-        lens = [int(b[0].shape[0]) for b in batch]
-        any_flow = any(b[1] is not None for b in batch)
-        row_bytes = sum(int(t.shape[1]) * t.element_size() for t in (batch[0][0],) + ((next(b[1] for b in batch if b[1] is not None),) if any_flow else ()))
+        lens = [int(b.features.shape[0]) for b in batch]
+        any_flow = any(b.flow is not None for b in batch)
+        row_bytes = sum(int(t.shape[1]) * t.element_size() for t in (batch[0].features,) + ((next(b.flow for b in batch if b.flow is not None),) if any_flow else ()))
         start, n_steps = eng.plan_starts(lens, row_bytes)
         pieces = sorted((start[i] + a, i, a, b_) for i, T in enumerate(lens) for a, b_ in self._pieces_of(T))
         upto, events, acc = [], [], 0
         with torch.cuda.stream(self._copy_stream):
             # the destination tensors belong to the COPY stream (allocated inside its context): the copies of this batch follow the
             # previous batch's copies at once - they do not wait for the compute stream, which is still running the previous forward
-            rgb = [torch.empty(b[0].shape, dtype=b[0].dtype, device=dev) for b in batch]
-            flow = [None if b[1] is None else torch.empty(b[1].shape, dtype=b[1].dtype, device=dev) for b in batch] if any_flow else None
+            rgb = [torch.empty(b.features.shape, dtype=b.features.dtype, device=dev) for b in batch]
+            flow = [None if b.flow is None else torch.empty(b.flow.shape, dtype=b.flow.dtype, device=dev) for b in batch] if any_flow else None
             for k, (need, i, a, b) in enumerate(pieces):
-                rgb[i][a:b].copy_(batch[i][0][a:b], non_blocking=True)
+                rgb[i][a:b].copy_(batch[i].features[a:b], non_blocking=True)
                 acc += (b - a) * int(rgb[i].shape[1]) * rgb[i].element_size()
                 if flow is not None and flow[i] is not None:
-                    flow[i][a:b].copy_(batch[i][1][a:b], non_blocking=True)
+                    flow[i][a:b].copy_(batch[i].flow[a:b], non_blocking=True)
                     acc += (b - a) * int(flow[i].shape[1]) * flow[i].element_size()
                 last = k + 1 == len(pieces)
                 if acc >= self.EVENT_BYTES or last:
@@ -280,7 +343,6 @@ class Evaluate(nn.Module):
                     acc = 0
         for t in rgb + [f for f in (flow or []) if f is not None]:
             t.record_stream(cur)                               # allocated on the copy stream (inside its context), read on `cur`
-        self._feed_events = events                           # keep the hipEvent_t objects alive until the stream has used them
         eng.set_feed_events(upto, events, row_bytes)
         try:
             probs, args, _ = model.forward_clips(rgb, flow, want_probs=True, want_argmax=True)
@@ -289,122 +351,96 @@ class Evaluate(nn.Module):
             raise
         # the targets are only needed behind the forward: reduced / copied now that everything else is enqueued, behind the features
         with torch.cuda.stream(self._copy_stream):
-            tgt = self._targets_to_device([b[2] for b in batch], dev)
+            tgt, keep, n_valid = self._targets_to_device([b.target for b in batch], dev)
             ready = torch.cuda.Event()
             ready.record(self._copy_stream)
         for t in tgt:
             t.record_stream(cur)
         cur.wait_event(ready)
-        return probs, args, tgt, rgb, flow
+        return _Enqueued(probs, args, tgt, rgb, flow, n_valid, keep + events)      # the hipEvent_t objects stay alive until the stream has used them
 
     def _flush(self, model, batch, device, resident=False):
         """enqueue one batch (H2D + forward + argmax ids D2H): nothing here waits for the GPU.  Returns the record _collect finishes.
         resident: the batch comes from the feature cache (device tensors, targets in their device form)."""
         if not batch:
             return None
-        # Pinned host features + a model that can be fed while it runs: ONE link-fed forward (_enqueue_link_fed).  Otherwise a batch
-        # runs as long as its longest video's recurrence and its H2D copy would sit in front of that, so large batches go in two
-        # sub-batches ordered by length: the few longest videos first (little to copy, the long critical path), then the bulk of
-        # the bytes, whose copy runs under the first sub-batch's recurrence.  Results return to the loader's order below.
-        order = list(range(len(batch)))
-        parts = [order]
-        frames = [int(b[0].shape[0]) for b in batch]
+        # Pinned host features + a model that can be fed while it runs: ONE link-fed forward (_enqueue_link_fed).  Otherwise the batch is
+        # copied and then forwarded (_enqueue), a large one in two parts (split_by_length).  Results return to the loader's order below.
         on_gpu = torch.device(device).type == "cuda"
         link_fed = on_gpu and bool(getattr(model, "link_fed_eval", False)) and bool(self.cfg.get("eval_link_fed", True)) and len(batch) >= 2 and \
-            all(b[0].device.type == "cpu" and b[0].is_pinned() and (b[1] is None or (b[1].device.type == "cpu" and b[1].is_pinned())) for b in batch)
-        if len(batch) >= 16 and on_gpu and not link_fed and not resident and self.cfg.get("eval_split_by_length", True):
-            order.sort(key=lambda i: -frames[i])
-            # share of the frames in the first part: its forward should last about as long as the second part's copy.  Measured on
-            # the 60-video bench set (scripts/eval_e2e_bench.py): fp32 features 0.2: 4.23, 0.5: 4.72, 0.6: 4.41 M frames/s;
-            # 16-bit features (half the bytes) 0.2: 5.87, 0.5: 5.62
-            frac = self.cfg.get("eval_split_fraction")
-            if frac is None:
-                frac = 0.5 if batch[0][0].element_size() >= 4 else 0.2
-            budget, k, acc = float(frac) * sum(frames), 0, 0
-            while k < len(order) - 1 and acc + frames[order[k]] <= budget:
-                acc += frames[order[k]]
-                k += 1
-            if k >= 1:
-                parts = [order[:k], order[k:]]
-        res = {}
-        fed = {}                             # batch index -> (rgb, flow or None) as the forward read them on the device: what the cache keeps
-        if resident:
-            for i, (p, a, t) in enumerate(zip(*self._enqueue_resident(model, batch))):
-                res[i] = (p, a, t)
-        elif link_fed:
-            probs, args, tgt, rgb, flow = self._enqueue_link_fed(model, batch, device)
-            for i, (p, a, t) in enumerate(zip(probs, args, tgt)):
-                res[i] = (p, a, t)
-                fed[i] = (rgb[i], None if flow is None else flow[i])
+            all(b.features.device.type == "cpu" and b.features.is_pinned() and
+                (b.flow is None or (b.flow.device.type == "cpu" and b.flow.is_pinned())) for b in batch)
+        enqueue = self._enqueue_resident if resident else self._enqueue_link_fed if link_fed else self._enqueue
+        if on_gpu and not resident and not link_fed and self.cfg.get("eval_split_by_length", True):
+            parts = split_by_length([int(b.features.shape[0]) for b in batch], batch[0].features.element_size(), self.cfg.get("eval_split_fraction"))
         else:
-            for part in parts:
-                probs, args, tgt, rgb, flow = self._enqueue(model, [batch[i] for i in part], device)
-                for k, (i, p, a, t) in enumerate(zip(part, probs, args, tgt)):
-                    res[i] = (p, a, t)
-                    fed[i] = (rgb[k], None if flow is None else flow[k])
-        want_json = self.cfg["eval"] is not None
-        # np.argmax of the one-hot targets (eval.py:55) on the device, where they are anyway for the AP kernel (on the host it reads
-        # frames x classes floats through one core: 25 ms for the bench set); ONE device -> host copy of the whole batch's pred and gt
-        # ids is ENQUEUED here (into pinned memory, behind the forward) and waited for in _collect - one batch later, so that the next
-        # batch's copies and forward are already running while the host waits for these ids and formats their text
-        rec = {"items": [(b[3], res[i]) for i, b in enumerate(batch)], "ids": None, "ev": None, "link_fed": link_fed,
-               "src": list(batch), "feed": getattr(self, "_feed_events", None)}       # the loader's tensors / the feed events stay alive until _collect
-        if want_json:
-            pred_ids = torch.cat([res[i][1] for i in range(len(batch))])
-            gt_ids = torch.cat([res[i][2] if res[i][2].dim() == 1 else torch.argmax(res[i][2], dim=1)
-                                for i in range(len(batch))]).to(pred_ids.dtype)
-            ids_dev = torch.stack([pred_ids, gt_ids])
-            if ids_dev.is_cuda:
-                ids_host = torch.empty(ids_dev.shape, dtype=ids_dev.dtype, pin_memory=True)
-                ids_host.copy_(ids_dev, non_blocking=True)
-                if ids_dev.dtype == torch.int32 and len(self.all_class_names) <= 1000:
-                    # the JSON text of the ids as well (prego_format_ids: four bytes "%3d," per id), so that behind the last frame
-                    # the host only cuts it per video: formatting 2 x 2.3 M numbers through a numpy table took 10-15 ms there
-                    from . import _lib
-                    from ._lib import check
-                    import ctypes as C
-                    ids_dev = ids_dev.contiguous()
-                    text_dev = torch.empty(ids_dev.shape, dtype=torch.int32, device=ids_dev.device)
-                    bad_dev = torch.zeros(1, dtype=torch.int32, device=ids_dev.device)
-                    with torch.cuda.device(ids_dev.device):
-                        check(_lib.load().prego_format_ids(C.c_void_p(ids_dev.data_ptr()), ids_dev.numel(), C.c_void_p(text_dev.data_ptr()),
-                                                           C.c_void_p(bad_dev.data_ptr()),
-                                                           C.c_void_p(torch.cuda.current_stream(ids_dev.device).cuda_stream)))
-                    text_host = torch.empty(ids_dev.shape, dtype=torch.int32, pin_memory=True)
-                    bad_host = torch.empty(1, dtype=torch.int32, pin_memory=True)
-                    text_host.copy_(text_dev, non_blocking=True)
-                    bad_host.copy_(bad_dev, non_blocking=True)
-                    rec["text"], rec["bad"], rec["_keep_text"] = text_host, bad_host, (text_dev, bad_dev)
-                ev = torch.cuda.Event()
-                ev.record()
-                rec["ids"], rec["ev"], rec["_keep"] = ids_host, ev, ids_dev
-            else:                                  # a stand-in model on a CPU box (the gloo tests of the sharding logic)
-                rec["ids"] = ids_dev
+            parts = [list(range(len(batch)))]
+        rec = _Launched([None] * len(batch), link_fed, keep=list(batch))
+        fed = [None] * len(batch)            # (rgb, flow or None) as the forward read them on the device: what the cache keeps
+        for part in parts:
+            r = enqueue(model, [batch[i] for i in part], device)
+            for k, i in enumerate(part):
+                rec.videos[i] = (batch[i].name, r.probs[k], r.argmax[k], r.targets[k])
+                fed[i] = (r.rgb[k], None if r.flow is None else r.flow[k])
+            rec.keep += r.keep
+            rec.n_valid = None if (rec.n_valid is None or r.n_valid is None) else rec.n_valid + r.n_valid
+        if self.cfg["eval"] is not None:
+            self._enqueue_ids(rec)
         if self._cache is not None and self._cache.filling:
             # behind everything this batch's ids wait for: the features (fp32 ones of a 16-bit engine converted by prego_cast_features, on
-            # this stream, behind the forward that read them) and the device targets stay; an fp32 source lives until _collect drops rec
-            n = range(len(batch))
-            self._cache.retain(batch, [fed[i][0] for i in n], [fed[i][1] for i in n], [res[i][2] for i in n], torch.device(device))
-            rec["fed"] = fed
+            # this stream, behind the forward that read them) and the device targets stay; an fp32 source lives until _collect drops it
+            self._cache.retain(batch, [rgb for rgb, _fl in fed], [fl for _rgb, fl in fed], [t for _vid, _p, _a, t in rec.videos], torch.device(device))
+            rec.fed = fed
         batch.clear()
         return rec
 
-    def _collect(self, rec, pred_scores, gt_targets, output, json_parts):
+    def _enqueue_ids(self, rec):
+        """enqueue the batch's ids to the host.  np.argmax of the one-hot targets (eval.py:55) on the device, where they are anyway for the
+        AP kernel (on the host it reads frames x classes floats through one core: 25 ms for the bench set); ONE device -> host copy of the
+        whole batch's pred and gt ids is ENQUEUED here (into pinned memory, behind the forward) and waited for in _collect - one batch
+        later, so that the next batch's copies and forward are already running while the host waits for these ids and formats their text"""
+        pred_ids = torch.cat([a for _vid, _p, a, _t in rec.videos])
+        gt_ids = torch.cat([t if t.dim() == 1 else torch.argmax(t, dim=1) for _vid, _p, _a, t in rec.videos]).to(pred_ids.dtype)
+        ids_dev = torch.stack([pred_ids, gt_ids])
+        if not ids_dev.is_cuda:                    # a stand-in model on a CPU box (the gloo tests of the sharding logic)
+            rec.ids = ids_dev
+            return
+        rec.ids = torch.empty(ids_dev.shape, dtype=ids_dev.dtype, pin_memory=True)
+        rec.ids.copy_(ids_dev, non_blocking=True)
+        rec.keep.append(ids_dev)
+        if ids_dev.dtype == torch.int32 and len(self.all_class_names) <= 1000:
+            # the JSON text of the ids as well (prego_format_ids: four bytes "%3d," per id), so that behind the last frame
+            # the host only cuts it per video: formatting 2 x 2.3 M numbers through a numpy table took 10-15 ms there
+            text_dev = torch.empty(ids_dev.shape, dtype=torch.int32, device=ids_dev.device)
+            bad_dev = torch.zeros(1, dtype=torch.int32, device=ids_dev.device)
+            with torch.cuda.device(ids_dev.device):
+                check(_lib.load().prego_format_ids(C.c_void_p(ids_dev.data_ptr()), ids_dev.numel(), C.c_void_p(text_dev.data_ptr()),
+                                                   C.c_void_p(bad_dev.data_ptr()),
+                                                   C.c_void_p(torch.cuda.current_stream(ids_dev.device).cuda_stream)))
+            rec.text = torch.empty(ids_dev.shape, dtype=torch.int32, pin_memory=True)
+            rec.text_bad = torch.empty(1, dtype=torch.int32, pin_memory=True)
+            rec.text.copy_(text_dev, non_blocking=True)
+            rec.text_bad.copy_(bad_dev, non_blocking=True)
+            rec.keep += [text_dev, bad_dev]
+        rec.ids_ready = torch.cuda.Event()
+        rec.ids_ready.record()
+
+    def _collect(self, rec, output, json_parts):
         """the host half of a batch, one batch behind its launch: wait for its ids, cut them per video, format the videos' JSON text"""
         if rec is None:
             return
         ids = None
-        if rec["ids"] is not None:
-            if rec["ev"] is not None:
-                rec["ev"].synchronize()
-            ids = rec["ids"].numpy()
-        elif rec["link_fed"]:
+        if rec.ids is not None:
+            if rec.ids_ready is not None:
+                rec.ids_ready.synchronize()
+            ids = rec.ids.numpy()
+        elif rec.link_fed:
             self._copy_stream.synchronize()      # the copies read the loader's pinned tensors: keep them alive until then
         text = None
-        if ids is not None and rec.get("text") is not None and int(rec["bad"][0]) == 0:
-            text = rec["text"].numpy().view(np.uint8).reshape(2, -1, 4)      # [pred | gt][frame] = b"%3d," (prego_format_ids)
+        if ids is not None and rec.text is not None and int(rec.text_bad[0]) == 0:
+            text = rec.text.numpy().view(np.uint8).reshape(2, -1, 4)      # [pred | gt][frame] = b"%3d," (prego_format_ids)
         o = 0
-        for vid, (p, a, t) in rec["items"]:
+        for vid, _p, a, _t in rec.videos:
             if ids is not None:
                 n = int(a.shape[0])
                 output[vid] = {"pred": ids[0, o:o + n], "gt": ids[1, o:o + n]}      # int arrays; text below
@@ -422,7 +458,7 @@ class Evaluate(nn.Module):
                     self._cache.gt_ids[vid] = output[vid]["gt"].copy()
                 o += n
                 self.last_device_argmax[vid] = a          # int32 on the device: input of aggregate_device (utils/aggregate.py)
-        rec.pop("fed", None)                 # a filling call's device features: what the cache does not keep (fp32 sources of its 16-bit copies) goes now
+        rec.fed = []                         # a filling call's device features: what the cache does not keep (fp32 sources of its 16-bit copies) goes now
 
     def _cat_targets(self, gt_targets, matrix=False):
         """the eval set's ground truth: one class-id vector [frames] when every video came as class ids (and the caller takes them), else
@@ -431,32 +467,15 @@ class Evaluate(nn.Module):
             return torch.cat(gt_targets, 0)
         return torch.cat([self._gt_matrix(t) for t in gt_targets], 0)
 
-    def _postprocessed(self, pred, gt):
+    def _postprocessed(self, pred, gt, n_valid):
         """the eval set's device scores and targets as the metrics see them: unchanged, or - cfg['eval_thumos_postprocessing'] -
         post-processed ONCE on the device (prego_thumos_postprocess, enqueued on the current stream) for the per-frame and the per-stage
         metric; the third value compares the device's row count with the host's when the metric is collected (None: nothing to
         compare).  The output file, the logged frame count and the FPS keep every frame: the reference post-processes inside the metric."""
         if self.data_processing is None:
             return pred, gt, None
-        res = thumos_postprocessing_device(pred, gt, self.data_processing, self._n_valid)
-        return res[1], res[0], (res.check if self._n_valid is not None else None)
-
-    @staticmethod
-    def _scores(rec, pred_scores, gt_targets):
-        """the [T, C] score and target matrices of a batch's videos, taken at launch time: they stay torch tensors on the model's device
-        (one entry per video, concatenated once at the end; the reference extends Python lists by one row object per frame,
-        eval.py:46-49), so the metric's kernels can be enqueued behind the last forward before the host waits for anything"""
-        if rec is not None:
-            for _vid, (p, _a, t) in rec["items"]:
-                pred_scores.append(p)
-                gt_targets.append(t)
-
-    @staticmethod
-    def _argmax(rec, argmax_ids):
-        """the device argmax of a batch's videos, taken at launch time as _scores takes the scores"""
-        if rec is not None:
-            for _vid, (_p, a, _t) in rec["items"]:
-                argmax_ids.append(a)
+        res = thumos_postprocessing_device(pred, gt, self.data_processing, n_valid)
+        return res[1], res[0], (res.check if n_valid is not None else None)
 
     def _enqueue_segmental(self, argmax_ids, gt_targets, dev):
         """cfg['eval_segmental']: prego_segmental_scores twice on the current stream - over the per-video device argmax and the device
@@ -464,10 +483,6 @@ class Evaluate(nn.Module):
         frames and cut to the video's length.  Returns the function that collects {"frames": report, "vote": report}; a vote marker of
         -1 (a window with an id outside the classes) raises there, as in aggregate_device.  cfg['eval_thumos_postprocessing'] does not
         feed this metric: it works on the argmax of the raw scores, every frame kept."""
-        import ctypes as C
-
-        from . import _lib
-        from ._lib import check
         lib, w, ncls = _lib.load(), self.segmental_window, len(self.all_class_names)
         if w < 1 or ncls > 128:
             raise PregoError(f"cfg['eval_segmental']: eval_segmental_window {w} (>= 1), {ncls} classes (prego_window_vote takes up to 128)")
@@ -497,8 +512,7 @@ class Evaluate(nn.Module):
         return finish
 
     def _loader_videos(self, model, dataloader, world, rank, skip_flow):
-        """this rank's videos as the loop below batches them, one list per loader item: (features, flow or None, target rows, name,
-        position in the loader's order, loader item)"""
+        """this rank's videos (EvalVideo) as the loop below batches them, one list per loader item"""
         pos = 0
         for item, (rgb_input, flow_input, target, vid, start, end) in enumerate(dataloader):
             group = []
@@ -510,7 +524,7 @@ class Evaluate(nn.Module):
                     continue
                 name = vid[b] if isinstance(vid, (list, tuple)) else vid
                 fl = None if (skip_flow or self._flow_zero(model, flow_input[b])) else self._features(model, flow_input[b])
-                group.append((self._features(model, rgb_input[b]), fl, target[b], name, pos - 1, item))
+                group.append(EvalVideo(self._features(model, rgb_input[b]), fl, target[b], name, pos - 1, item))
             yield group
 
     def eval(self, model, dataloader, logger, device):
@@ -575,181 +589,177 @@ class Evaluate(nn.Module):
 
     def _eval_pass(self, model, videos, logger, device, world, rank):
         """`videos`: _loader_videos, or the feature cache's record of them (device tensors: every batch is one resident forward)"""
-        output = {}
         self.last_device_argmax = {}
         max_clips = model.max_clips          # MROAD: the engine's clip capacity; ViTEnc (`model: 'Transformer'`): its own bound
         resident = self.last_source == "cache"
+        t0_ = time.perf_counter()
+        self.phase_log = []                  # (phase, host seconds since the start of this eval): where an end-to-end eval spends its time
         # the THUMOS post-processing's row count: summed over the batches' host targets; a cached set's targets are on the device, so
         # its count is read back from there (8 bytes, behind the last forward)
-        self._n_valid = 0 if (self.data_processing is not None and not resident) else None
+        ps = _Pass(mark=lambda name: self.phase_log.append((name, time.perf_counter() - t0_)), t_begin=time.time(),
+                   json_parts=[] if (self.cfg["eval"] is not None and world == 1) else None,
+                   n_valid=0 if (self.data_processing is not None and not resident) else None)
         with torch.no_grad():
-            pred_scores, gt_targets = [], []
-            argmax_ids = []                      # cfg['eval_segmental']: the videos' device argmax, in the order of pred_scores
-            per_video = []                       # (loader position, n_frames) to restore the loader's order on rank 0
-            t_begin = time.time()
-            t0_ = time.perf_counter()
-            self.phase_log = []                  # (phase, host seconds since the start of this eval): where an end-to-end eval spends its time
-            mark = lambda name: self.phase_log.append((name, time.perf_counter() - t0_))
             batch, frames = [], 0
-            pending = None                       # the batch whose launch is out and whose host half (_collect) is still due
-            json_parts = [] if (self.cfg["eval"] is not None and world == 1) else None      # per-video JSON text, formatted batch by batch
             for group in videos:
-                for it in group:
-                    batch.append(it)
-                    per_video.append((it[4], int(it[0].shape[0])))
-                    frames += int(it[0].shape[0])
+                for v in group:
+                    batch.append(v)
+                    ps.per_video.append((v.pos, int(v.features.shape[0])))
+                    frames += int(v.features.shape[0])
                 if len(batch) >= max_clips or frames >= self.max_frames_per_batch:
-                    mark("loader")
-                    rec = self._flush(model, batch, device, resident)       # batch k: enqueued ...
-                    self._scores(rec, pred_scores, gt_targets)
-                    self._argmax(rec, argmax_ids)
-                    mark("launch")
-                    self._collect(pending, pred_scores, gt_targets, output, json_parts)      # ... while the host finishes batch k - 1
-                    mark("collect")
-                    pending = rec
+                    self._step(ps, model, batch, device, resident)
                     frames = 0
-            mark("loader")
-            rec = self._flush(model, batch, device, resident)
-            self._scores(rec, pred_scores, gt_targets)
-            self._argmax(rec, argmax_ids)
-            finish_ap = None
-            if world == 1 and torch.device(device).type == "cuda" and pred_scores:
-                # the metric in libprego_amd.so (prego_perframe_ap, or prego_perframe_cap for metric 'cAP'), ENQUEUED here behind the last forward and collected behind the
-                # output file: the GPU ranks the positives while the host waits for the ids and writes the JSON
-                # ... on a stream of its own behind an event, so that model.check() below (which drains the forward's stream to read its
-                # timeout word) does not wait for the metric as well
-                if self._ap_stream is None:
-                    self._ap_stream = torch.cuda.Stream(torch.device(device))
-                fwd_done = torch.cuda.Event()
-                fwd_done.record(torch.cuda.current_stream(torch.device(device)))
-                with torch.cuda.stream(self._ap_stream):
-                    self._ap_stream.wait_event(fwd_done)
-                    pred_all = torch.cat(pred_scores, 0)
-                    gt_all = self._cat_targets(gt_targets).to(pred_all.device)
-                    pred_m, gt_m, post_check = self._postprocessed(pred_all.to(device), gt_all.to(device))
-                    ap_fn = perframe_average_precision_device(pred_m, gt_m, self.all_class_names, None, self.metric, defer=True)
-
-                def finish_ap(_fn=ap_fn, _s=self._ap_stream, _check=post_check):
-                    with torch.cuda.stream(_s):           # the result's device -> host copy follows the kernels on THEIR stream
-                        rep = _fn()
-                        if _check is not None:
-                            _check()
-                        return rep
-            finish_ps = None
-            self.last_perstage = None
-            if self.perstage and pred_scores:
-                # the per-stage report on the same device-resident scores and class ids, enqueued behind the per-frame metric and
-                # collected behind everything eval writes and logs today
-                if not all(t.dim() == 1 for t in gt_targets):
-                    raise PregoError("cfg['eval_perstage']: per-stage AP needs targets that are one class id per frame (one-hot rows, "
-                                     "cfg['eval_label_targets'] on); this eval set has rows that are not (dense multi-label targets: "
-                                     "prego_amd.metrics.perstage_average_precision on the host)")
-                if self._ap_stream is None:
-                    self._ap_stream = torch.cuda.Stream(torch.device(device))
-                fwd_done = torch.cuda.Event()
-                fwd_done.record(torch.cuda.current_stream(torch.device(device)))
-                with torch.cuda.stream(self._ap_stream):
-                    self._ap_stream.wait_event(fwd_done)
-                    if finish_ap is None:                 # nothing is concatenated yet
-                        pred_all = torch.cat(pred_scores, 0)
-                        gt_all = self._cat_targets(gt_targets).to(pred_all.device)
-                        pred_m, gt_m, _ = self._postprocessed(pred_all.to(device), gt_all.to(device))
-                    ps_fn = perstage_average_precision_device(pred_m, gt_m, self.all_class_names, defer=True, metrics=self.perstage_metric)
-
-                def finish_ps(_fn=ps_fn, _s=self._ap_stream):
-                    with torch.cuda.stream(_s):
-                        return _fn()
-            finish_seg = None
-            self.last_segmental = None
-            if self.segmental and pred_scores:
-                # the segmental records of the same device-resident ids, enqueued behind the other metrics on their stream
-                if not all(t.dim() == 1 for t in gt_targets):
-                    raise PregoError("cfg['eval_segmental']: the segmental metrics need targets that are one class id per frame (one-hot "
-                                     "rows, cfg['eval_label_targets'] on); this eval set has rows that are not (dense multi-label targets "
-                                     "have no transcript)")
-                if self._ap_stream is None:
-                    self._ap_stream = torch.cuda.Stream(torch.device(device))
-                fwd_done = torch.cuda.Event()
-                fwd_done.record(torch.cuda.current_stream(torch.device(device)))
-                with torch.cuda.stream(self._ap_stream):
-                    self._ap_stream.wait_event(fwd_done)
-                    seg_fn = self._enqueue_segmental(argmax_ids, gt_targets, torch.device(device))
-
-                def finish_seg(_fn=seg_fn, _s=self._ap_stream):
-                    with torch.cuda.stream(_s):
-                        return _fn()
-            mark("launch")
-            self._collect(pending, pred_scores, gt_targets, output, json_parts)
-            mark("collect")
-            self._collect(rec, pred_scores, gt_targets, output, json_parts)
-            mark("collect_last")
+            self._step(ps, model, batch, device, resident, behind=lambda: self._enqueue_metrics(ps, device, world))
+            self._collect(ps.pending, ps.output, ps.json_parts)
+            ps.mark("collect_last")
             model.check()
-            mark("check")
+            ps.mark("check")
             if world > 1:
-                # the small things go to rank 0 as objects: per-video frame counts and the pred / gt id arrays of the output file
-                # (8 bytes per frame).  The [frames x classes] score and target matrices do NOT travel whole (round 3 pickled 0.8 GB of
-                # them through gather_object): the metric is computed class-sharded, see _sharded_ap
-                gathered = [None] * world if rank == 0 else None
-                dist.gather_object((per_video, output), gathered, dst=0)
-                if rank == 0:                       # back into the loader's order (a rank's dict is in the order of its per_video list)
-                    entries = []
-                    for pv, out in gathered:
-                        entries += [(p_idx, vid, ent) for (p_idx, _n), (vid, ent) in zip(pv, out.items())]
-                    output = {vid: ent for _p, vid, ent in sorted(entries, key=lambda e: e[0])}
-                pred_local = torch.cat(pred_scores, 0) if pred_scores else torch.zeros((0, len(self.all_class_names)), device=device)
-                gt_local = self._cat_targets(gt_targets).to(pred_local.device) if gt_targets else torch.zeros_like(pred_local)
-                result = self._sharded_ap(pred_local, gt_local, world, rank)
-                if rank == 0 and self.cfg["eval"] is not None:
-                    os.makedirs(self.output_dir, exist_ok=True)
-                    with open(os.path.join(self.output_dir, "output_miniROAD.json"), "wb") as file:
-                        file.write(self._json_int_lists(output))
-                t_end = time.time()
-                nf = torch.tensor([int(pred_local.shape[0])], dtype=torch.int64, device=pred_local.device)
-                dist.all_reduce(nf)
-                num_frames = int(nf.item())
-                self.last_fps = num_frames / max(t_end - t_begin, 1e-9)
-                if rank == 0:
-                    logger.info(f"Processed {num_frames} frames in {t_end - t_begin:.1f} seconds ({self.last_fps:.1f} FPS)")
-                return result["mean_AP"]
-            if finish_ap is None:
-                pred_all = torch.cat(pred_scores, 0) if pred_scores else torch.zeros((0, len(self.all_class_names)))
-                gt_all = self._cat_targets(gt_targets, matrix=True).to(pred_all.device) if gt_targets else torch.zeros_like(pred_all)
-                if torch.device(device).type == "cuda":        # an empty eval set: the empty report
-                    finish_ap = perframe_average_precision_device(pred_all.to(device), gt_all.to(device), self.all_class_names,
-                                                                  self.data_processing, self.metric, defer=True)
-            num_frames = int(gt_all.shape[0])
-            if self.cfg["eval"] is not None:
-                os.makedirs(self.output_dir, exist_ok=True)
-                with open(os.path.join(self.output_dir, "output_miniROAD.json"), "wb") as file:
-                    if json_parts is not None:          # per-video pieces (bytes and slices of the device-made text), ", " between videos
-                        file.write(b"{")
-                        file.writelines(json_parts)
-                        file.write(b"}")
-                    else:
-                        file.write(self._json_int_lists(output))
-            mark("json_written")
-            self.last_metric_path = "device" if finish_ap is not None else "host"
-            if finish_ap is not None:
-                result = finish_ap()
-                mark("ap_done")
-            else:       # a stand-in model on a CPU box (the gloo tests of the sharding logic)
-                result = perframe_average_precision(pred_all.cpu().numpy(), gt_all.cpu().numpy(), self.all_class_names, self.data_processing, self.metric)
-            t_end = time.time()
-            time_taken = max(t_end - t_begin, 1e-9)
-            self.last_fps = num_frames / time_taken
-            logger.info(f"Processed {num_frames} frames in {time_taken:.1f} seconds ({self.last_fps:.1f} FPS)")
-            if self.perstage:
-                self.last_perstage = finish_ps() if finish_ps is not None else \
-                    perstage_report(np.zeros((N_STAGES, len(self.all_class_names))), self.all_class_names)
-                mark("perstage_done")
-                for stage, rep_ in self.last_perstage.items():
-                    logger.info(f"per-stage mAP {stage}: {rep_['mean_AP'] * 100:.2f}")
-            if finish_seg is not None:
-                self.last_segmental = finish_seg()
-                mark("segmental_done")
-                for key in [k for k in self.last_segmental["frames"] if k not in ("videos", "per_video")]:      # MoF, Edit, three F1
-                    logger.info(f"segmental {key}: frames {self.last_segmental['frames'][key]:.2f}, "
-                                f"vote({self.segmental_window}) {self.last_segmental['vote'][key]:.2f}")
+                return self._end_multi_rank(ps, logger, device, world, rank)
+            return self._end_single_process(ps, logger, device)
+
+    def _step(self, ps, model, batch, device, resident, behind=None):
+        """one step of the pass loop, in the loop and behind it: batch k is enqueued, then the host finishes batch k - 1.
+        behind: enqueues what follows the last forward (the metrics), before the host waits for anything"""
+        ps.mark("loader")
+        rec = self._flush(model, batch, device, resident)       # batch k: enqueued ...
+        if rec is not None:
+            for _vid, p, a, t in rec.videos:
+                ps.pred_scores.append(p)
+                ps.gt_targets.append(t)
+                ps.argmax_ids.append(a)
+            if ps.n_valid is not None:       # one batch whose rows were not counted: no hint for the pass
+                ps.n_valid = None if rec.n_valid is None else ps.n_valid + rec.n_valid
+        if behind is not None:
+            behind()
+        ps.mark("launch")
+        self._collect(ps.pending, ps.output, ps.json_parts)      # ... while the host finishes batch k - 1
+        ps.mark("collect")
+        ps.pending = rec
+
+    def _on_metric_stream(self, dev, enqueue):
+        """The metric queue: `enqueue()` runs on a stream of its own behind an event on the forward's stream, so that model.check() (which
+        drains the forward's stream to read its timeout word) does not wait for the metric as well.  enqueue returns the function that
+        collects the metric; what is returned here calls it under the same stream: the result's device -> host copy follows the kernels
+        on THEIR stream."""
+        if self._ap_stream is None:
+            self._ap_stream = torch.cuda.Stream(dev)
+        fwd_done = torch.cuda.Event()
+        fwd_done.record(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(self._ap_stream):
+            self._ap_stream.wait_event(fwd_done)
+            fn = enqueue()
+
+        def finish(_s=self._ap_stream):
+            with torch.cuda.stream(_s):
+                return fn()
+        return finish
+
+    def _metric_inputs(self, ps, dev):
+        """(pred, gt, check) of _postprocessed for the pass's concatenated scores and targets, made once (on the current stream)"""
+        if ps.metric_inputs is None:
+            pred_all = torch.cat(ps.pred_scores, 0)
+            gt_all = self._cat_targets(ps.gt_targets).to(pred_all.device)
+            ps.metric_inputs = self._postprocessed(pred_all.to(dev), gt_all.to(dev), ps.n_valid)
+        return ps.metric_inputs
+
+    def _need_class_ids(self, key, gt_targets):
+        if not all(t.dim() == 1 for t in gt_targets):
+            raise PregoError(f"cfg['{key}'] needs targets that are one class id per frame (one-hot rows, cfg['eval_label_targets'] on); this "
+                             "eval set has rows that are not (dense multi-label targets: no runs of one action, no transcript)")
+
+    def _enqueue_metrics(self, ps, device, world):
+        """behind the last forward: per-frame AP, per-stage AP and the segmental metrics, each enqueued on the metric stream in this order"""
+        dev = torch.device(device)
+        self.last_perstage = self.last_segmental = None
+        if not ps.pred_scores:
+            return
+        if world == 1 and dev.type == "cuda":
+            # the metric in libprego_amd.so (prego_perframe_ap, or prego_perframe_cap for metric 'cAP'), ENQUEUED here behind the last
+            # forward and collected behind the output file: the GPU ranks the positives while the host waits for the ids and writes the JSON
+            def enqueue_ap():
+                pred, gt, post_check = self._metric_inputs(ps, dev)
+                ap_fn = perframe_average_precision_device(pred, gt, self.all_class_names, None, self.metric, defer=True)
+                return ap_fn if post_check is None else lambda: (ap_fn(), post_check())[0]      # the report, behind it the row count's check
+            ps.finish_ap = self._on_metric_stream(dev, enqueue_ap)
+        if self.perstage:
+            # the per-stage report on the same device-resident scores and class ids, enqueued behind the per-frame metric and
+            # collected behind everything eval writes and logs today
+            self._need_class_ids("eval_perstage", ps.gt_targets)
+            ps.finish_ps = self._on_metric_stream(dev, lambda: perstage_average_precision_device(
+                *self._metric_inputs(ps, dev)[:2], self.all_class_names, defer=True, metrics=self.perstage_metric))
+        if self.segmental:
+            # the segmental records of the same device-resident ids, enqueued behind the other metrics on their stream
+            self._need_class_ids("eval_segmental", ps.gt_targets)
+            ps.finish_seg = self._on_metric_stream(dev, lambda: self._enqueue_segmental(ps.argmax_ids, ps.gt_targets, dev))
+
+    def _write_output(self, chunks):
+        os.makedirs(self.output_dir, exist_ok=True)
+        with open(os.path.join(self.output_dir, "output_miniROAD.json"), "wb") as file:
+            file.writelines(chunks)
+
+    def _end_multi_rank(self, ps, logger, device, world, rank):
+        """the ending of a pass on several ranks: gather, class-sharded AP, rank 0 writes the file, FPS"""
+        # the small things go to rank 0 as objects: per-video frame counts and the pred / gt id arrays of the output file
+        # (8 bytes per frame).  The [frames x classes] score and target matrices do NOT travel whole (round 3 pickled 0.8 GB of
+        # them through gather_object): the metric is computed class-sharded, see _sharded_ap
+        output = ps.output
+        gathered = [None] * world if rank == 0 else None
+        dist.gather_object((ps.per_video, output), gathered, dst=0)
+        if rank == 0:                       # back into the loader's order (a rank's dict is in the order of its per_video list)
+            entries = []
+            for pv, out in gathered:
+                entries += [(p_idx, vid, ent) for (p_idx, _n), (vid, ent) in zip(pv, out.items())]
+            output = {vid: ent for _p, vid, ent in sorted(entries, key=lambda e: e[0])}
+        pred_local = torch.cat(ps.pred_scores, 0) if ps.pred_scores else torch.zeros((0, len(self.all_class_names)), device=device)
+        gt_local = self._cat_targets(ps.gt_targets).to(pred_local.device) if ps.gt_targets else torch.zeros_like(pred_local)
+        result = self._sharded_ap(pred_local, gt_local, world, rank)
+        if rank == 0 and self.cfg["eval"] is not None:
+            self._write_output([self._json_int_lists(output)])
+        t_end = time.time()
+        nf = torch.tensor([int(pred_local.shape[0])], dtype=torch.int64, device=pred_local.device)
+        dist.all_reduce(nf)
+        num_frames = int(nf.item())
+        self.last_fps = num_frames / max(t_end - ps.t_begin, 1e-9)
+        if rank == 0:
+            logger.info(f"Processed {num_frames} frames in {t_end - ps.t_begin:.1f} seconds ({self.last_fps:.1f} FPS)")
+        return result["mean_AP"]
+
+    def _end_single_process(self, ps, logger, device):
+        """the ending of a single-process pass: write the file, collect the metrics behind it, log"""
+        finish_ap = ps.finish_ap
+        if finish_ap is None:
+            pred_all = torch.cat(ps.pred_scores, 0) if ps.pred_scores else torch.zeros((0, len(self.all_class_names)))
+            gt_all = self._cat_targets(ps.gt_targets, matrix=True).to(pred_all.device) if ps.gt_targets else torch.zeros_like(pred_all)
+            if torch.device(device).type == "cuda":        # an empty eval set: the empty report
+                finish_ap = perframe_average_precision_device(pred_all.to(device), gt_all.to(device), self.all_class_names,
+                                                              self.data_processing, self.metric, defer=True)
+        num_frames = sum(n for _pos, n in ps.per_video)
+        if self.cfg["eval"] is not None:      # per-video pieces (bytes and slices of the device-made text), ", " between videos
+            self._write_output([self._json_int_lists(ps.output)] if ps.json_parts is None else [b"{", *ps.json_parts, b"}"])
+        ps.mark("json_written")
+        self.last_metric_path = "device" if finish_ap is not None else "host"
+        if finish_ap is not None:
+            result = finish_ap()
+            ps.mark("ap_done")
+        else:       # a stand-in model on a CPU box (the gloo tests of the sharding logic)
+            result = perframe_average_precision(pred_all.cpu().numpy(), gt_all.cpu().numpy(), self.all_class_names, self.data_processing, self.metric)
+        t_end = time.time()
+        time_taken = max(t_end - ps.t_begin, 1e-9)
+        self.last_fps = num_frames / time_taken
+        logger.info(f"Processed {num_frames} frames in {time_taken:.1f} seconds ({self.last_fps:.1f} FPS)")
+        if self.perstage:
+            self.last_perstage = ps.finish_ps() if ps.finish_ps is not None else \
+                perstage_report(np.zeros((N_STAGES, len(self.all_class_names))), self.all_class_names)
+            ps.mark("perstage_done")
+            for stage, rep_ in self.last_perstage.items():
+                logger.info(f"per-stage mAP {stage}: {rep_['mean_AP'] * 100:.2f}")
+        if ps.finish_seg is not None:
+            self.last_segmental = ps.finish_seg()
+            ps.mark("segmental_done")
+            for key in [k for k in self.last_segmental["frames"] if k not in ("videos", "per_video")]:      # MoF, Edit, three F1
+                logger.info(f"segmental {key}: frames {self.last_segmental['frames'][key]:.2f}, "
+                            f"vote({self.segmental_window}) {self.last_segmental['vote'][key]:.2f}")
         return result["mean_AP"]
 
     def _sharded_ap(self, pred, gt, world, rank):
@@ -815,7 +825,6 @@ class Evaluate(nn.Module):
     def aggregate_last(self, output_path=None, window_size: int = 200):
         """utils/aggregate.py:46-90 on the per-frame argmax the last eval left in HBM (`last_device_argmax`), with this config's
         number of classes; ground truth from the output JSON's "gt" lists"""
-        from .aggregate import aggregate_device
         js = json.load(open(os.path.join(self.output_dir, "output_miniROAD.json")))
         return aggregate_device(self.last_device_argmax, {k: v["gt"] for k, v in js.items()}, output_path, window_size,
                                 n_classes=len(self.all_class_names))

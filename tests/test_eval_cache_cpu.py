@@ -101,7 +101,7 @@ def test_cache_bookkeeping_with_stand_in_tensors():
     video, the video that would pass the budget releases everything, the key (dataset object + signature), the loader-item grouping the
     evaluator's loop sees again, and that a filling call that raised leaves nothing behind"""
     import types
-    from prego_amd.eval_cache import EvalFeatureCache
+    from prego_amd.eval_cache import EvalFeatureCache, EvalVideo
     dev, log = types.SimpleNamespace(type="cuda"), logging.getLogger("t")
 
     class _DS:
@@ -112,8 +112,9 @@ def test_cache_bookkeeping_with_stand_in_tensors():
     def fill(c, sig=("sig",)):
         assert c.begin(ds, sig, dev, torch.float32, log) is False and c.filling
         for first, lens in ((0, [3, 5, 2]), (3, [4])):
-            items = [(torch.ones(T, 8), None if (first + i) % 2 else torch.ones(T, 8), None, f"v{first + i}", first + i, (first + i) // 2) for i, T in enumerate(lens)]
-            c.retain(items, [b[0] for b in items], [b[1] for b in items], [torch.zeros(b[0].shape[0], dtype=torch.int32) for b in items], dev)
+            items = [EvalVideo(torch.ones(T, 8), None if (first + i) % 2 else torch.ones(T, 8), None, f"v{first + i}", first + i, (first + i) // 2)
+                     for i, T in enumerate(lens)]
+            c.retain(items, [b.features for b in items], [b.flow for b in items], [torch.zeros(b.features.shape[0], dtype=torch.int32) for b in items], dev)
 
     c = EvalFeatureCache(10 ** 9)
     fill(c)
@@ -122,8 +123,8 @@ def test_cache_bookkeeping_with_stand_in_tensors():
     need = (3 + 5 + 2 + 4) * 8 * 4 + (3 + 2) * 8 * 4 + 14 * 4       # rgb of every video, flow of videos 0 and 2, one int32 id per frame
     assert c.info() == dict(enabled=True, state="filled", reason=None, videos=4, frames=14, bytes=need, dtype="fp32")
     assert c.begin(ds, ("sig",), dev, torch.float32, log) is True
-    assert [[e[3] for e in g] for g in c.videos()] == [["v0", "v1"], ["v2", "v3"]]      # two videos per loader item, as they came
-    assert [e[1] is None for g in c.videos() for e in g] == [False, True, False, True]
+    assert [[e.name for e in g] for g in c.videos()] == [["v0", "v1"], ["v2", "v3"]]      # two videos per loader item, as they came
+    assert [e.flow is None for g in c.videos() for e in g] == [False, True, False, True]
     fill(c, ("another signature",))                                    # a mismatch drops and refills ...
     c.abort()                                                          # ... and a filling call that raised keeps nothing
     assert c.info()["state"] == "empty" and c.info()["bytes"] == 0 and c.info()["videos"] == 0
