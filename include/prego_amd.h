@@ -622,6 +622,61 @@ size_t prego_segmental_workspace_bytes(int64_t n_frames, int n_videos);
 int prego_segmental_scores(const int32_t* pred, const int32_t* gt, const int32_t* offsets, int n_videos, int64_t n_frames,
                            const uint32_t bg_mask[4], const int32_t overlap_num[3], const int32_t overlap_den[3], int32_t* records,
                            void* workspace, size_t workspace_bytes, prego_stream_t stream);
+/* Viterbi decoding on the device: the cheapest label sequence of every video under per-frame emission costs and a first-order
+ * transition matrix - the smoother Edit / F1 on Assembly101 are reported with.  Everything is integer: the same words come out on
+ * every run, and the device and the host model (prego_amd/decode.py) agree to the bit.
+ * UNITS.  Costs are in 1/256 bit: 256 units = a factor 2 in probability.  PREGO_DECODE_CAP = 32767.  PREGO_DECODE_FORBIDDEN = -1.
+ * EMISSION COST OF A PROBABILITY.  Take the fp32 word of p.  No log2f is used, so host and device cannot differ.
+ *   - If the sign bit is set, p is NaN, or the exponent field E is 0 (zero or denormal): cost = CAP.
+ *   - If p >= 1.0f (+inf included): cost = 0.
+ *   - Otherwise E is in 1..126 and k = mantissa >> 15 is in 0..255: cost = 256 * (127 - E) - LUT[k], with
+ *     LUT[k] = rint(256 * log2(1 + (k + 0.5) / 256)).
+ *   - The largest value is 256 * 126 - LUT[0] = 32255, so CAP only marks non-positive and denormal inputs.
+ * LUT is a table of 256 literals, present once on the host (prego_amd/decode.py) and once in the kernel (csrc/decode.hip).  The closest
+ * any of the 256 values comes to a rounding tie is 1.6e-3 (k = 118), so the table is the same under any libm.
+ * MODEL.  C classes, 1 <= C <= 128.  trans: int32 [C][C]; trans[i][j] is the cost of label i at frame t-1 followed by j at frame t.  A
+ * negative word is FORBIDDEN.  A word above CAP is read as CAP.  init: int32 [C] or NULL (= zeros), with the same clamping.
+ * PER VIDEO (frames [offsets[v], offsets[v+1]), clamped exactly as in prego_segmental_scores: every word of offsets into
+ * [0, n_frames], a descending pair is an empty video; videos that overlap share workspace and labels: their results are unspecified,
+ * nothing is read or written out of bounds).  Here e_t(j) is the emission cost of frame t and class j.
+ *   - d_0(j) = init[j] + e_0(j), or INFINITE if init[j] is forbidden.
+ *   - d_t(j) = e_t(j) + min over i with trans[i][j] allowed and d_{t-1}(i) finite of (d_{t-1}(i) + trans[i][j]).  The back-pointer is
+ *     the LOWEST i that attains the minimum.  With no such i, d_t(j) is INFINITE.
+ *   - End state: the lowest j with the minimal finite d_{T-1}(j).
+ *   - The labels are the back-pointer chain.
+ *   - If every state is INFINITE at some frame the video is infeasible: all its labels are -1 and its record is -1 | -1.
+ *   - An empty video has record 0 | -1.
+ * RECORD.  records: device int64 [n_videos][2], 16-byte aligned:  total cost | end state.  labels: device int32 [n_frames].
+ * EXACTNESS.  d is exact for every accepted input: 64-bit accumulators (a finite d reaches n_frames * 65534, which passes 2^31 beyond
+ * 32769 frames); no state is saturated, however far above the step's minimum it is - it may be the only one with an allowed
+ * continuation.  (Stretches of at most PREGO_DECODE_BLOCK steps at whose start every finite d lies within 2^24 - 64 * 65534 of the
+ * smallest run on 32-bit values relative to it; csrc/decode.hip carries the proof that they cannot overflow.  The others run in 64 bits.)
+ * INPUTS.  prego_viterbi_decode: probs device fp32 [n_frames][ld], quantised on load by the rule above.  prego_viterbi_decode_costs:
+ * costs device int32 [n_frames][ld], every word clamped into [0, CAP] on load.  prego_emission_costs: probs [n_frames][ld] -> costs
+ * int32 [n_frames][n_classes] (dense rows) by the same quantiser; decoding its output equals decoding the probabilities.
+ * One launch, one 256-thread workgroup per video (csrc/decode.hip): the forward pass keeps a column slice of trans in registers and
+ * d_{t-1} in LDS, one barrier per step, emission rows requested PREGO_DECODE_PREFETCH frames ahead, one back-pointer byte per
+ * (frame, class) to the workspace; the backtrace cuts the video into blocks of PREGO_DECODE_BLOCK frames: every block's end -> start
+ * map in parallel, the maps composed in LDS, every block walked once more from its known end state.  Everything is enqueued on
+ * `stream`; nothing is allocated, nothing waits.  Workspace: prego_viterbi_workspace_bytes (n_classes bytes per frame and per block).
+ * n_frames == 0: returns 0, every record is 0 | -1, no workspace is needed.  PREGO_EINVAL, decided before any launch (labels,
+ * records and workspace untouched): a NULL probs / costs, offsets, trans, labels or records, a NULL workspace with n_frames > 0,
+ * n_videos < 1, n_frames < 0 or >= 2^31, n_classes outside 1..128, ld < n_classes, records not 16-byte aligned, labels, records or
+ * workspace overlapping an input (or, prego_emission_costs, costs overlapping probs).  PREGO_EWORKSPACE: workspace_bytes below the
+ * query.  An addition to ABI 7 (existing signatures unchanged). */
+#define PREGO_DECODE_CAP 32767
+#define PREGO_DECODE_FORBIDDEN (-1)
+#define PREGO_DECODE_MAX_CLASSES 128
+#define PREGO_DECODE_BLOCK 64
+#define PREGO_DECODE_PREFETCH 8
+size_t prego_viterbi_workspace_bytes(int64_t n_frames, int n_videos, int n_classes);
+int prego_viterbi_decode(const float* probs, int64_t ld, const int32_t* offsets, int n_videos, int64_t n_frames, int n_classes,
+                         const int32_t* trans, const int32_t* init, int32_t* labels, int64_t* records, void* workspace,
+                         size_t workspace_bytes, prego_stream_t stream);
+int prego_viterbi_decode_costs(const int32_t* costs, int64_t ld, const int32_t* offsets, int n_videos, int64_t n_frames, int n_classes,
+                               const int32_t* trans, const int32_t* init, int32_t* labels, int64_t* records, void* workspace,
+                               size_t workspace_bytes, prego_stream_t stream);
+int prego_emission_costs(const float* probs, int64_t ld, int64_t n_frames, int n_classes, int32_t* costs, prego_stream_t stream);
 /* HOST function (no device work): the reference's loader yields fp32 target rows [n_frames][n_classes] per video (one-hot for both
  * shipped configs).  targets: n_videos host pointers, n_frames: their row counts; labels: host int32 [sum of n_frames], the videos one
  * after the other, labels[i] = np.argmax(row i) (eval.py:55, the first maximum); onehot[v] = 1 iff every row of video v holds exactly one

@@ -65,10 +65,12 @@ SYMBOLS = [
     "prego_procedure_forecast", "prego_stream_pool_feed_forecast", "prego_vit_stream_pool_feed_forecast",
     "prego_stream_pool_forecast", "prego_vit_stream_pool_forecast",
     "prego_segmental_workspace_bytes", "prego_segmental_scores",
+    "prego_viterbi_workspace_bytes", "prego_viterbi_decode", "prego_viterbi_decode_costs", "prego_emission_costs",
 ]
 THUMOS_SMOOTH, THUMOS_SWITCH = 1, 2          # PREGO_THUMOS_SMOOTH / _SWITCH
 SEGMENTAL_LDS_SEGMENTS = 2047                # PREGO_SEGMENTAL_LDS_SEGMENTS: the short side up to which prego_segmental_scores keeps its diagonals in LDS
 SEGMENTAL_CHUNK = 1024                       # frames per scan step of its workgroups (csrc/kernels.h kSegmentalChunk)
+DECODE_BLOCK, DECODE_PREFETCH = 64, 8        # PREGO_DECODE_BLOCK / _PREFETCH: the backtrace block and the emission prefetch depth of prego_viterbi_decode
 THUMOS_TILE_ROWS = 128                       # PREGO_THUMOS_TILE_ROWS: rows per scatter tile of prego_thumos_postprocess
 # include/prego_amd_debug.h: only in libprego_amd_debug.so
 DEBUG_SYMBOLS = ["prego_miniroad_debug_stamps", "prego_debug_gemm_bf16", "prego_debug_attention_bwd", "prego_debug_attention_fwd",
@@ -203,6 +205,11 @@ def _open(path: str, debug: bool) -> C.CDLL:
     lib.prego_segmental_workspace_bytes.argtypes = [i64, i32]
     lib.prego_segmental_workspace_bytes.restype = sz
     lib.prego_segmental_scores.argtypes = [vp, vp, vp, i32, i64, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, sz, vp]
+    lib.prego_viterbi_workspace_bytes.argtypes = [i64, i32, i32]
+    lib.prego_viterbi_workspace_bytes.restype = sz
+    lib.prego_viterbi_decode.argtypes = [vp, i64, vp, i32, i64, i32, vp, vp, vp, vp, vp, sz, vp]
+    lib.prego_viterbi_decode_costs.argtypes = [vp, i64, vp, i32, i64, i32, vp, vp, vp, vp, vp, sz, vp]
+    lib.prego_emission_costs.argtypes = [vp, i64, i64, i32, vp, vp]
     lib.prego_onehot_labels.argtypes =[i32, C.POINTER(vp), C.POINTER(i64), i32, vp, C.POINTER(C.c_int32)]
     f32 = C.c_float
     lib.prego_adamw_step.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), i64, f32, f32, f32, f32, f32, vp]

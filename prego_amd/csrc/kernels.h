@@ -371,6 +371,19 @@ size_t segmental_workspace_bytes(long long n_frames, int n_videos);
 int launch_segmental(const int* pred, const int* gt, const int* offsets, int n_videos, long long n_frames, const unsigned* bg, const int* num,
                      const int* den, int* records, void* workspace, hipStream_t s);
 
+// Viterbi decoding (decode.hip): labels [n_frames] and records [n_videos][2] (total cost | end state) from probabilities (fp32 words,
+// quantised on load) or emission costs (int32 words, clamped on load: `costs`) [n_frames][ld]; one launch, one workgroup per video.
+// -1 = refused, nothing launched.  ws: the query's bytes (n_frames == 0: not touched)
+constexpr int kDecodeCap = 32767;               // PREGO_DECODE_CAP of the public header
+constexpr int kDecodeMaxClasses = 128;          // PREGO_DECODE_MAX_CLASSES
+constexpr int kDecodeBlock = 64;                // PREGO_DECODE_BLOCK: frames per block of the backtrace
+constexpr int kDecodePrefetch = 8;              // PREGO_DECODE_PREFETCH: frames the emission rows are requested ahead of the step
+size_t viterbi_workspace_bytes(long long n_frames, int n_videos, int n_classes);
+int launch_viterbi(bool costs, const void* src, long long ld, const int* offsets, int n_videos, long long n_frames, int n_classes,
+                   const int* trans, const int* init, int* labels, long long* records, void* workspace, hipStream_t s);
+// probabilities [n_frames][ld] -> emission costs [n_frames][n_classes] with the decode kernel's quantiser; -1 = refused
+int launch_emission_costs(const float* probs, long long ld, long long n_frames, int n_classes, int* costs, hipStream_t s);
+
 // THUMOS post-processing (thumos_post.hip): 5-frame max, column merge, stable removal of the ambiguous rows; count, scan, scatter
 constexpr int kThumosTileRows = 128;     // rows per scatter tile (PREGO_THUMOS_TILE_ROWS of the public header)
 constexpr int kThumosChunkCols = 96;     // columns of a tile staged in LDS at a time

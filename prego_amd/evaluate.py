@@ -31,6 +31,7 @@ from .metrics import (N_STAGES, perframe_ap_raw, perframe_ap_raw_device, perfram
                       perstage_average_precision_device, perstage_report, report_from_raw)
 from .postprocessing import ThumosPostprocessing, thumos_postprocessing_device
 from .registry import EVAL
+from .decode import DECODE_MAX_CLASSES, uniform_transitions, viterbi_decode_device
 from .segmental import segmental_scores_device
 
 
@@ -102,12 +103,14 @@ class _Pass:
     pred_scores: list = field(default_factory=list)
     gt_targets: list = field(default_factory=list)
     argmax_ids: list = field(default_factory=list)      # cfg['eval_segmental']: the videos' device argmax, in the order of pred_scores
+    video_ids: list = field(default_factory=list)       # cfg['eval_decode']: the videos' names, in the order of pred_scores
     per_video: list = field(default_factory=list)       # (loader position, n_frames) to restore the loader's order on rank 0
     pending: Optional[_Launched] = None  # the batch whose launch is out and whose host half (_collect) is still due
     metric_inputs: Optional[tuple] = None
     finish_ap: Optional[Callable] = None
     finish_ps: Optional[Callable] = None
     finish_seg: Optional[Callable] = None
+    finish_decode: Optional[Callable] = None
 
 
 @EVAL.register("OAD")
@@ -150,6 +153,17 @@ class Evaluate(nn.Module):
         self.segmental = bool(cfg.get("eval_segmental", False))
         self.segmental_window = int(cfg.get("eval_segmental_window", 200))
         self.last_segmental = None
+        # cfg['eval_decode'] (not a reference key, off by default): the pass's score matrix decoded on the device by a first-order Viterbi
+        # pass (`prego_viterbi_decode`: emission cost = the quantised -log2 of the score, cfg['eval_decode_switch_cost'] per change of
+        # label, cfg['eval_decode_stay_cost'] per frame that keeps it, or cfg['eval_decode_transitions'] = (trans, init), e.g.
+        # ProcedureModel.transition_costs) and the segmental metrics of the decoded ids; kept in `last_decode` and logged, nothing else
+        # about the pass changes.  Costs are in 1/256 bit.  The default of 2048 (8 bits per switch) is NOT tuned: there are no real
+        # features here to tune it on.
+        self.decode = bool(cfg.get("eval_decode", False))
+        self.decode_switch_cost = int(cfg.get("eval_decode_switch_cost", 2048))
+        self.decode_stay_cost = int(cfg.get("eval_decode_stay_cost", 0))
+        self.decode_transitions = cfg.get("eval_decode_transitions")
+        self.last_decode = None
         self.last_metric_path = None         # "device" | "host": where the last call computed cfg['metric']
 
     @staticmethod
@@ -511,6 +525,35 @@ class Evaluate(nn.Module):
             return {"frames": fn_frames(), "vote": fn_vote()}
         return finish
 
+    def _enqueue_decode(self, ps, dev):
+        """cfg['eval_decode']: prego_viterbi_decode over the pass's concatenated scores and the per-video offsets, then
+        prego_segmental_scores over the decoded ids, both on the current stream.  Returns the function that collects
+        {"labels": {video: int32 tensor}, "records": int64 tensor [videos, 2] (total cost | end state), "segmental": report}.
+        The RAW scores are decoded: cfg['eval_thumos_postprocessing'] does not feed this."""
+        ncls = len(self.all_class_names)
+        lens = [int(p.shape[0]) for p in ps.pred_scores]
+        offsets = torch.tensor(np.concatenate(([0], np.cumsum(lens, dtype=np.int64))), dtype=torch.int32).to(dev)
+        # the concatenation the AP kernels read is the same matrix unless the THUMOS post-processing has changed it
+        scores = self._metric_inputs(ps, dev)[0] if self.data_processing is None else torch.cat(ps.pred_scores, 0).to(dev)
+        if scores.dim() != 2 or int(scores.shape[1]) != ncls:
+            raise PregoError(f"cfg['eval_decode']: the pass's scores have shape {tuple(scores.shape)}, the data set has {ncls} classes")
+        # fp32 contiguous scores (what the engines' eval forward returns) pass through; anything else is copied once, at full size
+        scores = scores.to(dtype=torch.float32).contiguous()
+        gt = torch.cat([t.to(device=dev, dtype=torch.int32) for t in ps.gt_targets]).contiguous()
+        if self.decode_transitions is not None:
+            trans, init = self.decode_transitions
+        else:
+            trans, init = uniform_transitions(ncls, self.decode_switch_cost, self.decode_stay_cost), None
+        labels, records = viterbi_decode_device(scores, offsets, trans, init)
+        fn_seg = segmental_scores_device(labels, gt, offsets, defer=True)
+        names = list(ps.video_ids)
+
+        def finish():
+            lab = labels.cpu()
+            cuts = np.concatenate(([0], np.cumsum(lens, dtype=np.int64))).tolist()
+            return {"labels": {vid: lab[cuts[i]:cuts[i + 1]] for i, vid in enumerate(names)}, "records": records.cpu(), "segmental": fn_seg()}
+        return finish
+
     def _loader_videos(self, model, dataloader, world, rank, skip_flow):
         """this rank's videos (EvalVideo) as the loop below batches them, one list per loader item"""
         pos = 0
@@ -552,6 +595,18 @@ class Evaluate(nn.Module):
         if self.segmental and torch.device(device).type != "cuda":
             raise PregoError("cfg['eval_segmental']: the segmental metrics of an eval pass run on the device (prego_segmental_scores); host "
                              "arrays: prego_amd.segmental.segmental_scores")
+        if self.decode:
+            if world > 1:
+                raise PregoError("cfg['eval_decode']: the decode of an eval pass is computed by a single process only (the ranks' score "
+                                 f"matrices are not gathered); this eval runs on {world} ranks")
+            if torch.device(device).type != "cuda":
+                raise PregoError("cfg['eval_decode']: the decode of an eval pass runs on the device (prego_viterbi_decode); host arrays: "
+                                 "prego_amd.decode.viterbi_decode")
+            if self.cfg.get("model") == "Transformer":
+                raise PregoError("cfg['eval_decode']: model 'Transformer' returns raw logits from its eval forward (ViT.py:140-143), not "
+                                 "probabilities; the decoder's emission cost is defined on probabilities")
+            if len(self.all_class_names) > DECODE_MAX_CLASSES:
+                raise PregoError(f"cfg['eval_decode']: {len(self.all_class_names)} classes (prego_viterbi_decode takes up to {DECODE_MAX_CLASSES})")
         if self.perstage and torch.device(device).type != "cuda":
             raise PregoError("cfg['eval_perstage']: the per-stage AP of an eval pass runs on the device (prego_perstage_ap_labels); host "
                              "arrays: prego_amd.metrics.perstage_average_precision")
@@ -625,6 +680,7 @@ class Evaluate(nn.Module):
         rec = self._flush(model, batch, device, resident)       # batch k: enqueued ...
         if rec is not None:
             for _vid, p, a, t in rec.videos:
+                ps.video_ids.append(_vid)
                 ps.pred_scores.append(p)
                 ps.gt_targets.append(t)
                 ps.argmax_ids.append(a)
@@ -669,9 +725,10 @@ class Evaluate(nn.Module):
                              "eval set has rows that are not (dense multi-label targets: no runs of one action, no transcript)")
 
     def _enqueue_metrics(self, ps, device, world):
-        """behind the last forward: per-frame AP, per-stage AP and the segmental metrics, each enqueued on the metric stream in this order"""
+        """behind the last forward: per-frame AP, per-stage AP, the segmental metrics and the decode, each enqueued on the metric stream in
+        this order"""
         dev = torch.device(device)
-        self.last_perstage = self.last_segmental = None
+        self.last_perstage = self.last_segmental = self.last_decode = None
         if not ps.pred_scores:
             return
         if world == 1 and dev.type == "cuda":
@@ -692,6 +749,10 @@ class Evaluate(nn.Module):
             # the segmental records of the same device-resident ids, enqueued behind the other metrics on their stream
             self._need_class_ids("eval_segmental", ps.gt_targets)
             ps.finish_seg = self._on_metric_stream(dev, lambda: self._enqueue_segmental(ps.argmax_ids, ps.gt_targets, dev))
+        if self.decode:
+            # the decode of the same device-resident scores and the segmental records of its ids, behind everything above on that stream
+            self._need_class_ids("eval_decode", ps.gt_targets)
+            ps.finish_decode = self._on_metric_stream(dev, lambda: self._enqueue_decode(ps, dev))
 
     def _write_output(self, chunks):
         os.makedirs(self.output_dir, exist_ok=True)
@@ -760,6 +821,12 @@ class Evaluate(nn.Module):
             for key in [k for k in self.last_segmental["frames"] if k not in ("videos", "per_video")]:      # MoF, Edit, three F1
                 logger.info(f"segmental {key}: frames {self.last_segmental['frames'][key]:.2f}, "
                             f"vote({self.segmental_window}) {self.last_segmental['vote'][key]:.2f}")
+        if ps.finish_decode is not None:
+            self.last_decode = ps.finish_decode()
+            ps.mark("decode_done")
+            how = "given transitions" if self.decode_transitions is not None else f"switch {self.decode_switch_cost}, stay {self.decode_stay_cost}"
+            for key in [k for k in self.last_decode["segmental"] if k not in ("videos", "per_video")]:      # MoF, Edit, three F1
+                logger.info(f"decoded ({how}) {key}: {self.last_decode['segmental'][key]:.2f}")
         return result["mean_AP"]
 
     def _sharded_ap(self, pred, gt, world, rank):

@@ -323,6 +323,30 @@ class ProcedureModel:
                     top[k] += int(int(step) in ids[:k])
         return {"positions": positions, "unknown": unknown, "top": top}
 
+    # -- a decoding grammar ----------------------------------------------------------------------------
+    def transition_costs(self, group: int = -1, switch_cost: int = 2048, unseen: int = -1, stay_cost: int = 0):
+        """(trans int32 [C, C], init int32 [C]) for prego_amd.decode (`viterbi_decode`, `viterbi_decode_device`) from the corpus's
+        order-1 counts of `group` (-1: every group).  trans[i][i] = stay_cost; trans[i][j] = switch_cost where step j followed step i
+        somewhere in the group, `unseen` otherwise (default DECODE_FORBIDDEN = -1: such a switch cannot be decoded at all); init[j] = 0
+        where a transcript of the group starts with j, `unseen` otherwise.  Costs are in 1/256 bit; 2048 = 8 bits per switch, not tuned.
+        Host only.  A grammar of CORRECT procedures with unseen = FORBIDDEN decodes mistakes away: whatever the recogniser saw is bent
+        into an order the corpus knows.  That is what transcript scoring (Edit / F1 against a correct ground truth) wants and the
+        opposite of what the mistake monitor needs - feed the monitor from a decode with a finite `unseen`, or from none."""
+        import numpy as np
+        C_ = self.n_classes
+        rows = self._examples().get(None if int(group) == -1 else int(group), {})
+        trans = np.full((C_, C_), int(unseen), np.int32)
+        init = np.full(C_, int(unseen), np.int32)
+        for i in range(C_):
+            for j, n in enumerate(rows.get((i,), ())):
+                if n > 0:
+                    trans[i, j] = int(switch_cost)
+        for j, n in enumerate(rows.get((START,), ())):
+            if n > 0:
+                init[j] = 0
+        np.fill_diagonal(trans, int(stay_cost))
+        return trans, init
+
     # -- the device ----------------------------------------------------------------------------------
     def flat(self):
         """(groups, offsets, symbols, target flags) of the corpus as prego_procedure_model_create takes them"""
