@@ -632,7 +632,7 @@ int prego_segmental_scores(const int32_t* pred, const int32_t* gt, const int32_t
  *   - Otherwise E is in 1..126 and k = mantissa >> 15 is in 0..255: cost = 256 * (127 - E) - LUT[k], with
  *     LUT[k] = rint(256 * log2(1 + (k + 0.5) / 256)).
  *   - The largest value is 256 * 126 - LUT[0] = 32255, so CAP only marks non-positive and denormal inputs.
- * LUT is a table of 256 literals, present once on the host (prego_amd/decode.py) and once in the kernel (csrc/decode.hip).  The closest
+ * LUT is a table of 256 literals, present once on the host (prego_amd/decode.py) and once for the kernels (csrc/decode_model.h).  The closest
  * any of the 256 values comes to a rounding tie is 1.6e-3 (k = 118), so the table is the same under any libm.
  * MODEL.  C classes, 1 <= C <= 128.  trans: int32 [C][C]; trans[i][j] is the cost of label i at frame t-1 followed by j at frame t.  A
  * negative word is FORBIDDEN.  A word above CAP is read as CAP.  init: int32 [C] or NULL (= zeros), with the same clamping.
@@ -981,6 +981,84 @@ int prego_stream_pool_forecast(const prego_stream_pool* p, const prego_procedure
                                const int32_t* slot_groups, void* forecasts, size_t forecast_bytes, prego_stream_t stream);
 int prego_vit_stream_pool_forecast(const prego_vit_stream_pool* p, const prego_procedure_model* m, const int32_t* slots, int n,
                                    const int32_t* slot_groups, void* forecasts, size_t forecast_bytes, prego_stream_t stream);
+
+/* Decode pool (an addition to ABI 7, existing signatures unchanged): online fixed-lag Viterbi per live stream on the device - the
+ * decoder of prego_viterbi_decode for streams whose last frame has not arrived.  Every live stream owns a SLOT of one device block that
+ * holds its Viterbi state; a push of score rows advances any subset of the slots; every frame's label is committed a fixed number of
+ * frames (`lag`) after it arrived, and the committed labels feed a vote record of the stream pools' layout, so the event feed and both
+ * monitors work on the decoded transcript unchanged.
+ * DEFINITIONS.  The model and the quantiser are prego_viterbi_decode's.
+ *   - trans[i][j] and init[j] are int32.
+ *   - A negative word is forbidden.  A word above PREGO_DECODE_CAP is read as CAP.  init NULL means zeros.
+ *   - At most 128 classes.
+ *   - Emission costs come from the fp32 word by DECODE_LUT, or from int32 cost words clamped into [0, CAP].
+ *   - d_0, d_t and the back-pointer (lowest i on a tie) are as in viterbi_decode.
+ *   - e_t is the lowest j with the smallest finite d_t(j).
+ * FIXED LAG L (0..256).
+ *   - After frame t of a stream has been ingested and t >= L, frame f = t - L is committed.  label(f) is the state at frame f on the
+ *     back-pointer chain that starts at e_t.
+ *   - flush commits the remaining frames [max(0, T - L), T) from the chain that starts at e_{T-1}.
+ *   - Dead streams: a frame at which no state is finite makes the stream dead.  Every label committed from then on is -1, at flush too.
+ *     Labels already committed stay.
+ * Equivalently, and this is the oracle identity:  label(f) = viterbi_decode(x[: min(f + L, T - 1) + 1])[0][f].
+ * After T frames, (cost, end state) equals viterbi_decode(x[:T])'s record.  With L >= T - 1 the labels equal the offline decode.
+ * Consecutive labels come from different chains, so the committed sequence need not be an allowed path.
+ * The result depends on the frames only.  It does not depend on how they were cut into calls, on slot numbers, on the order of `slots`,
+ * or on the other slots.
+ * RECORD.  Each committed label goes, in frame order, through the stream pools' update rule into a record of their layout (window =
+ * vote_window; with 1 every change of the committed label is an event: id, first frame).  A label of -1 sets the bad-id bit and counts
+ * no frame, as an id outside the classes does there.
+ * BLOCK.  Device memory, 256-byte aligned, at least prego_decode_pool_bytes(capacity, n_classes, lag, max_events) bytes, the caller's:
+ * the clamped model, then per slot a header, the keys d as int64 [n_classes rounded up to 4] (d << 7 | state; "no path" 2^62; exact,
+ * finite d < 2^47, nothing saturates) and a ring of back-pointer rows, one byte per (frame, state), addressed by frame index modulo
+ * lag + 32; then the records.  create enqueues the block's zeroing and one small kernel that clamps trans / init (DEVICE int32
+ * [n_classes][n_classes] / [n_classes] or NULL) into it on `stream`; the caller may free them stream-ordered.  An all-zero slot is an
+ * empty stream, so opening a slot needs no call.
+ * prego_decode_pool_push / _push_costs (int32 cost rows): slots HOST int32 [n] (the stream pools' rules: 1 <= n <= min(256, capacity),
+ * inside the pool, named once); counts HOST int32 [n], 1..32 each, with sum R <= 256; rows DEVICE [R][ld] packed in `slots` order,
+ * ld >= n_classes (4-byte aligned is enough; words behind n_classes are not read).  Outputs are device pointers and all nullable:
+ *   labels   int32 [R].  In slot i's row block, the first m_i words are the labels this call committed in frame order.  The rest are
+ *            PREGO_DECODE_PENDING.
+ *   commit   int32 [n][2]: (index of the first frame committed by this call, or of the next one due when m_i = 0; m_i).
+ *   now      int32 [R]: e_t of every ingested frame, -1 once dead.  This is the zero-lag provisional label.
+ * One launch, one 256-thread workgroup per named slot (csrc/decode_pool.hip); no workspace, no global atomic, no float arithmetic, no
+ * allocation, no host wait.
+ * prego_decode_pool_flush: commits the tail (labels DEVICE int32 [n][lag], nullable: slot i's labels then PREGO_DECODE_PENDING; commit
+ * as above), then votes the record's unfinished window as prego_stream_pool_flush does, and marks the slot flushed.  A push on a
+ * flushed slot ingests nothing, writes PREGO_DECODE_PENDING into its rows of labels and now, (next frame, 0) into commit, and sets
+ * status bit 2.  Only reset reopens it.  prego_decode_pool_reset zeroes the slots; prego_decode_pool_record as for the other pools.
+ * prego_decode_pool_state: the slot's header and keys for one D2H copy.  int32 words frames | committed | status (bit 0 dead, bit 1
+ * flushed, bit 2 pushed after flush) | end state (-1 dead; 0 while empty) | total cost as int64 (-1 dead) | two zero words, then the keys.
+ * prego_decode_pool_feed_create / _feed_judge / _feed_forecast / prego_decode_pool_forecast: the prego_stream_pool_ entries of those
+ * names over this pool's records.
+ * PREGO_EINVAL with a message, decided before any launch (pool and outputs untouched): everything the slot lists of the other pools
+ * refuse; a count outside 1..32, or R > 256; n_classes outside 1..128; lag outside 0..256; vote_window < 1; capacity or max_events
+ * outside 1..1 048 576; ld < n_classes; NULL rows, counts or trans; a NULL, unaligned or short block; a procedure model of another
+ * class count; outputs overlapping the rows, the block or each other; trans or init inside the block. */
+#define PREGO_DECODE_POOL_MAX_LAG 256
+#define PREGO_DECODE_PENDING (-2)
+typedef struct prego_decode_pool prego_decode_pool;
+size_t prego_decode_pool_bytes(int capacity, int n_classes, int lag, int max_events);
+int prego_decode_pool_create(prego_decode_pool** out, int capacity, int n_classes, int lag, int vote_window, int max_events,
+                             const int32_t* trans, const int32_t* init /* nullable */, void* device_block, size_t bytes,
+                             prego_stream_t stream);
+void prego_decode_pool_destroy(prego_decode_pool* p);
+int prego_decode_pool_push(prego_decode_pool* p, int n, const int32_t* slots, const int32_t* counts, const float* probs, int64_t ld,
+                           int32_t* labels, int32_t* commit, int32_t* now, prego_stream_t stream);
+int prego_decode_pool_push_costs(prego_decode_pool* p, int n, const int32_t* slots, const int32_t* counts, const int32_t* costs, int64_t ld,
+                                 int32_t* labels, int32_t* commit, int32_t* now, prego_stream_t stream);
+int prego_decode_pool_flush(prego_decode_pool* p, int n, const int32_t* slots, int32_t* labels, int32_t* commit, prego_stream_t stream);
+int prego_decode_pool_reset(prego_decode_pool* p, int n, const int32_t* slots, prego_stream_t stream);
+int prego_decode_pool_record(const prego_decode_pool* p, int slot, const void** device_record, size_t* bytes);
+int prego_decode_pool_state(const prego_decode_pool* p, int slot, const void** device_state, size_t* bytes);
+int prego_decode_pool_feed_create(prego_stream_pool_feed** out, const prego_decode_pool* p, int max_out, void* device_block, size_t bytes,
+                                  prego_stream_t stream);
+int prego_decode_pool_feed_judge(const prego_stream_pool_feed* f, const prego_procedure_model* m, const void* report, size_t report_bytes,
+                                 const int32_t* slot_groups, void* verdicts, size_t verdict_bytes, prego_stream_t stream);
+int prego_decode_pool_feed_forecast(const prego_stream_pool_feed* f, const prego_procedure_model* m, const void* report, size_t report_bytes,
+                                    const int32_t* slot_groups, void* forecasts, size_t forecast_bytes, prego_stream_t stream);
+int prego_decode_pool_forecast(const prego_decode_pool* p, const prego_procedure_model* m, const int32_t* slots, int n,
+                               const int32_t* slot_groups, void* forecasts, size_t forecast_bytes, prego_stream_t stream);
 
 /* Training of the "Transformer" registry entry: trainer/train.py:20-24 (fwd, loss, backward) over ViTEnc (ViT.py:117-143,
  * Transformer.py:5-82, Attention.py:21-41).  forward_train is ViTEnc.forward in training mode with every dropout rate 0

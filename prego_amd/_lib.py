@@ -66,10 +66,14 @@ SYMBOLS = [
     "prego_stream_pool_forecast", "prego_vit_stream_pool_forecast",
     "prego_segmental_workspace_bytes", "prego_segmental_scores",
     "prego_viterbi_workspace_bytes", "prego_viterbi_decode", "prego_viterbi_decode_costs", "prego_emission_costs",
+    "prego_decode_pool_bytes", "prego_decode_pool_create", "prego_decode_pool_destroy", "prego_decode_pool_push", "prego_decode_pool_push_costs",
+    "prego_decode_pool_flush", "prego_decode_pool_reset", "prego_decode_pool_record", "prego_decode_pool_state",
+    "prego_decode_pool_feed_create", "prego_decode_pool_feed_judge", "prego_decode_pool_feed_forecast", "prego_decode_pool_forecast",
 ]
 THUMOS_SMOOTH, THUMOS_SWITCH = 1, 2          # PREGO_THUMOS_SMOOTH / _SWITCH
 SEGMENTAL_LDS_SEGMENTS = 2047                # PREGO_SEGMENTAL_LDS_SEGMENTS: the short side up to which prego_segmental_scores keeps its diagonals in LDS
 SEGMENTAL_CHUNK = 1024                       # frames per scan step of its workgroups (csrc/kernels.h kSegmentalChunk)
+DECODE_POOL_MAX_LAG, DECODE_PENDING = 256, -2     # PREGO_DECODE_POOL_MAX_LAG / PREGO_DECODE_PENDING of the decode pool
 DECODE_BLOCK, DECODE_PREFETCH = 64, 8        # PREGO_DECODE_BLOCK / _PREFETCH: the backtrace block and the emission prefetch depth of prego_viterbi_decode
 THUMOS_TILE_ROWS = 128                       # PREGO_THUMOS_TILE_ROWS: rows per scatter tile of prego_thumos_postprocess
 # include/prego_amd_debug.h: only in libprego_amd_debug.so
@@ -210,6 +214,22 @@ def _open(path: str, debug: bool) -> C.CDLL:
     lib.prego_viterbi_decode.argtypes = [vp, i64, vp, i32, i64, i32, vp, vp, vp, vp, vp, sz, vp]
     lib.prego_viterbi_decode_costs.argtypes = [vp, i64, vp, i32, i64, i32, vp, vp, vp, vp, vp, sz, vp]
     lib.prego_emission_costs.argtypes = [vp, i64, i64, i32, vp, vp]
+    i32p = C.POINTER(C.c_int32)
+    lib.prego_decode_pool_bytes.argtypes = [i32, i32, i32, i32]
+    lib.prego_decode_pool_bytes.restype = sz
+    lib.prego_decode_pool_create.argtypes = [C.POINTER(vp), i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]
+    lib.prego_decode_pool_destroy.argtypes = [vp]
+    lib.prego_decode_pool_destroy.restype = None
+    lib.prego_decode_pool_push.argtypes = [vp, i32, i32p, i32p, vp, i64, vp, vp, vp, vp]
+    lib.prego_decode_pool_push_costs.argtypes = [vp, i32, i32p, i32p, vp, i64, vp, vp, vp, vp]
+    lib.prego_decode_pool_flush.argtypes = [vp, i32, i32p, vp, vp, vp]
+    lib.prego_decode_pool_reset.argtypes = [vp, i32, i32p, vp]
+    lib.prego_decode_pool_record.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz)]
+    lib.prego_decode_pool_state.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz)]
+    lib.prego_decode_pool_feed_create.argtypes = [C.POINTER(vp), vp, i32, vp, sz, vp]
+    lib.prego_decode_pool_feed_judge.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
+    lib.prego_decode_pool_feed_forecast.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
+    lib.prego_decode_pool_forecast.argtypes = [vp, vp, vp, i32, vp, vp, sz, vp]
     lib.prego_onehot_labels.argtypes =[i32, C.POINTER(vp), C.POINTER(i64), i32, vp, C.POINTER(C.c_int32)]
     f32 = C.c_float
     lib.prego_adamw_step.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), i64, f32, f32, f32, f32, f32, vp]

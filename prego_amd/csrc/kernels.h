@@ -637,3 +637,32 @@ int launch_vit_burst_tokens(const VitRing& r, const int* slots, int n, const Rag
 // ring[slots[i]][(head + k) mod T] <- enc[off[i] + k], k < count[i]; then head and fill advance by count[i]
 int launch_vit_ring_commit_burst(const VitRing& r, const int* slots, int n, const RaggedMap& by_slot, int n_rows, const float* enc,
                                  hipStream_t s);
+
+// decode pool (decode_pool.hip): online fixed-lag Viterbi, one slot of the caller's device block per live stream.  A slot is
+//   header [kDecodePoolHeaderWords] int32: frames | committed | status | end state | total cost (int64, words 4..5) | 0 | 0
+//   keys   [ncls_pad] int64: d_{frames-1}(j) << 7 | j, "no path" 2^62 (not read while frames == 0)
+//   ring   [ring_rows][row_bytes] bytes: the back-pointer row of frame f at row f mod ring_rows, ring_rows = lag + kDecodePoolBurst
+// and an all-zero slot is an empty stream.  The model sits in front of the slots, clamped and in the order the step reads it:
+//   model  init [128] int32 (-1 forbidden, -1 for the states >= C) | trans^T [C][2 len] int32: word (j, i) = trans[i][j], -1 for i >= C
+constexpr int kDecodePoolMaxLag = 256;        // PREGO_DECODE_POOL_MAX_LAG
+constexpr int kDecodePoolBurst = 32;          // frames a slot takes per call at most
+constexpr int kDecodePending = -2;            // PREGO_DECODE_PENDING
+constexpr int kDecodePoolHeaderWords = 8;
+constexpr int kDecodeDead = 1, kDecodeFlushed = 2, kDecodePushedAfterFlush = 4;      // bits of the status word
+struct DecodePoolGeom {
+  PoolGeom rec;                          // the records (h is NULL, hid 0; window = the vote window)
+  int* model;
+  char* state;                           // [capacity][slot_bytes]
+  int lag, ring_rows, row_bytes, len, ring_off, slot_bytes;      // len: the step's slice (8, 16, 32, 48 or 64; 2 len >= C)
+};
+int decode_pool_len(int n_classes);
+// trans [C][C], init [C] or NULL: device int32, read by the launch and free to go behind it
+int launch_decode_pool_model(const DecodePoolGeom& g, const int* trans, const int* init, hipStream_t s);
+// slots: HOST, n in 1..256, inside the pool, named once; rows.e[i]: slot i's packed rows (off, count 1..32, off + count <= n_rows <= 256) of
+// src [n_rows][ld] (fp32 probabilities, or int32 costs with `costs`); labels [n_rows], commit [n][2], now [n_rows]: device, nullable.
+// -1 = refused, nothing launched
+int launch_decode_pool_push(const DecodePoolGeom& g, bool costs, const int* slots, int n, const RaggedMap& rows, int n_rows, const void* src,
+                            long long ld, int* labels, int* commit, int* now, hipStream_t s);
+// labels [n][lag], commit [n][2]: device, nullable
+int launch_decode_pool_flush(const DecodePoolGeom& g, const int* slots, int n, int* labels, int* commit, hipStream_t s);
+int launch_decode_pool_reset(const DecodePoolGeom& g, const int* slots, int n, hipStream_t s);

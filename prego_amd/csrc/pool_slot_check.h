@@ -10,6 +10,7 @@
 // the vote records of a pool, for what serves both pool types (stream_feed.cpp); each is defined beside its pool's struct
 const PoolGeom* stream_pool_geom(const prego_stream_pool* p);
 const PoolGeom* vit_stream_pool_geom(const prego_vit_stream_pool* p);
+const PoolGeom* decode_pool_geom(const prego_decode_pool* p);      // decode_pool.cpp: the records of the decode pool's committed labels
 // what the slot images need on top (stream_image.cpp): a pool's stamp table, its block, the Transformer pool's ring, and of a feed the pool
 // it was created over and its cursor words
 struct SlotStamps;

@@ -182,6 +182,19 @@ extern "C" int prego_vit_stream_pool_feed_judge(const prego_stream_pool_feed* f,
   return feed_judge("vit_stream_pool_feed_judge", f, m, report, report_bytes, slot_groups, verdicts, verdict_bytes, stream);
 }
 
+// the decode pool's feed: its step ids are the decoder's classes, so a model of another class count cannot judge them
+static int decode_model_refusal(const char* who, const PoolGeom* g, const prego_procedure_model* m) {
+  if (g && m && m->g.ncls != g->ncls)
+    return prego_fail_(PREGO_EINVAL, "%s: the procedure model has %d classes, the decode pool %d", who, m->g.ncls, g->ncls);
+  return 0;
+}
+
+extern "C" int prego_decode_pool_feed_judge(const prego_stream_pool_feed* f, const prego_procedure_model* m, const void* report, size_t report_bytes,
+                                            const int32_t* slot_groups, void* verdicts, size_t verdict_bytes, prego_stream_t stream) {
+  if (int rc = decode_model_refusal("decode_pool_feed_judge", f ? stream_pool_feed_pool(f) : nullptr, m)) return rc;
+  return feed_judge("decode_pool_feed_judge", f, m, report, report_bytes, slot_groups, verdicts, verdict_bytes, stream);
+}
+
 // ---- next-step forecast: the same refusals in the same order for the five entries, decided before the launch ------------------------------
 namespace {
 size_t forecast_bytes_for(long long n) { return (size_t)n * kProcForecastWords * 4; }
@@ -269,4 +282,17 @@ extern "C" int prego_vit_stream_pool_forecast(const prego_vit_stream_pool* p, co
                                               const int32_t* slot_groups, void* forecasts, size_t forecast_bytes, prego_stream_t stream) {
   return pool_forecast("vit_stream_pool_forecast", p ? vit_stream_pool_geom(p) : nullptr, m, slots, n, slot_groups, forecasts, forecast_bytes,
                        stream);
+}
+
+extern "C" int prego_decode_pool_feed_forecast(const prego_stream_pool_feed* f, const prego_procedure_model* m, const void* report,
+                                               size_t report_bytes, const int32_t* slot_groups, void* forecasts, size_t forecast_bytes,
+                                               prego_stream_t stream) {
+  if (int rc = decode_model_refusal("decode_pool_feed_forecast", f ? stream_pool_feed_pool(f) : nullptr, m)) return rc;
+  return feed_forecast("decode_pool_feed_forecast", f, m, report, report_bytes, slot_groups, forecasts, forecast_bytes, stream);
+}
+
+extern "C" int prego_decode_pool_forecast(const prego_decode_pool* p, const prego_procedure_model* m, const int32_t* slots, int n,
+                                          const int32_t* slot_groups, void* forecasts, size_t forecast_bytes, prego_stream_t stream) {
+  if (int rc = decode_model_refusal("decode_pool_forecast", p ? decode_pool_geom(p) : nullptr, m)) return rc;
+  return pool_forecast("decode_pool_forecast", p ? decode_pool_geom(p) : nullptr, m, slots, n, slot_groups, forecasts, forecast_bytes, stream);
 }

@@ -78,6 +78,11 @@ extern "C" int prego_vit_stream_pool_feed_create(prego_stream_pool_feed** out, c
   return feed_create("vit_stream_pool_feed_create", out, p ? vit_stream_pool_geom(p) : nullptr, max_out, device_block, bytes, stream);
 }
 
+extern "C" int prego_decode_pool_feed_create(prego_stream_pool_feed** out, const prego_decode_pool* p, int max_out, void* device_block,
+                                             size_t bytes, prego_stream_t stream) {
+  return feed_create("decode_pool_feed_create", out, p ? decode_pool_geom(p) : nullptr, max_out, device_block, bytes, stream);
+}
+
 extern "C" void prego_stream_pool_feed_destroy(prego_stream_pool_feed* f) { delete f; }
 
 extern "C" int prego_stream_pool_feed_drain(prego_stream_pool_feed* f, void* report, size_t report_bytes_, prego_stream_t stream) {

@@ -20,6 +20,28 @@ record (-1, -1).  An empty video has the record (0, -1).  Record = (total cost, 
   * `viterbi_decode_device`                 - the HIP path, `prego_viterbi_decode` / `prego_viterbi_decode_costs` (csrc/decode.hip): one
                                               launch, one workgroup per video.  No CPU fallback.
   * `emission_costs_device`                 - `prego_emission_costs`, the kernel's quantiser alone.
+  * `OnlineDecoder`                         - the host model of one slot of a decode pool (online fixed-lag decoding, below): the oracle
+                                              of csrc/decode_pool.hip.
+  * `online_decode_device`                  - whole videos through a `stream_pool.DecodePool`: what a lag costs against the offline decode.
+
+Online, fixed lag (include/prego_amd.h, prego_decode_pool_*, carries this word for word).  The model and the quantiser are the ones above.
+  - trans[i][j] and init[j] are int32.
+  - A negative word is forbidden.  A word above DECODE_CAP is read as CAP.  init None means zeros.
+  - At most 128 classes.
+  - Emission costs come from the fp32 word by DECODE_LUT, or from int32 cost words clamped into [0, CAP].
+  - d_0, d_t and the back-pointer (lowest i on a tie) are as in viterbi_decode.
+  - e_t is the lowest j with the smallest finite d_t(j).
+Fixed lag L (0..256).
+  - After frame t of a stream has been ingested and t >= L, frame f = t - L is committed.  label(f) is the state at frame f on the
+    back-pointer chain that starts at e_t.
+  - flush commits the remaining frames [max(0, T - L), T) from the chain that starts at e_{T-1}.
+  - Dead streams: a frame at which no state is finite makes the stream dead.  Every label committed from then on is -1, at flush too.
+    Labels already committed stay.
+Equivalently, and this is the oracle identity:  label(f) = viterbi_decode(x[: min(f + L, T - 1) + 1])[0][f].
+After T frames, (cost, end state) equals viterbi_decode(x[:T])'s record.  With L >= T - 1 the labels equal the offline decode.
+Consecutive labels come from different chains, so the committed sequence need not be an allowed path.
+The result depends on the frames only.  It does not depend on how they were cut into calls, on slot numbers, on the order of `slots`,
+or on the other slots.
 `ProcedureModel.transition_costs` (procedure.py) turns a corpus of correct transcripts into (trans, init)."""
 from __future__ import annotations
 
@@ -30,6 +52,10 @@ DECODE_FORBIDDEN = -1              # PREGO_DECODE_FORBIDDEN
 DECODE_MAX_CLASSES = 128           # PREGO_DECODE_MAX_CLASSES
 DECODE_BLOCK = 64                  # PREGO_DECODE_BLOCK: frames per block of the kernel's backtrace
 DECODE_PREFETCH = 8                # PREGO_DECODE_PREFETCH: frames ahead of the step the kernel requests its emission rows
+DECODE_POOL_MAX_LAG = 256          # PREGO_DECODE_POOL_MAX_LAG
+DECODE_PENDING = -2                # PREGO_DECODE_PENDING: the filler behind the labels a push or a flush committed
+DECODE_POOL_BURST = 32             # frames a slot takes per push at most
+STATUS_DEAD, STATUS_FLUSHED, STATUS_PUSHED_AFTER_FLUSH = 1, 2, 4      # the status word of a slot's header
 _INF = 1 << 62                     # the oracle's "no path": above every finite cost (below 2^31 frames x 65534)
 
 DECODE_LUT = np.array([
@@ -213,3 +239,180 @@ def emission_costs_device(probs):
         check(_lib.load().prego_emission_costs(C_.c_void_p(probs.data_ptr()), int(probs.stride(0)) if n > 1 else C, n, C,
                                                C_.c_void_p(out.data_ptr()), C_.c_void_p(torch.cuda.current_stream(probs.device).cuda_stream)))
     return out
+
+
+class OnlineDecoder:
+    """OnlineDecoder(trans, init=None, lag=64, n_classes=None, vote_window=1, max_events=1024): the host model of ONE slot of a decode
+    pool, in integer numpy (the definitions are the module's).  `push(rows)` - rows [K, C], floating = probabilities, integer = costs -
+    returns (labels, now): the labels the rows committed, in frame order, and e_t of every row (-1 once dead).  `flush()` commits the
+    tail and returns its labels; afterwards a push ingests nothing and returns DECODE_PENDING fillers.  `frames`, `committed`, `dead`,
+    `flushed`, `cost`, `end` are the header; `record` is the `aggregate.OnlineRecord` the committed labels went through, one by one;
+    `state_words()` is the slot's header and keys as the device keeps them."""
+
+    def __init__(self, trans, init=None, lag: int = 64, n_classes=None, vote_window: int = 1, max_events: int = 1024):
+        from .aggregate import OnlineRecord
+        C = int(np.asarray(trans).shape[0]) if n_classes is None else int(n_classes)
+        if not 1 <= C <= DECODE_MAX_CLASSES:
+            raise ValueError(f"decode: {C} classes (1..{DECODE_MAX_CLASSES})")
+        if not 0 <= int(lag) <= DECODE_POOL_MAX_LAG:
+            raise ValueError(f"decode: lag {lag} (0..{DECODE_POOL_MAX_LAG})")
+        tr, self._ini = _clamp_model(trans, init, C)
+        self._step = np.where(tr < 0, _INF, tr)
+        self.n_classes, self.lag = C, int(lag)
+        self.record = OnlineRecord(int(vote_window), C, int(max_events))
+        self.frames, self.committed, self.dead, self.flushed, self.pushed_after_flush = 0, 0, False, False, False
+        self._d, self._back = None, {}                       # the keys' costs; frame -> back-pointer row, the last `lag` frames
+
+    def _costs(self, rows):
+        x = np.asarray(rows)
+        if x.ndim == 1:
+            x = x[None]
+        if x.ndim != 2 or x.shape[1] != self.n_classes:
+            raise ValueError(f"decode: rows of shape {x.shape} ([frames, {self.n_classes}])")
+        return emission_costs(x).astype(np.int64) if x.dtype.kind == "f" else np.clip(x.astype(np.int64), 0, DECODE_CAP)
+
+    def _finite(self):
+        return self._d is not None and bool((self._d < _INF).any())
+
+    @property
+    def end(self) -> int:
+        """e of the last frame: -1 for a dead or an empty stream"""
+        return int(np.argmin(self._d)) if self._finite() else -1
+
+    @property
+    def cost(self) -> int:
+        """the total cost so far: 0 for an empty stream, -1 for a dead one"""
+        return 0 if self.frames == 0 else (int(self._d.min()) if self._finite() else -1)
+
+    def _walk(self, s: int, t: int, f: int) -> int:
+        for u in range(t, f, -1):
+            s = int(self._back[u][s])
+        return s
+
+    def _commit(self, label: int):
+        self.record.push(label)
+        self.committed += 1
+
+    def push(self, rows):
+        e = self._costs(rows)
+        if self.flushed:
+            self.pushed_after_flush = True
+            fill = np.full(e.shape[0], DECODE_PENDING, np.int32)
+            return fill, fill.copy()
+        labels, now, C = [], [], self.n_classes
+        for row in e:
+            t = self.frames
+            if t == 0:
+                self._d = np.where(self._ini < 0, _INF, self._ini + row)
+            else:
+                cand = np.where((self._d[:, None] >= _INF) | (self._step >= _INF), _INF, self._d[:, None] + self._step)
+                back = np.argmin(cand, axis=0)
+                best = cand[back, np.arange(C)]
+                self._back[t] = np.where(best >= _INF, 0, back)
+                self._back.pop(t - self.lag - 1, None)
+                self._d = np.where(best >= _INF, _INF, best + row)
+            self.frames += 1
+            en = self.end
+            self.dead = self.dead or en < 0
+            now.append(en)
+            if t >= self.lag:
+                labels.append(-1 if en < 0 else self._walk(en, t, t - self.lag))
+                self._commit(labels[-1])
+        return np.asarray(labels, np.int32), np.asarray(now, np.int32)
+
+    def flush(self):
+        """commits the frames [committed, frames) from the chain of the last frame, votes the record's unfinished window, marks the
+        stream flushed; returns the labels (a second flush: none)"""
+        labels = []
+        if not self.flushed:
+            en, T = self.end, self.frames
+            labels = [-1 if en < 0 else self._walk(en, T - 1, f) for f in range(self.committed, T)]
+            for lab in labels:
+                self._commit(lab)
+            self.flushed = True
+        self.record.flush()
+        return np.asarray(labels, np.int32)
+
+    @property
+    def status(self) -> int:
+        return (STATUS_DEAD if self.dead else 0) | (STATUS_FLUSHED if self.flushed else 0) | (STATUS_PUSHED_AFTER_FLUSH if self.pushed_after_flush else 0)
+
+    def keys(self) -> np.ndarray:
+        """int64 [n_classes rounded up to 4]: d << 7 | state, 2^62 for "no path"; zeros while the stream is empty, and in the padding"""
+        k = np.zeros((self.n_classes + 3) // 4 * 4, np.int64)
+        if self.frames:
+            k[:self.n_classes] = np.where(self._d >= _INF, _INF, (self._d << 7) | np.arange(self.n_classes))
+        return k
+
+    def state_words(self) -> np.ndarray:
+        """the slot's header and keys as int32 words (prego_decode_pool_state): frames | committed | status | end state (0 while empty) |
+        cost (int64) | 0 | 0, then the keys"""
+        head = np.array([self.frames, self.committed, self.status, self.end if self.frames else 0], np.int32)
+        return np.concatenate((head, np.array([self.cost], np.int64).view(np.int32), np.zeros(2, np.int32), self.keys().view(np.int32)))
+
+
+def online_decode_device(scores, offsets, trans, init=None, lag: int = 64, costs: bool = False):
+    """Whole videos through a `stream_pool.DecodePool`, as live streams would pass: scores a CUDA tensor [frames, classes] (fp32
+    probabilities, or int32 costs with costs=True), the videos one after the other; offsets [videos + 1] (host ints or a tensor).  Up
+    to 256 videos at a time, each fed 32 frames per call (at most 256 rows a call, gathered by `index_select`), then flushed.  Returns
+    (labels int32 CUDA tensor [frames] - label(f) of the module's definition -, records int64 CUDA tensor [videos, 2] - total cost |
+    end state as `viterbi_decode_device` gives them).  Host glue over the pool: it measures what a lag costs against the offline
+    decode.  No CPU fallback."""
+    import torch
+
+    from .stream_pool import MAX_ACTIVE, DecodePool
+    what = "online_decode_device"
+    C = int(scores.shape[1]) if hasattr(scores, "shape") and len(scores.shape) == 2 else 0
+    _device_args(what, scores, C)
+    off = [int(v) for v in (offsets.cpu().tolist() if isinstance(offsets, torch.Tensor) else offsets)]
+    n, nv, dev = int(scores.shape[0]), len(off) - 1, scores.device
+    if nv < 1 or off[0] < 0 or off[-1] > n or any(b < a for a, b in zip(off, off[1:])):
+        from ._lib import PregoError
+        raise PregoError(f"{what}: offsets must ascend within [0, {n}] and name at least one video")
+    lag = int(lag)
+    labels = torch.full((max(n, 1),), DECODE_PENDING, dtype=torch.int32, device=dev)
+    records = torch.empty((nv, 2), dtype=torch.int64, device=dev)
+    for g0 in range(0, nv, MAX_ACTIVE):
+        vids = list(range(g0, min(g0 + MAX_ACTIVE, nv)))
+        pool = DecodePool(C, trans, init, lag=lag, capacity=len(vids), device=dev)
+        slot_of = {v: pool.open() for v in vids}
+        done = {v: 0 for v in vids}                          # frames of video v pushed so far
+        while True:
+            call, rows = [], 0
+            for v in vids:
+                k = min(DECODE_POOL_BURST, off[v + 1] - off[v] - done[v], MAX_ACTIVE - rows)
+                if k > 0:
+                    call.append((v, k))
+                    rows += k
+            if not call:
+                break
+            src, dst_from, dst_to, at = [], [], [], 0
+            for v, k in call:
+                F = done[v]
+                src.extend(range(off[v] + F, off[v] + F + k))
+                first, m = max(0, F - lag), max(0, F + k - lag) - max(0, F - lag)       # what this call commits: known without asking
+                dst_from.extend(range(at, at + m))
+                dst_to.extend(range(off[v] + first, off[v] + first + m))
+                done[v] += k
+                at += k
+            x = scores.index_select(0, torch.tensor(src, dtype=torch.int64).to(dev))
+            lab, _, _ = pool.push([slot_of[v] for v, _ in call], x, counts=[k for _, k in call], costs=costs)
+            if dst_to:
+                labels.index_copy_(0, torch.tensor(dst_to, dtype=torch.int64).to(dev), lab.index_select(0, torch.tensor(dst_from, dtype=torch.int64).to(dev)))
+        tail, _ = pool.flush([slot_of[v] for v in vids])
+        dst_from, dst_to = [], []
+        for i, v in enumerate(vids):
+            T = off[v + 1] - off[v]
+            first = max(0, T - lag)
+            dst_from.extend(range(i * lag, i * lag + T - first))
+            dst_to.extend(range(off[v] + first, off[v] + T))
+        if dst_to:
+            labels.index_copy_(0, torch.tensor(dst_to, dtype=torch.int64).to(dev),
+                               tail.reshape(-1).index_select(0, torch.tensor(dst_from, dtype=torch.int64).to(dev)))
+        head = pool.headers()                                # int32 [capacity, 8] on the device
+        h = head[torch.tensor([slot_of[v] for v in vids], dtype=torch.int64).to(dev)]
+        cost = h[:, 4:6].contiguous().view(torch.int64).reshape(-1)
+        empty = h[:, 0] == 0
+        records[g0:g0 + len(vids), 0] = cost
+        records[g0:g0 + len(vids), 1] = torch.where(empty, torch.full_like(cost, -1), h[:, 3].to(torch.int64))
+    return labels[:n], records

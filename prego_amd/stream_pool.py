@@ -5,7 +5,8 @@ returns what `aggregate` would return for the stream's per-frame predictions ('p
 the way.  `SlotTable` is the host bookkeeping (which slots are open), usable without a device.  `EventFeed` (`pool.event_feed()`,
 csrc/stream_feed.hip) tells a live consumer which slots gained an event since it last asked, in one asynchronous report per tick;
 `FeedModel` is its host model; `MistakeMonitor` (`pool.mistake_monitor(model)`, csrc/procedure.hip) judges every drained event against a
-procedure model on the device, `MonitorModel` is its host model.  `pool.snapshot` / `restore` / `detach` (csrc/stream_image.hip) take live slots out of a pool as a
+procedure model on the device, `MonitorModel` is its host model; `DecodePool` is the online fixed-lag Viterbi decoder beside a pool (csrc/decode_pool.hip): the scores a
+push returns go into it, and its record - the decoded transcript - serves the same feed and monitors.  `pool.snapshot` / `restore` / `detach` (csrc/stream_image.hip) take live slots out of a pool as a
 `PoolSnapshot` of canonical images and put them into a pool again - another pool, other slot numbers, another device or process -,
 validated on the device before a slot is written; `image_fault`, `image_layout` and `model_image` are their host model."""
 from __future__ import annotations
@@ -73,7 +74,16 @@ class SlotTable:
     def is_open(self, slot: int) -> bool:
         return slot in self._open
 
-    def open(self) -> int:
+    def open(self, slot=None) -> int:
+        """the lowest free slot, or exactly `slot` when a number is given (a pool that mirrors another pool's numbering)"""
+        if slot is not None:
+            slot = int(slot)
+            if not 0 <= slot < self.capacity or slot in self._open:
+                raise PregoError(f"stream pool: slot {slot} is " + ("already open" if slot in self._open else f"outside the pool (capacity {self.capacity})"))
+            self._free.remove(slot)
+            heapq.heapify(self._free)
+            self._open.add(slot)
+            return slot
         if not self._free:
             raise PregoError(f"stream pool: all {self.capacity} slots are open")
         slot = heapq.heappop(self._free)
@@ -1144,3 +1154,160 @@ class TransformerStreamPool(_RecordPool):
             self._check(self.lib.prego_vit_stream_pool_window(self.p, slot, C.c_void_p(rows.data_ptr()), C.c_void_p(fill.data_ptr()),
                                                               C.c_void_p(self._stream_ptr(self.device))))
         return rows, int(fill.item())
+
+
+class DecodePool(_RecordPool):
+    """DecodePool(n_classes, trans, init=None, lag=64, capacity=256, vote_window=1, max_events=1024, device="cuda"): online fixed-lag
+    Viterbi per live stream (prego_decode_pool_*, csrc/decode_pool.hip; definitions: prego_amd/decode.py).  Every slot of one device block
+    holds a stream's Viterbi state; `push` gives any subset of the slots 1..32 rows of scores each - what `StreamPool.push` /
+    `push_frames` / `push_ragged` return with softmax=True - and every frame's label is committed `lag` frames after it arrived, into a
+    record of the stream pools' layout: `events`, `close`, `event_feed`, `mistake_monitor` and `forecast_monitor` work on the decoded
+    transcript.  With vote_window 1 every change of the committed label is an event.  `decode.OnlineDecoder` is the host model of a
+    slot.  Consecutive labels come from different back-pointer chains, so the committed sequence need not be an allowed path."""
+    _C = {"destroy": "prego_decode_pool_destroy", "flush": "prego_decode_pool_flush", "reset": "prego_decode_pool_reset",
+          "record": "prego_decode_pool_record", "feed_create": "prego_decode_pool_feed_create"}
+
+    def __init__(self, n_classes: int, trans, init=None, lag: int = 64, capacity: int = 256, vote_window: int = 1, max_events: int = 1024,
+                 device="cuda"):
+        import numpy as np
+
+        from . import _lib
+        from .engine import _stream_ptr
+        self.lib, self._stream_ptr = _lib.load(), _stream_ptr
+        dev = torch.device(device)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if dev.type == "cuda" and dev.index is None else dev
+        if self.device.type != "cuda":
+            raise PregoError("decode pool needs a CUDA device; there is no CPU fallback (host model: prego_amd.decode.OnlineDecoder)")
+        self.lag, self.vote_window, self.max_events = int(lag), int(vote_window), int(max_events)
+        self._vote_window, self._ncls, self._ncls_pad = self.vote_window, int(n_classes), (int(n_classes) + 3) // 4 * 4
+        self.slots = SlotTable(capacity)
+        need = self.lib.prego_decode_pool_bytes(int(capacity), self._ncls, self.lag, self.max_events)
+        if need == 0:
+            raise PregoError(f"decode pool: capacity {capacity}, max_events {max_events} (each 1..{1 << 20}), n_classes {n_classes} (1..128), "
+                             f"lag {lag} (0..256)")
+        as_dev = lambda a, n: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))).to(
+            device=self.device, dtype=torch.int32).reshape(n).contiguous()
+        tr = as_dev(trans, self._ncls * self._ncls)
+        ini = None if init is None else as_dev(init, self._ncls)
+        self._block = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self.p = None
+        p = C.c_void_p()
+        with torch.cuda.device(self.device):
+            rc = self.lib.prego_decode_pool_create(C.byref(p), int(capacity), self._ncls, self.lag, self.vote_window, self.max_events,
+                                                   C.c_void_p(tr.data_ptr()), C.c_void_p(ini.data_ptr()) if ini is not None else None,
+                                                   C.c_void_p(self._block.data_ptr()), need, C.c_void_p(_stream_ptr(self.device)))
+        self._check(rc)                                          # trans / init go back to the allocator behind the clamp, on its stream
+        self.p = p
+
+    def open(self, slot=None) -> int:
+        """the lowest free slot, or exactly `slot`: a decoder beside a `StreamPool` mirrors its numbering.  Nothing is launched"""
+        return self.slots.open(slot)
+
+    def _out(self, buf, shape, name):
+        if buf is None:
+            return torch.empty(shape, dtype=torch.int32, device=self.device)
+        if not buf.is_cuda or buf.dtype != torch.int32 or not buf.is_contiguous() or tuple(buf.shape) != tuple(shape):
+            raise PregoError(f"decode pool: expected {name} as contiguous int32 cuda {tuple(shape)}, got {tuple(buf.shape)} {buf.dtype}")
+        return buf
+
+    def push(self, slots, scores, counts=None, costs: bool = False, labels=None, commit=None, now=None):
+        """Rows of scores for the open slots named: [n, C] (one frame each), [n, K, C] (K <= 32 each) or packed [R, C] with
+        counts[i] rows (1..32, R <= 256) for slots[i] - fp32 probabilities, or int32 emission costs with costs=True; cuda, rows
+        contiguous.  Returns (labels int32 [R], commit int32 [n, 2], now int32 [R]) on the device: in slot i's row block the labels this
+        call committed, in frame order, then DECODE_PENDING; (first frame committed or next due, how many); e_t of every row, the
+        zero-lag provisional label (-1 once the stream is dead).  Nothing waits.  Pass buffers to reuse them."""
+        who = "decode pool push"
+        slots = self.slots.check(slots, "push")
+        n, Cn = len(slots), self._ncls
+        if not (isinstance(scores, torch.Tensor) and scores.is_cuda) or scores.dtype != (torch.int32 if costs else torch.float32):
+            raise PregoError(f"{who}: expected scores as a {'int32' if costs else 'float32'} cuda tensor (costs={costs}); there is no CPU fallback")
+        if scores.dim() == 3 and counts is None:
+            if scores.shape[0] != n or scores.shape[2] != Cn:
+                raise PregoError(f"{who}: expected scores as [{n}, K, {Cn}], got {tuple(scores.shape)}")
+            counts = [int(scores.shape[1])] * n
+            scores = scores.reshape(n * scores.shape[1], Cn)
+        elif scores.dim() == 2 and counts is None:
+            counts = [1] * n
+        else:
+            counts = SC.counts_list(who, counts, n)
+        R = sum(counts)
+        if scores.dim() != 2 or tuple(scores.shape) != (R, Cn) or (scores.stride(1) != 1 and R > 0):
+            raise PregoError(f"{who}: expected scores as [{R}, {Cn}] rows (sum(counts) = {R}) with contiguous rows, got {tuple(scores.shape)}")
+        ld = int(scores.stride(0)) if R > 1 else Cn
+        labels, commit, now = self._out(labels, (max(R, 0),), "labels"), self._out(commit, (n, 2), "commit"), self._out(now, (max(R, 0),), "now")
+        entry = self.lib.prego_decode_pool_push_costs if costs else self.lib.prego_decode_pool_push
+        with torch.cuda.device(self.device):
+            self._check(entry(self.p, n, self._slot_array(slots), self._slot_array(counts), C.c_void_p(scores.data_ptr()), ld,
+                              C.c_void_p(labels.data_ptr()), C.c_void_p(commit.data_ptr()), C.c_void_p(now.data_ptr()),
+                              C.c_void_p(self._stream_ptr(self.device))))
+        return labels, commit, now
+
+    def flush(self, slots, labels=None, commit=None):
+        """Ends the streams named without freeing them: the tail is committed from the last frame's chain, the record's unfinished window
+        voted, the slot marked flushed (a later push ingests nothing; `close` reopens it).  Returns (labels int32 [n, lag]: slot i's tail
+        then DECODE_PENDING, commit int32 [n, 2]) on the device; nothing waits."""
+        slots = self.slots.check(slots, "flush")
+        n = len(slots)
+        labels, commit = self._out(labels, (n, self.lag), "labels"), self._out(commit, (n, 2), "commit")
+        with torch.cuda.device(self.device):
+            self._check(self.lib.prego_decode_pool_flush(self.p, n, self._slot_array(slots), C.c_void_p(labels.data_ptr()) if self.lag else None,
+                                                         C.c_void_p(commit.data_ptr()), C.c_void_p(self._stream_ptr(self.device))))
+        return labels, commit
+
+    def _state_view(self, slot: int):
+        ptr, nbytes = C.c_void_p(), C.c_size_t()
+        self._check(self.lib.prego_decode_pool_state(self.p, slot, C.byref(ptr), C.byref(nbytes)))
+        off = ptr.value - self._block.data_ptr()
+        return self._block[off:off + nbytes.value].view(torch.int32)
+
+    def state_words(self, slot: int):
+        """the slot's header and keys as int32 numpy words (prego_decode_pool_state; `OnlineDecoder.state_words`): one D2H copy, it waits"""
+        slot = self.slots.check([slot], "state_words")[0]
+        return self._state_view(slot).cpu().numpy()
+
+    def headers(self):
+        """int32 [capacity, 8] on the device: a copy of every slot's header; nothing waits"""
+        a = self._state_view(0)
+        base = a.data_ptr() - self._block.data_ptr()
+        stride = (self._state_view(1).data_ptr() - a.data_ptr()) if self.capacity > 1 else a.numel() * 4
+        return torch.as_strided(self._block[base:].view(torch.int32), (self.capacity, 8), (stride // 4, 1)).clone()
+
+    def status(self, slot: int) -> dict:
+        """the slot's header: {'frames', 'committed', 'dead', 'flushed', 'pushed_after_flush', 'end', 'cost'} ('end' -1 for an empty or
+        a dead stream, 'cost' -1 for a dead one).  One small D2H copy; it waits."""
+        w = self.state_words(slot)
+        frames, st = int(w[0]), int(w[2])
+        return {"frames": frames, "committed": int(w[1]), "dead": bool(st & 1), "flushed": bool(st & 2), "pushed_after_flush": bool(st & 4),
+                "end": int(w[3]) if frames else -1, "cost": int(w[4:6].view("int64")[0])}
+
+    def _raise_overflow(self, slot: int, overflow: int):
+        if overflow & OVERFLOW_BAD_ID:
+            raise PregoError(f"decode pool: the stream of slot {slot} is infeasible: at some frame no state had a finite cost under the model "
+                             "(forbidden transitions or starts); the labels committed from then on are -1")
+        super()._raise_overflow(slot, overflow)
+
+    def close(self, slot: int) -> dict:
+        """Ends the stream: commits its tail, votes the record's unfinished window, reads header and record (small D2H copies), zeroes the
+        slot and frees it.  Returns {'pred', 'changes_pred'} of the committed labels as the other pools give them for their ids, plus
+        'labels_tail' (the labels the flush committed) and 'cost' (the decoded path's total).  Raises PregoError, the slot freed all
+        the same, for a dead (infeasible) stream or a record that overflowed."""
+        slot = self.slots.check([slot], "close")[0]
+        arr, s = self._slot_array([slot]), C.c_void_p(self._stream_ptr(self.device))
+        with torch.cuda.device(self.device):
+            tail, commit = self.flush([slot])
+            w = self._state_view(slot).cpu().numpy()
+            frames, overflow, ev_id, ev_start = self._record(slot)
+            m = int(commit[0, 1])
+            self._check(self.lib.prego_decode_pool_reset(self.p, 1, arr, s))
+            for feed in self._feeds:
+                feed.forget([slot])
+        self.slots.release(slot)
+        if int(w[2]) & 1:
+            self._raise_overflow(slot, OVERFLOW_BAD_ID)
+        self._raise_overflow(slot, overflow)
+        return {"pred": ev_id, "changes_pred": ev_start[1:] + [frames], "labels_tail": tail[0, :m].cpu().tolist(), "cost": int(w[4:6].view("int64")[0])}
+
+    def _no_images(self, *a, **k):
+        raise PregoError("decode pool: slot images of decode pools are not supported yet (snapshot / restore / detach)")
+
+    snapshot = restore = detach = _no_images
